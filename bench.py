@@ -10,9 +10,17 @@ audio samples (320 per semantic token @16 kHz) / max-over-ranks wall time. Each 
 BiCodec decoder (HIP MFMA conv stack, assumed SparkTTS dims, random-init weights) turning every
 request's 32 global + 512 semantic tokens into PCM, so the timed region is tokens -> waveform.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]. N > 1 runs one process per GPU:
-under torch.distributed.run (RANK / WORLD_SIZE set by the launcher), or, when WORLD_SIZE is unset,
-bench.py starts the N ranks itself (before anything touches a GPU) and relays rank 0's line.
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full].
+N > 1 runs one process per GPU: under torch.distributed.run (RANK / WORLD_SIZE set by the
+launcher), or, when WORLD_SIZE is unset, bench.py starts the N ranks itself (before anything
+touches a GPU) and relays rank 0's line.
+
+A plain run sets up, warms up, times the K steps and prints the result line (throughput,
+ms_per_step, where a step's wall time went). --dump-outputs DIR also writes what the last timed
+step returned (rank 0's tokens and PCM) as DIR/<name>.npy: the inputs are seeded, so two builds
+can be compared output for output. --full adds, after the timed region, everything that takes
+runs of its own: the per-kernel passes and rooflines, the one-request (config 2) leg and the CPU
+baseline (each with its own --no-... switch).
 """
 import argparse
 import json
@@ -197,6 +205,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel passes (rooflines), the one-request "
+                         "leg and the CPU baseline, and report them in the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0: global_tokens, semantic_tokens, "
+                         "pcm) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--token-chunk-size", type=int, default=2048,
                     help="prompt rows per engine step (all admitted prompts share it; outputs are chunk-invariant, bitwise)")
@@ -210,6 +224,8 @@ def main():
     ap.add_argument("--no-pipeline", dest="pipeline", action="store_false",
                     help="run the vocoder of each batch after its LM decode instead of overlapped")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -281,15 +297,17 @@ def main():
     # Every batch's PCM is complete inside the timed region.
     from concurrent.futures import ThreadPoolExecutor
 
-    def vocode(out):
+    def vocode(out, keep=False):
         if args.voc_delay_ms > 0:  # start after the next batch's prefill (A/B switch)
             time.sleep(args.voc_delay_ms / 1000.0)
         pcm = voc.decode_audio_batch([(g, s) for g, s in out])
         assert sum(p.size for p in pcm) == 320 * sum(len(s) for _, s in out), "vocoder output length mismatch"
-        return len(pcm)
+        return pcm if keep else len(pcm)
 
-    def pipelined(steps, step0):
-        acc = {"gen_ms": 0.0, "decode_ms": 0.0, "prefill_ms": 0.0, "dec_steps": 0, "sem_tokens": 0, "out": None}
+    def pipelined(steps, step0, keep_last=False):
+        """`steps` batches from request step `step0`; keep_last: the last batch's PCM stays in acc["pcm"]."""
+        acc = {"gen_ms": 0.0, "decode_ms": 0.0, "prefill_ms": 0.0, "dec_steps": 0, "sem_tokens": 0, "out": None,
+               "pcm": None}
         futs = []
         with ThreadPoolExecutor(max_workers=1) as pool:
             for s in range(step0, step0 + steps):
@@ -302,19 +320,21 @@ def main():
                 acc["prefill_ms"] += st["prefill_ms"]
                 acc["dec_steps"] += st["steps"]
                 acc["out"] = out
-                futs.append(pool.submit(vocode, out) if args.pipeline else None)
+                keep = keep_last and s == step0 + steps - 1
+                futs.append(pool.submit(vocode, out, keep) if args.pipeline else None)
                 if not args.pipeline:
-                    vocode(out)
+                    acc["pcm"] = vocode(out, keep)
             for f in futs:
                 if f is not None:
-                    f.result()
+                    acc["pcm"] = f.result()
         return acc
 
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    acc = pipelined(args.steps, 0)  # the timed region: no instrumentation in the decode graphs
+    # the timed region: no instrumentation in the decode graphs
+    acc = pipelined(args.steps, 0, keep_last=bool(args.dump_outputs))
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -322,12 +342,14 @@ def main():
     gen_ms, decode_ms, prefill_ms = acc["gen_ms"], acc["decode_ms"], acc["prefill_ms"]
     dec_steps, sem_tokens, out = acc["dec_steps"], acc["sem_tokens"], acc["out"]
     elapsed, total_tokens = D.reduce_run(elapsed, sem_tokens, device="cuda")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, acc["pcm"])
     # in-graph kernel timing (rwkvtts_set_profiling mode 2), in a SEPARATE pass after the timed region
     # (ADVICE r4): the decode graphs are recaptured with launch-timeline slots and two more batches
     # run pipelined exactly as timed (the vocoder of each beside the next one's decode); the last step
     # of every decode window is sampled (per launch: first workgroup start -> last workgroup end)
     gprof = {}
-    if args.graph_timing and rank == 0:
+    if args.full and args.graph_timing and rank == 0:
         rt.set_profiling(2)
         pipelined(2, 10**5)
         gprof = rt.profile()
@@ -342,7 +364,7 @@ def main():
     kernels = {}
     step_roof = None
     codec_roof = None
-    if rank == 0:
+    if args.full and rank == 0:
         # decode-step kernels: the in-graph samples of the timed region (the same launches rocprof
         # traces); without them (--no-graph-timing) an eager HIP-event pass of one batch. The
         # vocoder's own pass runs alone.
@@ -406,10 +428,10 @@ def main():
                          "achieved": round(step_bytes / (step_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS,
                          "frac": round(step_bytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
 
-    b1 = batch1_leg(rt, voc, requests, dims) if rank == 0 and not args.no_batch1 else None
+    b1 = batch1_leg(rt, voc, requests, dims) if args.full and rank == 0 and not args.no_batch1 else None
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(dims, cdims, args.cpu_seconds)
 
     if rank == 0:
@@ -431,18 +453,25 @@ def main():
                                        "decode": round(decode_ms / args.steps, 3),
                                        "prefill": round(prefill_ms / args.steps, 3),
                                        "decode_steps": dec_steps // max(1, args.steps)},
-            "roofline": roofline,
-            "decode_step_roofline": step_roof,
-            "batch1": b1,
-            "codec_roofline": codec_roof,
-            "kernels": kernels,
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            line.update({"roofline": roofline, "decode_step_roofline": step_roof, "batch1": b1,
+                         "codec_roofline": codec_roof, "kernels": kernels, "cpu_baseline": cpu})
         print(json.dumps(line))
     rt.close()
     voc.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, out, pcm):
+    """What the last timed step returned, one array per name, a row per request of the batch:
+    global_tokens [B, 32] and semantic_tokens [B, S] (token ids, exact in float64) and pcm
+    [B, 320 * S] float32 (fixed-length benchmark mode: every request has the same S)."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "global_tokens.npy"), np.stack([np.asarray(g, dtype=np.float64) for g, _ in out]))
+    np.save(os.path.join(path, "semantic_tokens.npy"), np.stack([np.asarray(s, dtype=np.float64) for _, s in out]))
+    np.save(os.path.join(path, "pcm.npy"), np.stack([np.asarray(p, dtype=np.float32) for p in pcm]))
 
 
 def spawn_ranks(n):

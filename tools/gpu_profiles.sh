@@ -1,4 +1,4 @@
-# Round profiles: rocprofv3 kernel-trace --stats of a bench run (the bench's default command minus
+# Round profiles: rocprofv3 kernel-trace --stats of a bench run (the bench's --full command minus
 # the CPU baseline) + separate PMC passes (FETCH_SIZE, WRITE_SIZE) on the short LM workload, then
 # the summaries (decode-launch statistics, PMC traffic per decode kernel) made on the box; the
 # large per-launch CSVs are deleted (gpurun copies back <= 64 MiB). Usage: gpu_profiles.sh TAG
@@ -8,7 +8,7 @@ T=${1:-r04}
 O=$R/gpurun_out/prof_$T
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python3 $R/bench.py --no-cpu-baseline > $O/bench_trace.log 2>&1 || { tail -20 $O/bench_trace.log; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python3 $R/bench.py --full --no-cpu-baseline > $O/bench_trace.log 2>&1 || { tail -20 $O/bench_trace.log; exit 1; }
 tail -c 400 $O/bench_trace.log
 export LM_GRAPHS=0
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o run -- python3 $R/tools/lm_short.py > $O/fetch.log 2>&1 || exit 1

@@ -1,5 +1,5 @@
-# One GPU session (one gpurun call): the -m gpu suite (full-length report kept), smoke, bench.py's
-# default line, the rocprof kernel-trace + PMC traffic profiles of the bench (gpu_profiles.sh) and the
+# One GPU session (one call): the -m gpu suite (full-length report kept), smoke, bench.py's
+# --full line, the rocprof kernel-trace + PMC traffic profiles of the bench (gpu_profiles.sh) and the
 # MFMA-busy counter passes (pmc_mfma.sh), any subset, each step under its own time limit; the first
 # failing step ends the call. Every summary is stamped with the library's build id
 # (rwkvtts._ffi.build_id()), which bench.py matches when it cites profiles/.
@@ -23,7 +23,7 @@ if has smoke; then
   tail -1 $O/smoke.txt
 fi
 if has bench; then
-  timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || { echo BENCH FAILED; tail $O/bench.err; exit 1; }
+  timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { echo BENCH FAILED; tail $O/bench.err; exit 1; }
   tail -c 300 $O/bench.json
 fi
 if has prof; then

@@ -7,7 +7,7 @@ timeout -k 10 ${TEST_TIMEOUT:-900} python -u -m pytest ${PYTEST_ARGS:-tests} -m 
 rc=$?; echo "TESTS EXIT $rc"; tail -8 $O/gpu_tests.log
 [ $rc -eq 0 ] || exit $rc
 [ -n "$NO_BENCH" ] && exit 0
-timeout -k 10 600 python -u bench.py --steps ${STEPS:-5} --warmup 1 ${BENCH_ARGS:---no-cpu-baseline} > $O/bench.json 2> $O/bench.err
+timeout -k 10 600 python -u bench.py --full --steps ${STEPS:-5} --warmup 1 ${BENCH_ARGS:---no-cpu-baseline} > $O/bench.json 2> $O/bench.err
 rc=$?; echo "BENCH EXIT $rc"
 [ $rc -eq 0 ] || { tail -20 $O/bench.err; exit $rc; }
 python3 - "$O/bench.json" <<'PY'

@@ -7,7 +7,7 @@ T=${1:-outl}
 O=$R/gpurun_out/outl_$T
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $O/trace -o run -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-batch1 --no-graph-timing > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $O/trace -o run -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-batch1 --no-graph-timing > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
 KT=$(find $O/trace -name "*kernel_trace.csv" | head -1)
 python3 $R/tools/outlier_attrib.py $KT 4 25 > $O/${T}_outliers.txt || exit 1
 rm -f $KT
