@@ -289,6 +289,27 @@ typedef struct {
 int rwkvtts_generate_batch(rwkvtts_engine* e, const rwkvtts_request* reqs, int n,
                            rwkvtts_result* results);
 
+/* ---- token progress (streaming; no reference counterpart: generate_tts returns at the end) -- */
+/* fn(user, global_tokens, n_global, semantic, first, count, done, status): semantic tokens
+ * [first, first + count) of one request (`semantic` points at the first of them; the pointers are
+ * valid during the call only), with the global tokens known so far (all 32 before the first
+ * semantic token of a normal-mode request). Tokens arrive in order, each exactly once; the last
+ * call has done = 1 and the request's status (then count may be 0). A request that fails ends with
+ * done = 1 and a negative status; tokens of a unit of work that faulted are never delivered. */
+typedef void (*rwkvtts_token_fn)(void* user, const int32_t* global_tokens, int32_t n_global,
+                                 const int32_t* semantic, int32_t first, int32_t count, int32_t done,
+                                 int32_t status);
+typedef struct {
+  rwkvtts_token_fn fn; /* NULL: no progress for this request */
+  void* user;
+} rwkvtts_token_sink;
+/* rwkvtts_generate_batch with one sink per request (sinks == NULL: none). The sinks run on the
+ * calling thread, between the engine's units of work (a mixed prompt step, or up to 8 decode steps);
+ * they must not call into this engine. Results are those of rwkvtts_generate_batch, and a batch
+ * without sinks enqueues exactly the GPU work rwkvtts_generate_batch enqueues. */
+int rwkvtts_generate_batch_stream(rwkvtts_engine* e, const rwkvtts_request* reqs, int n,
+                                  rwkvtts_result* results, const rwkvtts_token_sink* sinks);
+
 /* ---- request manager: DynamicBatchManager (dynamic_batch_manager.rs:22-164,185-405) ------ */
 /* The reference collects requests (enqueue_worker: first request, then try_recv up to
  * max_batch_size; a lone request waits >= 10 ms for company, :185-264) and hands each batch to
@@ -329,6 +350,20 @@ int rwkvtts_manager_destroy(rwkvtts_manager* m);
  * request has not finished yet. out->semantic_tokens must hold RWKVTTS_SEMANTIC_LIMIT ids. */
 int rwkvtts_manager_submit(rwkvtts_manager* m, const rwkvtts_request* req, uint64_t* ticket);
 int rwkvtts_manager_wait(rwkvtts_manager* m, uint64_t ticket, int timeout_ms, rwkvtts_result* out);
+/* Streaming by polling (no foreign thread ever calls back into the caller): submit_stream is submit
+ * for a request whose token progress the engine publishes after every unit of work. wait_tokens
+ * blocks up to timeout_ms (< 0: forever) until more than have_semantic semantic tokens are known or
+ * the request is done, then copies everything known so far: global32 (32 ids), *n_global,
+ * semantic_out (capacity RWKVTTS_SEMANTIC_LIMIT), *n_semantic, *done and *status (the request's,
+ * once done). RWKVTTS_EBUSY on a timeout (the outputs are filled all the same). It does not release
+ * the ticket: rwkvtts_manager_wait still returns the final result and releases it. Completion
+ * publishes whatever was not published before, so a stream always terminates; a ticket from plain
+ * submit can be polled too (its tokens then appear at completion). One thread at a time may be in
+ * wait / wait_tokens on a ticket. */
+int rwkvtts_manager_submit_stream(rwkvtts_manager* m, const rwkvtts_request* req, uint64_t* ticket);
+int rwkvtts_manager_wait_tokens(rwkvtts_manager* m, uint64_t ticket, int32_t have_semantic, int timeout_ms,
+                                int32_t* global32, int32_t* n_global, int32_t* semantic_out,
+                                int32_t* n_semantic, int32_t* done, int32_t* status);
 /* generate_tts_batch (dynamic_batch_manager.rs:124-164): submit all, wait all. */
 int rwkvtts_manager_generate_batch(rwkvtts_manager* m, const rwkvtts_request* reqs, int n,
                                    rwkvtts_result* results);
@@ -423,6 +458,40 @@ int rwkvtts_codec_decode(rwkvtts_codec* c, const int64_t* semantic, int T, const
 /* decode_audio_batch (lightweight_tts_pipeline.rs:625-703): n utterances in one pass. */
 int rwkvtts_codec_decode_batch(rwkvtts_codec* c, const int64_t* const* semantic, const int* T,
                                const int64_t* const* global, int n, float* const* pcm);
+/* ---- codec, streaming: exact windowed decode (no reference counterpart: the reference decodes a
+ * finished utterance only) --------------------------------------------------------------------
+ * The decoder is a finite stack of convolutions (its LayerNorms work per frame, the speaker vector
+ * comes from the global tokens alone), so the samples of frames [t0, t1) depend only on the tokens
+ * [t0 - H, t1 + H), with zero padding at the true ends of the utterance only. H = prenet_halo +
+ * wave_halo frames per side: wave_halo for conv_in .. conv_out (10 at the SparkTTS rates), and
+ * prenet_halo = 3 * (prenet_layers + 1) for the prenet's 7-tap convolutions. Host only. */
+int rwkvtts_codec_halo(const rwkvtts_codec_dims* d, int32_t* prenet_halo, int32_t* wave_halo);
+/* New structs start with struct_size = sizeof(the struct) as the caller compiled it, so they can
+ * grow without a new entry point. */
+typedef struct {
+  uint32_t struct_size;
+  int32_t ctx0, ctx1;   /* tokens [ctx0, ctx1) the prenet runs on: at most (t1 - t0) + 2 H */
+  int32_t wave0, wave1; /* frames [wave0, wave1) conv_in .. conv_out run on: at most (t1 - t0) + 2 wave_halo */
+} rwkvtts_codec_plan;
+/* The work rwkvtts_codec_decode_windows does for one window (it calls this same function). Host
+ * only. Ranges are clipped at 0 and at n_known. RWKVTTS_EINVAL unless 0 <= t0 < t1 <= n_known and
+ * (final or t1 + H <= n_known). */
+int rwkvtts_codec_window_plan(const rwkvtts_codec_dims* d, int32_t t0, int32_t t1, int32_t n_known,
+                              int32_t final, rwkvtts_codec_plan* out);
+typedef struct {
+  uint32_t struct_size;
+  int32_t n_known;         /* semantic tokens known so far */
+  int32_t final;           /* 1: n_known is the utterance's length */
+  int32_t t0, t1;          /* frames to decode */
+  const int64_t* semantic; /* [n_known], from frame 0 */
+  const int64_t* global;   /* [n_global] */
+  float* pcm;              /* capacity (t1 - t0) * 320 */
+} rwkvtts_codec_window;
+/* n windows (ragged, of any utterances) in one batched pass. pcm = samples [t0 * 320, t1 * 320) of
+ * rwkvtts_codec_decode over the whole utterance, bitwise (tests/test_gpu_codec_windows.py), whatever
+ * tokens follow t1 + H. A window that breaks window_plan's precondition, or a code out of range
+ * inside its context, fails the call with RWKVTTS_EINVAL before anything is launched. */
+int rwkvtts_codec_decode_windows(rwkvtts_codec* c, const rwkvtts_codec_window* w, int n);
 /* Verification forms of later decode calls (0 = shipping); the PCM is bitwise equal either way
  * (tests/test_gpu_codec.py). No reference counterpart (ORT runs one graph). */
 #define RWKVTTS_CODEC_FORM_SEPARATE_RESUNIT 1u /* 96-channel residual units as conv7 + conv1 launches */

@@ -140,6 +140,21 @@ int rwkvtts_generate_batch(rwkvtts_engine* e, const rwkvtts_request* reqs, int n
   })
 }
 
+int rwkvtts_generate_batch_stream(rwkvtts_engine* e, const rwkvtts_request* reqs, int n, rwkvtts_result* results,
+                                  const rwkvtts_token_sink* sinks) {
+  RT_CHECK(e && reqs && results && n >= 0, RWKVTTS_EINVAL, "generate_batch_stream: bad arguments");
+  LOCK(e);
+  GUARD({
+    const int rc = e->eng.generate(reqs, n, results, sinks);
+    if (rc != RWKVTTS_OK)
+      for (int i = 0; i < n; ++i) {  // (every sink has had its done call with this status: Engine::generate)
+        results[i].status = rc;
+        results[i].n_global = results[i].n_semantic = 0;
+      }
+    return rc;
+  })
+}
+
 int rwkvtts_get_stats(rwkvtts_engine* e, rwkvtts_stats* out) {
   RT_CHECK(e && out, RWKVTTS_EINVAL, "null argument");
   LOCK(e);

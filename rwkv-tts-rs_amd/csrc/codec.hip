@@ -639,9 +639,68 @@ __global__ void k_f32_split_bf16(const float* in, bf16_t* hi, bf16_t* lo, int64_
   }
 }
 
+// windowed decode: rows [off[req], off[req] + nrow[req]) of each utterance's prenet output planes
+// ([t][L], stride s_bs) -> rows [0, nrow[req]) of the WaveGenerator's input planes (stride d_bs).
+// 16 B per lane and plane (L % 64 == 0).
+__global__ __launch_bounds__(64) void k_crop_rows(const bf16_t* sh, const bf16_t* sl, int64_t s_bs, bf16_t* dh,
+                                                  bf16_t* dl, int64_t d_bs, int L, const int* nrow, const int* off) {
+  const int r = blockIdx.x, req = blockIdx.y;
+  if (r >= nrow[req]) return;
+  const int64_t so = req * s_bs + (int64_t)(off[req] + r) * L, dof = req * d_bs + (int64_t)r * L;
+  for (int c = threadIdx.x * 8; c < L; c += 64 * 8) {
+    *(uint4*)(dh + dof + c) = *(const uint4*)(sh + so + c);
+    *(uint4*)(dl + dof + c) = *(const uint4*)(sl + so + c);
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+// Receptive-field halo of the decoder, in frames per side: samples of frames [t0, t1) depend on the
+// prenet output of frames [t0 - wave, t1 + wave) and those on tokens [.. - prenet, .. + prenet).
+// The walk goes backwards from the samples of one frame: conv_out (k7) +-3; per up block, last to
+// first, the three residual units +-3 * (1 + 3 + 9), then the ConvTranspose (k, s, p = (k - s) / 2),
+// whose output q reads inputs ceil((q + p - k + 1) / s) .. floor((q + p) / s); conv_in (k7) +-3.
+// The prenet is the embed conv7 and one depthwise conv7 per ConvNeXt block: +-3 each.
+static int codec_halo(const rwkvtts_codec_dims* d, int* prenet_halo, int* wave_halo) {
+  if (!d || d->n_up < 1 || d->n_up > 4 || d->prenet_layers < 0 || d->prenet_layers > 4096) return RWKVTTS_EINVAL;
+  int64_t hop = 1;
+  for (int i = 0; i < d->n_up; ++i) {
+    const int s = d->up_rates[i], K = d->up_kernels[i];
+    if (s < 1 || s > 4096 || K < s || K > 65536 || ((K - s) % 2) != 0) return RWKVTTS_EINVAL;
+    hop *= s;
+  }
+  auto fdiv = [](int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };  // floor, b > 0
+  int64_t lo = -3, hi = hop - 1 + 3;  // conv_out over the samples [0, hop) of frame 0
+  for (int ub = d->n_up - 1; ub >= 0; --ub) {
+    const int64_t s = d->up_rates[ub], K = d->up_kernels[ub], p = (K - s) / 2;
+    lo -= 39;
+    hi += 39;
+    lo = -fdiv(-(lo + p - K + 1), s);  // ceil
+    hi = fdiv(hi + p, s);
+  }
+  lo -= 3;
+  hi += 3;
+  *wave_halo = (int)std::max(-lo, hi);
+  *prenet_halo = 3 * (d->prenet_layers + 1);
+  return RWKVTTS_OK;
+}
+
+// The work one window needs (rwkvtts_codec_window_plan; the decode uses this same function).
+static int codec_window_plan(const rwkvtts_codec_dims* d, int t0, int t1, int n_known, int final_, int* ctx0,
+                             int* ctx1, int* wave0, int* wave1) {
+  int hp = 0, hw = 0;
+  if (codec_halo(d, &hp, &hw) != RWKVTTS_OK) return RWKVTTS_EINVAL;
+  if (t0 < 0 || t0 >= t1 || t1 > n_known) return RWKVTTS_EINVAL;
+  if (!final_ && (int64_t)t1 + hp + hw > n_known) return RWKVTTS_EINVAL;
+  // clipped at 0 and at n_known: a true end of the utterance (final), or beyond t1 + halo anyway
+  *wave0 = std::max(0, t0 - hw);
+  *wave1 = (int)std::min<int64_t>(n_known, (int64_t)t1 + hw);
+  *ctx0 = std::max(0, *wave0 - hp);
+  *ctx1 = (int)std::min<int64_t>(n_known, (int64_t)*wave1 + hp);
+  return RWKVTTS_OK;
+}
+
 struct Planes {  // activated activations as bf16 hi + lo (x = hi + lo)
   bf16_t* h = nullptr;
   bf16_t* l = nullptr;
@@ -661,6 +720,7 @@ class Codec {
   uint32_t forms = 0;    // RWKVTTS_CODEC_FORM_* of later decode calls (rwkvtts_codec_set_forms)
   int cap_n = 0, cap_T = 0;
   int *d_tok = nullptr, *d_glob = nullptr, *d_ntok = nullptr;
+  const int* ntok_dev = nullptr;  // lengths the conv launches read: d_ntok, or a windowed decode's d_win
   // prenet: x f32 residual stream [n][T][P]; zp/up/hp planes [n][T][L|P|I]
   float *xb = nullptr, *hs = nullptr, *dvec = nullptr, *cond = nullptr, *pcm = nullptr;
   Planes zp, up, hp;
@@ -669,6 +729,12 @@ class Codec {
   Planes pp[2];
   int64_t big_per_tok = 0;
   std::vector<void*> bufs;
+  // windowed decode only (allocated on its first use): the WaveGenerator's cropped input planes
+  // and, per window, its frame count and first prenet row ([2][n] ints)
+  Planes zq;
+  int64_t cap_zq = 0;
+  int* d_win = nullptr;
+  int cap_win = 0;
   // profiling (HIP events around each launch class)
   bool profiling = false;
   std::vector<std::pair<std::string, std::pair<int64_t, double>>> prof;
@@ -679,6 +745,8 @@ class Codec {
     if (wb) (void)hipFree(wb);
     if (wlb) (void)hipFree(wlb);
     if (zeros) (void)hipFree(zeros);
+    if (zq.h) (void)hipFree(zq.h);
+    if (d_win) (void)hipFree(d_win);
     if (stream) (void)hipStreamDestroy(stream);
   }
   void release() {
@@ -906,7 +974,7 @@ class Codec {
     a.xh = x.h; a.xl = x.l; a.x_bs = bs; a.Ci = Ci; a.tin_mul = tin_mul; a.w = w; a.wl = wlb ? wlb + (w - wb) : nullptr; a.K = K; a.Co = Co;
     a.mode = mode; a.dil = dil; a.pad = pad; a.s = s; a.bias = bias; a.rbias = o.rbias; a.rb_bs = o.rb_bs;
     a.gamma = o.gamma; a.res = o.res; a.act = o.act; a.y = o.y; a.yh = o.p.h; a.yl = o.p.l;
-    a.y_alpha = o.alpha; a.y_bs = o.y_bs >= 0 ? o.y_bs : bs; a.ntok = d_ntok; a.zeros = zeros;
+    a.y_alpha = o.alpha; a.y_bs = o.y_bs >= 0 ? o.y_bs : bs; a.ntok = ntok_dev; a.zeros = zeros;
     a.x_cs = x.cs; a.y_cs = o.p.cs;
     const int phases = mode == 1 ? s : 1;
     dim3 grid((unsigned)((Tmax * (int64_t)tin_mul + TM - 1) / TM), (unsigned)(phases * (Co / TN)), (unsigned)n);
@@ -967,7 +1035,7 @@ class Codec {
     a.xh = x.h; a.xl = x.l; a.x_bs = bs; a.Ci = C; a.tin_mul = tin_mul; a.w = w7; a.wl = wlb ? wlb + (w7 - wb) : nullptr; a.K = 7; a.Co = C;
     a.mode = 0; a.dil = dil; a.pad = 3 * dil; a.s = 1; a.bias = b7; a.rbias = nullptr; a.rb_bs = 0;
     a.gamma = nullptr; a.res = o.res; a.act = 0; a.y = o.y; a.yh = o.p.h; a.yl = o.p.l;
-    a.y_alpha = o.alpha; a.y_bs = o.y_bs >= 0 ? o.y_bs : bs; a.ntok = d_ntok; a.zeros = zeros;
+    a.y_alpha = o.alpha; a.y_bs = o.y_bs >= 0 ? o.y_bs : bs; a.ntok = ntok_dev; a.zeros = zeros;
     a.mid_alpha = mid_alpha; a.w1 = w1; a.bias1 = b1;
     a.x_cs = x.cs; a.y_cs = o.p.cs;
     a.xmap = 0;
@@ -1020,12 +1088,93 @@ class Codec {
     return RWKVTTS_OK;
   }
 
+  // Windowed decode: out[i] = samples [t0 * 320, t1 * 320) of the whole utterance's decode, bitwise.
+  // The prenet runs on the plan's token context, the WaveGenerator on the plan's frame range (the
+  // rows k_crop_rows takes out of the prenet's output); a cut that is no true end of the utterance
+  // gets the kernels' zero padding, which reaches no further than the halo that is dropped here.
+  // Every window is validated before anything is enqueued.
+  int decode_windows(const rwkvtts_codec_window* const* w, int n) {
+    RT_CHECK(n > 0, RWKVTTS_EINVAL, "codec decode_windows: n must be > 0");
+    int n_codes = 1;
+    for (int i = 0; i < d.fsq_dims; ++i) n_codes *= d.fsq_levels;
+    std::vector<int> c0(n), c1(n), w0(n), w1(n);
+    int Tp = 0, Tw = 0;
+    for (int i = 0; i < n; ++i) {
+      RT_CHECK(w[i]->semantic && w[i]->global && w[i]->pcm, RWKVTTS_EINVAL, "codec decode_windows: null pointer");
+      RT_CHECK(codec_window_plan(&d, w[i]->t0, w[i]->t1, w[i]->n_known, w[i]->final, &c0[i], &c1[i], &w0[i], &w1[i]) ==
+                   RWKVTTS_OK,
+               RWKVTTS_EINVAL, "codec decode_windows: need 0 <= t0 < t1 <= n_known and final or t1 + halo <= n_known");
+      RT_CHECK(0 <= c0[i] && c0[i] <= w0[i] && w0[i] <= w[i]->t0 && w[i]->t1 <= w1[i] && w1[i] <= c1[i] &&
+                   c1[i] <= w[i]->n_known,
+               RWKVTTS_EINVAL, "codec decode_windows: inconsistent plan");
+      for (int t = c0[i]; t < c1[i]; ++t)
+        RT_CHECK(w[i]->semantic[t] >= 0 && w[i]->semantic[t] < d.codebook_size, RWKVTTS_EINVAL,
+                 "codec decode_windows: semantic code out of range");
+      for (int t = 0; t < d.n_global; ++t)
+        RT_CHECK(w[i]->global[t] >= 0 && w[i]->global[t] < n_codes, RWKVTTS_EINVAL,
+                 "codec decode_windows: global code out of range");
+      Tp = std::max(Tp, c1[i] - c0[i]);
+      Tw = std::max(Tw, w1[i] - w0[i]);
+    }
+    std::vector<int> tok((size_t)n * Tp, 0), glob((size_t)n * d.n_global), ntok(n), win(2 * (size_t)n);
+    for (int i = 0; i < n; ++i) {
+      for (int t = c0[i]; t < c1[i]; ++t) tok[(size_t)i * Tp + (t - c0[i])] = (int)w[i]->semantic[t];
+      for (int t = 0; t < d.n_global; ++t) glob[(size_t)i * d.n_global + t] = (int)w[i]->global[t];
+      ntok[i] = c1[i] - c0[i];
+      win[i] = w1[i] - w0[i];      // WaveGenerator frames
+      win[n + i] = w0[i] - c0[i];  // their first row in the prenet's output
+    }
+    RT_HIP(hipSetDevice(device));
+    int rc = ensure(n, Tp);
+    if (rc) return rc;
+    const int L = d.latent_dim;
+    if ((int64_t)n * Tw * L > cap_zq) {
+      if (zq.h) (void)hipFree(zq.h);
+      zq = Planes{};
+      cap_zq = 0;
+      RT_HIP(hipMalloc((void**)&zq.h, 2 * (size_t)n * Tw * L * sizeof(bf16_t)));
+      cap_zq = (int64_t)n * Tw * L;
+    }
+    zq.l = zq.h + (int64_t)n * Tw * L;
+    if (n > cap_win) {
+      if (d_win) (void)hipFree(d_win);
+      d_win = nullptr;
+      cap_win = 0;
+      RT_HIP(hipMalloc((void**)&d_win, 2 * (size_t)n * sizeof(int)));
+      cap_win = n;
+    }
+    RT_HIP(hipMemcpyAsync(d_tok, tok.data(), tok.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+    RT_HIP(hipMemcpyAsync(d_glob, glob.data(), glob.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+    RT_HIP(hipMemcpyAsync(d_ntok, ntok.data(), n * sizeof(int), hipMemcpyHostToDevice, stream));
+    RT_HIP(hipMemcpyAsync(d_win, win.data(), 2 * (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream));
+    if ((rc = prenet(n, Tp))) return rc;
+    pbeg();
+    k_crop_rows<<<dim3(Tw, n), 64, 0, stream>>>(zp.h, zp.l, (int64_t)Tp * L, zq.h, zq.l, (int64_t)Tw * L, L, d_win,
+                                                d_win + n);
+    RT_HIP(hipGetLastError());
+    pend("codec_crop");
+    if ((rc = wavegen(n, Tw, zq, (int64_t)Tw * L, d_win))) return rc;
+    for (int i = 0; i < n; ++i)
+      RT_HIP(hipMemcpyAsync(w[i]->pcm, pcm + ((int64_t)i * Tw + (w[i]->t0 - w0[i])) * RWKVTTS_HOP,
+                            (size_t)(w[i]->t1 - w[i]->t0) * RWKVTTS_HOP * sizeof(float), hipMemcpyDeviceToHost, stream));
+    RT_HIP(hipStreamSynchronize(stream));
+    return RWKVTTS_OK;
+  }
+
   int forward(int n, int Tmax) {
+    int rc = prenet(n, Tmax);
+    if (rc) return rc;
+    return wavegen(n, Tmax, zp, (int64_t)Tmax * d.latent_dim, d_ntok);
+  }
+
+  // speaker conditioning and the prenet over d_tok / d_ntok: -> zp planes [n][Tmax][latent_dim]
+  int prenet(int n, int Tmax) {
     const int L = d.latent_dim, P = d.prenet_dim, I = d.prenet_inter, S = d.spk_dim, G = d.n_global;
     const int Q = RWKVTTS_CODEC_SPK_LATENT;
     const int64_t tL = (int64_t)Tmax * L, tP = (int64_t)Tmax * P, tI = (int64_t)Tmax * I;
     const int64_t cstr = 2 * (int64_t)(d.prenet_layers + 1) * P;  // cond stride per utterance
     int rc;
+    ntok_dev = d_ntok;
     // speaker d-vector and every AdaLN scale/shift (cond[req][2 * (layer + 1) + {0, 1}][P])
     pbeg();
     k_fsq<<<n, 256, 0, stream>>>(d_glob, G, d.fsq_levels, d.fsq_dims, F(0, 0, CD_FSQ_W), F(0, 0, CD_FSQ_B), Q, hs);
@@ -1105,6 +1254,15 @@ class Codec {
       if ((rc = conv(n, Tmax, "codec_prenet_gemm", up, tP, P, 1, B(0, 0, CD_LIN_W), 1, L, 0, 1, 0, 1,
                      F(0, 0, CD_LIN_B), o))) return rc;
     }
+    return RWKVTTS_OK;
+  }
+
+  // WaveGenerator over the latent planes z ([n][..][latent_dim], per-utterance stride z_bs, lens[i]
+  // frames each, at most Tmax): -> pcm [n][Tmax * 320]
+  int wavegen(int n, int Tmax, Planes z, int64_t z_bs, const int* lens) {
+    const int L = d.latent_dim;
+    int rc;
+    ntok_dev = lens;
     // WaveGenerator: conv_in -> [snake -> convT -> 3 x residual unit] x n_up -> snake -> conv_out
     // Its planes are channel-blocked ([C / 32][Tmax * mul][32] per utterance) unless
     // RWKVTTS_CODEC_FORM_CHANNEL_LAST (the arithmetic is the same either way)
@@ -1122,7 +1280,7 @@ class Codec {
       o.alpha = F(2, 0, CU_SNAKE);
       // conv_in reads the prenet planes with the prenet's per-utterance stride
       o.y_bs = bs;
-      if ((rc = conv(n, Tmax, "codec_conv_in", zp, tL, L, 1, B(0, 0, CD_CIN_W), 7, C, 0, 1, 3, 1,
+      if ((rc = conv(n, Tmax, "codec_conv_in", z, z_bs, L, 1, B(0, 0, CD_CIN_W), 7, C, 0, 1, 3, 1,
                      F(0, 0, CD_CIN_B), o))) return rc;
     }
     static const int dils[3] = {1, 3, 9};
@@ -1177,7 +1335,7 @@ class Codec {
     pbeg();
     const size_t shm = (size_t)(kOutT + 6) * (C + 1) * sizeof(float);
     k_conv_out<<<dim3((unsigned)((Tmax * (int64_t)mul + kOutT - 1) / kOutT), n), kOutT, shm, stream>>>(
-        pp[cur].h, pp[cur].l, bs, PB(cur, mul).cs, C, mul, d_ntok, F(0, 0, CD_COUT_W), F(0, 0, CD_COUT_B), pcm,
+        pp[cur].h, pp[cur].l, bs, PB(cur, mul).cs, C, mul, ntok_dev, F(0, 0, CD_COUT_W), F(0, 0, CD_COUT_B), pcm,
         (int64_t)Tmax * RWKVTTS_HOP);
     RT_HIP(hipGetLastError());
     pend("codec_conv_out");
@@ -1327,6 +1485,48 @@ int rwkvtts_codec_decode_batch(rwkvtts_codec* c, const int64_t* const* semantic,
   RT_CHECK(c && semantic && T && global && pcm && n > 0, RWKVTTS_EINVAL, "codec_decode_batch: bad arguments");
   try {
     return c->c.decode(semantic, T, global, n, pcm);
+  } catch (const std::exception& ex) {
+    set_error(ex.what());
+    return RWKVTTS_ENOMEM;
+  }
+}
+
+int rwkvtts_codec_halo(const rwkvtts_codec_dims* d, int32_t* prenet_halo, int32_t* wave_halo) {
+  RT_CHECK(d && prenet_halo && wave_halo, RWKVTTS_EINVAL, "codec_halo: null argument");
+  int hp = 0, hw = 0;
+  RT_CHECK(codec_halo(d, &hp, &hw) == RWKVTTS_OK, RWKVTTS_EINVAL, "codec_halo: unsupported dims");
+  *prenet_halo = hp;
+  *wave_halo = hw;
+  return RWKVTTS_OK;
+}
+
+int rwkvtts_codec_window_plan(const rwkvtts_codec_dims* d, int32_t t0, int32_t t1, int32_t n_known, int32_t final_,
+                              rwkvtts_codec_plan* out) {
+  RT_CHECK(d && out && out->struct_size >= sizeof(rwkvtts_codec_plan), RWKVTTS_EINVAL,
+           "codec_window_plan: null argument or struct_size too small");
+  int c0, c1, w0, w1;
+  RT_CHECK(codec_window_plan(d, t0, t1, n_known, final_ != 0, &c0, &c1, &w0, &w1) == RWKVTTS_OK, RWKVTTS_EINVAL,
+           "codec_window_plan: need 0 <= t0 < t1 <= n_known and final or t1 + halo <= n_known");
+  out->ctx0 = c0;
+  out->ctx1 = c1;
+  out->wave0 = w0;
+  out->wave1 = w1;
+  return RWKVTTS_OK;
+}
+
+int rwkvtts_codec_decode_windows(rwkvtts_codec* c, const rwkvtts_codec_window* w, int n) {
+  RT_CHECK(c && w && n > 0, RWKVTTS_EINVAL, "codec_decode_windows: bad arguments");
+  // the array's stride is the caller's struct_size (a later, longer struct still reads here)
+  const size_t stride = w->struct_size;
+  RT_CHECK(stride >= sizeof(rwkvtts_codec_window) && stride % alignof(rwkvtts_codec_window) == 0, RWKVTTS_EINVAL,
+           "codec_decode_windows: struct_size too small");
+  try {
+    std::vector<const rwkvtts_codec_window*> ws(n);
+    for (int i = 0; i < n; ++i) {
+      ws[i] = (const rwkvtts_codec_window*)((const uint8_t*)w + i * stride);
+      RT_CHECK(ws[i]->struct_size == stride, RWKVTTS_EINVAL, "codec_decode_windows: struct_size differs between windows");
+    }
+    return c->c.decode_windows(ws.data(), n);
   } catch (const std::exception& ex) {
     set_error(ex.what());
     return RWKVTTS_ENOMEM;

@@ -57,7 +57,7 @@ constexpr int kLookahead = 8;  // decode steps queued per host poll of the contr
 struct Job {
   rwkvtts_request req{};
   rwkvtts_result* res = nullptr;
-  void* user = nullptr;
+  void* user = nullptr;  // const rwkvtts_token_sink*: the request's token progress (null: none)
 };
 
 class Engine;
@@ -98,7 +98,8 @@ class Engine {
             int32_t* has_logits);
   int sample(const float* logits, int n_rows, int row_len, const rwkvtts_sample_args* args,
              rwkvtts_rng* const* rngs, int32_t* out, float* dbg_host = nullptr);
-  int generate(const rwkvtts_request* reqs, int n, rwkvtts_result* res);
+  // sinks: one per request (null: none), called on this thread between units of work
+  int generate(const rwkvtts_request* reqs, int n, rwkvtts_result* res, const rwkvtts_token_sink* sinks = nullptr);
   // Test hook (rwkvtts_debug_advance): k_advance itself -- advance_prep + the prepped
   // sample_block, the certified fast path or the exact walk -- on caller-given logit rows and
   // per-row controller states, for n_steps consecutive launches on the same rows.
@@ -259,6 +260,9 @@ class Engine {
   SlotCtrl* d_ctrl_ = nullptr;
   int32_t* d_sem_ = nullptr;
   SlotCtrl* h_ctrl_ = nullptr;  // pinned mirror
+  // token progress: pinned [2 unit buffers][S][RWKVTTS_SEMANTIC_LIMIT], token i of a slot at index i;
+  // allocated when the first request with a sink is admitted (engines that never see one: no change)
+  int32_t* h_prog_ = nullptr;
   // sampler API scratch
   float* d_samp_logits_ = nullptr;
   size_t samp_cap_ = 0;     // logits elements

@@ -106,6 +106,7 @@ Engine::~Engine() {
   for (void* p : {(void*)d_samp_logits_, (void*)d_keys_, (void*)d_draws_, (void*)d_out_, d_wide_})
     if (p) hipFree(p);
   if (h_ctrl_) hipHostFree(h_ctrl_);
+  if (h_prog_) hipHostFree(h_prog_);
   if (h_gt_) hipHostFree(h_gt_);
   if (stream_) hipStreamDestroy(stream_);
 }
@@ -1232,27 +1233,52 @@ struct Active {
   int advances = 0;  // phase-controller invocations so far
   int total = 0;     // advances after which the request is certainly done (its step limit)
   bool zero_shot = false;
+  // token progress (Job::user): semantic tokens handed to the sink so far, and per unit buffer the
+  // end of the range of this slot's d_sem_ that the unit copied to h_prog_
+  const rwkvtts_token_sink* sink = nullptr;
+  int delivered = 0;
+  int copied_hi[2] = {0, 0};
 };
 
 namespace {
 
+const rwkvtts_token_sink* sink_of(const Job* j) {
+  const rwkvtts_token_sink* s = (const rwkvtts_token_sink*)j->user;
+  return s && s->fn ? s : nullptr;
+}
+// the last call of a request that failed (j->res->status < 0): no tokens, done
+void sink_fail(const Job* j, int first) {
+  if (const rwkvtts_token_sink* s = sink_of(j)) s->fn(s->user, nullptr, 0, nullptr, first, 0, 1, j->res->status);
+}
+
 // generate_batch: a fixed list of requests
 class ListSource : public JobSource {
  public:
-  ListSource(const rwkvtts_request* reqs, int n, rwkvtts_result* res) : jobs_(n) {
+  ListSource(const rwkvtts_request* reqs, int n, rwkvtts_result* res, const rwkvtts_token_sink* sinks)
+      : jobs_(n), finished_(n, 0) {
     for (int i = 0; i < n; ++i) {
       jobs_[i].req = reqs[i];
       jobs_[i].res = &res[i];
+      jobs_[i].user = sinks && sinks[i].fn ? (void*)&sinks[i] : nullptr;
     }
   }
   bool next(int max, bool, std::vector<Job*>& out) override {
     while (max-- > 0 && pos_ < jobs_.size()) out.push_back(&jobs_[pos_++]);
     return pos_ < jobs_.size();
   }
-  void finish(Job*) override {}
+  void finish(Job* j) override { finished_[j - jobs_.data()] = 1; }
+  // the engine failed: every request serve() never finished ends its stream with that status
+  void fail_rest(int rc) {
+    for (size_t i = 0; i < jobs_.size(); ++i)
+      if (!finished_[i]) {
+        jobs_[i].res->status = rc;
+        sink_fail(&jobs_[i], 0);
+      }
+  }
 
  private:
   std::vector<Job> jobs_;
+  std::vector<char> finished_;
   size_t pos_ = 0;
 };
 }  // namespace
@@ -1298,11 +1324,13 @@ static int sem_limit_of(const rwkvtts_request& q) {
   return std::min(std::max(q.max_tokens, 0), RWKVTTS_SEMANTIC_LIMIT);  // normal_mode_inference.rs:316
 }
 
-int Engine::generate(const rwkvtts_request* reqs, int n, rwkvtts_result* res) {
+int Engine::generate(const rwkvtts_request* reqs, int n, rwkvtts_result* res, const rwkvtts_token_sink* sinks) {
   stats = rwkvtts_stats{};
   max_active = 0;
-  ListSource src(reqs, n, res);
-  return serve(src);
+  ListSource src(reqs, n, res, sinks);
+  const int rc = serve(src);
+  if (rc != RWKVTTS_OK && sinks) src.fail_rest(rc);
+  return rc;
 }
 
 // Waits for a unit's end event (polling: a blocking wait adds its wake-up latency to the GPU's
@@ -1372,6 +1400,24 @@ int Engine::finish_unit(int b, bool prefill, std::vector<Active>& act, std::vect
     }
   }
   if (copied) RT_HIP(hipStreamSynchronize(stream_));
+  // token progress (after the fault check: a faulted unit's tokens are never delivered): the new
+  // semantic ids of each sink-carrying slot came with this unit's snapshot (serve: the copy to
+  // h_prog_ sits before the unit's end event), so nothing is waited for here
+  // (the synchronisation above is the retiring slots', as before)
+  for (auto& a : act) {
+    if (!a.sink || a.prefilled < (int)a.prompt.size()) continue;
+    const SlotCtrl& c = snap[a.slot];
+    const bool done = c.phase == kPhDone;
+    const int n = std::min(c.n_sem, a.copied_hi[b]);
+    RT_CHECK(!done || n == c.n_sem, RWKVTTS_EHIP, "token progress: a finished slot holds tokens its unit did not copy");
+    if (n <= a.delivered && !done) continue;
+    const int first = a.delivered, count = std::max(n - first, 0);
+    a.delivered = first + count;
+    const rwkvtts_token_sink* sk = a.sink;
+    if (done) a.sink = nullptr;  // the stream has ended: no later failure reports it again
+    sk->fn(sk->user, c.global_out, c.n_global, h_prog_ + ((size_t)b * S_ + a.slot) * RWKVTTS_SEMANTIC_LIMIT + first,
+           first, count, done ? 1 : 0, 0);
+  }
   src.progress(*this);
   for (size_t i = 0; i < act.size();) {
     Active& a = act[i];
@@ -1426,9 +1472,13 @@ int Engine::serve(JobSource& src) {
     if (!validate(q, why)) {  // dynamic_batch_manager.rs:466-469: this request fails alone
       r.status = RWKVTTS_EINVAL;
       set_error("request rejected: " + why);
+      sink_fail(j, 0);
       src.finish(j);
       return RWKVTTS_OK;
     }
+    if (sink_of(j) && !h_prog_)
+      RT_HIP(hipHostMalloc((void**)&h_prog_, sizeof(int32_t) * 2 * (size_t)S_ * RWKVTTS_SEMANTIC_LIMIT,
+                           hipHostMallocDefault));
     // test hook: RWKVTTS_TEST_FAIL_ADMIT=k fails this engine's k-th admission as a HIP error would
     if (const char* fa = getenv("RWKVTTS_TEST_FAIL_ADMIT")) {
       if (++admissions_ == atoi(fa)) {
@@ -1441,6 +1491,7 @@ int Engine::serve(JobSource& src) {
     Active a;
     a.job = j;
     a.slot = slot;
+    a.sink = sink_of(j);
     a.zero_shot = q.ref_global != nullptr && q.ref_semantic != nullptr;
     for (int i = 0; i < q.n_property; ++i) a.prompt.push_back((uint32_t)q.property_tokens[i]);
     a.prompt.push_back(RWKVTTS_TAG_2);
@@ -1511,6 +1562,7 @@ int Engine::serve(JobSource& src) {
           if (std::any_of(act.begin(), act.end(), [&](const Active& a) { return a.job == j; })) continue;
           j->res->status = rc;
           j->res->n_global = j->res->n_semantic = 0;
+          sink_fail(j, 0);
           src.finish(j);
         }
         break;
@@ -1605,6 +1657,19 @@ int Engine::serve(JobSource& src) {
       stats.decode_rows += (int64_t)dp.rows.size() * K;
       max_active = std::max<int64_t>(max_active, (int64_t)dp.rows.size());
     }
+    // token progress: the semantic ids this unit may have added to each sink-carrying slot, copied
+    // beside the snapshot (a slot holds at most one id per advance, and the host knows the ids it
+    // has handed out: [delivered, min(sem_limit, advances)) covers whatever the snapshot will show).
+    // Slots without a sink add nothing, so a run without sinks enqueues what it always did.
+    for (auto& a : act) {
+      if (!a.sink) continue;
+      const int lo = a.delivered, hi = std::min(ctrl_stage_[a.slot].sem_limit, a.advances);
+      a.copied_hi[b] = hi;
+      if (hi <= lo) continue;
+      const size_t so = (size_t)a.slot * RWKVTTS_SEMANTIC_LIMIT + lo;
+      RT_HIP(hipMemcpyAsync(h_prog_ + (size_t)b * S_ * RWKVTTS_SEMANTIC_LIMIT + so, d_sem_ + so, sizeof(int32_t) * (hi - lo),
+                            hipMemcpyDeviceToHost, stream_));
+    }
     RT_HIP(hipMemcpyAsync(h_ctrl_ + (size_t)b * (S_ + 1), d_ctrl_, sizeof(SlotCtrl) * (S_ + 1), hipMemcpyDeviceToHost, stream_));
     unit_graph_[b] = {-1, -1};
     if (graph_timing() && !any_prefill && last_graph_.first >= 0) {  // the window's last step's stamps
@@ -1664,6 +1729,7 @@ int Engine::serve(JobSource& src) {
     for (auto& a : act) {
       a.job->res->status = rc;
       a.job->res->n_global = a.job->res->n_semantic = 0;
+      if (a.sink) sink_fail(a.job, a.delivered);  // the stream ends: done = 1, the engine's status
       src.finish(a.job);
     }
     return rc;

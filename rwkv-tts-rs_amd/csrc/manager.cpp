@@ -14,6 +14,12 @@
 // has one owner thread running Engine::serve, which admits queued requests into free state slots
 // between forward steps (continuous batching). One engine per GPU = request-level data
 // parallelism over the node; no collective is needed on this path.
+//
+// Streaming (no reference counterpart): submit_stream hands the engine a token sink through
+// Job::user; the engine's owner thread publishes each unit's new tokens into the job under the
+// ticket lock, and wait_tokens callers poll them (no thread of the library ever calls back into the
+// caller). Completion publishes whatever is missing, so a stream ends with every token of the
+// result whatever the engine delivered on the way.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -75,14 +81,24 @@ const Rccl& rccl() {
   return r;
 }
 
+class Manager;
+
 struct MJob : Job {
   uint64_t ticket = 0;
   std::vector<int32_t> text, props, ref_g, ref_s;  // owned copies of the request arrays
   std::vector<int32_t> sem;                        // semantic token buffer
   rwkvtts_result out{};
   bool done = false;
-  bool claimed = false;  // a wait() is in progress on this ticket (a second waiter is refused)
+  bool claimed = false;  // a wait() / wait_tokens() is in progress on this ticket (a second waiter is refused)
   int engine = -1;
+  // token progress, under the manager's ticket lock: what wait_tokens hands out. The engine's owner
+  // thread publishes into it through `sink` (Job::user, submit_stream) after a unit of work;
+  // completion publishes whatever is still missing (engines that send no progress, plain submit).
+  rwkvtts_token_sink sink{};
+  Manager* mgr = nullptr;
+  std::vector<int32_t> prog;  // semantic ids [0, prog_sem)
+  int prog_sem = 0, prog_nglobal = 0;
+  int32_t prog_global[RWKVTTS_N_GLOBAL] = {0};
 };
 
 class Manager;
@@ -321,8 +337,40 @@ class Manager {
     jobs_.clear();
   }
 
-  int submit(const rwkvtts_request& q, uint64_t* ticket) {
+  // the engine's owner thread, between units of work: tokens [first, first + count) of a streamed job
+  static void on_tokens(void* user, const int32_t* global_tokens, int32_t n_global, const int32_t* semantic,
+                        int32_t first, int32_t count, int32_t /*done*/, int32_t /*status*/) {
+    MJob* j = (MJob*)user;  // (done and status are published by complete(), which follows the last call)
+    j->mgr->publish(j, global_tokens, n_global, semantic, first, count);
+  }
+  void publish(MJob* j, const int32_t* global_tokens, int n_global, const int32_t* semantic, int first, int count) {
+    {
+      std::lock_guard<std::mutex> lk(t_mu_);
+      publish_locked(j, global_tokens, n_global, semantic, first, count);
+    }
+    t_cv_.notify_all();
+  }
+  void publish_locked(MJob* j, const int32_t* global_tokens, int n_global, const int32_t* semantic, int first,
+                      int count) {
+    if (global_tokens && n_global > 0) {
+      j->prog_nglobal = std::min(n_global, RWKVTTS_N_GLOBAL);
+      memcpy(j->prog_global, global_tokens, sizeof(int32_t) * j->prog_nglobal);
+    }
+    // in order, each token once: a range that does not continue the published prefix is ignored
+    if (!semantic || count <= 0 || first != j->prog_sem || first + count > RWKVTTS_SEMANTIC_LIMIT) return;
+    if (j->prog.empty()) j->prog.assign(RWKVTTS_SEMANTIC_LIMIT, 0);
+    memcpy(j->prog.data() + first, semantic, sizeof(int32_t) * count);
+    j->prog_sem = first + count;
+  }
+
+  int submit(const rwkvtts_request& q, uint64_t* ticket, bool stream = false) {
     MJob* j = new MJob();
+    j->mgr = this;
+    if (stream) {
+      j->sink.fn = &Manager::on_tokens;
+      j->sink.user = j;
+      j->user = &j->sink;
+    }
     auto copy = [](const int32_t* p, int n, std::vector<int32_t>& v) {
       if (p && n > 0) v.assign(p, p + n);
     };
@@ -393,9 +441,56 @@ class Manager {
     return rc;
   }
 
+  // a finished job's result into its progress: the tokens not published yet, the global tokens
+  void publish_rest_locked(MJob* j) {
+    if (j->out.status != 0) return;  // a failed request: what was published stands, nothing is added
+    const int have = j->prog_sem;
+    publish_locked(j, j->out.global_tokens, j->out.n_global, j->out.n_semantic > have ? j->sem.data() + have : nullptr,
+                   have, j->out.n_semantic - have);
+  }
+
+  int wait_tokens(uint64_t ticket, int have_semantic, int timeout_ms, int32_t* global32, int32_t* n_global,
+                  int32_t* semantic_out, int32_t* n_semantic, int32_t* done, int32_t* status) {
+    std::unique_lock<std::mutex> lk(t_mu_);
+    RT_CHECK(!t_closed_, RWKVTTS_ECLOSED, "manager_wait_tokens: manager is shutting down");
+    auto it = jobs_.find(ticket);
+    RT_CHECK(it != jobs_.end(), RWKVTTS_EINVAL, "manager_wait_tokens: unknown ticket");
+    MJob* j = it->second;
+    RT_CHECK(!j->claimed, RWKVTTS_EINVAL, "manager_wait_tokens: another thread is already waiting on this ticket");
+    j->claimed = true;  // wait() cannot release the job under us
+    ++waiters_;
+    auto ready = [&] { return j->prog_sem > have_semantic || j->done || t_closed_; };
+    bool got = true;
+    if (timeout_ms < 0)
+      t_cv_.wait(lk, ready);
+    else
+      got = t_cv_.wait_for(lk, std::chrono::milliseconds(timeout_ms), ready);
+    int rc = RWKVTTS_OK;
+    if (!got) {
+      rc = RWKVTTS_EBUSY;
+    } else if (!j->done && j->prog_sem <= have_semantic) {  // shutdown woke us before anything new
+      rc = RWKVTTS_ECLOSED;
+      set_error("manager_wait_tokens: manager shut down");
+    }
+    if (j->done) publish_rest_locked(j);
+    if (global32 && j->prog_nglobal > 0) memcpy(global32, j->prog_global, sizeof(int32_t) * j->prog_nglobal);
+    if (n_global) *n_global = j->prog_nglobal;
+    if (semantic_out && j->prog_sem > 0) memcpy(semantic_out, j->prog.data(), sizeof(int32_t) * j->prog_sem);
+    if (n_semantic) *n_semantic = j->prog_sem;
+    if (done) *done = j->done ? 1 : 0;
+    if (status) *status = j->done ? j->out.status : 0;
+    j->claimed = false;  // the ticket stays: wait() releases it
+    if (--waiters_ == 0 && t_closed_) t_cv_.notify_all();  // shutdown waits for the last waiter
+    return rc;
+  }
+
   void complete(MJob* j, int engine) {
     {
       std::lock_guard<std::mutex> lk(t_mu_);
+      // whatever progress was not published yet (all of it on an engine that sends none): a
+      // stream always terminates with every token of the result
+      // (a plain submit's ticket gets the same in wait_tokens, if anyone polls it)
+      if (j->user) publish_rest_locked(j);
       j->done = true;
       j->engine = engine;
       completed_++;
@@ -623,6 +718,29 @@ int rwkvtts_manager_submit(rwkvtts_manager* m, const rwkvtts_request* req, uint6
 int rwkvtts_manager_wait(rwkvtts_manager* m, uint64_t ticket, int timeout_ms, rwkvtts_result* out) {
   RT_CHECK(m && out, RWKVTTS_EINVAL, "manager_wait: null argument");
   return m->m.wait(ticket, timeout_ms, out);
+}
+
+int rwkvtts_manager_submit_stream(rwkvtts_manager* m, const rwkvtts_request* req, uint64_t* ticket) {
+  RT_CHECK(m && req && ticket, RWKVTTS_EINVAL, "manager_submit_stream: null argument");
+  try {
+    return m->m.submit(*req, ticket, true);
+  } catch (const std::exception& ex) {
+    set_error(ex.what());
+    return RWKVTTS_ENOMEM;
+  }
+}
+
+int rwkvtts_manager_wait_tokens(rwkvtts_manager* m, uint64_t ticket, int32_t have_semantic, int timeout_ms,
+                                int32_t* global32, int32_t* n_global, int32_t* semantic_out, int32_t* n_semantic,
+                                int32_t* done, int32_t* status) {
+  RT_CHECK(m, RWKVTTS_EINVAL, "manager_wait_tokens: null argument");
+  try {
+    return m->m.wait_tokens(ticket, have_semantic, timeout_ms, global32, n_global, semantic_out, n_semantic, done,
+                            status);
+  } catch (const std::exception& ex) {
+    set_error(ex.what());
+    return RWKVTTS_ENOMEM;
+  }
 }
 
 int rwkvtts_manager_generate_batch(rwkvtts_manager* m, const rwkvtts_request* reqs, int n,

@@ -8,3 +8,7 @@ from .runtime import (DynamicBatchConfig, DynamicBatchManager, LayeredRandomness
                       RnnInputBatch, RnnOption, SamplerArgs, SharedRwkvRuntime, StdRng, TtsBatchRequest,
                       sample_logits_with_top_p_k)
 from . import weights  # noqa: F401
+# streaming (audio during decode): BiCodecDetokenizer.halo / decode_windows, SharedRwkvRuntime.generate_batch(on_tokens=),
+# DynamicBatchManager.stream_tts, LightweightTtsPipeline.stream_speech, server.handle_tts_stream
+from .codec import BiCodecDetokenizer, codec_halo, window_plan  # noqa: F401
+from .pipeline import LightweightTtsPipeline, LightweightTtsPipelineArgs, SpeechChunk  # noqa: F401

@@ -131,6 +131,27 @@ class CodecDims(ctypes.Structure):
         ("up_rates", ctypes.c_int32 * 4), ("up_kernels", ctypes.c_int32 * 4)]
 
 
+# rwkvtts_token_fn(user, global_tokens, n_global, semantic, first, count, done, status)
+TokenFn = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+                           ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                           ctypes.c_int32)
+
+
+class TokenSink(ctypes.Structure):
+    _fields_ = [("fn", TokenFn), ("user", ctypes.c_void_p)]
+
+
+class CodecPlan(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("ctx0", ctypes.c_int32), ("ctx1", ctypes.c_int32),
+                ("wave0", ctypes.c_int32), ("wave1", ctypes.c_int32)]
+
+
+class CodecWindow(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_known", ctypes.c_int32), ("final", ctypes.c_int32),
+                ("t0", ctypes.c_int32), ("t1", ctypes.c_int32), ("semantic", ctypes.c_void_p),
+                ("global_", ctypes.c_void_p), ("pcm", ctypes.c_void_p)]
+
+
 # Every symbol include/rwkvtts.h declares (checked by tests/test_abi.py against the header).
 EXPORTS = {
     "rwkvtts_synth_weights": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p]),
@@ -150,6 +171,15 @@ EXPORTS = {
                                       ctypes.POINTER(SampleArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "rwkvtts_generate_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Request), ctypes.c_int,
                                               ctypes.POINTER(Result)]),
+    # streaming: token progress
+    "rwkvtts_generate_batch_stream": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Request), ctypes.c_int,
+                                                     ctypes.POINTER(Result), ctypes.POINTER(TokenSink)]),
+    "rwkvtts_manager_submit_stream": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Request),
+                                                     ctypes.POINTER(ctypes.c_uint64)]),
+    "rwkvtts_manager_wait_tokens": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int,
+                                                   ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p,
+                                                   ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                                   ctypes.POINTER(ctypes.c_int32)]),
     "rwkvtts_manager_create": (ctypes.c_int, [ctypes.POINTER(ManagerDesc), ctypes.c_void_p, ctypes.c_size_t,
                                               ctypes.POINTER(ctypes.c_void_p)]),
     "rwkvtts_manager_destroy": (ctypes.c_int, [ctypes.c_void_p]),
@@ -179,6 +209,12 @@ EXPORTS = {
                                             ctypes.c_void_p]),
     "rwkvtts_codec_decode_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    # streaming: exact windowed decode
+    "rwkvtts_codec_halo": (ctypes.c_int, [ctypes.POINTER(CodecDims), ctypes.POINTER(ctypes.c_int32),
+                                          ctypes.POINTER(ctypes.c_int32)]),
+    "rwkvtts_codec_window_plan": (ctypes.c_int, [ctypes.POINTER(CodecDims), ctypes.c_int32, ctypes.c_int32,
+                                                 ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(CodecPlan)]),
+    "rwkvtts_codec_decode_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CodecWindow), ctypes.c_int]),
     "rwkvtts_codec_set_profiling": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "rwkvtts_codec_profile_count": (ctypes.c_int, [ctypes.c_void_p]),
     "rwkvtts_codec_profile_entry": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,

@@ -7,6 +7,7 @@ The batch call returns an empty array for an utterance that fails, as the refere
 spawn_blocking tasks do (:650-690); the single call raises.
 """
 import ctypes
+import threading
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -57,6 +58,24 @@ def synth_codec_blob_f32(d: dict, seed: int = 20251205, rel: float = 2.0 ** -12)
     return w
 
 
+def codec_halo(d: dict) -> tuple:
+    """(prenet_halo, wave_halo) frames per side of an exact decode window (rwkvtts_codec_halo; host only)."""
+    hp, hw = ctypes.c_int32(), ctypes.c_int32()
+    check(lib().rwkvtts_codec_halo(ctypes.byref(make_codec_dims(d)), ctypes.byref(hp), ctypes.byref(hw)),
+          "codec_halo")
+    return hp.value, hw.value
+
+
+def window_plan(d: dict, t0: int, t1: int, n_known: int, final: bool) -> dict:
+    """The work decode_windows does for frames [t0, t1): tokens ctx = (c0, c1) through the prenet,
+    frames wave = (w0, w1) through the WaveGenerator (rwkvtts_codec_window_plan; host only).
+    Raises RwkvTtsError(EINVAL) unless 0 <= t0 < t1 <= n_known and (final or t1 + halo <= n_known)."""
+    p = _ffi.CodecPlan(struct_size=ctypes.sizeof(_ffi.CodecPlan))
+    check(lib().rwkvtts_codec_window_plan(ctypes.byref(make_codec_dims(d)), t0, t1, n_known, 1 if final else 0,
+                                          ctypes.byref(p)), "codec_window_plan")
+    return {"ctx": (p.ctx0, p.ctx1), "wave": (p.wave0, p.wave1)}
+
+
 class BiCodecDetokenizer:
     """One decoder per GPU (replaces the 4-session ORT pool of src/onnx_session_pool.rs:204-279)."""
 
@@ -71,6 +90,9 @@ class BiCodecDetokenizer:
         check(lib().rwkvtts_codec_create_ex(device, ctypes.byref(self._cd), w.ctypes.data_as(ctypes.c_void_p),
                                             int(weight_path), ctypes.byref(h)), "codec_create")
         self._h = h
+        # one decode at a time: the decoder owns one stream and one set of activation buffers, and
+        # streaming callers (the server's worker threads) decode many small windows concurrently
+        self._lock = threading.Lock()
 
     def set_forms(self, forms: int):
         """Verification forms of later decode calls (_ffi.CODEC_FORM_*; 0 = shipping, PCM bitwise equal)."""
@@ -93,9 +115,10 @@ class BiCodecDetokenizer:
         if g.size != self.dims["n_global"] or s.size == 0:
             raise ValueError(f"decode_audio: need {self.dims['n_global']} global and >0 semantic tokens")
         pcm = np.empty(s.size * _ffi.HOP, dtype=np.float32)
-        check(lib().rwkvtts_codec_decode(self._h, s.ctypes.data_as(ctypes.c_void_p), int(s.size),
-                                         g.ctypes.data_as(ctypes.c_void_p), pcm.ctypes.data_as(ctypes.c_void_p)),
-              "codec_decode")
+        with self._lock:
+            rc = lib().rwkvtts_codec_decode(self._h, s.ctypes.data_as(ctypes.c_void_p), int(s.size),
+                                            g.ctypes.data_as(ctypes.c_void_p), pcm.ctypes.data_as(ctypes.c_void_p))
+            check(rc, "codec_decode")
         return pcm
 
     def decode_audio_batch(self, batch: Sequence[tuple]) -> List[np.ndarray]:
@@ -117,11 +140,44 @@ class BiCodecDetokenizer:
             glob = P(*[g.ctypes.data for g in gs])
             pcm = P(*[o.ctypes.data for o in outs])
             T = (ctypes.c_int * n)(*[s.size for s in ss])
-            rc = lib().rwkvtts_codec_decode_batch(self._h, sem, T, glob, n, pcm)
+            with self._lock:
+                rc = lib().rwkvtts_codec_decode_batch(self._h, sem, T, glob, n, pcm)
             if rc != 0:
                 outs = [np.empty(0, dtype=np.float32) for _ in ss]
         it = iter(outs)
         return [next(it) if v else np.empty(0, dtype=np.float32) for v in ok]
+
+    # ---- streaming: exact windowed decode ----
+    def halo(self) -> int:
+        """Frames of look-ahead (and look-back) an exact window needs: 49 at the full dims."""
+        return sum(codec_halo(self.dims))
+
+    def decode_windows(self, items: Sequence[tuple]) -> List[np.ndarray]:
+        """[(global_tokens, semantic_tokens_known_so_far, t0, t1, final)] -> [pcm of frames [t0, t1)],
+        all windows in one batched pass (they may be ragged and of different utterances). Each pcm
+        is bitwise samples [t0 * 320, t1 * 320) of decode_audio over the finished utterance; a
+        window needs `final` (the tokens given are the whole utterance) or t1 + halo() tokens.
+        Raises on a window that breaks that (nothing is decoded then)."""
+        n = len(items)
+        if n == 0:
+            return []
+        ws = (_ffi.CodecWindow * n)()
+        keep, outs = [], []
+        for w, (g, s, t0, t1, final) in zip(ws, items):
+            g = np.ascontiguousarray(g, dtype=np.int64)
+            s = np.ascontiguousarray(s, dtype=np.int64)
+            if g.size != self.dims["n_global"] or not 0 <= t0 < t1 <= s.size:
+                raise ValueError(f"decode_windows: need {self.dims['n_global']} global tokens and "
+                                 f"0 <= t0 < t1 <= len(semantic), got {g.size}, [{t0}, {t1}) of {s.size}")
+            out = np.empty((t1 - t0) * _ffi.HOP, dtype=np.float32)
+            keep.append((g, s))
+            outs.append(out)
+            w.struct_size = ctypes.sizeof(_ffi.CodecWindow)
+            w.n_known, w.final, w.t0, w.t1 = int(s.size), 1 if final else 0, int(t0), int(t1)
+            w.semantic, w.global_, w.pcm = s.ctypes.data, g.ctypes.data, out.ctypes.data
+        with self._lock:
+            check(lib().rwkvtts_codec_decode_windows(self._h, ws, n), "codec_decode_windows")
+        return outs
 
     # ---- profiling (per-stage HIP-event timing) ----
     def set_profiling(self, on: bool):

@@ -46,6 +46,20 @@ class LightweightTtsPipelineArgs:  # :18-65 (Default)
     voice_semantic_tokens: Optional[List[int]] = None
 
 
+class SpeechChunk(np.ndarray):
+    """One item of stream_speech: float32 PCM of frames [t0, t1) (an ndarray, so b"".join(chunks) and
+    np.concatenate work on it), decoded when n_known semantic tokens were known; done: the request had
+    finished by then."""
+    t0 = t1 = n_known = 0
+    done = False
+
+    @classmethod
+    def make(cls, pcm, t0, t1, n_known, done):
+        c = np.ascontiguousarray(pcm, dtype=np.float32).view(cls)
+        c.t0, c.t1, c.n_known, c.done = int(t0), int(t1), int(n_known), bool(done)
+        return c
+
+
 class LightweightTtsPipeline:
     """manager: rwkvtts.DynamicBatchManager (with a tokenizer); codec: BiCodecDetokenizer."""
 
@@ -121,6 +135,65 @@ class LightweightTtsPipeline:
         if not g and not s:
             return np.zeros(SAMPLE_RATE, dtype=np.float32)  # :828-830
         return self.codec.decode_audio(g, s)
+
+    def stream_speech(self, args: LightweightTtsPipelineArgs, chunk_frames: int = 16):
+        """generate_speech as a generator of float32 PCM chunks (SpeechChunk: an ndarray that also
+        carries t0, t1, n_known, done), each decoded while the request is still generating tokens.
+
+        Chunk [t0, t1) (frames of 320 samples; chunk_frames each, the last one shorter) is decoded by
+        the exact windowed vocoder as soon as t1 + H semantic tokens are known, or the request is
+        done; chunks that become ready together go through one batched decode. H = codec.halo() is
+        the decoder's receptive field per side -- 49 frames, 0.98 s of audio, at the full dims -- and
+        that look-ahead is inherent to an exact chunk: with fewer tokens known, the chunk's last
+        samples would still change. So the concatenation of the chunks is bitwise
+        generate_speech(args) for the same seed, the first chunk exists after chunk_frames + H
+        decode steps instead of after the whole request, and a request that fails before any chunk
+        yields the same one second of zeros. A request that fails after some chunks were yielded
+        ends the stream there (its last item has done = False). An item's done says that the request
+        had finished when the chunk was decoded; the last chunk has done and t1 == n_known."""
+        if chunk_frames < 1:
+            raise ValueError("chunk_frames must be >= 1")
+        try:
+            req = self._request(args)
+        except ValueError:  # untokenisable text: the request fails -> one second of silence
+            req = None
+        return self.stream_request(req, chunk_frames)
+
+    def stream_request(self, req: Optional[TtsBatchRequest], chunk_frames: int = 16):
+        """stream_speech for a request that is already built (None: a request that failed before it
+        was submitted)."""
+        if chunk_frames < 1:
+            raise ValueError("chunk_frames must be >= 1")
+        H = self.codec.halo()
+        g, sem, t0, yielded, status = None, [], 0, False, 0
+        it = self.manager.stream_tts(req) if req is not None else iter([(None, [], True)])
+        try:
+            for gi, new, done in it:
+                if gi is not None:
+                    g = gi
+                sem.extend(new)
+                n = len(sem)
+                if done and req is not None:
+                    status = (self.manager.last_status or [0])[0]
+                if done and (status != 0 or (not g and not sem)):
+                    if not yielded:
+                        yield SpeechChunk.make(np.zeros(SAMPLE_RATE, dtype=np.float32), 0, 0, 0, True)  # :828-830
+                    return
+                if done and not sem:
+                    self.codec.decode_audio(g, sem)  # (raises as generate_speech does: no semantic tokens)
+                wins = []
+                while g is not None and t0 < n and (done or t0 + chunk_frames + H <= n):
+                    t1 = min(t0 + chunk_frames, n)
+                    wins.append((t0, t1))
+                    t0 = t1
+                if wins:
+                    pcm = self.codec.decode_windows([(g, sem, a, b, done) for a, b in wins])
+                    for (a, b), p in zip(wins, pcm):
+                        yielded = True
+                        yield SpeechChunk.make(p, a, b, n, done)
+        finally:
+            if hasattr(it, "close"):
+                it.close()  # (a stream left early: the ticket is released once the request has finished)
 
     def generate_speech_batch(self, batch_args: Sequence[LightweightTtsPipelineArgs]) -> List[np.ndarray]:
         reqs, idx = [], []

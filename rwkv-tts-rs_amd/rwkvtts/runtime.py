@@ -265,9 +265,19 @@ class SharedRwkvRuntime:
 
     # ---- scheduler ----
     @_locked
-    def generate_batch(self, requests: Sequence["TtsBatchRequest"]):
+    def generate_batch(self, requests: Sequence["TtsBatchRequest"], on_tokens=None):
         """generate_tts_batch on this engine; failed requests give ([], []) (status in
-        self.last_status)."""
+        self.last_status).
+
+        on_tokens (a callable for every request, or a sequence with one callable or None per
+        request): token progress, rwkvtts_generate_batch_stream. It is called on this thread between
+        the engine's units of work as on_tokens(i, global_tokens or None, first, new_semantic_tokens,
+        done, status): request i's semantic tokens [first, first + len(new)), in order and each
+        once, the 32 global tokens once they are known, and a last call with done = True. It must
+        not call into this runtime. An exception it raises is re-raised after the batch has run
+        (later calls for that batch are dropped). The returned results are the same either way."""
+        if on_tokens is not None:
+            return self._generate_batch_stream(requests, on_tokens)
         n = len(requests)
         reqs = (_ffi.Request * n)()
         res = (_ffi.Result * n)()
@@ -280,6 +290,44 @@ class SharedRwkvRuntime:
             sem_bufs.append(sb)
             res[i].semantic_tokens = sb.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
         check(lib().rwkvtts_generate_batch(self._h, reqs, n, res), "generate_batch")
+        out, self.last_status = _unpack_results(res, sem_bufs)
+        return out
+
+    def _generate_batch_stream(self, requests, on_tokens):
+        n = len(requests)
+        cbs = list(on_tokens) if isinstance(on_tokens, (list, tuple)) else [on_tokens] * n
+        if len(cbs) != n:
+            raise ValueError("on_tokens: one callable (or None) per request")
+        reqs = (_ffi.Request * n)()
+        res = (_ffi.Result * n)()
+        sinks = (_ffi.TokenSink * n)()
+        keep, sem_bufs, fns, raised = [], [], [], []
+
+        def make(i, cb):
+            def fn(_user, g, n_g, sem, first, count, done, status):
+                if raised:
+                    return
+                try:
+                    cb(i, [int(g[k]) for k in range(n_g)] if n_g == _ffi.N_GLOBAL or (done and n_g) else None, int(first),
+                       [int(sem[k]) for k in range(count)], bool(done), int(status))
+                except BaseException as e:  # never unwind through the native frames
+                    raised.append(e)
+            return _ffi.TokenFn(fn)
+
+        for i, r in enumerate(requests):
+            q, k = request_struct(r)
+            keep.append(k)
+            reqs[i] = q
+            sb = np.zeros(_ffi.SEMANTIC_LIMIT, dtype=np.int32)
+            sem_bufs.append(sb)
+            res[i].semantic_tokens = sb.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+            if cbs[i] is not None:
+                fns.append(make(i, cbs[i]))
+                sinks[i].fn = fns[-1]
+        rc = lib().rwkvtts_generate_batch_stream(self._h, reqs, n, res, sinks)
+        if raised:
+            raise raised[0]
+        check(rc, "generate_batch_stream")
         out, self.last_status = _unpack_results(res, sem_bufs)
         return out
 
@@ -457,15 +505,58 @@ class DynamicBatchManager:
             return self.tokenizer.encode(text)  # dynamic_batch_manager.rs:512-515
         return list(text)
 
-    def submit(self, request: "TtsBatchRequest") -> int:
+    def submit(self, request: "TtsBatchRequest", stream: bool = False) -> int:
+        """stream: the engine publishes the request's tokens after every unit of work (wait_tokens)."""
         q, keep = request_struct(request)
         t = ctypes.c_uint64()
         self._enter()
         try:
-            check(lib().rwkvtts_manager_submit(self._h, ctypes.byref(q), ctypes.byref(t)), "manager_submit")
+            fn = lib().rwkvtts_manager_submit_stream if stream else lib().rwkvtts_manager_submit
+            check(fn(self._h, ctypes.byref(q), ctypes.byref(t)), "manager_submit")
         finally:
             self._leave()
         return int(t.value)
+
+    def wait_tokens(self, ticket: int, have_semantic: int = 0, timeout_ms: int = -1):
+        """Blocks until more than have_semantic semantic tokens of the request are known or it is
+        done (rwkvtts_manager_wait_tokens). Returns (global_tokens or None, all semantic tokens known
+        so far, done, status), or None on a timeout. The ticket stays valid: wait() releases it."""
+        g = np.zeros(_ffi.N_GLOBAL, dtype=np.int32)
+        sb = np.zeros(_ffi.SEMANTIC_LIMIT, dtype=np.int32)
+        ng, ns, done, status = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        self._enter()
+        try:
+            rc = lib().rwkvtts_manager_wait_tokens(self._h, ctypes.c_uint64(ticket), int(have_semantic), timeout_ms,
+                                                   g.ctypes.data_as(ctypes.c_void_p), ctypes.byref(ng),
+                                                   sb.ctypes.data_as(ctypes.c_void_p), ctypes.byref(ns),
+                                                   ctypes.byref(done), ctypes.byref(status))
+        finally:
+            self._leave()
+        if rc == _ffi.EBUSY:
+            return None
+        check(rc, "manager_wait_tokens")
+        have_g = ng.value == _ffi.N_GLOBAL or (done.value and ng.value)
+        return (g[:ng.value].tolist() if have_g else None, sb[:ns.value].tolist(), bool(done.value), status.value)
+
+    def stream_tts(self, request: "TtsBatchRequest"):
+        """Generator of (global_tokens or None, new_semantic_tokens, done) increments of one request,
+        by polling the native manager (no foreign thread calls into Python). The last increment has
+        done = True; its status is in last_status, and a failed request ends with (None, [], True)
+        after whatever was streamed before the failure. The ticket is released at the end (also when
+        the generator is closed early: the request then finishes unobserved first)."""
+        ticket = self.submit(request, stream=True)
+        have = 0
+        try:
+            while True:
+                g, sem, done, status = self.wait_tokens(ticket, have)
+                new, have = sem[have:], max(have, len(sem))
+                if done:
+                    self._tls.last_status = [status]
+                    yield (g if status == 0 else None), new, True
+                    return
+                yield g, new, False
+        finally:
+            self.wait_status(ticket)
 
     def wait(self, ticket: int, timeout_ms: int = -1):
         """(global, semantic) or None if not ready within timeout_ms; ([], []) for a failed request."""

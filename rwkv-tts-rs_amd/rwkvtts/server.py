@@ -14,6 +14,9 @@
   (multipart voice_name / prompt_text / audio_file; the feature extraction needs the
   BiCodecTokenize + wav2vec2 encoders, whose graphs are absent: a pipeline may supply
   `reference_tokenizer`, otherwise the route answers the reference's extraction-failure body).
+* `handle_tts_stream(body, pipeline, voice_dir)` (no reference counterpart): the same request as a
+  WAV stream, POST /api/tts/stream -- audio while the request is still decoding, at a fixed scale
+  (no peak normalisation: that needs the whole utterance).
 The embedded web UI and model download are out of scope.
 """
 import base64
@@ -98,15 +101,16 @@ def load_voice_feature(voice_dir: str, voice_id: str) -> dict:
     return dict(vf.__dict__)
 
 
-def handle_tts_json(body, pipeline, voice_dir: str = "assets/raf") -> Tuple[int, dict]:
-    t0 = time.perf_counter()
+def _tts_args(body, voice_dir: str):
+    """The request body of /api/tts -> (None, LightweightTtsPipelineArgs), or ((status, payload), None)
+    for a body the handler refuses."""
     if isinstance(body, (bytes, str)):
         try:
             body = json.loads(body)
         except ValueError as e:
-            return 400, {"success": False, "error": f"JSON解析失败: {e}"}
+            return (400, {"success": False, "error": f"JSON解析失败: {e}"}), None
     if not isinstance(body, dict) or not isinstance(body.get("text"), str):
-        return 400, {"success": False, "error": "JSON解析失败: missing field `text`"}
+        return (400, {"success": False, "error": "JSON解析失败: missing field `text`"}), None
     voice_id = body.get("voice_id")
     voice = None
     prompt_from_voice = None
@@ -115,7 +119,7 @@ def handle_tts_json(body, pipeline, voice_dir: str = "assets/raf") -> Tuple[int,
             voice = load_voice_feature(voice_dir, voice_id)
             prompt_from_voice = voice.get("prompt_text", "")
         except (OSError, ValueError) as e:
-            return 400, {"success": False, "error": f"音色ID '{voice_id}' 不存在或加载失败: {e}"}
+            return (400, {"success": False, "error": f"音色ID '{voice_id}' 不存在或加载失败: {e}"}), None
     prompt_text = prompt_from_voice if prompt_from_voice is not None else (body.get("prompt_text") or "")
     args = LightweightTtsPipelineArgs(
         text=body["text"], ref_audio_path="", zero_shot=voice_id is not None,
@@ -127,6 +131,14 @@ def handle_tts_json(body, pipeline, voice_dir: str = "assets/raf") -> Tuple[int,
         speed=map_speed(body.get("speed")), prompt_text=prompt_text,
         voice_global_tokens=list(voice["global_tokens"]) if voice else None,
         voice_semantic_tokens=list(voice["semantic_tokens"]) if voice else None)
+    return None, args
+
+
+def handle_tts_json(body, pipeline, voice_dir: str = "assets/raf") -> Tuple[int, dict]:
+    t0 = time.perf_counter()
+    err, args = _tts_args(body, voice_dir)
+    if err:
+        return err
     try:
         audio = pipeline.generate_speech(args)
     except Exception as e:  # noqa: BLE001 -- rendered as the reference's 500 body
@@ -136,6 +148,55 @@ def handle_tts_json(body, pipeline, voice_dir: str = "assets/raf") -> Tuple[int,
     total = time.perf_counter() - t0
     return 200, {"success": True, "message": "TTS生成成功", "audio_base64": b64,
                  "duration_ms": int(total * 1000), "rtf": calculate_rtf(audio, total)}
+
+
+def streaming_wav_header(sample_rate: int = 16000) -> bytes:
+    """The canonical 44-byte PCM WAV header (16-bit mono) with both sizes unknown (0xFFFFFFFF): the
+    length of a stream is not known when its header goes out."""
+    hdr = b"RIFF" + (0xFFFFFFFF).to_bytes(4, "little") + b"WAVE"
+    hdr += b"fmt " + (16).to_bytes(4, "little") + (1).to_bytes(2, "little") + (1).to_bytes(2, "little")
+    hdr += int(sample_rate).to_bytes(4, "little") + int(sample_rate * 2).to_bytes(4, "little")
+    hdr += (2).to_bytes(2, "little") + (16).to_bytes(2, "little")
+    return hdr + b"data" + (0xFFFFFFFF).to_bytes(4, "little")
+
+
+def samples_to_pcm16(samples) -> bytes:
+    """f32 -> little-endian i16 at scale 1.0: clamp to [-1, 1], x 32767, truncated toward zero, as
+    convert_samples_to_wav does after its scaling."""
+    x = np.asarray(samples, dtype=np.float32)
+    y = np.clip(x, np.float32(-1.0), np.float32(1.0)) * np.float32(32767.0)
+    return np.trunc(y).astype("<i2").tobytes()
+
+
+def handle_tts_stream(body, pipeline, voice_dir: str = "assets/raf", chunk_frames: int = 16):
+    """POST /api/tts/stream: the request body of /api/tts -> (HTTP status, iterator of bytes).
+
+    200: a 44-byte WAV header with unknown-length sizes (streaming_wav_header), then the int16 PCM of
+    pipeline.stream_speech's chunks as they are decoded (the first after chunk_frames + halo decode
+    steps, not after the whole request). The scale is fixed at 1.0: the vocoder ends in tanh, so its
+    samples already lie in (-1, 1). There is NO peak normalisation, unlike /api/tts
+    (convert_samples_to_wav): the peak rule needs the whole utterance, which a stream does not have
+    when its first sample goes out -- the same request is therefore quieter or louder here than in
+    /api/tts's WAV, by that rule's factor. Clamping and truncation are convert_samples_to_wav's.
+    A refused body gives /api/tts's status and JSON body (as one bytes item); so does a failure
+    before the first chunk (500). A failure after the first chunk can only end the stream."""
+    err, args = _tts_args(body, voice_dir)
+    if err:
+        return err[0], iter([json.dumps(err[1], ensure_ascii=False).encode("utf-8")])
+    try:
+        chunks = pipeline.stream_speech(args, chunk_frames=chunk_frames)
+        first = next(chunks, None)  # before the status line goes out: a failure is still a 500
+    except Exception as e:  # noqa: BLE001 -- rendered as the reference's 500 body
+        payload = {"success": False, "error": f"生成TTS音频失败: {e}"}
+        return 500, iter([json.dumps(payload, ensure_ascii=False).encode("utf-8")])
+
+    def gen():
+        yield streaming_wav_header(16000)
+        if first is not None:
+            yield samples_to_pcm16(first)
+        for c in chunks:
+            yield samples_to_pcm16(c)
+    return 200, gen()
 
 
 def handle_voice_list(voice_dir: str = "assets/raf") -> Tuple[int, dict]:
@@ -199,7 +260,7 @@ def handle_voice_extract(form: Optional[dict], audio_path: Optional[str], pipeli
 
 
 def create_app(pipeline, voice_dir: str = "assets/raf"):
-    """FastAPI app with POST /api/tts (server.rs:1447). Serve with uvicorn."""
+    """FastAPI app with POST /api/tts (server.rs:1447) and POST /api/tts/stream. Serve with uvicorn."""
     from fastapi import FastAPI, Request
     from fastapi.responses import JSONResponse
 
@@ -211,6 +272,16 @@ def create_app(pipeline, voice_dir: str = "assets/raf"):
         body = await request.body()
         code, payload = await anyio.to_thread.run_sync(handle_tts_json, body, pipeline, voice_dir)
         return JSONResponse(payload, status_code=code)
+
+    @app.post("/api/tts/stream")
+    async def api_tts_stream(request: Request):
+        import anyio
+        from fastapi.responses import Response, StreamingResponse
+        body = await request.body()
+        code, it = await anyio.to_thread.run_sync(handle_tts_stream, body, pipeline, voice_dir)
+        if code != 200:
+            return Response(b"".join(it), status_code=code, media_type="application/json")
+        return StreamingResponse(it, media_type="audio/wav")  # (a sync iterator: iterated in a worker thread)
 
     @app.get("/api/voice-clone/list")
     async def api_voice_list():
