@@ -522,6 +522,78 @@ int64_t rwkvtts_tokenizer_vocab_size(const rwkvtts_tokenizer* t); /* max id + 1 
 /* wav [n] f32 @16 kHz -> mel [128][n_frames] (n_frames = (n + 1024 - 1024) / 320 + 1). */
 int rwkvtts_mel(int device, const float* wav, int n, float* mel, int* n_frames);
 
+/* ---- resampler: rubato SincFixedIn as src/ref_audio_utilities.rs:532-576 configures it, on the
+ * GPU, for the reference-audio front end and for output rates other than 16 kHz (the reference
+ * resamples on the host and only when it loads a reference WAV) --------------------------------
+ * The arithmetic contract (what makes every output bitwise-testable):
+ *   table   sincs[O][L] f32 (O = oversampling, L = sinc_len): rubato's make_sincs with the
+ *           Blackman-Harris^2 window and cutoff = f_cutoff if ratio >= 1 else f_cutoff * ratio
+ *   ratio   = (double)sr_out / (double)sr_in, t_ratio = 1.0 / ratio
+ *   n_out   = (int64)ceil(n * ratio), in double
+ *   position of output o, every step one IEEE double operation (never fused):
+ *           idx = (double)o * t_ratio - delay, start = floor(idx), pos = (idx - start) * O,
+ *           p0 = floor(pos), w1 = (float)(pos - p0)
+ *   taps    tap k (0 .. L-1) reads input sample j = start + k - L/2 + 1, zero outside [0, n)
+ *   sums    a = sum_k x[j_k] * sincs[p0 % O][k], b = sum_k x[j_k] * sincs[(p0 + 1) % O][k]: each a
+ *           sequential f32 sum in ascending k starting from +0, one rounded multiply then one
+ *           rounded add per tap (no fused multiply-add)
+ *   result  out[o] = a + (b - a) * w1: three rounded f32 operations, no fma
+ *   align   RUBATO: delay = L/2 (rubato's start delay kept, the tail cut by L/2 input samples: the
+ *           behaviour of the Python restatement, for the reference-audio front end);
+ *           ZERO: delay = 0 (output o sits at input time o * t_ratio: for synthesised output). */
+#define RWKVTTS_RESAMPLE_ALIGN_RUBATO 0
+#define RWKVTTS_RESAMPLE_ALIGN_ZERO 1
+typedef struct {
+  uint32_t struct_size;
+  int32_t sr_in, sr_out; /* 1 .. 192000 each */
+  int32_t sinc_len;      /* L: a multiple of 8, 8 .. 1024; 0 = 256 */
+  int32_t oversampling;  /* O: 1 .. 1024; 0 = 256 */
+  double f_cutoff;       /* in (0, 1]; 0 = 0.95 */
+  int32_t align;         /* RWKVTTS_RESAMPLE_ALIGN_* */
+} rwkvtts_resample_desc;
+/* The library's own table builder (host only): out[O * L]. The normalising sum is taken in double.
+ * Anything outside the ranges above is RWKVTTS_EINVAL, here and in every call that takes a desc. */
+int rwkvtts_resample_sincs(const rwkvtts_resample_desc* desc, float* out);
+/* ceil(n_in * ratio) (host only); -1 for a bad desc or n_in < 0. */
+int64_t rwkvtts_resample_out_len(const rwkvtts_resample_desc* desc, int64_t n_in);
+/* Streaming plan (host only, a pure function). With samples [0, n_known) of a signal known:
+ * *out_ready_end = the first output some tap of which reaches sample n_known or later; never more
+ * than out_len(n_known), the signal's output count if it ended here (outputs from there on wait for
+ * more samples or for final). With final (n_known is the signal's length) it is out_len(n_known).
+ * *in_first_needed = max(0, lowest tap index of output out_first): samples before it are never read
+ * again once outputs [0, out_first) are done -- the tail a stream must keep. Either pointer may be
+ * NULL. It is monotone in n_known and in out_first. */
+int rwkvtts_resample_plan(const rwkvtts_resample_desc* desc, int64_t n_known, int final, int64_t out_first,
+                          int64_t* out_ready_end, int64_t* in_first_needed);
+typedef struct rwkvtts_resampler rwkvtts_resampler;
+/* table == NULL: the table of rwkvtts_resample_sincs; otherwise the caller's [O][L] table (copied). */
+int rwkvtts_resampler_create(int device, const rwkvtts_resample_desc* desc, const float* table,
+                             rwkvtts_resampler** out);
+int rwkvtts_resampler_destroy(rwkvtts_resampler* r);
+/* n signals (ragged) in one launch; host buffers; out[i] has capacity out_len(n_in[i]).
+ * n_in[i] == 0 is allowed and writes nothing. Calls on one resampler serialise on its lock. */
+int rwkvtts_resample_batch(rwkvtts_resampler* r, const float* const* in, const int64_t* n_in, int n,
+                           float* const* out);
+typedef struct {
+  uint32_t struct_size;
+  const float* in;    /* points at sample in_first of the signal */
+  int64_t in_first;
+  int64_t n_in;
+  int32_t final;      /* 1: in_first + n_in is the signal's length */
+  int64_t out_first;  /* outputs [out_first, out_first + out_count) */
+  int64_t out_count;
+  float* out;         /* capacity out_count */
+} rwkvtts_resample_window;
+/* n windows (of any signals) in one launch: outputs [out_first, out_first + out_count) of the
+ * whole-signal resample, bitwise, whatever follows the known samples. RWKVTTS_EINVAL before anything
+ * is launched (and nothing written) if a tap of a requested output falls outside the given samples --
+ * out_first + out_count > out_ready_end(in_first + n_in, final) or in_first >
+ * in_first_needed(out_first) by rwkvtts_resample_plan: taps below sample 0 and, with final, taps
+ * past the end are the only zeros. */
+int rwkvtts_resample_windows(rwkvtts_resampler* r, const rwkvtts_resample_window* w, int n);
+/* HIP-event time of the last launch's kernel alone (no copies), in ms; 0 before the first launch. */
+int rwkvtts_resampler_kernel_ms(rwkvtts_resampler* r, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

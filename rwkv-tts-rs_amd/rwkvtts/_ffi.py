@@ -152,6 +152,21 @@ class CodecWindow(ctypes.Structure):
                 ("global_", ctypes.c_void_p), ("pcm", ctypes.c_void_p)]
 
 
+RESAMPLE_ALIGN_RUBATO, RESAMPLE_ALIGN_ZERO = 0, 1
+
+
+class ResampleDesc(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("sr_in", ctypes.c_int32), ("sr_out", ctypes.c_int32),
+                ("sinc_len", ctypes.c_int32), ("oversampling", ctypes.c_int32), ("f_cutoff", ctypes.c_double),
+                ("align", ctypes.c_int32)]
+
+
+class ResampleWindow(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("in_", ctypes.c_void_p), ("in_first", ctypes.c_int64),
+                ("n_in", ctypes.c_int64), ("final", ctypes.c_int32), ("out_first", ctypes.c_int64),
+                ("out_count", ctypes.c_int64), ("out", ctypes.c_void_p)]
+
+
 # Every symbol include/rwkvtts.h declares (checked by tests/test_abi.py against the header).
 EXPORTS = {
     "rwkvtts_synth_weights": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p]),
@@ -228,6 +243,19 @@ EXPORTS = {
     "rwkvtts_tokenizer_vocab_size": (ctypes.c_int64, [ctypes.c_void_p]),
     "rwkvtts_mel": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                    ctypes.POINTER(ctypes.c_int)]),
+    # resampler: table, plan (host only), one-shot / batched / exact stream windows
+    "rwkvtts_resample_sincs": (ctypes.c_int, [ctypes.POINTER(ResampleDesc), ctypes.c_void_p]),
+    "rwkvtts_resample_out_len": (ctypes.c_int64, [ctypes.POINTER(ResampleDesc), ctypes.c_int64]),
+    "rwkvtts_resample_plan": (ctypes.c_int, [ctypes.POINTER(ResampleDesc), ctypes.c_int64, ctypes.c_int,
+                                             ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                                             ctypes.POINTER(ctypes.c_int64)]),
+    "rwkvtts_resampler_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ResampleDesc), ctypes.c_void_p,
+                                                ctypes.POINTER(ctypes.c_void_p)]),
+    "rwkvtts_resampler_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "rwkvtts_resample_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_void_p]),
+    "rwkvtts_resample_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ResampleWindow), ctypes.c_int]),
+    "rwkvtts_resampler_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None

@@ -15,11 +15,19 @@ and the clip / silence helpers it uses), feeding the HIP mel kernel (features.py
   in the reference pins its output: **parity unpinned**; restated from the library's published
   algorithm (the output keeps rubato's sinc_len / 2 input-sample delay and its
   ceil(n * ratio) output length).
+* `Resampler` (no reference counterpart: the reference resamples on the host, and only a
+  reference WAV): the same restatement as a HIP kernel (csrc/resample.hip), one-shot, batched and
+  exact over stream chunks, with rubato's alignment or none. The kernel is pinned bitwise to the
+  restatement's arithmetic contract (include/rwkvtts.h), not to rubato: parity stays unpinned.
 """
+import ctypes
 import struct
+import threading
 from typing import Tuple
 
 import numpy as np
+
+from . import _ffi
 
 F32 = np.float32
 
@@ -88,10 +96,21 @@ def _make_sincs(npoints: int, factor: int, f_cutoff: float) -> np.ndarray:
 
 
 def resample_audio_high_quality(audio, original_sr: int, target_sr: int, sinc_len: int = 256,
-                                f_cutoff: float = 0.95, oversampling: int = 256) -> np.ndarray:
+                                f_cutoff: float = 0.95, oversampling: int = 256, device=None) -> np.ndarray:
+    """device None: the numpy restatement below. An integer: the HIP kernel on that GPU with rubato
+    alignment (Resampler): the same positions, taps and table; its two sums per output run in
+    ascending tap order where einsum's order is unspecified, so the two agree to the forward-error
+    bound of an f32 sum, not bitwise (tests/test_gpu_resample.py)."""
     x = np.asarray(audio, dtype=F32)
     if original_sr == target_sr:
         return x.copy()
+    if device is not None:
+        r = Resampler(original_sr, target_sr, device=int(device), align="rubato", sinc_len=sinc_len,
+                      f_cutoff=f_cutoff, oversampling=oversampling)
+        try:
+            return r.resample(x)
+        finally:
+            r.close()
     ratio = target_sr / original_sr
     cutoff = f_cutoff if ratio >= 1.0 else f_cutoff * ratio
     sincs = _make_sincs(sinc_len, oversampling, cutoff)
@@ -115,6 +134,168 @@ def resample_audio_high_quality(audio, original_sr: int, target_sr: int, sinc_le
         b = np.einsum("ij,ij->i", seg, sincs[(p0[sl] + 1) % oversampling])
         out[sl] = a + (b - a) * w1[sl]
     return out
+
+
+# ---- the resampler on the GPU ----------------------------------------------------------------
+class Resampler:
+    """The restatement above as a HIP kernel (csrc/resample.hip; the arithmetic contract is in
+    include/rwkvtts.h): one-shot, batched and exact over stream chunks.
+
+    align "rubato" keeps rubato's sinc_len / 2 start delay and cuts the tail, as
+    resample_audio_high_quality does (the reference-audio front end); "zero" puts output o at input
+    time o / ratio (synthesised output: no delay, nothing cut). The kernel reads the table
+    `_make_sincs` builds, so the restatement has a single source; it is pinned bitwise to the
+    contract's numpy form (tests/test_gpu_resample.py), not to rubato (parity unpinned, as above).
+
+    evaluator: a callable (resampler, items) -> [ndarray] standing in for the native window call,
+    items being [(samples from in_first on, in_first, final, out_first, out_count)]; no GPU resampler
+    is created then (the host-only plan / out_len entry points are still the library's)."""
+
+    def __init__(self, sr_in: int, sr_out: int, device: int = 0, align: str = "zero", sinc_len: int = 256,
+                 f_cutoff: float = 0.95, oversampling: int = 256, evaluator=None):
+        if align not in ("zero", "rubato"):
+            raise ValueError('align must be "zero" or "rubato"')
+        self.sr_in, self.sr_out, self.align, self.device = int(sr_in), int(sr_out), align, int(device)
+        self.sinc_len, self.oversampling, self.f_cutoff = int(sinc_len), int(oversampling), float(f_cutoff)
+        self._desc = _ffi.ResampleDesc(
+            struct_size=ctypes.sizeof(_ffi.ResampleDesc), sr_in=self.sr_in, sr_out=self.sr_out,
+            sinc_len=self.sinc_len, oversampling=self.oversampling, f_cutoff=self.f_cutoff,
+            align=_ffi.RESAMPLE_ALIGN_ZERO if align == "zero" else _ffi.RESAMPLE_ALIGN_RUBATO)
+        self._h = None
+        self._evaluator = evaluator
+        # one native call at a time: the resampler owns one stream and one set of device buffers
+        self._lock = threading.Lock()
+        self.out_len(0)  # (refuses a bad description before anything is built)
+        self.ratio = self.sr_out / self.sr_in
+        self.sincs = _make_sincs(self.sinc_len, self.oversampling,
+                                 self.f_cutoff if self.ratio >= 1.0 else self.f_cutoff * self.ratio)
+        if evaluator is None:
+            h = ctypes.c_void_p()
+            _ffi.check(_ffi.lib().rwkvtts_resampler_create(self.device, ctypes.byref(self._desc),
+                                                           self.sincs.ctypes.data_as(ctypes.c_void_p),
+                                                           ctypes.byref(h)), "resampler_create")
+            self._h = h
+
+    def close(self):
+        if self._h:
+            _ffi.lib().rwkvtts_resampler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- host-only plan ----
+    def out_len(self, n_in: int) -> int:
+        n = int(_ffi.lib().rwkvtts_resample_out_len(ctypes.byref(self._desc), int(n_in)))
+        if n < 0:
+            raise _ffi.RwkvTtsError(_ffi.EINVAL, "resample_out_len")
+        return n
+
+    def plan(self, n_known: int, final: bool, out_first: int = 0):
+        """(out_ready_end, in_first_needed) of rwkvtts_resample_plan."""
+        end, first = ctypes.c_int64(), ctypes.c_int64()
+        _ffi.check(_ffi.lib().rwkvtts_resample_plan(ctypes.byref(self._desc), int(n_known), 1 if final else 0,
+                                                    int(out_first), ctypes.byref(end), ctypes.byref(first)),
+                   "resample_plan")
+        return end.value, first.value
+
+    # ---- the kernel ----
+    def resample_windows(self, items) -> list:
+        """[(samples from in_first on, in_first, final, out_first, out_count)] -> [outputs
+        [out_first, out_first + out_count) of the whole-signal resample], all windows in one launch.
+        Raises RwkvTtsError(EINVAL), with nothing computed, if a requested output needs a sample
+        that was not given (plan())."""
+        items = [(np.ascontiguousarray(x, dtype=F32).reshape(-1), int(a), bool(f), int(o), int(c))
+                 for x, a, f, o, c in items]
+        if self._evaluator is not None:
+            return [np.ascontiguousarray(y, dtype=F32) for y in self._evaluator(self, items)]
+        n = len(items)
+        if n == 0:
+            return []
+        ws = (_ffi.ResampleWindow * n)()
+        outs = []
+        for w, (x, in_first, final, out_first, count) in zip(ws, items):
+            out = np.empty(max(count, 0), dtype=F32)
+            outs.append(out)
+            w.struct_size = ctypes.sizeof(_ffi.ResampleWindow)
+            w.in_, w.in_first, w.n_in, w.final = x.ctypes.data, in_first, x.size, 1 if final else 0
+            w.out_first, w.out_count, w.out = out_first, count, out.ctypes.data
+        with self._lock:
+            _ffi.check(_ffi.lib().rwkvtts_resample_windows(self._h, ws, n), "resample_windows")
+        return outs
+
+    def resample_batch(self, signals) -> list:
+        """[signal] -> [resampled signal], ragged, in one launch; an empty signal gives an empty one."""
+        xs = [np.ascontiguousarray(x, dtype=F32).reshape(-1) for x in signals]
+        if self._evaluator is not None:
+            return self.resample_windows([(x, 0, True, 0, self.out_len(x.size)) for x in xs])
+        n = len(xs)
+        if n == 0:
+            return []
+        outs = [np.empty(self.out_len(x.size), dtype=F32) for x in xs]
+        P = ctypes.c_void_p * n
+        ins, ous = P(*[x.ctypes.data for x in xs]), P(*[o.ctypes.data for o in outs])
+        lens = (ctypes.c_int64 * n)(*[x.size for x in xs])
+        with self._lock:
+            _ffi.check(_ffi.lib().rwkvtts_resample_batch(self._h, ins, lens, n, ous), "resample_batch")
+        return outs
+
+    def resample(self, x) -> np.ndarray:
+        return self.resample_batch([x])[0]
+
+    def kernel_ms(self) -> float:
+        """HIP-event time of the last launch's kernel alone (no copies)."""
+        ms = ctypes.c_double()
+        _ffi.check(_ffi.lib().rwkvtts_resampler_kernel_ms(self._h, ctypes.byref(ms)), "resampler_kernel_ms")
+        return ms.value
+
+    def stream(self) -> "ResampleStream":
+        return ResampleStream(self)
+
+
+class ResampleStream:
+    """Resampler.stream(): feed(pcm_chunk, final=False) -> the outputs that became exact with it.
+    The concatenation of what feed returns is bitwise Resampler.resample(the concatenated input),
+    however the input was cut. Only the tail rwkvtts_resample_plan asks for is kept: fewer than
+    sinc_len + ceil(1 / ratio) + 1 samples."""
+
+    def __init__(self, resampler: Resampler):
+        self.r = resampler
+        self._tail = np.zeros(0, dtype=F32)
+        self._tail_first = 0   # signal index of _tail[0]
+        self._out_next = 0     # outputs [0, _out_next) went out
+        self._closed = False
+
+    @property
+    def kept(self) -> int:
+        return int(self._tail.size)
+
+    def feed(self, pcm_chunk, final: bool = False) -> np.ndarray:
+        if self._closed:
+            raise ValueError("the stream has ended (a chunk was fed with final=True)")
+        x = np.asarray(pcm_chunk, dtype=F32).reshape(-1)
+        if x.size:
+            self._tail = np.concatenate([self._tail, x])
+        n_known = self._tail_first + self._tail.size
+        end, _ = self.r.plan(n_known, final, self._out_next)
+        count = end - self._out_next
+        if count > 0:
+            out = self.r.resample_windows([(self._tail, self._tail_first, final, self._out_next, count)])[0]
+        else:
+            out = np.zeros(0, dtype=F32)
+        self._out_next = max(end, self._out_next)
+        if final:
+            self._closed, self._tail = True, np.zeros(0, dtype=F32)
+            return out
+        _, first = self.r.plan(n_known, False, self._out_next)
+        first = min(first, n_known)
+        if first > self._tail_first:
+            self._tail = self._tail[first - self._tail_first:].copy()
+            self._tail_first = first
+        return out
 
 
 # ---- normalisation / trimming ------------------------------------------------------------
@@ -194,7 +375,8 @@ def get_ref_clip(wav, sample_rate: int = 16000, ref_segment_duration: float = 6.
     return x[:seg].copy()
 
 
-def load_audio(path: str, target_sr: int = 16000, volume_normalize: bool = True) -> np.ndarray:
+def load_audio(path: str, target_sr: int = 16000, volume_normalize: bool = True, device=None) -> np.ndarray:
+    """device: None resamples with the numpy restatement, an integer on that GPU (Resampler)."""
     import os
     if not os.path.exists(path):
         raise FileNotFoundError(path)
@@ -211,7 +393,7 @@ def load_audio(path: str, target_sr: int = 16000, volume_normalize: bool = True)
     if ch > 1:
         x = x[::ch].copy()
     if sr != target_sr:
-        x = resample_audio_high_quality(x, sr, target_sr)
+        x = resample_audio_high_quality(x, sr, target_sr, device=device)
     if volume_normalize:
         x = audio_volume_normalize(x, 0.2)
     return trim_silence_only(x, 0.01)

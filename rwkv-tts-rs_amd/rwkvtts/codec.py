@@ -84,6 +84,7 @@ class BiCodecDetokenizer:
         """weight_path: _ffi.CODEC_WEIGHTS_AUTO (hi + lo weight planes iff some conv weight is not
         bf16-exact), CODEC_WEIGHTS_BF16 or CODEC_WEIGHTS_HILO (rwkvtts_codec_create_ex)."""
         self.dims = dict(dims or CODEC_DIMS_FULL)
+        self.device = int(device)
         self._cd = make_codec_dims(self.dims)
         w = np.ascontiguousarray(weights, dtype=np.float32)
         h = ctypes.c_void_p()

@@ -7,6 +7,9 @@ generation (a failed request) becomes one second of silence (:828-830, SURVEY B8
 generate_speech_batch (:855-1000): the same for a list of args through generate_tts_batch and
 decode_audio_batch (a failed item decodes to an empty array there, as the reference's
 spawn_blocking tasks return vec![]).
+generate_speech, generate_speech_batch and stream_speech take `sample_rate` (no reference counterpart:
+the reference emits 16 kHz only): None / 16000 is the vocoder's PCM as it is; any other rate is that
+PCM resampled on the GPU with zero alignment (audio.Resampler), exact over stream chunks.
 
 The voice store lookup by voice_id inside the pipeline (`VoiceFeatureManager::new("./raf")`,
 :751) goes through `voices.VoiceFeatureManager` on `raf_dir` (the server passes the
@@ -14,6 +17,7 @@ tokens directly instead).
 """
 import dataclasses
 import os
+import threading
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -71,6 +75,24 @@ class LightweightTtsPipeline:
         # whose graphs are not available; a callable (path -> (global, semantic))
         # may be supplied
         self.reference_tokenizer = reference_tokenizer
+        self._resamplers = {}  # output rate -> audio.Resampler (created on first use, kept)
+        self._resamplers_lock = threading.Lock()  # (the server's worker threads share the pipeline)
+
+    # ---- output rates other than 16 kHz (no reference counterpart: the reference emits 16 kHz only)
+    def resampler(self, sample_rate: Optional[int]):
+        """None for None / 16000 (nothing is created: the PCM is the vocoder's); otherwise the
+        pipeline's Resampler 16000 -> sample_rate with zero alignment (output o at input time
+        o * 16000 / sample_rate: no delay, nothing cut), on the codec's GPU."""
+        if sample_rate is None or int(sample_rate) == SAMPLE_RATE:
+            return None
+        rate = int(sample_rate)
+        with self._resamplers_lock:
+            r = self._resamplers.get(rate)
+            if r is None:
+                from .audio import Resampler
+                r = self._resamplers[rate] = Resampler(SAMPLE_RATE, rate, device=getattr(self.codec, "device", 0),
+                                                       align="zero")
+        return r
 
     # ---- text / attribute handling (:148-193)
     @staticmethod
@@ -126,17 +148,22 @@ class LightweightTtsPipeline:
                             layered_randomness=LayeredRandomnessConfig(), token_chunk_size=512)
         return TtsBatchRequest(self.manager._tokens(text), props, rg, rs, sargs, args.voice_id)
 
-    def generate_speech(self, args: LightweightTtsPipelineArgs) -> np.ndarray:
+    def generate_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None) -> np.ndarray:
+        """sample_rate None / 16000: the vocoder's 16 kHz PCM. Any other rate: that PCM resampled on
+        the GPU (resampler()); the failed-request second of silence is sample_rate zeros."""
+        rs = self.resampler(sample_rate)
         try:
             req = self._request(args)
         except ValueError:  # untokenisable text: the request fails -> empty result
             req = None
         g, s = self.manager.generate_tts_batch([req])[0] if req is not None else ([], [])
         if not g and not s:
-            return np.zeros(SAMPLE_RATE, dtype=np.float32)  # :828-830
-        return self.codec.decode_audio(g, s)
+            return np.zeros(rs.sr_out if rs else SAMPLE_RATE, dtype=np.float32)  # :828-830
+        pcm = self.codec.decode_audio(g, s)
+        return rs.resample(pcm) if rs else pcm
 
-    def stream_speech(self, args: LightweightTtsPipelineArgs, chunk_frames: int = 16):
+    def stream_speech(self, args: LightweightTtsPipelineArgs, chunk_frames: int = 16,
+                      sample_rate: Optional[int] = None):
         """generate_speech as a generator of float32 PCM chunks (SpeechChunk: an ndarray that also
         carries t0, t1, n_known, done), each decoded while the request is still generating tokens.
 
@@ -150,20 +177,29 @@ class LightweightTtsPipeline:
         decode steps instead of after the whole request, and a request that fails before any chunk
         yields the same one second of zeros. A request that fails after some chunks were yielded
         ends the stream there (its last item has done = False). An item's done says that the request
-        had finished when the chunk was decoded; the last chunk has done and t1 == n_known."""
+        had finished when the chunk was decoded; the last chunk has done and t1 == n_known.
+
+        sample_rate other than None / 16000: every chunk goes through one Resampler.stream(), which
+        is exact over chunks, so the items are resampled PCM whose concatenation is bitwise
+        generate_speech(args, sample_rate=...); an item then holds the outputs that became exact
+        with its frames (sinc_len / 2 = 128 input samples of look-ahead stay behind until the next
+        chunk or the end). t0, t1 and n_known stay in frames."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         try:
             req = self._request(args)
         except ValueError:  # untokenisable text: the request fails -> one second of silence
             req = None
-        return self.stream_request(req, chunk_frames)
+        return self.stream_request(req, chunk_frames, sample_rate=sample_rate)
 
-    def stream_request(self, req: Optional[TtsBatchRequest], chunk_frames: int = 16):
+    def stream_request(self, req: Optional[TtsBatchRequest], chunk_frames: int = 16,
+                       sample_rate: Optional[int] = None):
         """stream_speech for a request that is already built (None: a request that failed before it
         was submitted)."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
+        rs = self.resampler(sample_rate)
+        out_stream = rs.stream() if rs else None
         H = self.codec.halo()
         g, sem, t0, yielded, status = None, [], 0, False, 0
         it = self.manager.stream_tts(req) if req is not None else iter([(None, [], True)])
@@ -177,7 +213,8 @@ class LightweightTtsPipeline:
                     status = (self.manager.last_status or [0])[0]
                 if done and (status != 0 or (not g and not sem)):
                     if not yielded:
-                        yield SpeechChunk.make(np.zeros(SAMPLE_RATE, dtype=np.float32), 0, 0, 0, True)  # :828-830
+                        yield SpeechChunk.make(np.zeros(rs.sr_out if rs else SAMPLE_RATE, dtype=np.float32),
+                                               0, 0, 0, True)  # :828-830
                     return
                 if done and not sem:
                     self.codec.decode_audio(g, sem)  # (raises as generate_speech does: no semantic tokens)
@@ -190,12 +227,18 @@ class LightweightTtsPipeline:
                     pcm = self.codec.decode_windows([(g, sem, a, b, done) for a, b in wins])
                     for (a, b), p in zip(wins, pcm):
                         yielded = True
+                        if out_stream is not None:
+                            p = out_stream.feed(p, final=done and b == n)
                         yield SpeechChunk.make(p, a, b, n, done)
         finally:
             if hasattr(it, "close"):
                 it.close()  # (a stream left early: the ticket is released once the request has finished)
 
-    def generate_speech_batch(self, batch_args: Sequence[LightweightTtsPipelineArgs]) -> List[np.ndarray]:
+    def generate_speech_batch(self, batch_args: Sequence[LightweightTtsPipelineArgs],
+                              sample_rate: Optional[int] = None) -> List[np.ndarray]:
+        """sample_rate other than None / 16000: the whole batch is resampled in one resample_batch
+        call (a failed item stays an empty array)."""
+        rs = self.resampler(sample_rate)
         reqs, idx = [], []
         for i, a in enumerate(batch_args):
             try:
@@ -207,4 +250,5 @@ class LightweightTtsPipeline:
         results = [([], [])] * len(batch_args)
         for i, r in zip(idx, res):
             results[i] = r
-        return self.codec.decode_audio_batch(results)
+        pcm = self.codec.decode_audio_batch(results)
+        return rs.resample_batch(pcm) if rs else pcm

@@ -14,6 +14,9 @@
   (multipart voice_name / prompt_text / audio_file; the feature extraction needs the
   BiCodecTokenize + wav2vec2 encoders, whose graphs are absent: a pipeline may supply
   `reference_tokenizer`, otherwise the route answers the reference's extraction-failure body).
+* `sample_rate` in the body of both TTS routes (no reference counterpart: the reference emits
+  16 kHz only): one of SAMPLE_RATES, anything else a 400; the PCM is resampled on the GPU
+  (audio.Resampler) and the WAV header carries the rate. Without the field the routes are unchanged.
 * `handle_tts_stream(body, pipeline, voice_dir)` (no reference counterpart): the same request as a
   WAV stream, POST /api/tts/stream -- audio while the request is still decoding, at a fixed scale
   (no peak normalisation: that needs the whole utterance).
@@ -49,9 +52,14 @@ def convert_samples_to_wav(samples, sample_rate: int = 16000) -> bytes:
     return hdr + pcm.tobytes()
 
 
-def calculate_rtf(audio, processing_seconds: float) -> float:
-    dur = len(audio) / 16000.0
+def calculate_rtf(audio, processing_seconds: float, sample_rate: int = 16000) -> float:
+    dur = len(audio) / float(sample_rate)
     return processing_seconds / dur if dur > 0 else 0.0
+
+
+# `sample_rate` of the /api/tts and /api/tts/stream bodies (no reference counterpart: the reference
+# emits 16 kHz only): telephony, the vocoder's own rate, and what browsers / Opus / audio tools take
+SAMPLE_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
 
 
 def map_speed(speed) -> str:
@@ -102,15 +110,22 @@ def load_voice_feature(voice_dir: str, voice_id: str) -> dict:
 
 
 def _tts_args(body, voice_dir: str):
-    """The request body of /api/tts -> (None, LightweightTtsPipelineArgs), or ((status, payload), None)
-    for a body the handler refuses."""
+    """The request body of /api/tts -> (None, LightweightTtsPipelineArgs, sample_rate), or
+    ((status, payload), None, None) for a body the handler refuses. sample_rate: the body's optional
+    field, one of SAMPLE_RATES (16000 when absent)."""
     if isinstance(body, (bytes, str)):
         try:
             body = json.loads(body)
         except ValueError as e:
-            return (400, {"success": False, "error": f"JSON解析失败: {e}"}), None
+            return (400, {"success": False, "error": f"JSON解析失败: {e}"}), None, None
     if not isinstance(body, dict) or not isinstance(body.get("text"), str):
-        return (400, {"success": False, "error": "JSON解析失败: missing field `text`"}), None
+        return (400, {"success": False, "error": "JSON解析失败: missing field `text`"}), None, None
+    rate = body.get("sample_rate")
+    if rate is None:
+        rate = 16000
+    elif isinstance(rate, bool) or not isinstance(rate, int) or rate not in SAMPLE_RATES:
+        return (400, {"success": False, "error": f"不支持的采样率: {rate} (支持: "
+                                                 f"{', '.join(str(r) for r in SAMPLE_RATES)})"}), None, None
     voice_id = body.get("voice_id")
     voice = None
     prompt_from_voice = None
@@ -119,7 +134,7 @@ def _tts_args(body, voice_dir: str):
             voice = load_voice_feature(voice_dir, voice_id)
             prompt_from_voice = voice.get("prompt_text", "")
         except (OSError, ValueError) as e:
-            return (400, {"success": False, "error": f"音色ID '{voice_id}' 不存在或加载失败: {e}"}), None
+            return (400, {"success": False, "error": f"音色ID '{voice_id}' 不存在或加载失败: {e}"}), None, None
     prompt_text = prompt_from_voice if prompt_from_voice is not None else (body.get("prompt_text") or "")
     args = LightweightTtsPipelineArgs(
         text=body["text"], ref_audio_path="", zero_shot=voice_id is not None,
@@ -131,23 +146,25 @@ def _tts_args(body, voice_dir: str):
         speed=map_speed(body.get("speed")), prompt_text=prompt_text,
         voice_global_tokens=list(voice["global_tokens"]) if voice else None,
         voice_semantic_tokens=list(voice["semantic_tokens"]) if voice else None)
-    return None, args
+    return None, args, rate
 
 
 def handle_tts_json(body, pipeline, voice_dir: str = "assets/raf") -> Tuple[int, dict]:
     t0 = time.perf_counter()
-    err, args = _tts_args(body, voice_dir)
+    err, args, rate = _tts_args(body, voice_dir)
     if err:
         return err
     try:
-        audio = pipeline.generate_speech(args)
+        # (the keyword goes to the pipeline only for a rate other than its own: a body without
+        # sample_rate makes exactly the call it always made)
+        audio = pipeline.generate_speech(args) if rate == 16000 else pipeline.generate_speech(args, sample_rate=rate)
     except Exception as e:  # noqa: BLE001 -- rendered as the reference's 500 body
         return 500, {"success": False, "error": f"生成TTS音频失败: {e}"}
-    wav = convert_samples_to_wav(audio, 16000)
+    wav = convert_samples_to_wav(audio, rate)
     b64 = base64.standard_b64encode(wav).decode("ascii")
     total = time.perf_counter() - t0
     return 200, {"success": True, "message": "TTS生成成功", "audio_base64": b64,
-                 "duration_ms": int(total * 1000), "rtf": calculate_rtf(audio, total)}
+                 "duration_ms": int(total * 1000), "rtf": calculate_rtf(audio, total, rate)}
 
 
 def streaming_wav_header(sample_rate: int = 16000) -> bytes:
@@ -178,20 +195,23 @@ def handle_tts_stream(body, pipeline, voice_dir: str = "assets/raf", chunk_frame
     (convert_samples_to_wav): the peak rule needs the whole utterance, which a stream does not have
     when its first sample goes out -- the same request is therefore quieter or louder here than in
     /api/tts's WAV, by that rule's factor. Clamping and truncation are convert_samples_to_wav's.
+    An optional `sample_rate` (SAMPLE_RATES) streams that rate instead of 16 kHz: the chunks are
+    resampled on the GPU by a resampler that is exact over chunks, and the header carries the rate.
     A refused body gives /api/tts's status and JSON body (as one bytes item); so does a failure
     before the first chunk (500). A failure after the first chunk can only end the stream."""
-    err, args = _tts_args(body, voice_dir)
+    err, args, rate = _tts_args(body, voice_dir)
     if err:
         return err[0], iter([json.dumps(err[1], ensure_ascii=False).encode("utf-8")])
     try:
-        chunks = pipeline.stream_speech(args, chunk_frames=chunk_frames)
+        chunks = (pipeline.stream_speech(args, chunk_frames=chunk_frames) if rate == 16000 else
+                  pipeline.stream_speech(args, chunk_frames=chunk_frames, sample_rate=rate))
         first = next(chunks, None)  # before the status line goes out: a failure is still a 500
     except Exception as e:  # noqa: BLE001 -- rendered as the reference's 500 body
         payload = {"success": False, "error": f"生成TTS音频失败: {e}"}
         return 500, iter([json.dumps(payload, ensure_ascii=False).encode("utf-8")])
 
     def gen():
-        yield streaming_wav_header(16000)
+        yield streaming_wav_header(rate)
         if first is not None:
             yield samples_to_pcm16(first)
         for c in chunks:
