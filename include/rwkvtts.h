@@ -594,6 +594,89 @@ int rwkvtts_resample_windows(rwkvtts_resampler* r, const rwkvtts_resample_window
 /* HIP-event time of the last launch's kernel alone (no copies), in ms; 0 before the first launch. */
 int rwkvtts_resampler_kernel_ms(rwkvtts_resampler* r, double* ms);
 
+/* ---- time stretch: pitch-preserving time-scale modification (WSOLA, waveform-similarity
+ * overlap-add) on the GPU, the `tempo` of the pipeline (no reference counterpart: the reference's
+ * only rate control is the `speed` property token) ----------------------------------------------
+ * Rate-agnostic; the pipeline applies it to the vocoder's 16 kHz PCM, before any resampling.
+ * The arithmetic contract (every output bit is defined by IEEE f32 add, subtract and multiply: no
+ * division, no square root):
+ *   W, Hs, D  window (even), synthesis hop Hs = W/2, search radius
+ *   tempo     double, per signal, 0.25 .. 4.0; above 1 is faster speech
+ *   window    w[i] = (float)(0.5 - 0.5 * cos(2 * pi * i / W)), in double, i in [0, W)
+ *   n_out     = (int64)ceil((double)n / tempo), 0 for n = 0
+ *   frames    M = ceil(n_out / Hs) blocks; frames m = -1, 0, .. M-1 start at input sample s_m:
+ *             s_-1 = -Hs, s_0 = 0; for m >= 1 the anchor is a_m = (int64)floor((double)(m * Hs) * tempo)
+ *             (one double multiply) and s_m = a_m + shift_m
+ *   search    (m >= 1) template t[i] = x[s_{m-1} + Hs + i], i in [0, Hs): where frame m-1 would go on.
+ *             Candidate shifts in [-D, D), ranked k = 0, 1, 2, .. for 0, -1, +1, -2, +2, ..,
+ *             -(D-1), +(D-1), -D. d(shift) = sum_i (t[i] - x[a_m + shift + i])^2: a sequential f32
+ *             sum in ascending i starting from +0, each term one rounded subtract, one rounded
+ *             multiply and one rounded add (never fused). shift_m has the smallest d and, among
+ *             equal d, the lowest rank; a NaN d counts as +inf. As d >= 0 otherwise, the key
+ *             (f32 bits of d) << 32 | k is totally ordered as an unsigned 64-bit integer: the winner
+ *             is its minimum, whatever the reduction tree.
+ *   output    block j covers o in [j * Hs, (j+1) * Hs) below n_out; with i = o - j * Hs:
+ *             y[o] = w[Hs + i] * x[s_{j-1} + Hs + i] + w[i] * x[s_j + i]: two rounded multiplies and
+ *             one rounded add, the earlier frame's product on the left
+ *   zeros     every read of x outside [0, n) is +0
+ * So on silence every shift is 0, and at tempo 1.0 every shift is 0 (d(0) = 0 exactly) and the output
+ * differs from the input by the rounding of w[Hs + i] + w[i] alone. */
+typedef struct {
+  uint32_t struct_size;
+  int32_t window; /* W: even, 32 .. 2048; 0 = 512 */
+  int32_t search; /* D: 1 .. 1024; 0 = 128 (0 is the default, not a radius: negative is out of range) */
+} rwkvtts_tsm_desc;
+/* The window table (host only): out[W]. Anything outside the ranges above, and a tempo outside
+ * 0.25 .. 4.0 (NaN included), is RWKVTTS_EINVAL, here and in every call that takes a desc or a tempo. */
+int rwkvtts_tsm_window(const rwkvtts_tsm_desc* desc, float* out);
+/* ceil(n_in / tempo) (host only); -1 for a bad desc, a bad tempo or n_in < 0. */
+int64_t rwkvtts_tsm_out_len(const rwkvtts_tsm_desc* desc, double tempo, int64_t n_in);
+/* Streaming plan (host only, a pure function). With samples [0, n_known) of a signal known, blocks
+ * [0, block_first) done and s_prev = s_{block_first - 1} (-Hs for block_first 0; anything that is no
+ * possible start of that frame is RWKVTTS_EINVAL):
+ * *out_ready_end = the end (an output index, a multiple of Hs) of the ready blocks from block_first
+ * on, block_first * Hs if there is none. A block is ready when every sample that its two frames'
+ * searches and its own products can read lies below n_known -- for block block_first that is
+ * max(s_prev + 2 Hs, a_m + D + Hs - 1), for a later block the same with the highest start its earlier
+ * frame can take, a_{m-1} + D - 1 -- and the block lies wholly below out_len(n_known). So block j is
+ * ready at the latest when ceil((j+1) * Hs * tempo) + D + 2 Hs <= n_known. With final (n_known is the
+ * signal's length) it is out_len(n_known).
+ * *in_first_needed = max(0, min(s_prev + Hs, a_block_first - D)): samples before it are never read
+ * again -- the tail a stream must keep, fewer than 2 D + 2 Hs * max(tempo, 1) + 2 samples once the
+ * ready blocks are out. Either pointer may be NULL. Monotone in n_known. */
+int rwkvtts_tsm_plan(const rwkvtts_tsm_desc* desc, double tempo, int64_t n_known, int final, int64_t block_first,
+                     int64_t s_prev, int64_t* out_ready_end, int64_t* in_first_needed);
+typedef struct rwkvtts_tsm rwkvtts_tsm;
+/* table == NULL: the window of rwkvtts_tsm_window; otherwise the caller's [W] table (copied). */
+int rwkvtts_tsm_create(int device, const rwkvtts_tsm_desc* desc, const float* table, rwkvtts_tsm** out);
+int rwkvtts_tsm_destroy(rwkvtts_tsm* t);
+/* n signals (ragged), each with its own tempo, in one launch pair (search, overlap-add): one
+ * workgroup walks a signal's frames in order. Host buffers; out[i] has capacity
+ * out_len(tempo[i], n_in[i]). n_in[i] == 0 writes nothing. Calls on one handle serialise on its lock. */
+int rwkvtts_tsm_batch(rwkvtts_tsm* t, const float* const* in, const int64_t* n_in, const double* tempo, int n,
+                      float* const* out);
+typedef struct {
+  uint32_t struct_size;
+  const float* in;     /* points at sample in_first of the signal */
+  int64_t in_first;
+  int64_t n_in;
+  int32_t final;       /* 1: in_first + n_in is the signal's length */
+  double tempo;
+  int64_t block_first; /* outputs [block_first * Hs, block_first * Hs + out_count) */
+  int64_t s_prev;      /* s_{block_first - 1}: -Hs for block_first 0, else the last call's s_last */
+  int64_t out_count;
+  float* out;          /* capacity out_count */
+  int64_t s_last;      /* out: the start of the last frame used (s_prev if out_count is 0) */
+} rwkvtts_tsm_window_t;
+/* n windows (of any signals, any tempos) in one launch pair: outputs [block_first * Hs, + out_count)
+ * of the whole-signal result, bitwise, whatever follows the known samples. RWKVTTS_EINVAL before
+ * anything is launched (and nothing written, s_last included) if a window asks for more than
+ * rwkvtts_tsm_plan allows: block_first * Hs + out_count > out_ready_end(in_first + n_in, final,
+ * block_first, s_prev), in_first > in_first_needed, or an impossible s_prev. */
+int rwkvtts_tsm_windows(rwkvtts_tsm* t, rwkvtts_tsm_window_t* w, int n);
+/* HIP-event time of the last launch pair (both kernels, no copies), in ms; 0 before the first. */
+int rwkvtts_tsm_kernel_ms(rwkvtts_tsm* t, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,17 @@ class ResampleWindow(ctypes.Structure):
                 ("out_count", ctypes.c_int64), ("out", ctypes.c_void_p)]
 
 
+class TsmDesc(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("window", ctypes.c_int32), ("search", ctypes.c_int32)]
+
+
+class TsmWindow(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("in_", ctypes.c_void_p), ("in_first", ctypes.c_int64),
+                ("n_in", ctypes.c_int64), ("final", ctypes.c_int32), ("tempo", ctypes.c_double),
+                ("block_first", ctypes.c_int64), ("s_prev", ctypes.c_int64), ("out_count", ctypes.c_int64),
+                ("out", ctypes.c_void_p), ("s_last", ctypes.c_int64)]
+
+
 # Every symbol include/rwkvtts.h declares (checked by tests/test_abi.py against the header).
 EXPORTS = {
     "rwkvtts_synth_weights": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p]),
@@ -256,6 +267,19 @@ EXPORTS = {
                                               ctypes.c_void_p]),
     "rwkvtts_resample_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ResampleWindow), ctypes.c_int]),
     "rwkvtts_resampler_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    # time stretch (WSOLA): window, plan (host only), batched / exact stream windows
+    "rwkvtts_tsm_window": (ctypes.c_int, [ctypes.POINTER(TsmDesc), ctypes.c_void_p]),
+    "rwkvtts_tsm_out_len": (ctypes.c_int64, [ctypes.POINTER(TsmDesc), ctypes.c_double, ctypes.c_int64]),
+    "rwkvtts_tsm_plan": (ctypes.c_int, [ctypes.POINTER(TsmDesc), ctypes.c_double, ctypes.c_int64, ctypes.c_int,
+                                        ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                                        ctypes.POINTER(ctypes.c_int64)]),
+    "rwkvtts_tsm_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(TsmDesc), ctypes.c_void_p,
+                                          ctypes.POINTER(ctypes.c_void_p)]),
+    "rwkvtts_tsm_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "rwkvtts_tsm_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_int, ctypes.c_void_p]),
+    "rwkvtts_tsm_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TsmWindow), ctypes.c_int]),
+    "rwkvtts_tsm_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None

@@ -19,6 +19,11 @@ and the clip / silence helpers it uses), feeding the HIP mel kernel (features.py
   reference WAV): the same restatement as a HIP kernel (csrc/resample.hip), one-shot, batched and
   exact over stream chunks, with rubato's alignment or none. The kernel is pinned bitwise to the
   restatement's arithmetic contract (include/rwkvtts.h), not to rubato: parity stays unpinned.
+* `TimeStretcher` (no reference counterpart: the reference's only rate control is the `speed`
+  property token): pitch-preserving time-scale modification (WSOLA) as HIP kernels (csrc/tsm.hip),
+  one-shot, batched with a tempo per signal, and exact over stream chunks. Its arithmetic contract
+  (include/rwkvtts.h) has no division and no square root; the kernels are pinned
+  bitwise to its numpy restatement (tests/tsm_ref.py).
 """
 import ctypes
 import struct
@@ -291,6 +296,180 @@ class ResampleStream:
             self._closed, self._tail = True, np.zeros(0, dtype=F32)
             return out
         _, first = self.r.plan(n_known, False, self._out_next)
+        first = min(first, n_known)
+        if first > self._tail_first:
+            self._tail = self._tail[first - self._tail_first:].copy()
+            self._tail_first = first
+        return out
+
+
+# ---- time stretch on the GPU -----------------------------------------------------------------
+def _tsm_window(window: int) -> np.ndarray:
+    """w[i] = (float)(0.5 - 0.5 * cos(2 * pi * i / W)), in double: the table both sides read."""
+    i = np.arange(window, dtype=np.float64)
+    return (0.5 - 0.5 * np.cos(2.0 * np.pi * i / float(window))).astype(F32)
+
+
+class TimeStretcher:
+    """Pitch-preserving time-scale modification (WSOLA) as HIP kernels (csrc/tsm.hip; the arithmetic
+    contract is in include/rwkvtts.h): tempo 0.25 .. 4.0 per signal, above 1 is faster speech; the
+    output has ceil(n / tempo) samples. One-shot, batched (a tempo per signal in one launch) and exact
+    over stream chunks. Rate-agnostic: the pipeline applies it at 16 kHz, before any resampling.
+
+    window (even, 32 .. 2048) and search (1 .. 1024): the Hann window W and the search radius D in
+    samples; 0 means the default (512 / 128) as in the C desc. The kernels read the table
+    `_tsm_window` builds, so both sides read one table.
+
+    evaluator: a callable (stretcher, items) -> [(ndarray, s_last)] standing in for the native window
+    call, items being [(samples from in_first on, in_first, final, tempo, block_first, s_prev,
+    out_count)]; no GPU object is created then (the host-only plan / out_len entry points are still
+    the library's)."""
+
+    def __init__(self, device: int = 0, window: int = 512, search: int = 128, evaluator=None):
+        self.device = int(device)
+        self._desc = _ffi.TsmDesc(struct_size=ctypes.sizeof(_ffi.TsmDesc), window=int(window), search=int(search))
+        self._h = None
+        self._evaluator = evaluator
+        # one native call at a time: the stretcher owns one stream and one set of device buffers
+        self._lock = threading.Lock()
+        self.out_len(0, 1.0)  # (refuses a bad description before anything is built)
+        self.window = int(window) or 512
+        self.search = int(search) or 128
+        self.hop = self.window // 2
+        self.table = _tsm_window(self.window)
+        if evaluator is None:
+            h = ctypes.c_void_p()
+            _ffi.check(_ffi.lib().rwkvtts_tsm_create(self.device, ctypes.byref(self._desc),
+                                                     self.table.ctypes.data_as(ctypes.c_void_p), ctypes.byref(h)),
+                       "tsm_create")
+            self._h = h
+
+    def close(self):
+        if self._h:
+            _ffi.lib().rwkvtts_tsm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- host-only plan ----
+    def out_len(self, n_in: int, tempo: float) -> int:
+        n = int(_ffi.lib().rwkvtts_tsm_out_len(ctypes.byref(self._desc), float(tempo), int(n_in)))
+        if n < 0:
+            raise _ffi.RwkvTtsError(_ffi.EINVAL, "tsm_out_len")
+        return n
+
+    def plan(self, tempo: float, n_known: int, final: bool, block_first: int = 0, s_prev=None):
+        """(out_ready_end, in_first_needed) of rwkvtts_tsm_plan; s_prev None: -hop (block_first 0)."""
+        end, first = ctypes.c_int64(), ctypes.c_int64()
+        _ffi.check(_ffi.lib().rwkvtts_tsm_plan(ctypes.byref(self._desc), float(tempo), int(n_known),
+                                               1 if final else 0, int(block_first),
+                                               -self.hop if s_prev is None else int(s_prev),
+                                               ctypes.byref(end), ctypes.byref(first)), "tsm_plan")
+        return end.value, first.value
+
+    # ---- the kernels ----
+    def stretch_windows(self, items) -> list:
+        """[(samples from in_first on, in_first, final, tempo, block_first, s_prev, out_count)] ->
+        [(outputs [block_first * hop, + out_count) of the whole-signal result, s_last)], all windows
+        in one launch pair. Raises RwkvTtsError(EINVAL), with nothing computed, if a window asks for
+        more than plan() allows."""
+        items = [(np.ascontiguousarray(x, dtype=F32).reshape(-1), int(a), bool(f), float(t), int(b), int(s), int(c))
+                 for x, a, f, t, b, s, c in items]
+        if self._evaluator is not None:
+            return [(np.ascontiguousarray(y, dtype=F32), int(s)) for y, s in self._evaluator(self, items)]
+        n = len(items)
+        if n == 0:
+            return []
+        ws = (_ffi.TsmWindow * n)()
+        outs = []
+        for w, (x, in_first, final, tempo, block_first, s_prev, count) in zip(ws, items):
+            out = np.empty(max(count, 0), dtype=F32)
+            outs.append(out)
+            w.struct_size = ctypes.sizeof(_ffi.TsmWindow)
+            w.in_, w.in_first, w.n_in, w.final, w.tempo = x.ctypes.data, in_first, x.size, 1 if final else 0, tempo
+            w.block_first, w.s_prev, w.out_count, w.out = block_first, s_prev, count, out.ctypes.data
+        with self._lock:
+            _ffi.check(_ffi.lib().rwkvtts_tsm_windows(self._h, ws, n), "tsm_windows")
+        return [(o, int(w.s_last)) for o, w in zip(outs, ws)]
+
+    def stretch_batch(self, signals, tempos) -> list:
+        """[signal], [tempo] -> [stretched signal], ragged, a tempo per signal, in one launch pair."""
+        xs = [np.ascontiguousarray(x, dtype=F32).reshape(-1) for x in signals]
+        ts = [float(t) for t in tempos]
+        if len(xs) != len(ts):
+            raise ValueError("stretch_batch: one tempo per signal")
+        if self._evaluator is not None:
+            return [y for y, _ in self.stretch_windows([(x, 0, True, t, 0, -self.hop, self.out_len(x.size, t))
+                                                        for x, t in zip(xs, ts)])]
+        n = len(xs)
+        if n == 0:
+            return []
+        outs = [np.empty(self.out_len(x.size, t), dtype=F32) for x, t in zip(xs, ts)]
+        P = ctypes.c_void_p * n
+        ins, ous = P(*[x.ctypes.data for x in xs]), P(*[o.ctypes.data for o in outs])
+        lens = (ctypes.c_int64 * n)(*[x.size for x in xs])
+        tem = (ctypes.c_double * n)(*ts)
+        with self._lock:
+            _ffi.check(_ffi.lib().rwkvtts_tsm_batch(self._h, ins, lens, tem, n, ous), "tsm_batch")
+        return outs
+
+    def stretch(self, x, tempo: float) -> np.ndarray:
+        return self.stretch_batch([x], [tempo])[0]
+
+    def kernel_ms(self) -> float:
+        """HIP-event time of the last launch pair (search + overlap-add, no copies)."""
+        ms = ctypes.c_double()
+        _ffi.check(_ffi.lib().rwkvtts_tsm_kernel_ms(self._h, ctypes.byref(ms)), "tsm_kernel_ms")
+        return ms.value
+
+    def stream(self, tempo: float) -> "TimeStretchStream":
+        return TimeStretchStream(self, tempo)
+
+
+class TimeStretchStream:
+    """TimeStretcher.stream(tempo): feed(pcm_chunk, final=False) -> the blocks that became exact with
+    it. The concatenation of what feed returns is bitwise TimeStretcher.stretch(the concatenated
+    input, tempo), however the input was cut. Only the tail rwkvtts_tsm_plan asks for is kept: fewer
+    than 2 * search + window * max(tempo, 1) + 2 samples."""
+
+    def __init__(self, stretcher: TimeStretcher, tempo: float):
+        self.t = stretcher
+        self.tempo = float(tempo)
+        stretcher.out_len(0, self.tempo)  # (refuses a bad tempo)
+        self._tail = np.zeros(0, dtype=F32)
+        self._tail_first = 0              # signal index of _tail[0]
+        self._block_next = 0              # blocks [0, _block_next) went out
+        self._s_prev = -stretcher.hop     # start of frame _block_next - 1
+        self._closed = False
+
+    @property
+    def kept(self) -> int:
+        return int(self._tail.size)
+
+    def feed(self, pcm_chunk, final: bool = False) -> np.ndarray:
+        if self._closed:
+            raise ValueError("the stream has ended (a chunk was fed with final=True)")
+        x = np.asarray(pcm_chunk, dtype=F32).reshape(-1)
+        if x.size:
+            self._tail = np.concatenate([self._tail, x])
+        hop = self.t.hop
+        n_known = self._tail_first + self._tail.size
+        end, _ = self.t.plan(self.tempo, n_known, final, self._block_next, self._s_prev)
+        count = end - self._block_next * hop
+        if count > 0:
+            out, self._s_prev = self.t.stretch_windows([(self._tail, self._tail_first, final, self.tempo,
+                                                         self._block_next, self._s_prev, count)])[0]
+            self._block_next += -(-count // hop)
+        else:
+            out = np.zeros(0, dtype=F32)
+        if final:
+            self._closed, self._tail = True, np.zeros(0, dtype=F32)
+            return out
+        _, first = self.t.plan(self.tempo, n_known, False, self._block_next, self._s_prev)
         first = min(first, n_known)
         if first > self._tail_first:
             self._tail = self._tail[first - self._tail_first:].copy()

@@ -10,6 +10,10 @@ spawn_blocking tasks return vec![]).
 generate_speech, generate_speech_batch and stream_speech take `sample_rate` (no reference counterpart:
 the reference emits 16 kHz only): None / 16000 is the vocoder's PCM as it is; any other rate is that
 PCM resampled on the GPU with zero alignment (audio.Resampler), exact over stream chunks.
+The same four entry points take `tempo` (no reference counterpart: the reference's only rate control
+is the `speed` property token, which a cloned voice does not get): None / 1.0 leaves the PCM as it
+is; any other value in 0.25 .. 4.0 (above 1 is faster speech) stretches the 16 kHz PCM on the GPU
+without changing its pitch (audio.TimeStretcher), before any resampling, exact over stream chunks.
 
 The voice store lookup by voice_id inside the pipeline (`VoiceFeatureManager::new("./raf")`,
 :751) goes through `voices.VoiceFeatureManager` on `raf_dir` (the server passes the
@@ -77,6 +81,7 @@ class LightweightTtsPipeline:
         self.reference_tokenizer = reference_tokenizer
         self._resamplers = {}  # output rate -> audio.Resampler (created on first use, kept)
         self._resamplers_lock = threading.Lock()  # (the server's worker threads share the pipeline)
+        self._stretcher = None  # audio.TimeStretcher (created on the first tempo other than 1.0, kept)
 
     # ---- output rates other than 16 kHz (no reference counterpart: the reference emits 16 kHz only)
     def resampler(self, sample_rate: Optional[int]):
@@ -93,6 +98,21 @@ class LightweightTtsPipeline:
                 r = self._resamplers[rate] = Resampler(SAMPLE_RATE, rate, device=getattr(self.codec, "device", 0),
                                                        align="zero")
         return r
+
+    # ---- speaking rate (no reference counterpart: the reference has the `speed` property token only)
+    def stretcher(self, tempo: Optional[float]):
+        """None for None / 1.0 (nothing is created: the PCM is the vocoder's); otherwise the
+        pipeline's one TimeStretcher, on the codec's GPU. A tempo outside 0.25 .. 4.0 raises
+        ValueError before anything is generated."""
+        if tempo is None or float(tempo) == 1.0:
+            return None
+        if not 0.25 <= float(tempo) <= 4.0:  # (NaN fails)
+            raise ValueError("tempo must be in [0.25, 4.0]")
+        with self._resamplers_lock:
+            if self._stretcher is None:
+                from .audio import TimeStretcher
+                self._stretcher = TimeStretcher(device=getattr(self.codec, "device", 0))
+        return self._stretcher
 
     # ---- text / attribute handling (:148-193)
     @staticmethod
@@ -148,10 +168,14 @@ class LightweightTtsPipeline:
                             layered_randomness=LayeredRandomnessConfig(), token_chunk_size=512)
         return TtsBatchRequest(self.manager._tokens(text), props, rg, rs, sargs, args.voice_id)
 
-    def generate_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None) -> np.ndarray:
+    def generate_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
+                        tempo: Optional[float] = None) -> np.ndarray:
         """sample_rate None / 16000: the vocoder's 16 kHz PCM. Any other rate: that PCM resampled on
-        the GPU (resampler()); the failed-request second of silence is sample_rate zeros."""
+        the GPU (resampler()); the failed-request second of silence is sample_rate zeros.
+        tempo None / 1.0: nothing. Any other: the 16 kHz PCM time-stretched on the GPU (stretcher())
+        before the resampler; the failed-request second of silence is not stretched."""
         rs = self.resampler(sample_rate)
+        ts = self.stretcher(tempo)
         try:
             req = self._request(args)
         except ValueError:  # untokenisable text: the request fails -> empty result
@@ -160,10 +184,12 @@ class LightweightTtsPipeline:
         if not g and not s:
             return np.zeros(rs.sr_out if rs else SAMPLE_RATE, dtype=np.float32)  # :828-830
         pcm = self.codec.decode_audio(g, s)
+        if ts:
+            pcm = ts.stretch(pcm, tempo)
         return rs.resample(pcm) if rs else pcm
 
     def stream_speech(self, args: LightweightTtsPipelineArgs, chunk_frames: int = 16,
-                      sample_rate: Optional[int] = None):
+                      sample_rate: Optional[int] = None, tempo: Optional[float] = None):
         """generate_speech as a generator of float32 PCM chunks (SpeechChunk: an ndarray that also
         carries t0, t1, n_known, done), each decoded while the request is still generating tokens.
 
@@ -183,23 +209,30 @@ class LightweightTtsPipeline:
         is exact over chunks, so the items are resampled PCM whose concatenation is bitwise
         generate_speech(args, sample_rate=...); an item then holds the outputs that became exact
         with its frames (sinc_len / 2 = 128 input samples of look-ahead stay behind until the next
-        chunk or the end). t0, t1 and n_known stay in frames."""
+        chunk or the end). t0, t1 and n_known stay in frames.
+
+        tempo other than None / 1.0: every vocoder chunk first goes through one
+        TimeStretcher.stream(tempo), exact over chunks as well, then through the resampler's stream
+        if there is one: the concatenation is bitwise generate_speech(args, tempo=..., sample_rate=...).
+        An item then holds the stretched blocks that became exact with its frames (it may be empty)."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         try:
             req = self._request(args)
         except ValueError:  # untokenisable text: the request fails -> one second of silence
             req = None
-        return self.stream_request(req, chunk_frames, sample_rate=sample_rate)
+        return self.stream_request(req, chunk_frames, sample_rate=sample_rate, tempo=tempo)
 
     def stream_request(self, req: Optional[TtsBatchRequest], chunk_frames: int = 16,
-                       sample_rate: Optional[int] = None):
+                       sample_rate: Optional[int] = None, tempo: Optional[float] = None):
         """stream_speech for a request that is already built (None: a request that failed before it
         was submitted)."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         rs = self.resampler(sample_rate)
         out_stream = rs.stream() if rs else None
+        ts = self.stretcher(tempo)
+        tempo_stream = ts.stream(tempo) if ts else None
         H = self.codec.halo()
         g, sem, t0, yielded, status = None, [], 0, False, 0
         it = self.manager.stream_tts(req) if req is not None else iter([(None, [], True)])
@@ -227,6 +260,8 @@ class LightweightTtsPipeline:
                     pcm = self.codec.decode_windows([(g, sem, a, b, done) for a, b in wins])
                     for (a, b), p in zip(wins, pcm):
                         yielded = True
+                        if tempo_stream is not None:
+                            p = tempo_stream.feed(p, final=done and b == n)
                         if out_stream is not None:
                             p = out_stream.feed(p, final=done and b == n)
                         yield SpeechChunk.make(p, a, b, n, done)
@@ -235,10 +270,12 @@ class LightweightTtsPipeline:
                 it.close()  # (a stream left early: the ticket is released once the request has finished)
 
     def generate_speech_batch(self, batch_args: Sequence[LightweightTtsPipelineArgs],
-                              sample_rate: Optional[int] = None) -> List[np.ndarray]:
+                              sample_rate: Optional[int] = None, tempo: Optional[float] = None) -> List[np.ndarray]:
         """sample_rate other than None / 16000: the whole batch is resampled in one resample_batch
-        call (a failed item stays an empty array)."""
+        call (a failed item stays an empty array). tempo other than None / 1.0: the whole batch is
+        first stretched in one stretch_batch call, one tempo for the call."""
         rs = self.resampler(sample_rate)
+        ts = self.stretcher(tempo)
         reqs, idx = [], []
         for i, a in enumerate(batch_args):
             try:
@@ -251,4 +288,6 @@ class LightweightTtsPipeline:
         for i, r in zip(idx, res):
             results[i] = r
         pcm = self.codec.decode_audio_batch(results)
+        if ts:
+            pcm = ts.stretch_batch(pcm, [tempo] * len(pcm))
         return rs.resample_batch(pcm) if rs else pcm

@@ -17,6 +17,14 @@
 * `sample_rate` in the body of both TTS routes (no reference counterpart: the reference emits
   16 kHz only): one of SAMPLE_RATES, anything else a 400; the PCM is resampled on the GPU
   (audio.Resampler) and the WAV header carries the rate. Without the field the routes are unchanged.
+* `tempo` in the body of both TTS routes (no reference counterpart): a JSON number in
+  [TEMPO_MIN, TEMPO_MAX] = [0.5, 2.0], anything else a 400; above 1 is faster speech. It is not
+  `speed`: `speed` keeps the reference's meaning, the model's five-bucket property token, which
+  changes how the model speaks and which a request with a `voice_id` does not get at all
+  (pipeline.generate_property_tokens returns no property tokens for a cloned voice); `tempo` is a
+  continuous rate applied to the finished 16 kHz PCM by a pitch-preserving time stretch on the GPU
+  (audio.TimeStretcher), before any resampling, and works for every voice. Without the field (or
+  with 1.0) the routes are unchanged.
 * `handle_tts_stream(body, pipeline, voice_dir)` (no reference counterpart): the same request as a
   WAV stream, POST /api/tts/stream -- audio while the request is still decoding, at a fixed scale
   (no peak normalisation: that needs the whole utterance).
@@ -60,6 +68,9 @@ def calculate_rtf(audio, processing_seconds: float, sample_rate: int = 16000) ->
 # `sample_rate` of the /api/tts and /api/tts/stream bodies (no reference counterpart: the reference
 # emits 16 kHz only): telephony, the vocoder's own rate, and what browsers / Opus / audio tools take
 SAMPLE_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
+# `tempo` of the same bodies (no reference counterpart): the range in which the time stretch still
+# sounds like speech; the kernel itself takes 0.25 .. 4.0
+TEMPO_MIN, TEMPO_MAX = 0.5, 2.0
 
 
 def map_speed(speed) -> str:
@@ -110,9 +121,11 @@ def load_voice_feature(voice_dir: str, voice_id: str) -> dict:
 
 
 def _tts_args(body, voice_dir: str):
-    """The request body of /api/tts -> (None, LightweightTtsPipelineArgs, sample_rate), or
-    ((status, payload), None, None) for a body the handler refuses. sample_rate: the body's optional
-    field, one of SAMPLE_RATES (16000 when absent)."""
+    """The request body of /api/tts -> (None, LightweightTtsPipelineArgs, keywords), or
+    ((status, payload), None, None) for a body the handler refuses. keywords: what the pipeline call
+    takes beyond the args, each only when the body sets it to something other than its default --
+    sample_rate (one of SAMPLE_RATES, not 16000) and tempo (TEMPO_MIN .. TEMPO_MAX, not 1.0) -- so a
+    body without them makes exactly the call it always made."""
     if isinstance(body, (bytes, str)):
         try:
             body = json.loads(body)
@@ -126,6 +139,13 @@ def _tts_args(body, voice_dir: str):
     elif isinstance(rate, bool) or not isinstance(rate, int) or rate not in SAMPLE_RATES:
         return (400, {"success": False, "error": f"不支持的采样率: {rate} (支持: "
                                                  f"{', '.join(str(r) for r in SAMPLE_RATES)})"}), None, None
+    tempo = body.get("tempo")
+    if tempo is None:
+        tempo = 1.0
+    elif (isinstance(tempo, bool) or not isinstance(tempo, (int, float))
+          or not TEMPO_MIN <= tempo <= TEMPO_MAX):  # (NaN fails the comparison)
+        return (400, {"success": False, "error": f"不支持的语速倍率: {tempo} (支持: "
+                                                 f"{TEMPO_MIN} - {TEMPO_MAX})"}), None, None
     voice_id = body.get("voice_id")
     voice = None
     prompt_from_voice = None
@@ -146,18 +166,22 @@ def _tts_args(body, voice_dir: str):
         speed=map_speed(body.get("speed")), prompt_text=prompt_text,
         voice_global_tokens=list(voice["global_tokens"]) if voice else None,
         voice_semantic_tokens=list(voice["semantic_tokens"]) if voice else None)
-    return None, args, rate
+    kw = {}
+    if rate != 16000:
+        kw["sample_rate"] = rate
+    if float(tempo) != 1.0:
+        kw["tempo"] = float(tempo)
+    return None, args, kw
 
 
 def handle_tts_json(body, pipeline, voice_dir: str = "assets/raf") -> Tuple[int, dict]:
     t0 = time.perf_counter()
-    err, args, rate = _tts_args(body, voice_dir)
+    err, args, kw = _tts_args(body, voice_dir)
     if err:
         return err
+    rate = kw.get("sample_rate", 16000)
     try:
-        # (the keyword goes to the pipeline only for a rate other than its own: a body without
-        # sample_rate makes exactly the call it always made)
-        audio = pipeline.generate_speech(args) if rate == 16000 else pipeline.generate_speech(args, sample_rate=rate)
+        audio = pipeline.generate_speech(args, **kw)
     except Exception as e:  # noqa: BLE001 -- rendered as the reference's 500 body
         return 500, {"success": False, "error": f"生成TTS音频失败: {e}"}
     wav = convert_samples_to_wav(audio, rate)
@@ -199,12 +223,12 @@ def handle_tts_stream(body, pipeline, voice_dir: str = "assets/raf", chunk_frame
     resampled on the GPU by a resampler that is exact over chunks, and the header carries the rate.
     A refused body gives /api/tts's status and JSON body (as one bytes item); so does a failure
     before the first chunk (500). A failure after the first chunk can only end the stream."""
-    err, args, rate = _tts_args(body, voice_dir)
+    err, args, kw = _tts_args(body, voice_dir)
     if err:
         return err[0], iter([json.dumps(err[1], ensure_ascii=False).encode("utf-8")])
+    rate = kw.get("sample_rate", 16000)
     try:
-        chunks = (pipeline.stream_speech(args, chunk_frames=chunk_frames) if rate == 16000 else
-                  pipeline.stream_speech(args, chunk_frames=chunk_frames, sample_rate=rate))
+        chunks = pipeline.stream_speech(args, chunk_frames=chunk_frames, **kw)
         first = next(chunks, None)  # before the status line goes out: a failure is still a 500
     except Exception as e:  # noqa: BLE001 -- rendered as the reference's 500 body
         payload = {"success": False, "error": f"生成TTS音频失败: {e}"}
@@ -212,10 +236,13 @@ def handle_tts_stream(body, pipeline, voice_dir: str = "assets/raf", chunk_frame
 
     def gen():
         yield streaming_wav_header(rate)
-        if first is not None:
+        # (with `tempo` an item may be empty, its blocks waiting for the next chunk's samples: an empty
+        # body part would read as the end of a chunked response, so it is not sent)
+        if first is not None and len(first):
             yield samples_to_pcm16(first)
         for c in chunks:
-            yield samples_to_pcm16(c)
+            if len(c):
+                yield samples_to_pcm16(c)
     return 200, gen()
 
 
