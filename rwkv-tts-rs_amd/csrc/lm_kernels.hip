@@ -566,10 +566,14 @@ __global__ __launch_bounds__(256) void k_gemm(GemmArgs a) {
   }
   __syncthreads();
   if (gst) gst[1] = __builtin_amdgcn_s_memtime();
-  // 3) MFMA over the slice
-  float4_ acc[MT];
+  // 3) MFMA over the slice: the hi and the lo plane in chains of their own, added at the end --
+  // k_gemm2's and k_gemm_wide's order of summation, so that this fallback gives their bits. (An
+  // engine runs one GEMM through both: a bf16 value GEMM whose key split has no fused k_gemm2
+  // form stages relu^2 here up to kPlaneRows rows and takes the planes route above them, and the
+  // outputs are promised chunk-invariant.)
+  float4_ acc[MT], acc_l[MT];
 #pragma unroll
-  for (int m = 0; m < MT; ++m) acc[m] = (float4_){0.f, 0.f, 0.f, 0.f};
+  for (int m = 0; m < MT; ++m) acc[m] = acc_l[m] = (float4_){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int t = 0; t < KSTEPS; ++t) {
 #pragma unroll
@@ -580,16 +584,18 @@ __global__ __launch_bounds__(256) void k_gemm(GemmArgs a) {
       if constexpr (F16) {
         acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ah),
                                                         __builtin_bit_cast(f16x8, b[t]), acc[m], 0, 0, 0);
-        acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, al),
-                                                        __builtin_bit_cast(f16x8, b[t]), acc[m], 0, 0, 0);
+        acc_l[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, al),
+                                                          __builtin_bit_cast(f16x8, b[t]), acc_l[m], 0, 0, 0);
       } else {
         acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ah),
                                                          __builtin_bit_cast(bf16x8, b[t]), acc[m], 0, 0, 0);
-        acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, al),
-                                                         __builtin_bit_cast(bf16x8, b[t]), acc[m], 0, 0, 0);
+        acc_l[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, al),
+                                                           __builtin_bit_cast(bf16x8, b[t]), acc_l[m], 0, 0, 0);
       }
     }
   }
+#pragma unroll
+  for (int m = 0; m < MT; ++m) acc[m] += acc_l[m];
   if (gst) gst[2] = __builtin_amdgcn_s_memtime() + (uint64_t)(acc[0][0] != acc[0][0]);
   // 4) store (D layout: col = lane&15, row = 4*(lane>>4) + j)
   const int col = col0 + li;
