@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.h"
+#include "stage.h"
 #include "../../include/rwkvtts_codec_layout.h"
 
 namespace rwkvtts {
@@ -1516,17 +1517,12 @@ int rwkvtts_codec_window_plan(const rwkvtts_codec_dims* d, int32_t t0, int32_t t
 
 int rwkvtts_codec_decode_windows(rwkvtts_codec* c, const rwkvtts_codec_window* w, int n) {
   RT_CHECK(c && w && n > 0, RWKVTTS_EINVAL, "codec_decode_windows: bad arguments");
-  // the array's stride is the caller's struct_size (a later, longer struct still reads here)
-  const size_t stride = w->struct_size;
-  RT_CHECK(stride >= sizeof(rwkvtts_codec_window) && stride % alignof(rwkvtts_codec_window) == 0, RWKVTTS_EINVAL,
+  RT_CHECK(w->struct_size % alignof(rwkvtts_codec_window) == 0, RWKVTTS_EINVAL,
            "codec_decode_windows: struct_size too small");
   try {
-    std::vector<const rwkvtts_codec_window*> ws(n);
-    for (int i = 0; i < n; ++i) {
-      ws[i] = (const rwkvtts_codec_window*)((const uint8_t*)w + i * stride);
-      RT_CHECK(ws[i]->struct_size == stride, RWKVTTS_EINVAL, "codec_decode_windows: struct_size differs between windows");
-    }
-    return c->c.decode_windows(ws.data(), n);
+    std::vector<const rwkvtts_codec_window*> ws;
+    int rc = read_windows("codec_decode_windows", w, n, ws, [](const rwkvtts_codec_window* wi) { return wi; });
+    return rc ? rc : c->c.decode_windows(ws.data(), n);
   } catch (const std::exception& ex) {
     set_error(ex.what());
     return RWKVTTS_ENOMEM;

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "common.h"
+#include "stage.h"
 
 // the position arithmetic below is shared by the host plan and the kernel: no contraction anywhere
 #pragma clang fp contract(off)
@@ -195,44 +196,11 @@ struct RsWin {
 
 using namespace rwkvtts;
 
-struct rwkvtts_resampler {
+struct rwkvtts_resampler : Stage<RsTile> {  // d_table: the sinc tables
   RsCfg cfg;
-  int device = 0;
   int tile = kRsThreads;   // outputs per tile
   int lds_floats = 0;      // the widest tile's input span
-  float* d_sincs = nullptr;
-  float *d_in = nullptr, *d_out = nullptr;
-  RsTile* d_tiles = nullptr;
-  size_t cap_in = 0, cap_out = 0, cap_tiles = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double kernel_ms = 0.0;
-  std::mutex mu;
-  std::vector<RsTile> tiles;
 };
-
-static void rs_free(rwkvtts_resampler* r) {
-  if (r->d_sincs) (void)hipFree(r->d_sincs);
-  if (r->d_in) (void)hipFree(r->d_in);
-  if (r->d_out) (void)hipFree(r->d_out);
-  if (r->d_tiles) (void)hipFree(r->d_tiles);
-  if (r->ev0) (void)hipEventDestroy(r->ev0);
-  if (r->ev1) (void)hipEventDestroy(r->ev1);
-  if (r->stream) (void)hipStreamDestroy(r->stream);
-  delete r;
-}
-
-template <typename T>
-static int rs_reserve(T** p, size_t* cap, size_t want) {
-  if (want <= *cap) return RWKVTTS_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t n = want + want / 4;
-  RT_HIP(hipMalloc(p, n * sizeof(T)));
-  *cap = n;
-  return RWKVTTS_OK;
-}
 
 // Checks every window against the plan, then runs them all in one launch. Nothing is launched and
 // nothing written unless every window passes.
@@ -253,7 +221,7 @@ static int rs_run(rwkvtts_resampler* r, const std::vector<RsWin>& ws, const char
   }
   if (tot_out == 0) return RWKVTTS_OK;
   std::lock_guard<std::mutex> lock(r->mu);
-  r->tiles.clear();
+  r->desc.clear();
   int64_t in_off = 0, out_off = 0;
   for (const RsWin& w : ws) {
     if (w.out_count == 0) continue;
@@ -266,41 +234,19 @@ static int rs_run(rwkvtts_resampler* r, const std::vector<RsWin>& ws, const char
       t.out_off = out_off + o;
       t.count = (int32_t)std::min<int64_t>(r->tile, w.out_count - o);
       t.pad = 0;
-      r->tiles.push_back(t);
+      r->desc.push_back(t);
     }
     in_off += w.n_in;
     out_off += w.out_count;
   }
-  RT_CHECK(r->tiles.size() <= (size_t)0x7fffffff, RWKVTTS_EINVAL, std::string(who) + ": too many outputs for one launch");
-  RT_HIP(hipSetDevice(r->device));
+  RT_CHECK(r->desc.size() <= (size_t)0x7fffffff, RWKVTTS_EINVAL, std::string(who) + ": too many outputs for one launch");
   int rc;
-  if ((rc = rs_reserve(&r->d_in, &r->cap_in, (size_t)std::max<int64_t>(tot_in, 1)))) return rc;
-  if ((rc = rs_reserve(&r->d_out, &r->cap_out, (size_t)tot_out))) return rc;
-  if ((rc = rs_reserve(&r->d_tiles, &r->cap_tiles, r->tiles.size()))) return rc;
-  in_off = 0;
-  for (const RsWin& w : ws) {
-    if (w.out_count == 0) continue;
-    if (w.n_in > 0)
-      RT_HIP(hipMemcpyAsync(r->d_in + in_off, w.in, (size_t)w.n_in * sizeof(float), hipMemcpyHostToDevice, r->stream));
-    in_off += w.n_in;
-  }
-  RT_HIP(hipMemcpyAsync(r->d_tiles, r->tiles.data(), r->tiles.size() * sizeof(RsTile), hipMemcpyHostToDevice,
-                        r->stream));
-  hipExtLaunchKernelGGL(k_resample, dim3((unsigned)r->tiles.size()), dim3(kRsThreads),
-                        (size_t)r->lds_floats * sizeof(float), r->stream, r->ev0, r->ev1, 0u, r->d_in, r->d_sincs,
-                        r->d_tiles, r->d_out, c.t_ratio, c.delay, c.L, c.O, r->lds_floats);
+  if ((rc = stage_reserve(r, tot_in, tot_out)) || (rc = stage_upload(r, ws))) return rc;
+  hipExtLaunchKernelGGL(k_resample, dim3((unsigned)r->desc.size()), dim3(kRsThreads),
+                        (size_t)r->lds_floats * sizeof(float), r->stream, r->ev0, r->ev1, 0u, r->d_in.p, r->d_table,
+                        r->d_desc.p, r->d_out.p, c.t_ratio, c.delay, c.L, c.O, r->lds_floats);
   RT_HIP(hipGetLastError());
-  out_off = 0;
-  for (const RsWin& w : ws) {
-    if (w.out_count == 0) continue;
-    RT_HIP(hipMemcpyAsync(w.out, r->d_out + out_off, (size_t)w.out_count * sizeof(float), hipMemcpyDeviceToHost,
-                          r->stream));
-    out_off += w.out_count;
-  }
-  RT_HIP(hipStreamSynchronize(r->stream));
-  float ms = 0.0f;
-  if (hipEventElapsedTime(&ms, r->ev0, r->ev1) == hipSuccess) r->kernel_ms = (double)ms;
-  return RWKVTTS_OK;
+  return stage_download(r, ws);
 }
 
 extern "C" int rwkvtts_resample_sincs(const rwkvtts_resample_desc* desc, float* out) {
@@ -308,13 +254,10 @@ extern "C" int rwkvtts_resample_sincs(const rwkvtts_resample_desc* desc, float* 
   int rc = rs_config(desc, &c, "resample_sincs");
   if (rc) return rc;
   RT_CHECK(out, RWKVTTS_EINVAL, "resample_sincs: null output");
-  try {
+  return guard_alloc("resample_sincs", [&] {
     rs_make_sincs(c, out);
-  } catch (const std::bad_alloc&) {
-    set_error("resample_sincs: out of host memory");
-    return RWKVTTS_ENOMEM;
-  }
-  return RWKVTTS_OK;
+    return RWKVTTS_OK;
+  });
 }
 
 extern "C" int64_t rwkvtts_resample_out_len(const rwkvtts_resample_desc* desc, int64_t n_in) {
@@ -347,38 +290,13 @@ extern "C" int rwkvtts_resampler_create(int device, const rwkvtts_resample_desc*
   int rc = rs_config(desc, &c, "resampler_create");
   if (rc) return rc;
   rwkvtts_resampler* r = nullptr;
-  std::vector<float> own;
-  try {
-    r = new rwkvtts_resampler();
-    if (!table) {
-      own.resize((size_t)c.L * c.O);
-      rs_make_sincs(c, own.data());
-      table = own.data();
-    }
-  } catch (const std::bad_alloc&) {
-    delete r;
-    set_error("resampler_create: out of host memory");
-    return RWKVTTS_ENOMEM;
-  }
+  rc = stage_create("resampler_create", device, table, (size_t)c.L * c.O, [&](float* t) { rs_make_sincs(c, t); }, &r);
+  if (rc) return rc;
   r->cfg = c;
-  r->device = device;
   // the widest tile whose input span, (W - 1) * t_ratio + L + 2 samples at most, fits the LDS budget
   const double room = (double)(kRsLdsFloats - c.L - 2) / c.t_ratio;
   r->tile = (int)std::max(1.0, std::min((double)kRsThreads, floor(room) + 1.0));
   r->lds_floats = (int)std::min<int64_t>(kRsLdsFloats, (int64_t)ceil((double)(r->tile - 1) * c.t_ratio) + c.L + 2);
-  auto fail = [&](hipError_t e, const char* what) {
-    set_error(std::string("resampler_create: ") + what + ": " + hipGetErrorString(e));
-    rs_free(r);
-    return RWKVTTS_EHIP;
-  };
-  hipError_t e;
-  if ((e = hipSetDevice(device)) != hipSuccess) return fail(e, "hipSetDevice");
-  if ((e = hipStreamCreate(&r->stream)) != hipSuccess) return fail(e, "hipStreamCreate");
-  if ((e = hipEventCreate(&r->ev0)) != hipSuccess) return fail(e, "hipEventCreate");
-  if ((e = hipEventCreate(&r->ev1)) != hipSuccess) return fail(e, "hipEventCreate");
-  const size_t bytes = (size_t)c.L * c.O * sizeof(float);
-  if ((e = hipMalloc(&r->d_sincs, bytes)) != hipSuccess) return fail(e, "hipMalloc");
-  if ((e = hipMemcpy(r->d_sincs, table, bytes, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
   *out = r;
   return RWKVTTS_OK;
 }
@@ -386,49 +304,35 @@ extern "C" int rwkvtts_resampler_create(int device, const rwkvtts_resample_desc*
 extern "C" int rwkvtts_resampler_destroy(rwkvtts_resampler* r) {
   if (!r) return RWKVTTS_OK;
   (void)hipSetDevice(r->device);
-  rs_free(r);
+  stage_free(r);
   return RWKVTTS_OK;
 }
 
 extern "C" int rwkvtts_resample_batch(rwkvtts_resampler* r, const float* const* in, const int64_t* n_in, int n,
                                       float* const* out) {
   RT_CHECK(r && n >= 0 && (n == 0 || (in && n_in && out)), RWKVTTS_EINVAL, "resample_batch: bad arguments");
-  try {
+  return guard_alloc("resample_batch", [&] {
     std::vector<RsWin> ws((size_t)n);
     for (int i = 0; i < n; ++i) {
       RT_CHECK(n_in[i] >= 0 && n_in[i] <= kRsMaxSamples, RWKVTTS_EINVAL, "resample_batch: n_in out of range");
       ws[(size_t)i] = RsWin{in[i], 0, n_in[i], 1, 0, rs_out_len(r->cfg, n_in[i]), out[i]};
     }
     return rs_run(r, ws, "resample_batch");
-  } catch (const std::bad_alloc&) {
-    set_error("resample_batch: out of host memory");
-    return RWKVTTS_ENOMEM;
-  }
+  });
 }
 
 extern "C" int rwkvtts_resample_windows(rwkvtts_resampler* r, const rwkvtts_resample_window* w, int n) {
   RT_CHECK(r && n >= 0 && (n == 0 || w), RWKVTTS_EINVAL, "resample_windows: bad arguments");
   if (n == 0) return RWKVTTS_OK;
-  // the array's stride is the caller's struct_size (a later, longer struct still reads here)
-  const size_t stride = w->struct_size;
-  RT_CHECK(stride >= sizeof(rwkvtts_resample_window), RWKVTTS_EINVAL, "resample_windows: struct_size too small");
-  try {
-    std::vector<RsWin> ws((size_t)n);
-    for (int i = 0; i < n; ++i) {
-      const rwkvtts_resample_window* wi = (const rwkvtts_resample_window*)((const char*)w + (size_t)i * stride);
-      RT_CHECK(wi->struct_size == stride, RWKVTTS_EINVAL, "resample_windows: struct_size differs between windows");
-      ws[(size_t)i] = RsWin{wi->in, wi->in_first, wi->n_in, wi->final ? 1 : 0, wi->out_first, wi->out_count, wi->out};
-    }
-    return rs_run(r, ws, "resample_windows");
-  } catch (const std::bad_alloc&) {
-    set_error("resample_windows: out of host memory");
-    return RWKVTTS_ENOMEM;
-  }
+  return guard_alloc("resample_windows", [&] {
+    std::vector<RsWin> ws;
+    int rc = read_windows("resample_windows", w, n, ws, [](const rwkvtts_resample_window* wi) {
+      return RsWin{wi->in, wi->in_first, wi->n_in, wi->final ? 1 : 0, wi->out_first, wi->out_count, wi->out};
+    });
+    return rc ? rc : rs_run(r, ws, "resample_windows");
+  });
 }
 
 extern "C" int rwkvtts_resampler_kernel_ms(rwkvtts_resampler* r, double* ms) {
-  RT_CHECK(r && ms, RWKVTTS_EINVAL, "resampler_kernel_ms: null argument");
-  std::lock_guard<std::mutex> lock(r->mu);
-  *ms = r->kernel_ms;
-  return RWKVTTS_OK;
+  return stage_kernel_ms("resampler_kernel_ms", r, ms);
 }

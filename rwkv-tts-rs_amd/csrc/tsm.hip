@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "common.h"
+#include "stage.h"
 
 // frame positions are shared by the host plan and the kernels: no contraction anywhere
 #pragma clang fp contract(off)
@@ -271,45 +272,11 @@ struct TsmWin {
 
 using namespace rwkvtts;
 
-struct rwkvtts_tsm {
+struct rwkvtts_tsm : Stage<TsmJob> {  // d_table: the Hann window
   TsmCfg cfg;
-  int device = 0;
-  float* d_win = nullptr;
-  float *d_in = nullptr, *d_out = nullptr;
-  int64_t* d_starts = nullptr;
-  TsmJob* d_jobs = nullptr;
-  size_t cap_in = 0, cap_out = 0, cap_starts = 0, cap_jobs = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double kernel_ms = 0.0;
-  std::mutex mu;
-  std::vector<TsmJob> jobs;
+  DevBuf<int64_t> d_starts;
   std::vector<int64_t> last;
 };
-
-static void tsm_free(rwkvtts_tsm* t) {
-  if (t->d_win) (void)hipFree(t->d_win);
-  if (t->d_in) (void)hipFree(t->d_in);
-  if (t->d_out) (void)hipFree(t->d_out);
-  if (t->d_starts) (void)hipFree(t->d_starts);
-  if (t->d_jobs) (void)hipFree(t->d_jobs);
-  if (t->ev0) (void)hipEventDestroy(t->ev0);
-  if (t->ev1) (void)hipEventDestroy(t->ev1);
-  if (t->stream) (void)hipStreamDestroy(t->stream);
-  delete t;
-}
-
-template <typename T>
-static int tsm_reserve(T** p, size_t* cap, size_t want) {
-  if (want <= *cap) return RWKVTTS_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t n = want + want / 4;
-  RT_HIP(hipMalloc(p, n * sizeof(T)));
-  *cap = n;
-  return RWKVTTS_OK;
-}
 
 // Checks every window against the plan, then runs them all: one search launch, one overlap-add
 // launch. Nothing is launched and nothing written unless every window passes.
@@ -346,7 +313,7 @@ static int tsm_run(rwkvtts_tsm* t, const std::vector<TsmWin>& ws, const char* wh
   }
   RT_CHECK(n_jobs <= 65535 && max_blocks <= 0x7fffffff, RWKVTTS_EINVAL, std::string(who) + ": too much for one launch");
   std::lock_guard<std::mutex> lock(t->mu);
-  t->jobs.clear();
+  t->desc.clear();
   t->last.assign(n_jobs, 0);
   int64_t in_off = 0, out_off = 0, st_off = 0;
   for (const TsmWin& w : ws) {
@@ -362,50 +329,33 @@ static int tsm_run(rwkvtts_tsm* t, const std::vector<TsmWin>& ws, const char* wh
     j.out_off = out_off;
     j.out_count = w.out_count;
     j.tempo = w.tempo;
-    t->jobs.push_back(j);
+    t->desc.push_back(j);
     in_off += w.n_in;
     out_off += w.out_count;
     st_off += j.m_count + 1;
   }
-  RT_HIP(hipSetDevice(t->device));
-  if ((rc = tsm_reserve(&t->d_in, &t->cap_in, (size_t)std::max<int64_t>(tot_in, 1)))) return rc;
-  if ((rc = tsm_reserve(&t->d_out, &t->cap_out, (size_t)tot_out))) return rc;
-  if ((rc = tsm_reserve(&t->d_starts, &t->cap_starts, (size_t)tot_starts))) return rc;
-  if ((rc = tsm_reserve(&t->d_jobs, &t->cap_jobs, n_jobs))) return rc;
-  in_off = 0;
-  for (const TsmWin& w : ws) {
-    if (w.out_count == 0) continue;
-    if (w.n_in > 0)
-      RT_HIP(hipMemcpyAsync(t->d_in + in_off, w.in, (size_t)w.n_in * sizeof(float), hipMemcpyHostToDevice, t->stream));
-    in_off += w.n_in;
-  }
-  RT_HIP(hipMemcpyAsync(t->d_jobs, t->jobs.data(), n_jobs * sizeof(TsmJob), hipMemcpyHostToDevice, t->stream));
+  if ((rc = stage_reserve(t, tot_in, tot_out)) || (rc = t->d_starts.reserve((size_t)tot_starts)) ||
+      (rc = stage_upload(t, ws)))
+    return rc;
   // the event pair brackets both kernels: start of the search, end of the overlap-add
   const size_t lds = (size_t)2 * (size_t)(2 * c.D + 2 * c.Hs) * sizeof(float);  // 32 KB at the widest
   hipExtLaunchKernelGGL(k_tsm_search, dim3((unsigned)n_jobs), dim3(kTsmThreads), lds, t->stream, t->ev0, nullptr, 0u,
-                        t->d_in, t->d_jobs, t->d_starts, c.Hs, c.D);
+                        t->d_in.p, t->d_desc.p, t->d_starts.p, c.Hs, c.D);
   RT_HIP(hipGetLastError());
   hipExtLaunchKernelGGL(k_tsm_ola, dim3((unsigned)max_blocks, (unsigned)n_jobs), dim3(kTsmThreads), 0, t->stream,
-                        nullptr, t->ev1, 0u, t->d_in, t->d_win, t->d_jobs, t->d_starts, t->d_out, c.Hs);
+                        nullptr, t->ev1, 0u, t->d_in.p, t->d_table, t->d_desc.p, t->d_starts.p, t->d_out.p, c.Hs);
   RT_HIP(hipGetLastError());
-  size_t k = 0;
-  for (const TsmWin& w : ws) {
-    if (w.out_count == 0) continue;
-    const TsmJob& j = t->jobs[k];
-    RT_HIP(hipMemcpyAsync(w.out, t->d_out + j.out_off, (size_t)w.out_count * sizeof(float), hipMemcpyDeviceToHost,
+  for (size_t k = 0; k < n_jobs; ++k) {  // the start of each job's last frame
+    const TsmJob& j = t->desc[k];
+    RT_HIP(hipMemcpyAsync(&t->last[k], t->d_starts.p + j.st_off + j.m_count, sizeof(int64_t), hipMemcpyDeviceToHost,
                           t->stream));
-    RT_HIP(hipMemcpyAsync(&t->last[k], t->d_starts + j.st_off + j.m_count, sizeof(int64_t), hipMemcpyDeviceToHost,
-                          t->stream));
-    ++k;
   }
-  RT_HIP(hipStreamSynchronize(t->stream));
-  k = 0;
+  if ((rc = stage_download(t, ws))) return rc;
+  size_t k = 0;
   for (const TsmWin& w : ws) {
     if (w.s_last) *w.s_last = w.out_count == 0 ? w.s_prev : t->last[k];
     if (w.out_count != 0) ++k;
   }
-  float ms = 0.0f;
-  if (hipEventElapsedTime(&ms, t->ev0, t->ev1) == hipSuccess) t->kernel_ms = (double)ms;
   return RWKVTTS_OK;
 }
 
@@ -450,34 +400,9 @@ extern "C" int rwkvtts_tsm_create(int device, const rwkvtts_tsm_desc* desc, cons
   int rc = tsm_config(desc, &c, "tsm_create");
   if (rc) return rc;
   rwkvtts_tsm* t = nullptr;
-  std::vector<float> own;
-  try {
-    t = new rwkvtts_tsm();
-    if (!table) {
-      own.resize((size_t)c.W);
-      tsm_make_window(c, own.data());
-      table = own.data();
-    }
-  } catch (const std::bad_alloc&) {
-    delete t;
-    set_error("tsm_create: out of host memory");
-    return RWKVTTS_ENOMEM;
-  }
+  rc = stage_create("tsm_create", device, table, (size_t)c.W, [&](float* w) { tsm_make_window(c, w); }, &t);
+  if (rc) return rc;
   t->cfg = c;
-  t->device = device;
-  auto fail = [&](hipError_t e, const char* what) {
-    set_error(std::string("tsm_create: ") + what + ": " + hipGetErrorString(e));
-    tsm_free(t);
-    return RWKVTTS_EHIP;
-  };
-  hipError_t e;
-  if ((e = hipSetDevice(device)) != hipSuccess) return fail(e, "hipSetDevice");
-  if ((e = hipStreamCreate(&t->stream)) != hipSuccess) return fail(e, "hipStreamCreate");
-  if ((e = hipEventCreate(&t->ev0)) != hipSuccess) return fail(e, "hipEventCreate");
-  if ((e = hipEventCreate(&t->ev1)) != hipSuccess) return fail(e, "hipEventCreate");
-  const size_t bytes = (size_t)c.W * sizeof(float);
-  if ((e = hipMalloc(&t->d_win, bytes)) != hipSuccess) return fail(e, "hipMalloc");
-  if ((e = hipMemcpy(t->d_win, table, bytes, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
   *out = t;
   return RWKVTTS_OK;
 }
@@ -485,14 +410,14 @@ extern "C" int rwkvtts_tsm_create(int device, const rwkvtts_tsm_desc* desc, cons
 extern "C" int rwkvtts_tsm_destroy(rwkvtts_tsm* t) {
   if (!t) return RWKVTTS_OK;
   (void)hipSetDevice(t->device);
-  tsm_free(t);
+  stage_free(t, {t->d_starts.p});
   return RWKVTTS_OK;
 }
 
 extern "C" int rwkvtts_tsm_batch(rwkvtts_tsm* t, const float* const* in, const int64_t* n_in, const double* tempo,
                                  int n, float* const* out) {
   RT_CHECK(t && n >= 0 && (n == 0 || (in && n_in && tempo && out)), RWKVTTS_EINVAL, "tsm_batch: bad arguments");
-  try {
+  return guard_alloc("tsm_batch", [&] {
     std::vector<TsmWin> ws((size_t)n);
     for (int i = 0; i < n; ++i) {
       int rc = tsm_tempo_ok(tempo[i], "tsm_batch");
@@ -502,36 +427,20 @@ extern "C" int rwkvtts_tsm_batch(rwkvtts_tsm* t, const float* const* in, const i
                              out[i], nullptr};
     }
     return tsm_run(t, ws, "tsm_batch");
-  } catch (const std::bad_alloc&) {
-    set_error("tsm_batch: out of host memory");
-    return RWKVTTS_ENOMEM;
-  }
+  });
 }
 
 extern "C" int rwkvtts_tsm_windows(rwkvtts_tsm* t, rwkvtts_tsm_window_t* w, int n) {
   RT_CHECK(t && n >= 0 && (n == 0 || w), RWKVTTS_EINVAL, "tsm_windows: bad arguments");
   if (n == 0) return RWKVTTS_OK;
-  // the array's stride is the caller's struct_size (a later, longer struct still reads here)
-  const size_t stride = w->struct_size;
-  RT_CHECK(stride >= sizeof(rwkvtts_tsm_window_t), RWKVTTS_EINVAL, "tsm_windows: struct_size too small");
-  try {
-    std::vector<TsmWin> ws((size_t)n);
-    for (int i = 0; i < n; ++i) {
-      rwkvtts_tsm_window_t* wi = (rwkvtts_tsm_window_t*)((char*)w + (size_t)i * stride);
-      RT_CHECK(wi->struct_size == stride, RWKVTTS_EINVAL, "tsm_windows: struct_size differs between windows");
-      ws[(size_t)i] = TsmWin{wi->in, wi->in_first, wi->n_in, wi->final ? 1 : 0, wi->tempo, wi->block_first,
-                             wi->s_prev, wi->out_count, wi->out, &wi->s_last};
-    }
-    return tsm_run(t, ws, "tsm_windows");
-  } catch (const std::bad_alloc&) {
-    set_error("tsm_windows: out of host memory");
-    return RWKVTTS_ENOMEM;
-  }
+  return guard_alloc("tsm_windows", [&] {
+    std::vector<TsmWin> ws;
+    int rc = read_windows("tsm_windows", w, n, ws, [](rwkvtts_tsm_window_t* wi) {
+      return TsmWin{wi->in, wi->in_first, wi->n_in, wi->final ? 1 : 0, wi->tempo, wi->block_first,
+                    wi->s_prev, wi->out_count, wi->out, &wi->s_last};
+    });
+    return rc ? rc : tsm_run(t, ws, "tsm_windows");
+  });
 }
 
-extern "C" int rwkvtts_tsm_kernel_ms(rwkvtts_tsm* t, double* ms) {
-  RT_CHECK(t && ms, RWKVTTS_EINVAL, "tsm_kernel_ms: null argument");
-  std::lock_guard<std::mutex> lock(t->mu);
-  *ms = t->kernel_ms;
-  return RWKVTTS_OK;
-}
+extern "C" int rwkvtts_tsm_kernel_ms(rwkvtts_tsm* t, double* ms) { return stage_kernel_ms("tsm_kernel_ms", t, ms); }

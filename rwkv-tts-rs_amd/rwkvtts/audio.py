@@ -141,49 +141,33 @@ def resample_audio_high_quality(audio, original_sr: int, target_sr: int, sinc_le
     return out
 
 
-# ---- the resampler on the GPU ----------------------------------------------------------------
-class Resampler:
-    """The restatement above as a HIP kernel (csrc/resample.hip; the arithmetic contract is in
-    include/rwkvtts.h): one-shot, batched and exact over stream chunks.
+# ---- what the two GPU stages share (csrc/stage.h is the native side's counterpart) -------------
+def _native(name, *args):
+    _ffi.check(getattr(_ffi.lib(), "rwkvtts_" + name)(*args), name)
 
-    align "rubato" keeps rubato's sinc_len / 2 start delay and cuts the tail, as
-    resample_audio_high_quality does (the reference-audio front end); "zero" puts output o at input
-    time o / ratio (synthesised output: no delay, nothing cut). The kernel reads the table
-    `_make_sincs` builds, so the restatement has a single source; it is pinned bitwise to the
-    contract's numpy form (tests/test_gpu_resample.py), not to rubato (parity unpinned, as above).
 
-    evaluator: a callable (resampler, items) -> [ndarray] standing in for the native window call,
-    items being [(samples from in_first on, in_first, final, out_first, out_count)]; no GPU resampler
-    is created then (the host-only plan / out_len entry points are still the library's)."""
+class _NativeStage:
+    """A native object (rwkvtts_<_NAME>_create / _destroy / _kernel_ms) made from self._desc and one
+    f32 table on self.device, unless an evaluator stands in for it; its call lock; the marshalling of
+    a ragged batch."""
+    _NAME = None
 
-    def __init__(self, sr_in: int, sr_out: int, device: int = 0, align: str = "zero", sinc_len: int = 256,
-                 f_cutoff: float = 0.95, oversampling: int = 256, evaluator=None):
-        if align not in ("zero", "rubato"):
-            raise ValueError('align must be "zero" or "rubato"')
-        self.sr_in, self.sr_out, self.align, self.device = int(sr_in), int(sr_out), align, int(device)
-        self.sinc_len, self.oversampling, self.f_cutoff = int(sinc_len), int(oversampling), float(f_cutoff)
-        self._desc = _ffi.ResampleDesc(
-            struct_size=ctypes.sizeof(_ffi.ResampleDesc), sr_in=self.sr_in, sr_out=self.sr_out,
-            sinc_len=self.sinc_len, oversampling=self.oversampling, f_cutoff=self.f_cutoff,
-            align=_ffi.RESAMPLE_ALIGN_ZERO if align == "zero" else _ffi.RESAMPLE_ALIGN_RUBATO)
+    def __init__(self, evaluator):
         self._h = None
         self._evaluator = evaluator
-        # one native call at a time: the resampler owns one stream and one set of device buffers
+        # one native call at a time: the object owns one stream and one set of device buffers
         self._lock = threading.Lock()
-        self.out_len(0)  # (refuses a bad description before anything is built)
-        self.ratio = self.sr_out / self.sr_in
-        self.sincs = _make_sincs(self.sinc_len, self.oversampling,
-                                 self.f_cutoff if self.ratio >= 1.0 else self.f_cutoff * self.ratio)
-        if evaluator is None:
+
+    def _create(self, table):
+        if self._evaluator is None:
             h = ctypes.c_void_p()
-            _ffi.check(_ffi.lib().rwkvtts_resampler_create(self.device, ctypes.byref(self._desc),
-                                                           self.sincs.ctypes.data_as(ctypes.c_void_p),
-                                                           ctypes.byref(h)), "resampler_create")
+            _native(self._NAME + "_create", self.device, ctypes.byref(self._desc),
+                    table.ctypes.data_as(ctypes.c_void_p), ctypes.byref(h))
             self._h = h
 
     def close(self):
         if self._h:
-            _ffi.lib().rwkvtts_resampler_destroy(self._h)
+            getattr(_ffi.lib(), f"rwkvtts_{self._NAME}_destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -192,86 +176,49 @@ class Resampler:
         except Exception:
             pass
 
-    # ---- host-only plan ----
-    def out_len(self, n_in: int) -> int:
-        n = int(_ffi.lib().rwkvtts_resample_out_len(ctypes.byref(self._desc), int(n_in)))
-        if n < 0:
-            raise _ffi.RwkvTtsError(_ffi.EINVAL, "resample_out_len")
-        return n
-
-    def plan(self, n_known: int, final: bool, out_first: int = 0):
-        """(out_ready_end, in_first_needed) of rwkvtts_resample_plan."""
-        end, first = ctypes.c_int64(), ctypes.c_int64()
-        _ffi.check(_ffi.lib().rwkvtts_resample_plan(ctypes.byref(self._desc), int(n_known), 1 if final else 0,
-                                                    int(out_first), ctypes.byref(end), ctypes.byref(first)),
-                   "resample_plan")
-        return end.value, first.value
-
-    # ---- the kernel ----
-    def resample_windows(self, items) -> list:
-        """[(samples from in_first on, in_first, final, out_first, out_count)] -> [outputs
-        [out_first, out_first + out_count) of the whole-signal resample], all windows in one launch.
-        Raises RwkvTtsError(EINVAL), with nothing computed, if a requested output needs a sample
-        that was not given (plan())."""
-        items = [(np.ascontiguousarray(x, dtype=F32).reshape(-1), int(a), bool(f), int(o), int(c))
-                 for x, a, f, o, c in items]
-        if self._evaluator is not None:
-            return [np.ascontiguousarray(y, dtype=F32) for y in self._evaluator(self, items)]
-        n = len(items)
-        if n == 0:
-            return []
-        ws = (_ffi.ResampleWindow * n)()
-        outs = []
-        for w, (x, in_first, final, out_first, count) in zip(ws, items):
-            out = np.empty(max(count, 0), dtype=F32)
-            outs.append(out)
-            w.struct_size = ctypes.sizeof(_ffi.ResampleWindow)
-            w.in_, w.in_first, w.n_in, w.final = x.ctypes.data, in_first, x.size, 1 if final else 0
-            w.out_first, w.out_count, w.out = out_first, count, out.ctypes.data
+    def _call(self, name, *args):
         with self._lock:
-            _ffi.check(_ffi.lib().rwkvtts_resample_windows(self._h, ws, n), "resample_windows")
-        return outs
+            _native(name, self._h, *args)
 
-    def resample_batch(self, signals) -> list:
-        """[signal] -> [resampled signal], ragged, in one launch; an empty signal gives an empty one."""
-        xs = [np.ascontiguousarray(x, dtype=F32).reshape(-1) for x in signals]
-        if self._evaluator is not None:
-            return self.resample_windows([(x, 0, True, 0, self.out_len(x.size)) for x in xs])
-        n = len(xs)
-        if n == 0:
-            return []
-        outs = [np.empty(self.out_len(x.size), dtype=F32) for x in xs]
-        P = ctypes.c_void_p * n
-        ins, ous = P(*[x.ctypes.data for x in xs]), P(*[o.ctypes.data for o in outs])
-        lens = (ctypes.c_int64 * n)(*[x.size for x in xs])
-        with self._lock:
-            _ffi.check(_ffi.lib().rwkvtts_resample_batch(self._h, ins, lens, n, ous), "resample_batch")
-        return outs
+    @staticmethod
+    def _ragged(xs, out_lens):
+        """-> (outputs, void* inputs[], int64 lengths[], void* outputs[]) of a *_batch call."""
+        outs = [np.empty(n, dtype=F32) for n in out_lens]
+        P = ctypes.c_void_p * len(xs)
+        return (outs, P(*[x.ctypes.data for x in xs]), (ctypes.c_int64 * len(xs))(*[x.size for x in xs]),
+                P(*[o.ctypes.data for o in outs]))
 
-    def resample(self, x) -> np.ndarray:
-        return self.resample_batch([x])[0]
+    def _windows(self, name, Struct, items, **own):
+        """One rwkvtts_<name> call over items (samples, in_first, final, .., out_count) -> (the
+        Struct array, the outputs); own: the stage's further fields by their position in an item."""
+        ws = (Struct * len(items))()
+        outs = [np.empty(max(it[-1], 0), dtype=F32) for it in items]
+        for w, it, out in zip(ws, items, outs):
+            w.struct_size = ctypes.sizeof(Struct)
+            w.in_, w.in_first, w.n_in, w.final = it[0].ctypes.data, it[1], it[0].size, 1 if it[2] else 0
+            w.out_count, w.out = it[-1], out.ctypes.data
+            for field, k in own.items():
+                setattr(w, field, it[k])
+        if items:
+            self._call(name, ws, len(items))
+        return ws, outs
 
     def kernel_ms(self) -> float:
-        """HIP-event time of the last launch's kernel alone (no copies)."""
+        """HIP-event time of the last call's kernels alone (no copies)."""
         ms = ctypes.c_double()
-        _ffi.check(_ffi.lib().rwkvtts_resampler_kernel_ms(self._h, ctypes.byref(ms)), "resampler_kernel_ms")
+        _native(self._NAME + "_kernel_ms", self._h, ctypes.byref(ms))
         return ms.value
 
-    def stream(self) -> "ResampleStream":
-        return ResampleStream(self)
 
+class _ExactStream:
+    """feed(pcm_chunk, final=False) -> what became exact with it, over a kept tail of the input. A
+    subclass has _emit(n_known, final) -> the ready outputs, computed from _tail (signal samples
+    [_tail_first, n_known)), advancing its own cursor, and _first_needed(n_known) -> the first input
+    sample the outputs after the cursor still read."""
 
-class ResampleStream:
-    """Resampler.stream(): feed(pcm_chunk, final=False) -> the outputs that became exact with it.
-    The concatenation of what feed returns is bitwise Resampler.resample(the concatenated input),
-    however the input was cut. Only the tail rwkvtts_resample_plan asks for is kept: fewer than
-    sinc_len + ceil(1 / ratio) + 1 samples."""
-
-    def __init__(self, resampler: Resampler):
-        self.r = resampler
+    def __init__(self):
         self._tail = np.zeros(0, dtype=F32)
         self._tail_first = 0   # signal index of _tail[0]
-        self._out_next = 0     # outputs [0, _out_next) went out
         self._closed = False
 
     @property
@@ -285,6 +232,106 @@ class ResampleStream:
         if x.size:
             self._tail = np.concatenate([self._tail, x])
         n_known = self._tail_first + self._tail.size
+        out = self._emit(n_known, final)
+        if final:
+            self._closed, self._tail = True, np.zeros(0, dtype=F32)
+            return out
+        first = min(self._first_needed(n_known), n_known)
+        if first > self._tail_first:
+            self._tail = self._tail[first - self._tail_first:].copy()
+            self._tail_first = first
+        return out
+
+
+# ---- the resampler on the GPU ----------------------------------------------------------------
+class Resampler(_NativeStage):
+    """The restatement above as a HIP kernel (csrc/resample.hip; the arithmetic contract is in
+    include/rwkvtts.h): one-shot, batched and exact over stream chunks.
+
+    align "rubato" keeps rubato's sinc_len / 2 start delay and cuts the tail, as
+    resample_audio_high_quality does (the reference-audio front end); "zero" puts output o at input
+    time o / ratio (synthesised output: no delay, nothing cut). The kernel reads the table
+    `_make_sincs` builds, so the restatement has a single source; it is pinned bitwise to the
+    contract's numpy form (tests/test_gpu_resample.py), not to rubato (parity unpinned, as above).
+
+    evaluator: a callable (resampler, items) -> [ndarray] standing in for the native window call,
+    items being [(samples from in_first on, in_first, final, out_first, out_count)]; no GPU resampler
+    is created then (the host-only plan / out_len entry points are still the library's)."""
+    _NAME = "resampler"
+
+    def __init__(self, sr_in: int, sr_out: int, device: int = 0, align: str = "zero", sinc_len: int = 256,
+                 f_cutoff: float = 0.95, oversampling: int = 256, evaluator=None):
+        if align not in ("zero", "rubato"):
+            raise ValueError('align must be "zero" or "rubato"')
+        self.sr_in, self.sr_out, self.align, self.device = int(sr_in), int(sr_out), align, int(device)
+        self.sinc_len, self.oversampling, self.f_cutoff = int(sinc_len), int(oversampling), float(f_cutoff)
+        self._desc = _ffi.ResampleDesc(
+            struct_size=ctypes.sizeof(_ffi.ResampleDesc), sr_in=self.sr_in, sr_out=self.sr_out,
+            sinc_len=self.sinc_len, oversampling=self.oversampling, f_cutoff=self.f_cutoff,
+            align=_ffi.RESAMPLE_ALIGN_ZERO if align == "zero" else _ffi.RESAMPLE_ALIGN_RUBATO)
+        super().__init__(evaluator)
+        self.out_len(0)  # (refuses a bad description before anything is built)
+        self.ratio = self.sr_out / self.sr_in
+        self.sincs = _make_sincs(self.sinc_len, self.oversampling,
+                                 self.f_cutoff if self.ratio >= 1.0 else self.f_cutoff * self.ratio)
+        self._create(self.sincs)
+
+    # ---- host-only plan ----
+    def out_len(self, n_in: int) -> int:
+        n = int(_ffi.lib().rwkvtts_resample_out_len(ctypes.byref(self._desc), int(n_in)))
+        if n < 0:
+            raise _ffi.RwkvTtsError(_ffi.EINVAL, "resample_out_len")
+        return n
+
+    def plan(self, n_known: int, final: bool, out_first: int = 0):
+        """(out_ready_end, in_first_needed) of rwkvtts_resample_plan."""
+        end, first = ctypes.c_int64(), ctypes.c_int64()
+        _native("resample_plan", ctypes.byref(self._desc), int(n_known), 1 if final else 0, int(out_first),
+                ctypes.byref(end), ctypes.byref(first))
+        return end.value, first.value
+
+    # ---- the kernel ----
+    def resample_windows(self, items) -> list:
+        """[(samples from in_first on, in_first, final, out_first, out_count)] -> [outputs
+        [out_first, out_first + out_count) of the whole-signal resample], all windows in one launch.
+        Raises RwkvTtsError(EINVAL), with nothing computed, if a requested output needs a sample
+        that was not given (plan())."""
+        items = [(np.ascontiguousarray(x, dtype=F32).reshape(-1), int(a), bool(f), int(o), int(c))
+                 for x, a, f, o, c in items]
+        if self._evaluator is not None:
+            return [np.ascontiguousarray(y, dtype=F32) for y in self._evaluator(self, items)]
+        return self._windows("resample_windows", _ffi.ResampleWindow, items, out_first=3)[1]
+
+    def resample_batch(self, signals) -> list:
+        """[signal] -> [resampled signal], ragged, in one launch; an empty signal gives an empty one."""
+        xs = [np.ascontiguousarray(x, dtype=F32).reshape(-1) for x in signals]
+        if self._evaluator is not None:
+            return self.resample_windows([(x, 0, True, 0, self.out_len(x.size)) for x in xs])
+        if not xs:
+            return []
+        outs, ins, lens, ous = self._ragged(xs, [self.out_len(x.size) for x in xs])
+        self._call("resample_batch", ins, lens, len(xs), ous)
+        return outs
+
+    def resample(self, x) -> np.ndarray:
+        return self.resample_batch([x])[0]
+
+    def stream(self) -> "ResampleStream":
+        return ResampleStream(self)
+
+
+class ResampleStream(_ExactStream):
+    """Resampler.stream(): feed(pcm_chunk, final=False) -> the outputs that became exact with it.
+    The concatenation of what feed returns is bitwise Resampler.resample(the concatenated input),
+    however the input was cut. Only the tail rwkvtts_resample_plan asks for is kept: fewer than
+    sinc_len + ceil(1 / ratio) + 1 samples."""
+
+    def __init__(self, resampler: Resampler):
+        super().__init__()
+        self.r = resampler
+        self._out_next = 0     # outputs [0, _out_next) went out
+
+    def _emit(self, n_known, final):
         end, _ = self.r.plan(n_known, final, self._out_next)
         count = end - self._out_next
         if count > 0:
@@ -292,15 +339,10 @@ class ResampleStream:
         else:
             out = np.zeros(0, dtype=F32)
         self._out_next = max(end, self._out_next)
-        if final:
-            self._closed, self._tail = True, np.zeros(0, dtype=F32)
-            return out
-        _, first = self.r.plan(n_known, False, self._out_next)
-        first = min(first, n_known)
-        if first > self._tail_first:
-            self._tail = self._tail[first - self._tail_first:].copy()
-            self._tail_first = first
         return out
+
+    def _first_needed(self, n_known):
+        return self.r.plan(n_known, False, self._out_next)[1]
 
 
 # ---- time stretch on the GPU -----------------------------------------------------------------
@@ -310,7 +352,7 @@ def _tsm_window(window: int) -> np.ndarray:
     return (0.5 - 0.5 * np.cos(2.0 * np.pi * i / float(window))).astype(F32)
 
 
-class TimeStretcher:
+class TimeStretcher(_NativeStage):
     """Pitch-preserving time-scale modification (WSOLA) as HIP kernels (csrc/tsm.hip; the arithmetic
     contract is in include/rwkvtts.h): tempo 0.25 .. 4.0 per signal, above 1 is faster speech; the
     output has ceil(n / tempo) samples. One-shot, batched (a tempo per signal in one launch) and exact
@@ -324,36 +366,18 @@ class TimeStretcher:
     call, items being [(samples from in_first on, in_first, final, tempo, block_first, s_prev,
     out_count)]; no GPU object is created then (the host-only plan / out_len entry points are still
     the library's)."""
+    _NAME = "tsm"
 
     def __init__(self, device: int = 0, window: int = 512, search: int = 128, evaluator=None):
         self.device = int(device)
         self._desc = _ffi.TsmDesc(struct_size=ctypes.sizeof(_ffi.TsmDesc), window=int(window), search=int(search))
-        self._h = None
-        self._evaluator = evaluator
-        # one native call at a time: the stretcher owns one stream and one set of device buffers
-        self._lock = threading.Lock()
+        super().__init__(evaluator)
         self.out_len(0, 1.0)  # (refuses a bad description before anything is built)
         self.window = int(window) or 512
         self.search = int(search) or 128
         self.hop = self.window // 2
         self.table = _tsm_window(self.window)
-        if evaluator is None:
-            h = ctypes.c_void_p()
-            _ffi.check(_ffi.lib().rwkvtts_tsm_create(self.device, ctypes.byref(self._desc),
-                                                     self.table.ctypes.data_as(ctypes.c_void_p), ctypes.byref(h)),
-                       "tsm_create")
-            self._h = h
-
-    def close(self):
-        if self._h:
-            _ffi.lib().rwkvtts_tsm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(self.table)
 
     # ---- host-only plan ----
     def out_len(self, n_in: int, tempo: float) -> int:
@@ -365,10 +389,8 @@ class TimeStretcher:
     def plan(self, tempo: float, n_known: int, final: bool, block_first: int = 0, s_prev=None):
         """(out_ready_end, in_first_needed) of rwkvtts_tsm_plan; s_prev None: -hop (block_first 0)."""
         end, first = ctypes.c_int64(), ctypes.c_int64()
-        _ffi.check(_ffi.lib().rwkvtts_tsm_plan(ctypes.byref(self._desc), float(tempo), int(n_known),
-                                               1 if final else 0, int(block_first),
-                                               -self.hop if s_prev is None else int(s_prev),
-                                               ctypes.byref(end), ctypes.byref(first)), "tsm_plan")
+        _native("tsm_plan", ctypes.byref(self._desc), float(tempo), int(n_known), 1 if final else 0, int(block_first),
+                -self.hop if s_prev is None else int(s_prev), ctypes.byref(end), ctypes.byref(first))
         return end.value, first.value
 
     # ---- the kernels ----
@@ -381,19 +403,7 @@ class TimeStretcher:
                  for x, a, f, t, b, s, c in items]
         if self._evaluator is not None:
             return [(np.ascontiguousarray(y, dtype=F32), int(s)) for y, s in self._evaluator(self, items)]
-        n = len(items)
-        if n == 0:
-            return []
-        ws = (_ffi.TsmWindow * n)()
-        outs = []
-        for w, (x, in_first, final, tempo, block_first, s_prev, count) in zip(ws, items):
-            out = np.empty(max(count, 0), dtype=F32)
-            outs.append(out)
-            w.struct_size = ctypes.sizeof(_ffi.TsmWindow)
-            w.in_, w.in_first, w.n_in, w.final, w.tempo = x.ctypes.data, in_first, x.size, 1 if final else 0, tempo
-            w.block_first, w.s_prev, w.out_count, w.out = block_first, s_prev, count, out.ctypes.data
-        with self._lock:
-            _ffi.check(_ffi.lib().rwkvtts_tsm_windows(self._h, ws, n), "tsm_windows")
+        ws, outs = self._windows("tsm_windows", _ffi.TsmWindow, items, tempo=3, block_first=4, s_prev=5)
         return [(o, int(w.s_last)) for o, w in zip(outs, ws)]
 
     def stretch_batch(self, signals, tempos) -> list:
@@ -405,76 +415,46 @@ class TimeStretcher:
         if self._evaluator is not None:
             return [y for y, _ in self.stretch_windows([(x, 0, True, t, 0, -self.hop, self.out_len(x.size, t))
                                                         for x, t in zip(xs, ts)])]
-        n = len(xs)
-        if n == 0:
+        if not xs:
             return []
-        outs = [np.empty(self.out_len(x.size, t), dtype=F32) for x, t in zip(xs, ts)]
-        P = ctypes.c_void_p * n
-        ins, ous = P(*[x.ctypes.data for x in xs]), P(*[o.ctypes.data for o in outs])
-        lens = (ctypes.c_int64 * n)(*[x.size for x in xs])
-        tem = (ctypes.c_double * n)(*ts)
-        with self._lock:
-            _ffi.check(_ffi.lib().rwkvtts_tsm_batch(self._h, ins, lens, tem, n, ous), "tsm_batch")
+        outs, ins, lens, ous = self._ragged(xs, [self.out_len(x.size, t) for x, t in zip(xs, ts)])
+        self._call("tsm_batch", ins, lens, (ctypes.c_double * len(ts))(*ts), len(xs), ous)
         return outs
 
     def stretch(self, x, tempo: float) -> np.ndarray:
         return self.stretch_batch([x], [tempo])[0]
 
-    def kernel_ms(self) -> float:
-        """HIP-event time of the last launch pair (search + overlap-add, no copies)."""
-        ms = ctypes.c_double()
-        _ffi.check(_ffi.lib().rwkvtts_tsm_kernel_ms(self._h, ctypes.byref(ms)), "tsm_kernel_ms")
-        return ms.value
-
     def stream(self, tempo: float) -> "TimeStretchStream":
         return TimeStretchStream(self, tempo)
 
 
-class TimeStretchStream:
+class TimeStretchStream(_ExactStream):
     """TimeStretcher.stream(tempo): feed(pcm_chunk, final=False) -> the blocks that became exact with
     it. The concatenation of what feed returns is bitwise TimeStretcher.stretch(the concatenated
     input, tempo), however the input was cut. Only the tail rwkvtts_tsm_plan asks for is kept: fewer
     than 2 * search + window * max(tempo, 1) + 2 samples."""
 
     def __init__(self, stretcher: TimeStretcher, tempo: float):
+        super().__init__()
         self.t = stretcher
         self.tempo = float(tempo)
         stretcher.out_len(0, self.tempo)  # (refuses a bad tempo)
-        self._tail = np.zeros(0, dtype=F32)
-        self._tail_first = 0              # signal index of _tail[0]
         self._block_next = 0              # blocks [0, _block_next) went out
         self._s_prev = -stretcher.hop     # start of frame _block_next - 1
-        self._closed = False
 
-    @property
-    def kept(self) -> int:
-        return int(self._tail.size)
-
-    def feed(self, pcm_chunk, final: bool = False) -> np.ndarray:
-        if self._closed:
-            raise ValueError("the stream has ended (a chunk was fed with final=True)")
-        x = np.asarray(pcm_chunk, dtype=F32).reshape(-1)
-        if x.size:
-            self._tail = np.concatenate([self._tail, x])
+    def _emit(self, n_known, final):
         hop = self.t.hop
-        n_known = self._tail_first + self._tail.size
         end, _ = self.t.plan(self.tempo, n_known, final, self._block_next, self._s_prev)
         count = end - self._block_next * hop
-        if count > 0:
-            out, self._s_prev = self.t.stretch_windows([(self._tail, self._tail_first, final, self.tempo,
-                                                         self._block_next, self._s_prev, count)])[0]
-            self._block_next += -(-count // hop)
-        else:
-            out = np.zeros(0, dtype=F32)
-        if final:
-            self._closed, self._tail = True, np.zeros(0, dtype=F32)
-            return out
-        _, first = self.t.plan(self.tempo, n_known, False, self._block_next, self._s_prev)
-        first = min(first, n_known)
-        if first > self._tail_first:
-            self._tail = self._tail[first - self._tail_first:].copy()
-            self._tail_first = first
+        if count <= 0:
+            return np.zeros(0, dtype=F32)
+        out, self._s_prev = self.t.stretch_windows([(self._tail, self._tail_first, final, self.tempo,
+                                                     self._block_next, self._s_prev, count)])[0]
+        self._block_next += -(-count // hop)
         return out
+
+    def _first_needed(self, n_known):
+        return self.t.plan(self.tempo, n_known, False, self._block_next, self._s_prev)[1]
 
 
 # ---- normalisation / trimming ------------------------------------------------------------

@@ -68,6 +68,25 @@ class SpeechChunk(np.ndarray):
         return c
 
 
+def audio_stages(stretcher, tempo, resampler) -> list:
+    """The stages behind the vocoder in the order they apply -- the stretch at 16 kHz, then the
+    resampler; None is no stage -- each as (batch, stream): batch([pcm]) -> [pcm] in one native call
+    (one tempo for the call), stream() -> an object whose feed(pcm, final) is exact over chunks."""
+    stages = []
+    if stretcher is not None:
+        stages.append((lambda pcm: stretcher.stretch_batch(pcm, [tempo] * len(pcm)), lambda: stretcher.stream(tempo)))
+    if resampler is not None:
+        stages.append((resampler.resample_batch, resampler.stream))
+    return stages
+
+
+def feed_stages(streams, pcm, final: bool):
+    """One vocoder chunk through the stages' streams in order; each passes on what became exact."""
+    for s in streams:
+        pcm = s.feed(pcm, final=final)
+    return pcm
+
+
 class LightweightTtsPipeline:
     """manager: rwkvtts.DynamicBatchManager (with a tokenizer); codec: BiCodecDetokenizer."""
 
@@ -80,8 +99,8 @@ class LightweightTtsPipeline:
         # may be supplied
         self.reference_tokenizer = reference_tokenizer
         self._resamplers = {}  # output rate -> audio.Resampler (created on first use, kept)
-        self._resamplers_lock = threading.Lock()  # (the server's worker threads share the pipeline)
         self._stretcher = None  # audio.TimeStretcher (created on the first tempo other than 1.0, kept)
+        self._stage_cache_lock = threading.Lock()  # guards both (the server's worker threads share the pipeline)
 
     # ---- output rates other than 16 kHz (no reference counterpart: the reference emits 16 kHz only)
     def resampler(self, sample_rate: Optional[int]):
@@ -91,7 +110,7 @@ class LightweightTtsPipeline:
         if sample_rate is None or int(sample_rate) == SAMPLE_RATE:
             return None
         rate = int(sample_rate)
-        with self._resamplers_lock:
+        with self._stage_cache_lock:
             r = self._resamplers.get(rate)
             if r is None:
                 from .audio import Resampler
@@ -108,11 +127,15 @@ class LightweightTtsPipeline:
             return None
         if not 0.25 <= float(tempo) <= 4.0:  # (NaN fails)
             raise ValueError("tempo must be in [0.25, 4.0]")
-        with self._resamplers_lock:
+        with self._stage_cache_lock:
             if self._stretcher is None:
                 from .audio import TimeStretcher
                 self._stretcher = TimeStretcher(device=getattr(self.codec, "device", 0))
         return self._stretcher
+
+    def _stages(self, sample_rate: Optional[int], tempo: Optional[float]):  # -> (stages, output rate)
+        rs = self.resampler(sample_rate)
+        return audio_stages(self.stretcher(tempo), tempo, rs), rs.sr_out if rs else SAMPLE_RATE
 
     # ---- text / attribute handling (:148-193)
     @staticmethod
@@ -174,19 +197,18 @@ class LightweightTtsPipeline:
         the GPU (resampler()); the failed-request second of silence is sample_rate zeros.
         tempo None / 1.0: nothing. Any other: the 16 kHz PCM time-stretched on the GPU (stretcher())
         before the resampler; the failed-request second of silence is not stretched."""
-        rs = self.resampler(sample_rate)
-        ts = self.stretcher(tempo)
+        stages, rate = self._stages(sample_rate, tempo)
         try:
             req = self._request(args)
         except ValueError:  # untokenisable text: the request fails -> empty result
             req = None
         g, s = self.manager.generate_tts_batch([req])[0] if req is not None else ([], [])
         if not g and not s:
-            return np.zeros(rs.sr_out if rs else SAMPLE_RATE, dtype=np.float32)  # :828-830
+            return np.zeros(rate, dtype=np.float32)  # :828-830
         pcm = self.codec.decode_audio(g, s)
-        if ts:
-            pcm = ts.stretch(pcm, tempo)
-        return rs.resample(pcm) if rs else pcm
+        for batch, _ in stages:
+            pcm = batch([pcm])[0]
+        return pcm
 
     def stream_speech(self, args: LightweightTtsPipelineArgs, chunk_frames: int = 16,
                       sample_rate: Optional[int] = None, tempo: Optional[float] = None):
@@ -205,16 +227,12 @@ class LightweightTtsPipeline:
         ends the stream there (its last item has done = False). An item's done says that the request
         had finished when the chunk was decoded; the last chunk has done and t1 == n_known.
 
-        sample_rate other than None / 16000: every chunk goes through one Resampler.stream(), which
-        is exact over chunks, so the items are resampled PCM whose concatenation is bitwise
-        generate_speech(args, sample_rate=...); an item then holds the outputs that became exact
-        with its frames (sinc_len / 2 = 128 input samples of look-ahead stay behind until the next
-        chunk or the end). t0, t1 and n_known stay in frames.
-
-        tempo other than None / 1.0: every vocoder chunk first goes through one
-        TimeStretcher.stream(tempo), exact over chunks as well, then through the resampler's stream
-        if there is one: the concatenation is bitwise generate_speech(args, tempo=..., sample_rate=...).
-        An item then holds the stretched blocks that became exact with its frames (it may be empty)."""
+        tempo other than None / 1.0, sample_rate other than None / 16000: every vocoder chunk goes
+        through one stream per stage (audio_stages: TimeStretcher.stream(tempo), then
+        Resampler.stream()), each exact over chunks, so the concatenation is bitwise
+        generate_speech(args, tempo=..., sample_rate=...). An item then holds what became exact with
+        its frames: whole stretched blocks (it may be empty), resampled outputs short of the
+        sinc_len / 2 = 128 input samples of look-ahead. t0, t1 and n_known stay in frames."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         try:
@@ -229,10 +247,8 @@ class LightweightTtsPipeline:
         was submitted)."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
-        rs = self.resampler(sample_rate)
-        out_stream = rs.stream() if rs else None
-        ts = self.stretcher(tempo)
-        tempo_stream = ts.stream(tempo) if ts else None
+        stages, rate = self._stages(sample_rate, tempo)
+        streams = [stream() for _, stream in stages]
         H = self.codec.halo()
         g, sem, t0, yielded, status = None, [], 0, False, 0
         it = self.manager.stream_tts(req) if req is not None else iter([(None, [], True)])
@@ -246,8 +262,7 @@ class LightweightTtsPipeline:
                     status = (self.manager.last_status or [0])[0]
                 if done and (status != 0 or (not g and not sem)):
                     if not yielded:
-                        yield SpeechChunk.make(np.zeros(rs.sr_out if rs else SAMPLE_RATE, dtype=np.float32),
-                                               0, 0, 0, True)  # :828-830
+                        yield SpeechChunk.make(np.zeros(rate, dtype=np.float32), 0, 0, 0, True)  # :828-830
                     return
                 if done and not sem:
                     self.codec.decode_audio(g, sem)  # (raises as generate_speech does: no semantic tokens)
@@ -260,11 +275,7 @@ class LightweightTtsPipeline:
                     pcm = self.codec.decode_windows([(g, sem, a, b, done) for a, b in wins])
                     for (a, b), p in zip(wins, pcm):
                         yielded = True
-                        if tempo_stream is not None:
-                            p = tempo_stream.feed(p, final=done and b == n)
-                        if out_stream is not None:
-                            p = out_stream.feed(p, final=done and b == n)
-                        yield SpeechChunk.make(p, a, b, n, done)
+                        yield SpeechChunk.make(feed_stages(streams, p, done and b == n), a, b, n, done)
         finally:
             if hasattr(it, "close"):
                 it.close()  # (a stream left early: the ticket is released once the request has finished)
@@ -274,8 +285,7 @@ class LightweightTtsPipeline:
         """sample_rate other than None / 16000: the whole batch is resampled in one resample_batch
         call (a failed item stays an empty array). tempo other than None / 1.0: the whole batch is
         first stretched in one stretch_batch call, one tempo for the call."""
-        rs = self.resampler(sample_rate)
-        ts = self.stretcher(tempo)
+        stages, _ = self._stages(sample_rate, tempo)
         reqs, idx = [], []
         for i, a in enumerate(batch_args):
             try:
@@ -288,6 +298,6 @@ class LightweightTtsPipeline:
         for i, r in zip(idx, res):
             results[i] = r
         pcm = self.codec.decode_audio_batch(results)
-        if ts:
-            pcm = ts.stretch_batch(pcm, [tempo] * len(pcm))
-        return rs.resample_batch(pcm) if rs else pcm
+        for batch, _ in stages:
+            pcm = batch(pcm)
+        return pcm

@@ -223,6 +223,33 @@ def test_windows_bitwise_and_one_sample_short(rs, align):
 
 
 @pytest.mark.gpu
+def test_handle_reuse_across_growth_shrink_and_a_refused_call():
+    """A fresh resampler (its device buffers start empty): first allocation, regrowth (5120 > 40 * 1.25)
+    with a zero-length member in the batch, a refused windows call that writes nothing, and reuse
+    without regrowth after it."""
+    r = audio.Resampler(16000, 24000, device=0, align="zero")
+    try:
+        def run(ns, seed):
+            xs = [_signal(n, seed=seed + n) for n in ns]
+            got = r.resample_batch(xs)
+            for x, y in zip(xs, got):
+                assert np.array_equal(bits(y), bits(contract_resample(x, r.sincs, 16000, 24000, "zero"))), (ns, x.size)
+            assert r.kernel_ms() > 0.0
+        run([40], 500)
+        run([5120, 0, 321], 600)
+        x = _signal(400, seed=9)
+        end, _ = r.plan(x.size, False, 0)
+        assert 0 < end < contract_out_len(x.size, 16000, 24000)
+        canary = np.full(end + 1, 7.0, F32)      # one output more than the plan allows
+        w = _c_window(x, 0, False, 0, canary)
+        assert _ffi.lib().rwkvtts_resample_windows(r._h, ctypes.byref(w), 1) == _ffi.EINVAL
+        assert np.all(canary == 7.0)
+        run([40], 500)
+    finally:
+        r.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("align", ALIGNS)
 def test_window_far_into_a_long_signal(rs, align):
     """Sample and output indices past 2^31 (53 hours of 16 kHz audio into a stream): the plan, the

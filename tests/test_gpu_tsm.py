@@ -171,6 +171,35 @@ def test_windows_bitwise_and_one_sample_short(ts, W, D):
         assert _ffi.lib().rwkvtts_tsm_windows(t._h, ctypes.byref(w), 1) == _ffi.EINVAL and np.all(out == F32(7.25))
 
 
+@pytest.mark.gpu
+def test_handle_reuse_across_growth_shrink_and_a_refused_call():
+    """A fresh stretcher (its device buffers start empty): first allocation, regrowth with a
+    zero-length member in the batch, a refused windows call that writes nothing (s_last included),
+    and reuse without regrowth after it."""
+    W, D = 64, 10
+    Hs = W // 2
+    t = audio.TimeStretcher(device=0, window=W, search=D)
+    try:
+        def run(ns, tempos):
+            xs = [_signal("noise", n, k) for k, n in enumerate(ns)]
+            got = t.stretch_batch(xs, tempos)
+            for x, tempo, y in zip(xs, tempos, got):
+                assert np.array_equal(bits(y), bits(tsm_ref.stretch(x, tempo, W, D))), (ns, x.size, tempo)
+            assert t.kernel_ms() > 0.0
+        run([200], [1.25])
+        run([6000, 0, 333], [0.8, 1.0, 2.0])
+        x = _signal("noise", 2000, 5)
+        end, _ = t.plan(1.25, x.size, False, 0, -Hs)
+        assert 0 < end and end + Hs <= t.out_len(x.size, 1.25)
+        out = np.full(end + Hs, 7.25, F32)       # one block more than the plan allows
+        w = _c_window(x, 0, 0, 1.25, 0, -Hs, out)
+        assert _ffi.lib().rwkvtts_tsm_windows(t._h, ctypes.byref(w), 1) == _ffi.EINVAL
+        assert np.all(out == F32(7.25)) and w.s_last == -12345
+        run([200], [1.25])
+    finally:
+        t.close()
+
+
 def _gpu_starts(t, x, tempo):
     """[s_-1, s_0, ..] as the kernel found them: the final window cut after every block, in one launch."""
     n_out = t.out_len(x.size, tempo)

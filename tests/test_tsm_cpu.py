@@ -201,6 +201,41 @@ def test_stream_is_bitwise_the_whole_signal():
             assert got.size == ts.out_len(n, tempo) and np.array_equal(bits(got), bits(ts.stretch(x[:n], tempo)))
 
 
+def test_chained_streams_are_bitwise_the_resample_of_the_stretch():
+    """The pipeline's stage fold (pipeline.audio_stages / feed_stages, what stream_request runs per
+    vocoder chunk) over both stand-ins: stretch first, then resample, `final` reaching both streams,
+    stretched items that are empty passing through the resampler's stream."""
+    from rwkvtts.pipeline import audio_stages, feed_stages
+    from test_resample_cpu import _contract_evaluator
+    ts = audio.TimeStretcher(window=64, search=10, evaluator=tsm_ref.evaluator)
+    rs = audio.Resampler(16000, 24000, align="zero", evaluator=_contract_evaluator([]))
+    x = (np.random.default_rng(21).standard_normal(6000) * 0.3).astype(F32)
+    sizes = [1, 7, 640, 319, 1, 2048, 0, 33, 640, 2311]
+    assert sum(sizes) == x.size
+    for tempo in (0.8, 1.37):
+        want = rs.resample(ts.stretch(x, tempo))
+        stages = audio_stages(ts, tempo, rs)
+        assert len(stages) == 2
+        one = x
+        for batch, _ in stages:
+            one = batch([one])[0]
+        assert np.array_equal(bits(one), bits(want))
+        streams = [stream() for _, stream in stages]
+        parts, pos = [], 0
+        for n in sizes:
+            parts.append(feed_stages(streams, x[pos:pos + n], False))
+            pos += n
+        assert any(p.size == 0 for p in parts)
+        parts.append(feed_stages(streams, np.zeros(0, F32), True))
+        got = np.concatenate(parts)
+        assert got.dtype == F32 and got.size == want.size and np.array_equal(bits(got), bits(want)), tempo
+        assert [s.kept for s in streams] == [0, 0]
+        for s in streams:
+            with pytest.raises(ValueError):
+                s.feed(x[:1])
+    assert audio_stages(None, None, None) == [] and feed_stages([], x, True) is x
+
+
 # ---- the contract's sanity ------------------------------------------------------------------------
 def test_contract_on_a_periodic_signal():
     sr = 16000
