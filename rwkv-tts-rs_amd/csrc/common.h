@@ -115,7 +115,7 @@ __device__ inline void store_wt(__amdgpu_buffer_rsrc_t r, int off_bytes, float v
 // Launch timeline: start of the launch's first workgroup and end of its last one in
 // s_memrealtime ticks (100 MHz, one clock for every CU); ends are max-reduced over 64 slots to keep
 // the atomics off one address. Slot layout per launch: [0] start, [2..65] ends. The slot pointer
-// is null unless the engine records launch times: the debug timeline (RWKVTTS_TIMELINE, make TL=1)
+// is null unless the engine records launch times: the debug timeline (RWKVTTS_DEBUG_STAMPS timeline=path, make TL=1)
 // or the in-graph kernel timing the bench samples (rwkvtts_set_profiling(e, 2)); with a null slot
 // a hook is one uniform branch.
 constexpr int kTlStride = 66;

@@ -111,7 +111,7 @@ class Engine {
   bool validate(const rwkvtts_request& q, std::string& why) const;
   int max_slots() const { return S_; }
   // whether this engine holds its device's persistent-launch slot (claim_persistent)
-  bool persistent() const { return att_persist_ != 0 || ffn_persist_ != 0; }
+  bool persistent() const { return att_persist_ || ffn_persist_; }
   // true once after serve() returned an error because a persistent hand-off wait timed out: the
   // unit's jobs failed, the give-up word, every hand-off counter block and the failed slots were
   // reset, and the engine serves again (the manager keeps it; the next batch runs normally)
@@ -169,13 +169,19 @@ class Engine {
   void state_permute(const float* std_block, float* dev_block);
   void state_unpermute(const float* dev_block, float* std_block);
   int state_perm_ = 0;  // WKV state block layout (wkv_perm_layout; engine.hip perm_index)
-  // XCD-aware grids per launch class: bit 0 rkv, 1 Wo, 2 ffn key, 3 ffn value, 4 head, 5 wkv
-  static constexpr int kXmapMask = 0x28;  // measured (timeline A/B): value GEMM and WKV gain, rkv loses
-  // write-through (sc1) output stores per launch class, same bit order as kXmapMask, plus
-  // bit 6 ln_att, bit 7 ln_ffn
+  // launch classes of a forward step: the bit positions of the per-class masks below
+  enum LaunchClass { kClsRkv, kClsWo, kClsKey, kClsValue, kClsHead, kClsWkv, kClsLnAtt, kClsLnFfn };
+  // XCD-aware grids per launch class
+  static constexpr int kXmapMask = 1 << kClsValue | 1 << kClsWkv;  // measured (timeline A/B): value GEMM and WKV gain, rkv loses
+  // write-through (sc1) output stores per launch class
   static constexpr int kWtMask = 0xFF;
-  // GemmArgs::xalign per class: bit 0 rkv (-> WKV heads; within noise, off), bit 2 ffn key (-> value K-slices)
-  static constexpr int kXalignMask = 4;
+  // GemmArgs::xalign per class: rkv (-> WKV heads) within noise, off; ffn key (-> value K-slices) on
+  static constexpr int kXalignMask = 1 << kClsKey;
+  static constexpr int xmap(LaunchClass c) { return (kXmapMask >> c) & 1; }
+  static constexpr int wt(LaunchClass c) { return (kWtMask >> c) & 1; }
+  static constexpr int xalign(LaunchClass c) { return (kXalignMask >> c) & 1; }
+  // the layer whose launches carry the debug stamps (RWKVTTS_DEBUG_STAMPS gemm / ffn / att / wkv)
+  static constexpr int kStampLayer = 5;
   // The decode-step forms (rwkvtts_engine_desc.forms, RWKVTTS_FORM_*; the defaults are the shipping
   // forms, each measured faster than the launches it replaces):
   // one-row decode steps: the row-fused persistent form (each GEMM workgroup computes the row's
@@ -191,13 +197,11 @@ class Engine {
   bool lnrow_ = true;
   bool exact_sampler_ = false;  // RWKVTTS_FORM_EXACT_SAMPLER: k_advance without the certified fast path
   int* d_epoch_ = nullptr;
-  // decode steps' FFN / attention half as one persistent launch (k_ffn_persist / k_att_persist):
-  // 0 off (RWKVTTS_FORM_SEPARATE_FFN / _ATT), else 1 + 2 x launch options (opts 2: the longer poll
-  // sleep, the measured best)
-  static constexpr int kPersistOn = 5;
-  int ffn_persist_ = kPersistOn;
+  // decode steps' FFN / attention half as one persistent launch (k_ffn_persist / k_att_persist);
+  // RWKVTTS_FORM_SEPARATE_FFN / _ATT turn them off
+  bool ffn_persist_ = true;
   int* ffn_sync_ = nullptr; // its hand-off counters: [L][kFfnSyncInts] (give-up code: d_ctrl_[S_])
-  int att_persist_ = kPersistOn;
+  bool att_persist_ = true;
   int* att_sync_ = nullptr; // its hand-off counters: [L][kAttSyncInts]
   int device_ = 0;
   int f16_ = 0;  // fp16 matrices (else bf16): MFMA f16 and f16 activation planes
@@ -228,6 +232,37 @@ class Engine {
     unsigned long long* p = base + (size_t)kTlStride * tl_n_;
     ++tl_n_;
     return p;
+  }
+  // One launch of a forward step, always in this order: its timeline slot (tl_name; null: none),
+  // the profiling window, launch(slot), the window's end under prof_name.
+  template <class Fn>
+  void timed(const char* tl_name, const char* prof_name, Fn&& launch) {
+    unsigned long long* tl = tl_name ? tl_next(tl_name) : nullptr;
+    hipEvent_t ev;
+    prof_begin(&ev);
+    launch(tl);
+    prof_end(prof_name, ev);
+  }
+  // A persistent launch of layer l (launch(slot) says whether it covers the shapes). Not covered --
+  // layer 0 only: a later layer would leave its successor's counters dirty -- the form is off for the
+  // whole forward (use = false) and the timeline slot goes to the separate launches.
+  template <class Fn>
+  int try_persistent(const char* name, int l, bool& use, bool& done, Fn&& launch) {
+    unsigned long long* tl = tl_next(name);
+    hipEvent_t ev;
+    prof_begin(&ev);
+    done = launch(tl);
+    if (done) {
+      prof_end(name, ev);
+      return RWKVTTS_OK;
+    }
+    RT_CHECK(l == 0, RWKVTTS_EHIP, std::string("persistent launch ") + name + ": a layer after layer 0 fell back");
+    use = false;
+    if (tl_base() && tl_n_ > 0) {
+      --tl_n_;
+      if ((int)tl_names_.size() > tl_n_) tl_names_.resize(tl_n_);
+    }
+    return RWKVTTS_OK;
   }
   static constexpr int kTlMax = 1024;
   bf16_t* wpack_ = nullptr;      // GEMM matrices in MFMA fragment blocks (launch_pack_frag)

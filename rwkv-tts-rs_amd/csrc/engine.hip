@@ -175,14 +175,14 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
                                    RWKVTTS_FORM_SLAB_HANDOFF | RWKVTTS_FORM_SEPARATE_LNOUT |
                                    RWKVTTS_FORM_SEPARATE_EMBED | RWKVTTS_FORM_EXACT_SAMPLER;
   RT_CHECK((desc.forms & ~kKnownForms) == 0, RWKVTTS_EINVAL, "engine desc: unknown forms bits");
-  att_persist_ = (desc.forms & RWKVTTS_FORM_SEPARATE_ATT) ? 0 : kPersistOn;
-  ffn_persist_ = (desc.forms & RWKVTTS_FORM_SEPARATE_FFN) ? 0 : kPersistOn;
+  att_persist_ = !(desc.forms & RWKVTTS_FORM_SEPARATE_ATT);
+  ffn_persist_ = !(desc.forms & RWKVTTS_FORM_SEPARATE_FFN);
   fuse_ln1_ = !(desc.forms & RWKVTTS_FORM_LN_ROWS);
   gran_ = !(desc.forms & RWKVTTS_FORM_SLAB_HANDOFF);
   lnrow_ = !(desc.forms & RWKVTTS_FORM_SEPARATE_LNOUT);
   no_emb_fuse_ = (desc.forms & RWKVTTS_FORM_SEPARATE_EMBED) != 0;
   exact_sampler_ = (desc.forms & RWKVTTS_FORM_EXACT_SAMPLER) != 0;
-  if ((ffn_persist_ || att_persist_) && !claim_persistent(desc.device, this, &lock_fd_)) ffn_persist_ = att_persist_ = 0;
+  if ((ffn_persist_ || att_persist_) && !claim_persistent(desc.device, this, &lock_fd_)) ffn_persist_ = att_persist_ = false;
   // debug instrumentation (tools/: stamps of one layer's launches, the launch timeline), off in
   // production: RWKVTTS_DEBUG_STAMPS="kind=path[;kind=path...]", kind one of gemm (layer-5 rkv /
   // value GEMM), ffn / att (layer-5 persistent-launch block stamps), timeline (per-launch start /
@@ -567,7 +567,6 @@ static constexpr int kPlaneRows = 64;
 
 int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_from_ctrl, bool advance) {
   const int C = dims.n_embd, F = dims.n_ffn, Lc = dims.n_layer;
-  hipEvent_t ev;
   const int nb = (R + 255) / 256;
   // decode steps (tokens from the control blocks, one row per slot) keep each slot's shift
   // state in place: no parity refresh / flip kernels (rows[].w was set once at upload)
@@ -595,12 +594,11 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
   // launch (which bumps the pass epoch) has been issued
   const bool gran_pass = gran_ && d_gran_ && fuse_ln1_ && R == 1 && use_att && use_ffn;
   bool gran_live = false;
-  if (!emb_fused) {
-    prof_begin(&ev);
-    launch_embed(d_tok_, d_rows_, &d_ctrl_[0].next_token, (int)(sizeof(SlotCtrl) / 4), emb_,
-                 ln0_w_, ln0_b_, h0_, R, C, f16_, stream_, tl_next("embed"), dims.n_vocab);
-    prof_end("embed", ev);
-  }
+  if (!emb_fused)
+    timed("embed", "embed", [&](unsigned long long* tl) {
+      launch_embed(d_tok_, d_rows_, &d_ctrl_[0].next_token, (int)(sizeof(SlotCtrl) / 4), emb_, ln0_w_, ln0_b_, h0_, R, C,
+                   f16_, stream_, tl, dims.n_vocab);
+    });
   const int64_t RC = (int64_t)Rmax_ * C;
   // ---- att: residual (+ previous layer's ffn partials) -> LN1 -> 6 mixes (layer l's arguments)
   auto ln_att_args = [&](int l) {
@@ -629,7 +627,7 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
     m.rows = d_rows_;
     m.row_map = nullptr;
     m.inplace = inplace ? 1 : 0;
-    m.wt = (kWtMask >> 6) & 1;
+    m.wt = wt(kClsLnAtt);
     if (l == 0 && emb_fused) {
       m.emb_tok = d_tok_;
       m.emb_ctrl = &d_ctrl_[0].next_token;
@@ -690,10 +688,10 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
       for (int t = 0; t < 3 * C / 64; ++t) g.tinfo[t] |= 1u << 31;
     }
     g.xmode = kXPlanes; g.out = partA_; g.split_stride = (int64_t)Rmax_ * ldA_; g.ldo = ldA_;
-    g.allow_xmap = kXmapMask & 1;
-    g.xalign = (kXalignMask & 1) ? 1 : 0;  // r / k / v tile h (head h) on the XCD of WKV head h
-    g.wt = kWtMask & 1;
-    g.stamps = (l == 5 && dbg_gstamps_) ? dbg_gstamps_ : nullptr;
+    g.allow_xmap = xmap(kClsRkv);
+    g.xalign = xalign(kClsRkv) ? 1 : 0;  // r / k / v tile h (head h) on the XCD of WKV head h
+    g.wt = wt(kClsRkv);
+    g.stamps = (l == kStampLayer && dbg_gstamps_) ? dbg_gstamps_ : nullptr;
     // ---- WKV + LoRA-up + GroupNorm + bonus + gate
     WkvArgs k{};
     k.f16 = f16_;
@@ -706,10 +704,10 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
     k.v_first = vfirst_; k.ldv = C; k.z_hi = z_hi_; k.z_lo = z_lo_; k.ldz = C;
     k.segs = d_segs_; k.layer = l; k.C = C; k.n_slots = S_; k.n_seg = n_seg; k.multi_row = R > n_seg;
     k.perm = state_perm_;
-    k.allow_xmap = (kXmapMask >> 5) & 1;
-    k.wt = (kWtMask >> 5) & 1;
+    k.allow_xmap = xmap(kClsWkv);
+    k.wt = wt(kClsWkv);
     k.Dw = dims.d_decay; k.Da = dims.d_aaa; k.Dv = dims.d_mv; k.Dg = dims.d_gate;
-    k.stamps = (l == 5) ? dbg_stamps_ : nullptr;
+    k.stamps = (l == kStampLayer) ? dbg_stamps_ : nullptr;
     // ---- output projection (split-K partials)
     GemmArgs go{};
     go.f16 = f16_;
@@ -717,9 +715,9 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
     go.seg[0] = {w.wo, z_hi_, z_lo_, C, C, 0, 0};
     go.K = C; go.M = R; go.k_split = splitO_; go.kslice = C / splitO_;
     go.xmode = kXPlanes; go.out = partO_; go.split_stride = RC; go.ldo = C;
-    go.allow_xmap = (kXmapMask >> 1) & 1;
+    go.allow_xmap = xmap(kClsWo);
     if (w.quant) { go.q_fmt = w.quant; go.qw = w.q_o; go.qs = w.s_o; go.q_shift = w.qs_o; }
-    go.wt = (kWtMask >> 1) & 1;
+    go.wt = wt(kClsWo);
     // ---- ffn: residual + Wo partials -> LN2 -> mix
     LnMixArgs f = m;
     f.emb = nullptr;  // (layer 0's embedding fusion belongs to the attention LayerNorm only)
@@ -734,47 +732,32 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
     f.x_hi = xf_hi_;
     f.x_lo = xf_lo_;
     f.shift = ffn_sh_;
-    f.wt = (kWtMask >> 7) & 1;
+    f.wt = wt(kClsLnFfn);
     // decode steps: the attention half as ONE persistent launch (k_att_persist: LN1 + mixes, rkv +
     // LoRA-down, WKV, Wo with in-launch hand-offs; bit-identical outputs) where the shapes allow it
     bool att_persisted = false;
     if (use_att) {
-      m.tl = g.tl = k.tl = go.tl = tl_next("att_persist");
-      prof_begin(&ev);
-      att_persisted = launch_att_persist(m, g, k, go, att_sync_ + (size_t)l * kAttSyncInts,
-                                         att_sync_ + (size_t)((l + Lc - 1) % Lc) * kAttSyncInts, (int*)(d_ctrl_ + S_),
-                                         R, H_, stream_, l == 5 ? dbg_astamps2_ : nullptr, att_persist_ >> 1, d_drop_,
-                                         fuse_ln1_, l == 0 && gran_pass ? d_epoch_ : nullptr,
-                                         gran_live ? d_gran_att_ : nullptr, d_epoch_);
-      if (att_persisted) {
-        prof_end("att_persist", ev);
-        if (l == 0 && gran_pass) gran_live = true;  // this pass's epoch is bumped
-      } else {
-        RT_CHECK(l == 0, RWKVTTS_EHIP, "persistent attention launch: a layer after layer 0 fell back");
-        use_att = false;  // not covered: the separate launches for this whole forward
-        if (tl_base() && tl_n_ > 0) {
-          --tl_n_;
-          if ((int)tl_names_.size() > tl_n_) tl_names_.resize(tl_n_);
-        }
-      }
+      RT_OK(try_persistent("att_persist", l, use_att, att_persisted, [&](unsigned long long* tl) {
+        m.tl = g.tl = k.tl = go.tl = tl;
+        return launch_att_persist(m, g, k, go, att_sync_ + (size_t)l * kAttSyncInts,
+                                  att_sync_ + (size_t)((l + Lc - 1) % Lc) * kAttSyncInts, (int*)(d_ctrl_ + S_), R, H_,
+                                  stream_, l == kStampLayer ? dbg_astamps2_ : nullptr, d_drop_,
+                                  fuse_ln1_, l == 0 && gran_pass ? d_epoch_ : nullptr,
+                                  gran_live ? d_gran_att_ : nullptr, d_epoch_);
+      }));
+      if (att_persisted && l == 0 && gran_pass) gran_live = true;  // this pass's epoch is bumped
     }
     if (!att_persisted) {
-      m.tl = tl_next("ln_att");
-      prof_begin(&ev);
-      RT_CHECK(launch_ln_mix(m, R, stream_) >= 0, RWKVTTS_EUNSUPPORTED, "layer-0 embedding fusion: unsupported shape");
-      prof_end("ln_mix_att", ev);
-      g.tl = tl_next("gemm_rkv");
-      prof_begin(&ev);
-      launch_gemm(g, stream_);
-      prof_end("gemm_rkv_lora", ev);
-      k.tl = tl_next("wkv");
-      prof_begin(&ev);
-      launch_wkv(k, n_seg, H_, stream_);
-      prof_end("wkv", ev);
-      go.tl = tl_next("gemm_wo");
-      prof_begin(&ev);
-      launch_gemm(go, stream_);
-      prof_end("gemm_wo", ev);
+      {  // (timed() spelled out: a refused launch returns before prof_end)
+        hipEvent_t ev;
+        m.tl = tl_next("ln_att");
+        prof_begin(&ev);
+        RT_CHECK(launch_ln_mix(m, R, stream_) >= 0, RWKVTTS_EUNSUPPORTED, "layer-0 embedding fusion: unsupported shape");
+        prof_end("ln_mix_att", ev);
+      }
+      timed("gemm_rkv", "gemm_rkv_lora", [&](unsigned long long* tl) { g.tl = tl; launch_gemm(g, stream_); });
+      timed("wkv", "wkv", [&](unsigned long long* tl) { k.tl = tl; launch_wkv(k, n_seg, H_, stream_); });
+      timed("gemm_wo", "gemm_wo", [&](unsigned long long* tl) { go.tl = tl; launch_gemm(go, stream_); });
     }
     GemmArgs gk{};
     gk.f16 = f16_;
@@ -782,11 +765,11 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
     gk.seg[0] = {w.ffn_k, xf_hi_, xf_lo_, C, F, 0, 0};
     gk.K = C; gk.M = R; gk.k_split = splitK_; gk.kslice = C / splitK_;
     gk.xmode = kXPlanes; gk.out = partK_; gk.split_stride = (int64_t)Rmax_ * F; gk.ldo = F;
-    gk.allow_xmap = (kXmapMask >> 2) & 1;
+    gk.allow_xmap = xmap(kClsKey);
     if (w.quant) { gk.q_fmt = w.quant; gk.qw = w.q_fk; gk.qs = w.s_fk; gk.q_shift = w.qs_fk; }
     // key tiles of value K-slice s on the XCD that runs slice s (value xmap: split = xcd + 8 j)
-    if ((kXalignMask >> 2) & 1) gk.xalign = std::max(1, (F / splitF_) / 64);
-    gk.wt = (kWtMask >> 2) & 1;
+    if (xalign(kClsKey)) gk.xalign = std::max(1, (F / splitF_) / 64);
+    gk.wt = wt(kClsKey);
     GemmArgs gv{};
     gv.f16 = f16_;
     gv.nseg = 1;
@@ -802,82 +785,58 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
       gv.xmode = kXPlanes;
     }
     gv.out = partF_; gv.split_stride = RC; gv.ldo = C;
-    gv.allow_xmap = (kXmapMask >> 3) & 1;
+    gv.allow_xmap = xmap(kClsValue);
     if (w.quant) { gv.q_fmt = w.quant; gv.qw = w.q_fv; gv.qs = w.s_fv; gv.q_shift = w.qs_fv; }
-    gv.wt = (kWtMask >> 3) & 1;
-    gv.stamps = (l == 5 && dbg_gstamps_) ? dbg_gstamps_ + 4096 * 4 : nullptr;
+    gv.wt = wt(kClsValue);
+    gv.stamps = (l == kStampLayer && dbg_gstamps_) ? dbg_gstamps_ + 4096 * 4 : nullptr;
     // decode steps: the whole FFN half as ONE persistent launch (k_ffn_persist, in-launch
     // hand-offs; bit-identical outputs) where the shapes allow it
     bool persisted = false;
-    if (use_ffn) {
-      f.tl = gk.tl = gv.tl = tl_next("ffn_persist");
-      prof_begin(&ev);
-      persisted = launch_ffn_persist(f, gk, gv, ffn_sync_ + (size_t)l * kFfnSyncInts,
-                                     ffn_sync_ + (size_t)((l + Lc - 1) % Lc) * kFfnSyncInts,
-                                     (int*)(d_ctrl_ + S_), R, stream_, l == 5 ? dbg_fstamps_ : nullptr,
-                                     ffn_persist_ >> 1, fuse_ln1_, gran_live ? d_gran_ : nullptr, d_epoch_);
-      if (persisted) {
-        prof_end("ffn_persist", ev);
-      } else {
-        RT_CHECK(l == 0, RWKVTTS_EHIP, "persistent FFN launch: a layer after layer 0 fell back");
-        use_ffn = false;
-        if (tl_base() && tl_n_ > 0) {  // (the timeline slot goes to the three launches below)
-          --tl_n_;
-          if ((int)tl_names_.size() > tl_n_) tl_names_.resize(tl_n_);
-        }
-      }
-    }
+    if (use_ffn)
+      RT_OK(try_persistent("ffn_persist", l, use_ffn, persisted, [&](unsigned long long* tl) {
+        f.tl = gk.tl = gv.tl = tl;
+        return launch_ffn_persist(f, gk, gv, ffn_sync_ + (size_t)l * kFfnSyncInts,
+                                  ffn_sync_ + (size_t)((l + Lc - 1) % Lc) * kFfnSyncInts, (int*)(d_ctrl_ + S_), R,
+                                  stream_, l == kStampLayer ? dbg_fstamps_ : nullptr, fuse_ln1_,
+                                  gran_live ? d_gran_ : nullptr, d_epoch_);
+      }));
     if (!persisted) {
-      f.tl = tl_next("ln_ffn");
-      prof_begin(&ev);
-      launch_ln_mix(f, R, stream_);
-      prof_end("ln_mix_ffn", ev);
-      prof_begin(&ev);
-      gk.tl = tl_next("gemm_key");
-      launch_gemm(gk, stream_);
-      prof_end("gemm_ffn_key", ev);
+      timed("ln_ffn", "ln_mix_ffn", [&](unsigned long long* tl) { f.tl = tl; launch_ln_mix(f, R, stream_); });
+      timed("gemm_key", "gemm_ffn_key", [&](unsigned long long* tl) { gk.tl = tl; launch_gemm(gk, stream_); });
       if (planes) launch_relu2_planes(partK_, splitK_, (int64_t)Rmax_ * F, F, F, R, xk_hi_, xk_lo_, stream_);
-      prof_begin(&ev);
-      gv.tl = tl_next("gemm_value");
-      launch_gemm(gv, stream_);
-      prof_end("gemm_ffn_value", ev);
+      timed("gemm_value", "gemm_ffn_value", [&](unsigned long long* tl) { gv.tl = tl; launch_gemm(gv, stream_); });
     }
   }
   if (n_lg > 0) {
     LnMixArgs o = ln_out_args();
     // one-row steps: ln_out folded into the head GEMM (launch_gemm_lnrow) where covered
     const bool lnrow = lnrow_ && n_lg == 1 && R == 1;
-    if (!lnrow) {
-      o.tl = tl_next("ln_out");
-      prof_begin(&ev);
-      launch_ln_mix(o, n_lg, stream_);
-      prof_end("ln_out", ev);
-    }
+    auto ln_out = [&]() {
+      timed("ln_out", "ln_out", [&](unsigned long long* tl) { o.tl = tl; launch_ln_mix(o, n_lg, stream_); });
+    };
+    if (!lnrow) ln_out();
     GemmArgs gh{};
     gh.f16 = f16_;
     gh.nseg = 1;
     gh.seg[0] = {head_, xo_hi_, xo_lo_, C, head_rows, 0, 0};
     gh.K = C; gh.M = n_lg; gh.k_split = splitH_; gh.kslice = C / splitH_;
     gh.xmode = kXPlanes; gh.out = logits_; gh.split_stride = (int64_t)Rmax_ * Vpad_; gh.ldo = Vpad_;
-    gh.allow_xmap = (kXmapMask >> 4) & 1;
-    gh.wt = (kWtMask >> 4) & 1;
-    prof_begin(&ev);
-    gh.tl = tl_next("gemm_head");
-    bool headed = false;
-    if (lnrow) {
-      o.n_rows = 1;
-      headed = launch_gemm_lnrow(gh, o, stream_);
-      if (!headed) {  // not covered: the two launches
-        prof_end("gemm_head", ev);
-        o.tl = tl_next("ln_out");
-        prof_begin(&ev);
-        launch_ln_mix(o, n_lg, stream_);
-        prof_end("ln_out", ev);
-        prof_begin(&ev);
+    gh.allow_xmap = xmap(kClsHead);
+    gh.wt = wt(kClsHead);
+    bool headed = !lnrow;
+    timed("gemm_head", "gemm_head", [&](unsigned long long* tl) {
+      gh.tl = tl;
+      if (lnrow) {
+        o.n_rows = 1;
+        headed = launch_gemm_lnrow(gh, o, stream_);
+      } else {
+        launch_gemm(gh, stream_);
       }
+    });
+    if (!headed) {  // the folded form does not cover the shape: the two launches (the head keeps its slot)
+      ln_out();
+      timed(nullptr, "gemm_head", [&](unsigned long long*) { launch_gemm(gh, stream_); });
     }
-    if (!headed) launch_gemm(gh, stream_);
-    prof_end("gemm_head", ev);
     if (advance) {
       AdvanceArgs a{};
       a.logits = logits_;
@@ -888,11 +847,11 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
       a.ctrl = d_ctrl_;
       a.sem_out = d_sem_;
       a.n_rows = n_lg;
-      a.tl = tl_next("advance");
       a.stamps = dbg_astamps_;
-      prof_begin(&ev);
-      launch_advance(a, stream_, exact_sampler_ ? 0 : 1);
-      prof_end("sample_advance", ev);
+      timed("advance", "sample_advance", [&](unsigned long long* tl) {
+        a.tl = tl;
+        launch_advance(a, stream_, exact_sampler_ ? 0 : 1);
+      });
     }
   }
   if (!inplace)
@@ -1755,7 +1714,7 @@ int Engine::reset_persistent() {
 int Engine::degrade_persistent() {
   RT_HIP(hipSetDevice(device_));
   RT_HIP(hipStreamSynchronize(stream_));
-  att_persist_ = ffn_persist_ = 0;
+  att_persist_ = ffn_persist_ = false;
   for (auto& g : graphs_) hipGraphExecDestroy(g.second);  // they hold persistent launches
   graphs_.clear();
   graph_names_.clear();

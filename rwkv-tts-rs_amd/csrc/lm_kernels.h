@@ -63,9 +63,7 @@ struct GemmSeg {
   int tile_start;      // first 64-column tile index of this segment
 };
 
-// NSEG_ segments and NTINFO_ tile descriptors (the arrays last)
-template <int NSEG_, int NTINFO_>
-struct GemmArgsT {
+struct GemmArgs {
   int nseg;
   int K;
   int M;               // valid rows
@@ -114,21 +112,9 @@ struct GemmArgsT {
   // matrix's largest |w|) so that the lo half stays a normal f16 number; the product is scaled
   // back by 2^-q_shift in the epilogue (powers of two: exact)
   int q_shift;
-  GemmSeg seg[NSEG_];
-  uint32_t tinfo[NTINFO_];
+  GemmSeg seg[8];
+  uint32_t tinfo[128];  // one descriptor per 64-column tile (gemm_tile_table)
 };
-using GemmArgs = GemmArgsT<8, 128>;
-// a single-segment launch's arguments without the segment / descriptor tables (the roles of the
-// one-launch-per-layer form, whose kernel arguments must stay under 4 KB)
-using GemmArgs1 = GemmArgsT<1, 1>;
-inline GemmArgs1 gemm_args1(const GemmArgs& a) {
-  GemmArgs1 b;
-  static_assert(offsetof(GemmArgs, seg) == offsetof(GemmArgs1, seg), "shared scalar layout");
-  memcpy((void*)&b, (const void*)&a, offsetof(GemmArgs, seg));
-  b.seg[0] = a.seg[0];
-  b.tinfo[0] = 0;
-  return b;
-}
 
 struct WkvArgs {
   const float* part;   // [n_part][R][ldp]
@@ -189,7 +175,18 @@ constexpr int kAttLora = 24;   // kLnReplicas: the LoRA-down tiles published
 constexpr int kAttWkv = 32;    // 16: WKV workgroups of head h done (one per row)
 constexpr int kAttCounters = 48;
 constexpr int kAttRkvDone = kAttLn + 1;  // row-fused form (no LayerNorm rows): rkv workgroups done
-struct FfnSync {     // (both persistent launches)
+static_assert(kAttCounters == kAttWkv + 16, "the WKV counters (one per head) end the attention block");
+static_assert(kFfnSyncInts == (kLnReplicas + kFfnSlices) * kSyncStride, "FFN counter block: LN replicas + K-slices");
+// Give-up codes: the bit a bounded wait ORs into FfnSync::err when its hand-off timed out (4 and 64
+// belonged to waits that no longer exist)
+constexpr int kGiveUpLnRows = 1;       // LayerNorm rows -> the rkv / key workgroups
+constexpr int kGiveUpKey = 2;          // key slabs or granules -> a value workgroup
+constexpr int kGiveUpWkv = 8;          // WKV z rows or granules -> a Wo workgroup
+constexpr int kGiveUpHead = 16;        // a head's r / k / v tiles -> its WKV workgroups
+constexpr int kGiveUpLora = 32;        // LoRA-down tiles -> the WKV workgroups
+constexpr int kGiveUpKeyDone = 1024;   // row-fused FFN: key workgroups staged -> the shift writer
+constexpr int kGiveUpRkvDone = 2048;   // row-fused attention: rkv workgroups staged -> the shift writer
+struct FfnSync {     // (both persistent launches; a field marked FFN / attention is read by that launch only)
   int* cnt;          // this layer's counters (zero at launch)
   int* cnt_prev;     // the counters of the layer launched before this one: zeroed by block 0
   int n_prev;        // counters to zero there
@@ -205,17 +202,13 @@ struct FfnSync {     // (both persistent launches)
   int head_target;   // attention: rkv workgroups per head (3 tiles x splits)
   int lora_target;   // attention: LoRA-down workgroups (tiles x splits)
   int C;             // attention: channels (r / k / v columns [0, 3C), LoRA-down beyond)
-  int opts;          // bit 0: value workgroups request their weights only once the LN rows are
-                     // published (not at dispatch); bit 1: longer sleep between polls; bit 2: key
-                     // workgroups request their weights after the LN wait (with their X)
-  uint64_t* stamps;  // debug (RWKVTTS_FFN_STAMPS): [block][4] s_memrealtime: start, wait done, work
+  uint64_t* stamps;  // debug (RWKVTTS_DEBUG_STAMPS ffn= / att=): [block][4] s_memrealtime: start, wait done, work
                      // done, end (null in production)
   // dispatch-time prefetches held back by a fixed time (s_memrealtime ticks of 10 ns; 0 = none),
   // so the LayerNorm rows at the head of the launch run with less traffic beside them:
-  // d_w the rkv / key weight streams, d_late the Wo weights, d_s the WKV state + LoRA-up, d_v the
-  // FFN value weights
-  int d_w, d_late, d_s, d_v;
-  int d_k;  // the FFN key weight streams (d_w: the rkv ones)
+  // attention: d_w the rkv weight streams, d_late the Wo weights; FFN: d_k the key weight streams,
+  // d_v the value weights
+  int d_w, d_late, d_v, d_k;
 
   // test hook (RWKVTTS_TEST_DROP_ARRIVE, null in production): the first rkv workgroup to find *drop
   // set clears it and skips its head arrival (a hand-off that never completes: the waits time out)
@@ -249,13 +242,13 @@ constexpr int kAttSyncInts = kAttCounters * kSyncStride;  // counter block per l
 // and the new token-shift row once every GEMM workgroup has read the old one (kAttRkvDone /
 // kFfnKeyDone). Replaces the LayerNorm phase and its hand-off at batch 1.
 bool launch_att_persist(const LnMixArgs& ln, const GemmArgs& rkv, const WkvArgs& wkv, const GemmArgs& wo, int* cnt,
-                        int* cnt_prev, int* err, int R, int H, hipStream_t st, uint64_t* stamps, int opts,
+                        int* cnt_prev, int* err, int R, int H, hipStream_t st, uint64_t* stamps,
                         int* drop = nullptr, bool fused_ln = false, int* epoch_bump = nullptr,
                         uint64_t* gran = nullptr, const int* epoch = nullptr);
 // granules of the one-row attention form's WKV -> Wo hand-off (one per channel)
 inline int64_t att_gran_count(int C) { return (int64_t)C; }
 bool launch_ffn_persist(const LnMixArgs& ln, const GemmArgs& key, const GemmArgs& val, int* cnt, int* cnt_prev,
-                        int* err, int R, hipStream_t st, uint64_t* stamps = nullptr, int opts = 0,
+                        int* err, int R, hipStream_t st, uint64_t* stamps = nullptr,
                         bool fused_ln = false, uint64_t* gran = nullptr, const int* epoch = nullptr);
 // granules the row-fused FFN form's key -> value hand-off needs (FfnSync::gran)
 inline int64_t ffn_gran_count(int key_splits, int F) { return (int64_t)key_splits * F; }

@@ -281,7 +281,7 @@ __global__ __launch_bounds__(256) void k_ln_mix(LnMixArgs a) {
 
 // The C = 1024 LayerNorm of one row in a 256-thread workgroup, thread t holding columns
 // [4t, 4t + 4): two one-barrier block sums (mean, then the centred second moment), x = d * rstd * w
-// + b. Shared by ln1024_body and the row-fused GEMM roles (gemm2_body ROLE 5 / 6), so both give the
+// + b. Shared by ln1024_body and the row-fused GEMM roles (gemm2_body kRoleRkvRow / kRoleKeyRow), so both give the
 // same bits.
 __device__ __attribute__((always_inline)) inline void ln1024_apply(float4_& x, const float4_& w, const float4_& b,
                                                                    float* red, int slot_base) {
@@ -636,15 +636,19 @@ __device__ inline void sync_stamp(const FfnSync& sy, int slot) {
 typedef __attribute__((address_space(1))) int gint_t;
 // one lane polls the counter (relaxed agent-scope load = global_load sc1, s_sleep between polls),
 // bounded by ~50 ms of s_memrealtime; the other waves wait at the barrier. On a timeout the code
-// is ORed into err (the host fails the step) and the workgroup goes on (its output is garbage).
-__device__ inline void sync_wait(const int* c, int target, int* err, int code, int opts = 0) {
+// (lm_kernels.h kGiveUp*) is ORed into err (the host fails the step) and the workgroup goes on (its
+// output is garbage).
+constexpr uint64_t kWaitTicks = 5000000ull;  // every bounded wait's limit (10 ns ticks)
+__device__ inline void give_up(int* err, int code) {
+  __hip_atomic_fetch_or((gint_t*)err, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ inline void sync_wait(const int* c, int target, int* err, int code) {
   if (threadIdx.x == 0) {
     const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
     while (__hip_atomic_load((gint_t*)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-      if (opts & 2) __builtin_amdgcn_s_sleep(8);
-      else __builtin_amdgcn_s_sleep(1);
-      if (__builtin_amdgcn_s_memrealtime() - t0 > 5000000ull) {
-        __hip_atomic_fetch_or((gint_t*)err, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __builtin_amdgcn_s_sleep(8);  // (the measured best; the granule polls sleep 1)
+      if (__builtin_amdgcn_s_memrealtime() - t0 > kWaitTicks) {
+        give_up(err, code);
         break;
       }
     }
@@ -663,12 +667,14 @@ __device__ inline bool take_drop(int* drop) {
 // publish: every wave's write-through (sc1) stores drained, then ONE lane counts the workgroup in
 // (replicas > 1: lanes 0..replicas-1 of wave 0 add to one replica each, kSyncStride ints apart).
 // drop (test hook, replicas == 1 only): lane 0 skips the add if it takes a pending drop
-__device__ inline void sync_arrive(int* c, int replicas = 1, int* drop = nullptr, int inc = 1) {
+__device__ inline void count_in(int* c) {
+  __hip_atomic_fetch_add((gint_t*)c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ inline void sync_arrive(int* c, int replicas = 1, int* drop = nullptr) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (drop && threadIdx.x == 0 && take_drop(drop)) return;
-  if (threadIdx.x < replicas)
-    __hip_atomic_fetch_add((gint_t*)(c + threadIdx.x * kSyncStride), inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (threadIdx.x < replicas) count_in(c + threadIdx.x * kSyncStride);
 }
 // granule hand-off (FfnSync::gran): the tag of this pass and layer, one 8-byte {f32, tag} store
 typedef __attribute__((address_space(1))) uint64_t gu64_t;
@@ -698,7 +704,7 @@ __device__ inline void gran_store_bits(uint64_t* p, uint32_t bits, uint32_t tag)
 __device__ inline void gran_store(uint64_t* p, float v, uint32_t tag) {
   gran_store_bits(p, __builtin_bit_cast(uint32_t, v), tag);
 }
-// hold a prefetch back until `ticks` (10 ns) after the launch's first s_memrealtime read here
+// hold a prefetch back until `ticks` (10 ns) after the workgroup's s_memrealtime read here
 __device__ inline void hold_until(int ticks) {
   if (ticks <= 0) return;
   const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
@@ -710,15 +716,28 @@ __device__ inline u32x4_ ld_sc1_b128(__amdgpu_buffer_rsrc_t r, int off_bytes) {
   return __builtin_amdgcn_raw_buffer_load_b128(r, off_bytes, 0, 16);
 }
 
-// ROLE 0: a plain launch. ROLE 1: key workgroup of k_ffn_persist (weights first, then wait for
-// the LayerNorm rows, X by sc1 loads, publish the partial slab). ROLE 2: value workgroup (weights
-// first, then wait for its K-slice's key slabs, read them by sc1 loads). ROLE 3: rkv workgroup of
-// k_att_persist (as ROLE 1; publishes to its head's counter, or the LoRA-down counter). ROLE 4:
-// Wo workgroup (weights first, then wait for the WKV workgroups of its K-slice's two heads).
-// ROLE 5 / 6: the row-fused forms of ROLE 3 / 1 (one decode row): weights at dispatch, then the
-// row's LayerNorm computed here from the residual and the partial slabs (*lr: LN1 with 16 value
-// slabs / LN2 with 8 Wo slabs; ln1024_apply, the LayerNorm rows' arithmetic bit for bit) and only
-// this K-slice's mix staged as row 0 of the X image -- no LayerNorm rows, no hand-off before the GEMM.
+// gemm2_body's roles: what a workgroup waits for, how its X reaches LDS and what it publishes. Every
+// persistent role requests its weight fragments at dispatch (after its hold: kHoldRkv, kHoldKey and
+// kHold1* in the launch functions), reads handed-off bytes by sc1 loads only and stores write-through.
+//   role            waits for                    X arrives                           publishes             in
+//   kRolePlain      --                           plain loads, before the weights     --                    k_gemm2
+//   kRoleFfnKey     the LN rows (a replica)      planes, sc1                         its K-slice counter   k_ffn_persist
+//   kRoleFfnValue   its K-slice's key slabs      the NX key slabs, sc1               --                    k_ffn_persist
+//   kRoleRkv        the LN rows (a replica)      planes, sc1                         head / LoRA counter   k_att_persist
+//   kRoleWo         WKV of its two heads         z planes, sc1                       --                    k_att_persist
+//   kRoleRkvRow     -- (one row, layers > 0)     LN1 + its tile's mix here, row 0    as kRoleRkv, rkv-done k_att_persist FUSED
+//   kRoleKeyRow     -- (one row)                 LN2 + mix here, row 0               granules | its slice  k_ffn_persist FUSED
+//                                                                                    counter; key-done
+//   kRoleValueGran  its K-slice's key granules   the polled granules, row 0          --                    k_ffn_persist FUSED
+//   kRoleWoGran     its K-slice's z granules     the polled granules, row 0          --                    k_att_persist FUSED
+//   kRoleHeadLn     -- (one row, a plain launch) ln_out here (no mix), row 0         --                    k_gemm2_lnrow
+// The row-fused roles (one decode row) compute the row's LayerNorm themselves from the residual and
+// the partial slabs (*lr: LN1 with 16 value slabs / LN2 with 8 Wo slabs; ln1024_apply, the LayerNorm
+// rows' arithmetic bit for bit) and stage only their K-slice's mix as row 0 of the X image -- no
+// LayerNorm rows, no hand-off before the GEMM. The values are `int` template arguments of the kernels'
+// instantiations.
+constexpr int kRolePlain = 0, kRoleFfnKey = 1, kRoleFfnValue = 2, kRoleRkv = 3, kRoleWo = 4, kRoleRkvRow = 5,
+              kRoleKeyRow = 6, kRoleValueGran = 7, kRoleWoGran = 8, kRoleHeadLn = 10;
 // by: the split index of an xmap-0 grid (blockIdx.y for a plain launch).
 template <int MT, int KSTEPS, int XMODE, bool F16, int NX, int MS, bool QW, int ROLE, class GA>
 __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int bx, const int by,
@@ -828,7 +847,7 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
   auto x_col = [&](int u) { return (int)(((threadIdx.x + u * 256) % (KS / 4)) * 4); };
   auto load_x = [&]() {
   if constexpr (XMODE == kXPlanes) {
-    if constexpr (ROLE != 0) {  // handed-off planes: sc1 loads only
+    if constexpr (ROLE != kRolePlain) {  // handed-off planes: sc1 loads only
       // rows past M: an offset past the buffer's range, which the load returns as zeros with no
       // memory traffic (a one-row step reads 1/32 of the X bytes; no per-load branch: an
       // exec-masked branch around each load cost the 32-row step 4 %, round 5)
@@ -853,7 +872,7 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
     }
     }
   } else {
-    if constexpr (ROLE != 0) {  // handed-off key slabs: sc1 loads only (rows past M: zeros, as above)
+    if constexpr (ROLE != kRolePlain) {  // handed-off key slabs: sc1 loads only (rows past M: zeros, as above)
 #pragma unroll
       for (int p = 0; p < NX; ++p) {
         const auto rp = wt_rsrc(a.x_part + p * a.x_part_stride);
@@ -908,25 +927,22 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
 #pragma unroll
   for (int t = 0; t < KSTEPS; ++t) b[t] = __builtin_nontemporal_load((const short8*)(wp + t * 512));
   };
-  if constexpr (ROLE == 1 || ROLE == 3) {
-    // the weight stream does not depend on the LayerNorm: in flight during the wait (opts bit 2:
-    // requested after it, so the poll is not queued behind the weights and the LN rows' loads do
-    // not compete with them)
-    const bool late_w = ROLE == 1 ? (sy.opts & 4) != 0 : (sy.opts & 16) != 0;
-    hold_until(ROLE == 1 ? sy.d_k : sy.d_w);
-    if (!late_w) load_w();
-    sync_wait(sy.cnt + kSyncStride * (blockIdx.x & (kLnReplicas - 1)), sy.ln_rows, sy.err, 1, sy.opts);
+  if constexpr (ROLE == kRoleFfnKey || ROLE == kRoleRkv) {
+    // the weight stream does not depend on the LayerNorm: in flight during the wait
+    hold_until(ROLE == kRoleFfnKey ? sy.d_k : sy.d_w);
+    load_w();
+    sync_wait(sy.cnt + kSyncStride * (blockIdx.x & (kLnReplicas - 1)), sy.ln_rows, sy.err, kGiveUpLnRows);
     sync_stamp(sy, 1);
     load_x();
-    if (late_w) load_w();
-  } else if constexpr (ROLE == 4) {
+  } else if constexpr (ROLE == kRoleWo) {
     hold_until(sy.d_late);
     load_w();
     const int h0 = kbeg >> 6;  // the K-slice's first head (64 channels per head)
-    for (int hh = h0; hh < h0 + (KS >> 6); ++hh) sync_wait(sy.cnt + kSyncStride * (kAttWkv + hh), sy.ln_rows, sy.err, 8, sy.opts);
+    for (int hh = h0; hh < h0 + (KS >> 6); ++hh)
+      sync_wait(sy.cnt + kSyncStride * (kAttWkv + hh), sy.ln_rows, sy.err, kGiveUpWkv);
     sync_stamp(sy, 1);
     load_x();
-  } else if constexpr (ROLE == 8) {
+  } else if constexpr (ROLE == kRoleWoGran) {
     // Wo workgroup of the granule form (one row): weights at dispatch, then wave 0 polls the z
     // granules of its K-slice (row 0; each granule = the WKV's bf16 / f16 hi | lo << 16 split of one
     // channel, so no re-split) and writes them as row 0 of the X image; rows past 0 are not staged
@@ -945,8 +961,8 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
         const bool ok = (uint32_t)(q0 >> 32) == tag && (uint32_t)(q1 >> 32) == tag;
         if (__all(ok)) break;
         __builtin_amdgcn_s_sleep(1);
-        if (__builtin_amdgcn_s_memrealtime() - t0 > 5000000ull) {
-          if (lane == 0) __hip_atomic_fetch_or((gint_t*)sy.err, 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (__builtin_amdgcn_s_memrealtime() - t0 > kWaitTicks) {
+          if (lane == 0) give_up(sy.err, kGiveUpWkv);
           break;
         }
       }
@@ -956,7 +972,7 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
     }
     __syncthreads();
     sync_stamp(sy, 1);
-  } else if constexpr (ROLE == 10) {
+  } else if constexpr (ROLE == kRoleHeadLn) {
     // the head GEMM of a one-row step with ln_out fused (a plain launch): weights requested after
     // the row's inputs, the row's LayerNorm computed here (ln1024_body MODE 0's arithmetic: residual
     // + NP10 partial slabs in order, ln1024_apply) and this K-slice staged as row 0 of the X image
@@ -981,18 +997,18 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
       *(uint2*)(xl + (c - kbeg)) = make_uint2(l0, l1);
     }
     static_assert(C == 1024, "");
-  } else if constexpr (ROLE == 5 || ROLE == 6) {
+  } else if constexpr (ROLE == kRoleRkvRow || ROLE == kRoleKeyRow) {
     static_assert(MT == 1 && XMODE == kXPlanes, "row-fused LayerNorm: one row, planes");
     // the row's LayerNorm (all 256 threads: thread t owns columns [4t, 4t + 4)), then this
     // K-slice's mix split into row 0 of the X image (rows 1..15 are never stored). The LayerNorm
     // inputs (L2 / MALL hits, written by the previous launch) are requested BEFORE the weight stream
     // (HBM, behind the launch-start burst): loads return in order, so the sums wait for these alone.
-    constexpr int C = 1024, NPL = ROLE == 5 ? 16 : 8;
+    constexpr int C = 1024, NPL = ROLE == kRoleRkvRow ? 16 : 8;
     __shared__ float s_lnred[16];
     const LnMixArgs& L = *lr;
     const int c = 4 * (int)threadIdx.x;
     const float* mup = L.mu[0];
-    if constexpr (ROLE == 5) {
+    if constexpr (ROLE == kRoleRkvRow) {
 #pragma unroll
       for (int m = 1; m < 6; ++m)
         if (tile_mix == m) mup = L.mu[m];
@@ -1018,7 +1034,7 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
       *(uint2*)(xl + (c - kbeg)) = make_uint2(l0, l1);
     }
     sync_stamp(sy, 1);
-  } else if constexpr (ROLE == 7) {
+  } else if constexpr (ROLE == kRoleValueGran) {
     // value workgroup of the granule form (one row): weights at dispatch, then wave 0 polls its
     // K-slice's key granules for row 0 -- lane l: columns kbeg + 4l .. + 3 of the NX key splits,
     // two 16-byte sc1 loads (4 granules) per split -- until every tag is this pass's; the row's
@@ -1053,20 +1069,18 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
         }
         if (__all(ok)) break;
         __builtin_amdgcn_s_sleep(1);
-        if (__builtin_amdgcn_s_memrealtime() - t0 > 5000000ull) {
-          if (lane == 0) __hip_atomic_fetch_or((gint_t*)sy.err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (__builtin_amdgcn_s_memrealtime() - t0 > kWaitTicks) {
+          if (lane == 0) give_up(sy.err, kGiveUpKey);
           break;
         }
       }
     }
     __syncthreads();
     sync_stamp(sy, 1);
-  } else if constexpr (ROLE == 2) {
-    if (sy.opts & 1)  // weights after the LN rows
-      sync_wait(sy.cnt + kSyncStride * (blockIdx.x & (kLnReplicas - 1)), sy.ln_rows, sy.err, 4, sy.opts);
+  } else if constexpr (ROLE == kRoleFfnValue) {
     hold_until(sy.d_v);
     load_w();
-    sync_wait(sy.cnt + kSyncStride * (kLnReplicas + split), sy.key_per_slice, sy.err, 2, sy.opts);
+    sync_wait(sy.cnt + kSyncStride * (kLnReplicas + split), sy.key_per_slice, sy.err, kGiveUpKey);
     sync_stamp(sy, 1);
     load_x();
   } else {
@@ -1077,7 +1091,7 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
   // 3) X -> LDS (rows past M: zeros in the persistent roles (never fetched), a copy of row M-1 in the
   // plain launches; an MFMA output row depends on its own X row only, and those rows' outputs are not
   // stored)
-  if constexpr (ROLE == 5 || ROLE == 6 || ROLE == 8 || ROLE == 10) {
+  if constexpr (ROLE == kRoleRkvRow || ROLE == kRoleKeyRow || ROLE == kRoleWoGran || ROLE == kRoleHeadLn) {
     // (staged by the row-fused LayerNorm / the granule sweep above)
   } else if constexpr (XMODE == kXPlanes) {
 #pragma unroll
@@ -1092,12 +1106,12 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
     // of this K-slice is staged as relu^2 * 2^-e_r (e_r >= 0 the smallest power of two that
     // brings the row's maximum under 2^15) and its partial product is scaled back by 2^e_r in
     // the epilogue. Powers of two are exact, so rows in range (e_r = 0) are bit-unchanged.
-    // (ROLE 7, one row: only row 0 is staged -- rows past M hold stale bytes, which no stored
+    // (kRoleValueGran, one row: only row 0 is staged -- rows past M hold stale bytes, which no stored
     // output reads: an MFMA output row depends on its own X row only)
     float4_ y4[PERR];
 #pragma unroll
     for (int u = 0; u < PERR; ++u) {
-      if (ROLE == 7 && xrow0 + x_row(u) >= a.M) continue;
+      if (ROLE == kRoleValueGran && xrow0 + x_row(u) >= a.M) continue;
       float4_ x = xr[0][u];
 #pragma unroll
       for (int p = 1; p < NX; ++p) x += xr[p][u];
@@ -1110,7 +1124,7 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
 #pragma unroll
       for (int u = 0; u < PERR; ++u) {
         const int r = x_row(u);
-        if (ROLE == 7 && xrow0 + r >= a.M) continue;
+        if (ROLE == kRoleValueGran && xrow0 + r >= a.M) continue;
         const float m = fmaxf(fmaxf(y4[u][0], y4[u][1]), fmaxf(y4[u][2], y4[u][3]));
         if (m >= 32768.f) atomicMax(&s_rexp[r], as_u32(m));  // non-negative floats order as uints
       }
@@ -1119,7 +1133,7 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
 #pragma unroll
     for (int u = 0; u < PERR; ++u) {
       const int r = x_row(u), k4 = x_col(u);
-      if (ROLE == 7 && xrow0 + r >= a.M) continue;
+      if (ROLE == kRoleValueGran && xrow0 + r >= a.M) continue;
       float y[4] = {y4[u][0], y4[u][1], y4[u][2], y4[u][3]};
       if constexpr (F16) {
         const uint32_t mb = s_rexp[r];
@@ -1229,7 +1243,7 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
     }
     return v;
   };
-  if (ROLE == 6 && sy.gran) {
+  if (ROLE == kRoleKeyRow && sy.gran) {
     // granule form: row 0's 64 columns, one {f32, tag} granule per element (lanes 0..15 of each
     // wave hold row 0: g == 0, j == 0)
     if (g == 0 && col < Nn) gran_store(sy.gran + (int64_t)split * sy.gran_ld + col_off + col, result(0, 0), gran_tag(sy));
@@ -1273,46 +1287,38 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
   row0 = rg * ROWS;
   __syncthreads();  // every wave is done with the LDS X image / store staging
   }
-  if constexpr (ROLE != 0) sync_stamp(sy, 2);
-  if constexpr (ROLE == 1) sync_arrive(sy.cnt + kSyncStride * (kLnReplicas + tile / sy.key_group));
-  if constexpr (ROLE == 6) {  // K-slice counter (replica 0; not in the granule form) and key-done (lane 1)
+  if constexpr (ROLE != kRolePlain) sync_stamp(sy, 2);
+  if constexpr (ROLE == kRoleFfnKey) sync_arrive(sy.cnt + kSyncStride * (kLnReplicas + tile / sy.key_group));
+  if constexpr (ROLE == kRoleKeyRow) {  // K-slice counter (replica 0; not in the granule form) and key-done (lane 1)
     if (!sy.gran) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (threadIdx.x == 0 && !sy.gran)
-      __hip_atomic_fetch_add((gint_t*)(sy.cnt + kSyncStride * (kLnReplicas + tile / sy.key_group)), 1,
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (threadIdx.x == 1)
-      __hip_atomic_fetch_add((gint_t*)(sy.cnt + kSyncStride * kFfnKeyDone), 1, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0 && !sy.gran) count_in(sy.cnt + kSyncStride * (kLnReplicas + tile / sy.key_group));
+    if (threadIdx.x == 1) count_in(sy.cnt + kSyncStride * kFfnKeyDone);
   }
-  if constexpr (ROLE == 3) {
+  if constexpr (ROLE == kRoleRkv) {
     const int c0 = col_off + (tile - tstart) * 64;  // this tile's first output column
     if (c0 < 3 * sy.C) sync_arrive(sy.cnt + kSyncStride * (kAttHead + ((c0 % sy.C) >> 6)), 1, sy.drop);
     else sync_arrive(sy.cnt + kSyncStride * kAttLora, kLnReplicas);
   }
-  if constexpr (ROLE == 5) {  // as ROLE 3, plus rkv-done (lane 8) for the shift writer
+  if constexpr (ROLE == kRoleRkvRow) {  // as kRoleRkv, plus rkv-done (lane 8) for the shift writer
     const int c0 = col_off + (tile - tstart) * 64;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (c0 < 3 * sy.C) {
       // (test hook as in sync_arrive: a workgroup that takes a pending drop skips its arrival)
       if (threadIdx.x == 0 && !(sy.drop && take_drop(sy.drop)))
-        __hip_atomic_fetch_add((gint_t*)(sy.cnt + kSyncStride * (kAttHead + ((c0 % sy.C) >> 6))), 1,
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        count_in(sy.cnt + kSyncStride * (kAttHead + ((c0 % sy.C) >> 6)));
     } else if (threadIdx.x < kLnReplicas) {
-      __hip_atomic_fetch_add((gint_t*)(sy.cnt + kSyncStride * (kAttLora + threadIdx.x)), 1, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
+      count_in(sy.cnt + kSyncStride * (kAttLora + threadIdx.x));
     }
-    if (threadIdx.x == 8)
-      __hip_atomic_fetch_add((gint_t*)(sy.cnt + kSyncStride * kAttRkvDone), 1, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 8) count_in(sy.cnt + kSyncStride * kAttRkvDone);
   }
 }
 
 template <int MT, int KSTEPS, int XMODE, bool F16, int NX, int MS, bool QW = false>
 __global__ __launch_bounds__(256) void k_gemm2(GemmArgs a) {
   tl_begin(a.tl);
-  gemm2_body<MT, KSTEPS, XMODE, F16, NX, MS, QW, 0>(a, blockIdx.x, blockIdx.y, FfnSync{});
+  gemm2_body<MT, KSTEPS, XMODE, F16, NX, MS, QW, kRolePlain>(a, blockIdx.x, blockIdx.y, FfnSync{});
   tl_end(a.tl);
 }
 
@@ -1437,12 +1443,12 @@ __global__ __launch_bounds__(256) void k_gemm_wide(GemmArgs a) {
   tl_end(a.tl);
 }
 
-// the head GEMM of a one-row step with ln_out folded in (gemm2_body ROLE 10): one launch and one
+// the head GEMM of a one-row step with ln_out folded in (gemm2_body kRoleHeadLn): one launch and one
 // launch boundary fewer per step; logits bit for bit those of ln_out + k_gemm2
 template <bool F16>
 __global__ __launch_bounds__(256) void k_gemm2_lnrow(GemmArgs a, LnMixArgs lo) {
   tl_begin(a.tl);
-  gemm2_body<1, 16, kXPlanes, F16, 1, 0, false, 10>(a, blockIdx.x, blockIdx.y, FfnSync{}, &lo);
+  gemm2_body<1, 16, kXPlanes, F16, 1, 0, false, kRoleHeadLn>(a, blockIdx.x, blockIdx.y, FfnSync{}, &lo);
   tl_end(a.tl);
 }
 
@@ -1480,7 +1486,7 @@ bool launch_gemm_lnrow(const GemmArgs& a, const LnMixArgs& lo, hipStream_t st) {
 // the previously launched layer (that launch has finished: stream order).
 // ------------------------------------------------------------------------------------
 // FUSED (row-fused form, one decode row): no LayerNorm blocks; key workgroups compute the row's LN2
-// themselves (gemm2_body ROLE 6); the last workgroup (after the value ones) waits until every key
+// themselves (gemm2_body kRoleKeyRow); the last workgroup (after the value ones) waits until every key
 // workgroup has staged (kFfnKeyDone) and stores the residual and the new token-shift row.
 // Workgroups per CU the persistent kernels' register budgets are sized for (2: 256 VGPRs, two waves
 // per SIMD; 3 caps a kernel at 168 VGPRs so that three workgroups are resident per CU).
@@ -1506,18 +1512,18 @@ __global__ __launch_bounds__(256, RWKVTTS_FFN_WPC) void k_ffn_persist(LnMixArgs 
       sync_arrive(sy.cnt, kLnReplicas);
     }
   } else if ((b -= sy.n_ln_blocks) < sy.n_key) {
-    if constexpr (FUSED) gemm2_body<1, 8, kXPlanes, F16, 1, 0, false, 6>(ka, b, 0, sy, &ln);
-    else gemm2_body<2, 8, kXPlanes, F16, 1, 0, false, 1>(ka, b, 0, sy);
+    if constexpr (FUSED) gemm2_body<1, 8, kXPlanes, F16, 1, 0, false, kRoleKeyRow>(ka, b, 0, sy, &ln);
+    else gemm2_body<2, 8, kXPlanes, F16, 1, 0, false, kRoleFfnKey>(ka, b, 0, sy);
   } else if ((b -= sy.n_key) < sy.n_val || !FUSED) {
     if constexpr (FUSED) {
-      if (sy.gran) gemm2_body<1, 8, kXRelu2, F16, 4, 0, false, 7>(va, b, 0, sy);  // (one row: 16-row tile)
-      else gemm2_body<2, 8, kXRelu2, F16, 4, 0, false, 2>(va, b, 0, sy);
+      if (sy.gran) gemm2_body<1, 8, kXRelu2, F16, 4, 0, false, kRoleValueGran>(va, b, 0, sy);  // (one row: 16-row tile)
+      else gemm2_body<2, 8, kXRelu2, F16, 4, 0, false, kRoleFfnValue>(va, b, 0, sy);
     } else {
-      gemm2_body<2, 8, kXRelu2, F16, 4, 0, false, 2>(va, b, 0, sy);
+      gemm2_body<2, 8, kXRelu2, F16, 4, 0, false, kRoleFfnValue>(va, b, 0, sy);
     }
   } else if constexpr (FUSED) {  // the shift writer
     if (threadIdx.x < sy.n_prev) sy.cnt_prev[threadIdx.x * kSyncStride] = 0;
-    sync_wait(sy.cnt + kSyncStride * kFfnKeyDone, sy.n_key, sy.err, 1024, sy.opts);
+    sync_wait(sy.cnt + kSyncStride * kFfnKeyDone, sy.n_key, sy.err, kGiveUpKeyDone);
     ln1024_body<F16, 1, 0, 8>(ln, 0);
   }
   sync_stamp(sy, 3);
@@ -1880,7 +1886,7 @@ void launch_relu2_planes(const float* part, int nx, int64_t pstride, int ld, int
 // (the caller runs the three launches). ln / key / val: the three launches' arguments as built by
 // the engine; cnt / cnt_prev: this and the previous layer's counter blocks ((1 + kFfnSlices) x
 // kSyncStride ints, zero before this layer's first use); err: the give-up word.
-// Holds of the dispatch-time prefetches (FfnSync::d_w / d_k / d_late / d_s / d_v, 10 ns ticks).
+// Holds of the dispatch-time prefetches (FfnSync::d_w / d_k / d_late / d_v, 10 ns ticks).
 // The rkv / key weight streams wait 1 us, so the LayerNorm rows at the head of each persistent
 // launch load their slabs with less traffic beside them while the weights still land before the
 // LayerNorm ends (same-box decode A/B at B = 32: 771-776 -> 756-764 us per step, tokens unchanged;
@@ -1890,22 +1896,10 @@ constexpr int kHoldRkv = 100, kHoldKey = 100;
 // key ones feed the first GEMM there): 4 / 1 us (same-box B = 1 A/B: 525 -> 513-517 us per step,
 // round 5, profiles/r05u_holds1_ab.txt).
 constexpr int kHold1Wo = 400, kHold1Value = 100;
-static void prefetch_holds(FfnSync& sy) {
-  sy.d_w = kHoldRkv;
-  sy.d_late = 0;
-  sy.d_s = 0;
-  sy.d_v = 0;
-  sy.d_k = kHoldKey;
-}
 
-struct FfnPrep {
-  LnMixArgs l;
-  GemmArgs ka, va;
-  FfnSync sy;
-  int nv;
-};
-static bool prep_ffn_persist(const LnMixArgs& ln, const GemmArgs& key, const GemmArgs& val, int* cnt, int* cnt_prev,
-                             int* err, int R, uint64_t* stamps, int opts, FfnPrep& P) {
+bool launch_ffn_persist(const LnMixArgs& ln, const GemmArgs& key, const GemmArgs& val, int* cnt, int* cnt_prev,
+                        int* err, int R, hipStream_t st, uint64_t* stamps, bool fused_ln, uint64_t* gran,
+                        const int* epoch) {
   if (ln.C != 1024 || !ln.shift || ln.n_mix != 1 || ln.n_part != 8 || ln.emb || R < 1 || R > 32 ||
       key.xmode != kXPlanes || val.xmode != kXRelu2 || val.x_nsplit != 4 || key.kslice != 256 ||
       val.kslice != 256 || key.M != R || val.M != R || key.nseg != 1 || val.nseg != 1 || key.q_fmt || val.q_fmt ||
@@ -1920,73 +1914,37 @@ static bool prep_ffn_persist(const LnMixArgs& ln, const GemmArgs& key, const Gem
   if (kt % key.xalign || groups % 8 || groups != val.k_split || val.k_split % 8 || val.k_split > kFfnSlices ||
       key.xalign * 64 != val.kslice)
     return false;
-  LnMixArgs& l = P.l;
-  l = ln;
+  LnMixArgs l = ln;
   l.n_rows = R;
   l.wt = 1;
-  GemmArgs& ka = P.ka;
-  GemmArgs& va = P.va;
-  ka = key;
-  va = val;
+  GemmArgs ka = key, va = val;
   ka.xmap = 2; ka.ntiles = kt; ka.wt = 1;
   va.xmap = 1; va.ntiles = vt;
-  FfnSync& sy = P.sy;
-  sy = FfnSync{};
+  // the row-fused form (one row): no LayerNorm blocks, one trailing shift writer
+  const bool fused = fused_ln && R == 1 && ln.inplace;
+  FfnSync sy{};
   sy.cnt = cnt;
   sy.cnt_prev = cnt_prev;
+  sy.n_prev = kLnReplicas + kFfnSlices;
   sy.err = err;
-  sy.n_ln_blocks = 32;  // rows padded to 32 (a multiple of 8: the GEMM blocks keep their XCD order)
+  sy.n_ln_blocks = fused ? 0 : 32;  // rows padded to 32 (a multiple of 8: the GEMM blocks keep their XCD order)
   sy.ln_rows = R;
   sy.n_key = kt * key.k_split;
   sy.key_group = key.xalign;
   sy.key_per_slice = key.xalign * key.k_split;
+  sy.n_val = vt * val.k_split;
   sy.stamps = stamps;
-  sy.opts = opts;
-  prefetch_holds(sy);
-  sy.n_prev = kLnReplicas + kFfnSlices;
-  P.nv = vt * val.k_split;
-  sy.n_val = P.nv;
-  return true;
-}
-
-// the FFN half's arguments, its row-fused form (n_fix = 1: the trailing shift writer) and the
-// granule hand-off where they apply
-static bool ffn_setup(const LnMixArgs& ln, const GemmArgs& key, const GemmArgs& val, int* cnt, int* cnt_prev, int* err,
-                      int R, uint64_t* stamps, int opts, bool fused_ln, uint64_t* gran, const int* epoch, FfnPrep& P,
-                      int& n_fix) {
-  if (!prep_ffn_persist(ln, key, val, cnt, cnt_prev, err, R, stamps, opts, P)) return false;
-  const bool fused = fused_ln && R == 1 && ln.inplace;
-  n_fix = 0;
-  if (fused) {
-    P.sy.n_ln_blocks = 0;
-    P.sy.d_k = 0;
-    P.sy.opts &= ~1;  // (no LayerNorm rows for the value workgroups to wait for)
-    P.sy.d_v = kHold1Value;
-    n_fix = 1;
-    // the granule key -> value hand-off: four key splits (the value role's NX), one segment
-    if (gran && epoch && key.k_split == 4 && key.nseg == 1 && ln.layer < 64) {
-      P.sy.gran = gran;
-      P.sy.epoch = epoch;
-      P.sy.gran_ld = key.seg[0].N;
-      P.sy.layer = ln.layer;
-    }
+  sy.d_k = fused ? 0 : kHoldKey;
+  sy.d_v = fused ? kHold1Value : 0;
+  // the granule key -> value hand-off: four key splits (the value role's NX), one segment
+  if (fused && gran && epoch && key.k_split == 4 && key.nseg == 1 && ln.layer < 64) {
+    sy.gran = gran;
+    sy.epoch = epoch;
+    sy.gran_ld = key.seg[0].N;
+    sy.layer = ln.layer;
   }
-  return true;
-}
-
-bool launch_ffn_persist(const LnMixArgs& ln, const GemmArgs& key, const GemmArgs& val, int* cnt, int* cnt_prev,
-                        int* err, int R, hipStream_t st, uint64_t* stamps, int opts, bool fused_ln, uint64_t* gran,
-                        const int* epoch) {
-  FfnPrep P;
-  int n_fix = 0;
-  if (!ffn_setup(ln, key, val, cnt, cnt_prev, err, R, stamps, opts, fused_ln, gran, epoch, P, n_fix)) return false;
-  const bool fused = n_fix == 1;
-  LnMixArgs& l = P.l;
-  GemmArgs& ka = P.ka;
-  GemmArgs& va = P.va;
-  FfnSync& sy = P.sy;
   const size_t lds = (size_t)2 * 16 * (8 * 32 + 8) * 2 * 2;
-  const dim3 grid(sy.n_ln_blocks + sy.n_key + P.nv + n_fix);
+  const dim3 grid(sy.n_ln_blocks + sy.n_key + sy.n_val + (fused ? 1 : 0));
   if (key.f16) {
     if (fused) RT_LAUNCH((k_ffn_persist<true, true>), grid, dim3(256), lds, st, l, ka, va, sy);
     else RT_LAUNCH((k_ffn_persist<true, false>), grid, dim3(256), lds, st, l, ka, va, sy);
@@ -2428,7 +2386,7 @@ __global__ __launch_bounds__(128) void k_wkv4(WkvArgs a) {
   }
   const int C = a.C, c = h * N + i;
   tl_begin(a.tl);
-  // debug phase stamps (RWKVTTS_WKV_STAMPS, layer 5 only; null in production): [0] realtime
+  // debug phase stamps (RWKVTTS_DEBUG_STAMPS wkv=, one layer only; null in production): [0] realtime
   // start, [1..6] core clock at phase ends, [7] realtime end
   uint64_t* stp = (a.stamps && t == 0) ? a.stamps + ((int64_t)h * a.n_seg + seg_i) * 8 : nullptr;
   if (stp) { stp[0] = __builtin_amdgcn_s_memrealtime(); stp[1] = __builtin_amdgcn_s_memtime(); }
@@ -2624,16 +2582,20 @@ __global__ __launch_bounds__(128) void k_wkv4(WkvArgs a) {
 // State blocks: thread t's q-th float4 at float4 index q * 256 + t (engine.hip perm_index,
 // layout 2); LoRA-up rows: entry u of thread t at uint4 index u * 256 + t (launch_pack_lora6).
 // ------------------------------------------------------------------------------------
-// ROLE 0: a plain launch. ROLE 1: WKV workgroup of k_att_persist (decode rows only): the LoRA-up
-// rows and the state (independent of this layer's rkv launch) are requested at dispatch, then
-// the workgroup waits for its head's r / k / v tiles and the LoRA-down tiles, reads the partials
-// by sc1 loads, and publishes its z row (staged in LDS, stored write-through by one wave) to
-// its head's counter.
+// wkv6_body's roles (decode rows only in k_att_persist). The hand-off roles request the LoRA-up rows
+// and the state (independent of this layer's rkv workgroups) at dispatch, read the partials by sc1
+// loads, and store the final state after their hand-off.
+//   role       waits for                           publishes                                        in
+//   kWkvPlain  --                                  z planes, plain stores                           k_wkv6
+//   kWkvSlab   its head's r / k / v tiles and the  the z row (staged in LDS, written through by     k_att_persist
+//              LoRA-down tiles                     one wave), counted into its head's WKV counter
+//   kWkvGran   as kWkvSlab                         one {hi | lo << 16, tag} granule per channel     k_att_persist FUSED
+constexpr int kWkvPlain = 0, kWkvSlab = 1, kWkvGran = 2;
 template <bool F16, int ROLE>
 __device__ __attribute__((always_inline)) void wkv6_body(const WkvArgs& a, const int bx, const int by,
                                                          const FfnSync& sy) {
   constexpr int N = 64, DW = 64, DA = 64, DV = 32, DG = 128, DALL = DW + DA + DV + DG, NP = 4;
-  __shared__ __attribute__((aligned(16))) uint16_t s_zh[ROLE ? N : 4], s_zl[ROLE ? N : 4];
+  __shared__ __attribute__((aligned(16))) uint16_t s_zh[ROLE != kWkvPlain ? N : 4], s_zl[ROLE != kWkvPlain ? N : 4];
   __shared__ __attribute__((aligned(16))) float s_hid[DALL];
   __shared__ __attribute__((aligned(16))) float s_vec[5][N];  // w, kk (unnormalised), a, k, r
   __shared__ float s_red[4][4];
@@ -2645,7 +2607,7 @@ __device__ __attribute__((always_inline)) void wkv6_body(const WkvArgs& a, const
     seg_i = j % a.n_seg;
   }
   const int C = a.C, c = h * N + i;
-  // debug phase stamps (as k_wkv4: RWKVTTS_WKV_STAMPS, layer 5 only; null in production)
+  // debug phase stamps (as k_wkv4: RWKVTTS_DEBUG_STAMPS wkv=, one layer only; null in production)
   uint64_t* stp = (a.stamps && t == 0) ? a.stamps + ((int64_t)h * a.n_seg + seg_i) * 8 : nullptr;
   if (stp) { stp[0] = __builtin_amdgcn_s_memrealtime(); stp[1] = __builtin_amdgcn_s_memtime(); }
   const int4 sg = a.segs[seg_i];
@@ -2664,7 +2626,7 @@ __device__ __attribute__((always_inline)) void wkv6_body(const WkvArgs& a, const
   float rp[NP], kp[NP], vp[NP], vf = 0.f;
   auto load_parts = [&](int row) {
     const float* prow = a.part + (int64_t)row * a.ldp;
-    if constexpr (ROLE >= 1) {  // handed-off partial slabs: sc1 loads only
+    if constexpr (ROLE != kWkvPlain) {  // handed-off partial slabs: sc1 loads only
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
         const auto rs = wt_rsrc(prow + p * a.part_stride);
@@ -2683,7 +2645,7 @@ __device__ __attribute__((always_inline)) void wkv6_body(const WkvArgs& a, const
       vp[p] = pp[2 * C + c];
     }
     }
-    if constexpr (ROLE >= 1)
+    if constexpr (ROLE != kWkvPlain)
       vf = a.layer > 0 ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                                                      wt_rsrc(a.v_first + (int64_t)row * a.ldv), c * 4, 0, 16))
                        : 0.f;
@@ -2695,20 +2657,15 @@ __device__ __attribute__((always_inline)) void wkv6_body(const WkvArgs& a, const
   uint4 lw[9];  // 8 bf16 per entry: w 0..1 | a 2..3 | v 4 | g 5..8
   const uint4* pl = (const uint4*)(a.lup + (int64_t)h * 9 * 256 * 8);
   int slot, r_begin, n_rows;
-  if constexpr (ROLE >= 1) {
+  if constexpr (ROLE != kWkvPlain) {
     // LoRA-up rows and the state first (they do not depend on this layer's rkv workgroups), then
     // wait for the head's r / k / v tiles and the LoRA-down tiles, then their partials
     slot = sg.x; r_begin = sg.y; n_rows = sg.z;
-    // (opts bit 3: only once the LN rows are published -- the LN phase then runs without this
-    // prefetch beside it; the rkv phase still hides it)
-    if (sy.opts & 8) sync_wait(sy.cnt + kSyncStride * (kAttLn + (blockIdx.x & (kLnReplicas - 1))), sy.ln_rows, sy.err, 64, sy.opts);
-    hold_until(sy.d_s);
 #pragma unroll
     for (int u = 0; u < 9; ++u) lw[u] = pl[u * 256 + t];
     load_state(slot);
-    sync_wait(sy.cnt + kSyncStride * (kAttHead + h), sy.head_target, sy.err, 16, sy.opts);
-    sync_wait(sy.cnt + kSyncStride * (kAttLora + (blockIdx.x & (kLnReplicas - 1))), sy.lora_target, sy.err, 32,
-              sy.opts);
+    sync_wait(sy.cnt + kSyncStride * (kAttHead + h), sy.head_target, sy.err, kGiveUpHead);
+    sync_wait(sy.cnt + kSyncStride * (kAttLora + (blockIdx.x & (kLnReplicas - 1))), sy.lora_target, sy.err, kGiveUpLora);
     sync_stamp(sy, 1);
     load_parts(r_begin);
   } else {
@@ -2780,7 +2737,7 @@ __device__ __attribute__((always_inline)) void wkv6_body(const WkvArgs& a, const
     k = k * (1.0f + (av - 1.0f) * kac);
     if (a.layer == 0) {
       if (qq == 0) {
-        if constexpr (ROLE >= 1) store_wt(wt_rsrc(a.v_first + (int64_t)row * a.ldv), c * 4, v);
+        if constexpr (ROLE != kWkvPlain) store_wt(wt_rsrc(a.v_first + (int64_t)row * a.ldv), c * 4, v);
         else a.v_first[(int64_t)row * a.ldv + c] = v;
       }
     } else {
@@ -2827,7 +2784,7 @@ __device__ __attribute__((always_inline)) void wkv6_body(const WkvArgs& a, const
         y2 += sv * (float2_){rq[e], rq[e + 1]};
       }
     }
-    if (rr + 1 == n_rows && ROLE == 0) {  // (ROLE 1 stores the state after its hand-off)
+    if (rr + 1 == n_rows && ROLE == kWkvPlain) {  // (the hand-off roles store the state after their hand-off)
       if (a.wt) {
         const auto rs = wt_rsrc(a.state + (int64_t)slot * a.slot_stride + a.layer_off + (int64_t)h * N * N);
 #pragma unroll
@@ -2849,7 +2806,7 @@ __device__ __attribute__((always_inline)) void wkv6_body(const WkvArgs& a, const
     const float mean = ((s_red[2][0] + s_red[2][1]) + (s_red[2][2] + s_red[2][3])) * (1.0f / N);
     const float var =
         fmaxf(((s_red[3][0] + s_red[3][1]) + (s_red[3][2] + s_red[3][3])) * (1.0f / N) - mean * mean, 0.f);
-    if constexpr (ROLE == 2) {
+    if constexpr (ROLE == kWkvGran) {
       // granule form: the channel's split as ONE granule {hi | lo << 16, tag} (same expression
       // and threads as below, so the same bits) -- the Wo workgroups poll these directly
       if (qq == 0) {
@@ -2859,7 +2816,7 @@ __device__ __attribute__((always_inline)) void wkv6_body(const WkvArgs& a, const
         const uint16_t lb = f32_to_w16(zx - w16_to_f32(hb, F16), F16);
         gran_store_bits(sy.zgran + c, (uint32_t)hb | ((uint32_t)lb << 16), gran_tag(sy));
       }
-    } else if constexpr (ROLE == 1) {
+    } else if constexpr (ROLE == kWkvSlab) {
       // the row's 64 z values split by the same threads and expression as split_store (the
       // compiler fuses the product into the 16-bit conversion, so the split must stay here to
       // keep the bits), the planes through LDS; wave 0's lanes 0..15 store 4 channels each as one
@@ -2887,9 +2844,9 @@ __device__ __attribute__((always_inline)) void wkv6_body(const WkvArgs& a, const
     if (rr + 1 < n_rows) __syncthreads();
   }
   if (stp) { stp[6] = __builtin_amdgcn_s_memtime(); stp[7] = __builtin_amdgcn_s_memrealtime(); }
-  if constexpr (ROLE >= 1) {
+  if constexpr (ROLE != kWkvPlain) {
     sync_stamp(sy, 2);
-    if constexpr (ROLE == 1) sync_arrive(sy.cnt + kSyncStride * (kAttWkv + h));
+    if constexpr (ROLE == kWkvSlab) sync_arrive(sy.cnt + kSyncStride * (kAttWkv + h));
     // the final state (read by the next step's launch only) goes out after the hand-off, so its
     // write-through drain is not on the Wo workgroups' path
     const auto rs = wt_rsrc(a.state + (int64_t)slot * a.slot_stride + a.layer_off + (int64_t)h * N * N);
@@ -3133,7 +3090,7 @@ template <bool F16, bool MULTI_ROW = false>  // MULTI_ROW: steps whose segments 
 __global__ __launch_bounds__(256, MULTI_ROW ? 2 : 1) void k_wkv6(WkvArgs a) {
   tl_begin(a.tl);
   if constexpr (MULTI_ROW) wkv6_rows<F16>(a, blockIdx.x, blockIdx.y);
-  else wkv6_body<F16, 0>(a, blockIdx.x, blockIdx.y, FfnSync{});
+  else wkv6_body<F16, kWkvPlain>(a, blockIdx.x, blockIdx.y, FfnSync{});
   tl_end(a.tl);
 }
 
@@ -3159,7 +3116,7 @@ __global__ __launch_bounds__(256, MULTI_ROW ? 2 : 1) void k_wkv6(WkvArgs a) {
 // launches', bit for bit. Block 0 zeroes the previous layer's counters.
 // ------------------------------------------------------------------------------------
 // FUSED (row-fused form, one decode row, layers > 0): no LayerNorm blocks; rkv workgroups compute
-// the row's LN1 themselves (gemm2_body ROLE 5); the last workgroup waits until every rkv workgroup
+// the row's LN1 themselves (gemm2_body kRoleRkvRow); the last workgroup waits until every rkv workgroup
 // has staged (kAttRkvDone) and stores the residual and the new token-shift row.
 template <bool F16, bool EMB, bool FUSED>
 __global__ __launch_bounds__(256, RWKVTTS_ATT_WPC) void k_att_persist(LnMixArgs ln, GemmArgs ga, WkvArgs wa, GemmArgs go, FfnSync sy) {
@@ -3177,41 +3134,36 @@ __global__ __launch_bounds__(256, RWKVTTS_ATT_WPC) void k_att_persist(LnMixArgs 
       sync_arrive(sy.cnt + kSyncStride * kAttLn, kLnReplicas);
     }
   } else if ((b -= sy.n_ln_blocks) < sy.n_key) {
-    if constexpr (FUSED) gemm2_body<1, 8, kXPlanes, F16, 1, 2, false, 5>(ga, b % sy.rkv_tiles, b / sy.rkv_tiles, sy, &ln);
-    else gemm2_body<2, 8, kXPlanes, F16, 1, 2, false, 3>(ga, b % sy.rkv_tiles, b / sy.rkv_tiles, sy);
+    if constexpr (FUSED) gemm2_body<1, 8, kXPlanes, F16, 1, 2, false, kRoleRkvRow>(ga, b % sy.rkv_tiles, b / sy.rkv_tiles, sy, &ln);
+    else gemm2_body<2, 8, kXPlanes, F16, 1, 2, false, kRoleRkv>(ga, b % sy.rkv_tiles, b / sy.rkv_tiles, sy);
   } else if ((b -= sy.n_key) < sy.n_wkv) {
     if constexpr (FUSED && !EMB) {
-      if (sy.gran) wkv6_body<F16, 2>(wa, b, 0, sy);
-      else wkv6_body<F16, 1>(wa, b, 0, sy);
+      if (sy.gran) wkv6_body<F16, kWkvGran>(wa, b, 0, sy);
+      else wkv6_body<F16, kWkvSlab>(wa, b, 0, sy);
     } else {
-      wkv6_body<F16, 1>(wa, b, 0, sy);
+      wkv6_body<F16, kWkvSlab>(wa, b, 0, sy);
     }
   } else if ((b -= sy.n_wkv) < 16 * go.k_split || !FUSED) {
     if constexpr (FUSED && !EMB) {
-      if (sy.gran) gemm2_body<1, 4, kXPlanes, F16, 1, 0, false, 8>(go, b, 0, sy);
-      else gemm2_body<2, 4, kXPlanes, F16, 1, 0, false, 4>(go, b, 0, sy);
+      if (sy.gran) gemm2_body<1, 4, kXPlanes, F16, 1, 0, false, kRoleWoGran>(go, b, 0, sy);
+      else gemm2_body<2, 4, kXPlanes, F16, 1, 0, false, kRoleWo>(go, b, 0, sy);
     } else {
-      gemm2_body<2, 4, kXPlanes, F16, 1, 0, false, 4>(go, b, 0, sy);
+      gemm2_body<2, 4, kXPlanes, F16, 1, 0, false, kRoleWo>(go, b, 0, sy);
     }
   } else if constexpr (FUSED && !EMB) {  // the shift writer
     if (threadIdx.x < sy.n_prev) sy.cnt_prev[threadIdx.x * kSyncStride] = 0;
     if (threadIdx.x == 64 && sy.epoch_bump)
       __hip_atomic_fetch_add((gint_t*)sy.epoch_bump, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    sync_wait(sy.cnt + kSyncStride * kAttRkvDone, sy.n_key, sy.err, 2048, sy.opts);
+    sync_wait(sy.cnt + kSyncStride * kAttRkvDone, sy.n_key, sy.err, kGiveUpRkvDone);
     ln1024_body<F16, 1, 0, 16>(ln, 0);
   }
   sync_stamp(sy, 3);
   tl_end(ln.tl);
 }
 
-struct AttPrep {
-  LnMixArgs l;
-  GemmArgs ga, gw;
-  WkvArgs wa;
-  FfnSync sy;
-};
-static bool prep_att_persist(const LnMixArgs& ln, const GemmArgs& rkv, const WkvArgs& wkv, const GemmArgs& wo, int* cnt,
-                             int* cnt_prev, int* err, int R, int H, uint64_t* stamps, int opts, AttPrep& P) {
+bool launch_att_persist(const LnMixArgs& ln, const GemmArgs& rkv, const WkvArgs& wkv, const GemmArgs& wo, int* cnt,
+                        int* cnt_prev, int* err, int R, int H, hipStream_t st, uint64_t* stamps,
+                        int* drop, bool fused_ln, int* epoch_bump, uint64_t* gran, const int* epoch) {
   const bool emb = ln.emb != nullptr;
   const int rkv_tiles = rkv.seg[rkv.nseg - 1].tile_start + (rkv.seg[rkv.nseg - 1].N + 63) / 64;
   const int lora_tiles = rkv_tiles - 3 * ln.C / 64;
@@ -3224,27 +3176,22 @@ static bool prep_att_persist(const LnMixArgs& ln, const GemmArgs& rkv, const Wkv
       wo.stamps || (wo.seg[0].N + 63) / 64 != 16 ||
       rkv.f16 != ln.f16 || wo.f16 != ln.f16 || wkv.f16 != ln.f16 || cnt == cnt_prev)
     return false;
-  LnMixArgs& l = P.l;
-  l = ln;
+  LnMixArgs l = ln;
   l.n_rows = R;
   l.wt = 1;
-  GemmArgs& ga = P.ga;
-  GemmArgs& gw = P.gw;
-  ga = rkv;
-  gw = wo;
+  GemmArgs ga = rkv, gw = wo;
   ga.xmap = 0; ga.ntiles = rkv_tiles; ga.wt = 1;
-  gw.xmap = 1; gw.ntiles = 16;
-  gw.wt = 1;
-  WkvArgs& wa = P.wa;
-  wa = wkv;
+  gw.xmap = 1; gw.ntiles = 16; gw.wt = 1;
+  WkvArgs wa = wkv;
   wa.xmap = 1; wa.wt = 1;
-  FfnSync& sy = P.sy;
-  sy = FfnSync{};
+  // the row-fused form (one row, layers > 0): no LayerNorm blocks, one trailing shift writer
+  const bool fused = fused_ln && R == 1 && !emb && ln.inplace;
+  FfnSync sy{};
   sy.cnt = cnt;
   sy.cnt_prev = cnt_prev;
   sy.n_prev = kAttCounters;
   sy.err = err;
-  sy.n_ln_blocks = 32;
+  sy.n_ln_blocks = fused ? 0 : 32;
   sy.ln_rows = R;
   sy.n_key = rkv_tiles * rkv.k_split;
   sy.rkv_tiles = rkv_tiles;
@@ -3252,57 +3199,20 @@ static bool prep_att_persist(const LnMixArgs& ln, const GemmArgs& rkv, const Wkv
   sy.head_target = 3 * rkv.k_split;
   sy.lora_target = lora_tiles * rkv.k_split;
   sy.C = ln.C;
-  sy.opts = opts;
-  prefetch_holds(sy);
   sy.stamps = stamps;
-  return true;
-}
-
-// the attention half's arguments, its row-fused form (n_fix = 1: the trailing shift writer) and
-// the granule hand-offs where they apply
-static bool att_setup(const LnMixArgs& ln, const GemmArgs& rkv, const WkvArgs& wkv, const GemmArgs& wo, int* cnt,
-                      int* cnt_prev, int* err, int R, int H, uint64_t* stamps, int opts, int* drop, bool fused_ln,
-                      int* epoch_bump, uint64_t* gran, const int* epoch, AttPrep& P, int& n_fix) {
-  if (!prep_att_persist(ln, rkv, wkv, wo, cnt, cnt_prev, err, R, H, stamps, opts, P)) return false;
-  P.sy.drop = drop;
-  P.sy.epoch_bump = epoch_bump;
-  const bool fused = fused_ln && R == 1 && ln.emb == nullptr && ln.inplace;
-  n_fix = 0;
-  if (fused) {
-    P.sy.n_ln_blocks = 0;
-    P.sy.d_w = 0;  // (the hold only kept the weight streams off the LayerNorm rows' loads)
-    P.sy.d_late = kHold1Wo;
-    n_fix = 1;
-    // the granule hand-off WKV -> Wo: 64-channel heads, 128-channel Wo K-slices (its granule role's KS)
-    if (gran && epoch && wkv.C == 16 * 64 && wo.k_split == 8 && ln.layer < 64) {
-      P.sy.gran = gran;
-      P.sy.zgran = gran;
-      P.sy.gran_ld = 0;
-      P.sy.epoch = epoch;
-      P.sy.layer = ln.layer;
-    }
+  sy.drop = drop;
+  sy.epoch_bump = epoch_bump;
+  sy.d_w = fused ? 0 : kHoldRkv;  // (the hold only keeps the weight streams off the LayerNorm rows' loads)
+  sy.d_late = fused ? kHold1Wo : 0;
+  // the granule hand-off WKV -> Wo: 64-channel heads, 128-channel Wo K-slices (its granule role's KS)
+  if (fused && gran && epoch && wkv.C == 16 * 64 && wo.k_split == 8 && ln.layer < 64) {
+    sy.gran = gran;
+    sy.zgran = gran;
+    sy.epoch = epoch;
+    sy.layer = ln.layer;
   }
-  return true;
-}
-
-bool launch_att_persist(const LnMixArgs& ln, const GemmArgs& rkv, const WkvArgs& wkv, const GemmArgs& wo, int* cnt,
-                        int* cnt_prev, int* err, int R, int H, hipStream_t st, uint64_t* stamps, int opts,
-                        int* drop, bool fused_ln, int* epoch_bump, uint64_t* gran, const int* epoch) {
-  AttPrep P;
-  int n_fix = 0;  // the row-fused form's shift writer
-  if (!att_setup(ln, rkv, wkv, wo, cnt, cnt_prev, err, R, H, stamps, opts, drop, fused_ln, epoch_bump, gran, epoch, P,
-                 n_fix))
-    return false;
-  const bool fused = n_fix == 1;
-  const bool emb = ln.emb != nullptr;
-  LnMixArgs& l = P.l;
-  GemmArgs& ga = P.ga;
-  GemmArgs& gw = P.gw;
-  WkvArgs& wa = P.wa;
-  FfnSync& sy = P.sy;
-  const int n_wo = 16 * wo.k_split;
   const size_t lds = (size_t)2 * 16 * (8 * 32 + 8) * 2 * 2;  // the rkv body's X image (the largest)
-  const dim3 grid(sy.n_ln_blocks + sy.n_key + sy.n_wkv + n_wo + n_fix);
+  const dim3 grid(sy.n_ln_blocks + sy.n_key + sy.n_wkv + 16 * wo.k_split + (fused ? 1 : 0));
   if (ln.f16) {
     if (emb) RT_LAUNCH((k_att_persist<true, true, false>), grid, dim3(256), lds, st, l, ga, wa, gw, sy);
     else if (fused) RT_LAUNCH((k_att_persist<true, false, true>), grid, dim3(256), lds, st, l, ga, wa, gw, sy);
