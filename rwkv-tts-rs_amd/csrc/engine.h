@@ -8,6 +8,7 @@
 
 #include "lm_kernels.h"
 #include "sampler.h"
+#include "sched.h"
 
 namespace rwkvtts {
 
@@ -39,18 +40,6 @@ struct LayerW {
   int qs_rkv = 0, qs_o = 0, qs_fk = 0, qs_fv = 0;  // f16 models: GemmArgs::q_shift per launch
 };
 
-// One forward step description (host side).
-struct StepPlan {
-  std::vector<uint32_t> tok;   // per row
-  std::vector<int4> rows;      // slot, flags, prev_row, 0
-  std::vector<int4> segs;      // slot, row_begin, n_rows, 0
-  std::vector<int> lg_rows;    // rows whose logits are produced
-  std::vector<int> lg_slot;    // slot of each logits row (advance)
-  int head_rows = 0;
-  bool tok_from_ctrl = false;  // decode: token = ctrl[slot].next_token
-  bool advance = false;        // run the phase controller on the logits rows
-};
-
 constexpr int kLookahead = 8;  // decode steps queued per host poll of the control blocks
 
 // One request in flight through Engine::serve. The request's arrays stay valid until finish().
@@ -74,8 +63,6 @@ class JobSource {
   // called by the owner thread after every unit of work (live statistics)
   virtual void progress(const Engine&) {}
 };
-
-struct Active;  // a request decoding in a state slot (engine.hip, Engine::serve)
 
 struct ProfEntry {
   std::string name;
@@ -108,7 +95,7 @@ class Engine {
   // Continuous batching until `src` is closed and every admitted job has finished.
   int serve(JobSource& src);
   // Checks a request before admission; fills `why` and returns false for a bad one.
-  bool validate(const rwkvtts_request& q, std::string& why) const;
+  bool validate(const rwkvtts_request& q, std::string& why) const { return rwkvtts::validate(q, dims.n_vocab, why); }
   int max_slots() const { return S_; }
   // whether this engine holds its device's persistent-launch slot (claim_persistent)
   bool persistent() const { return att_persist_ || ffn_persist_; }
@@ -137,8 +124,18 @@ class Engine {
 
  private:
   int run_step(const StepPlan& p, bool upload);
-  int finish_unit(int b, bool prefill, std::vector<Active>& act, std::vector<int>& free_slots, JobSource& src,
-                  hipEvent_t* ev0, hipEvent_t* ev1);
+  // Engine::serve: the loop's state, a unit of work (a mixed step or a decode window), the steps
+  struct ServeState;
+  struct Unit {
+    bool valid = false, prefill = false, uploaded = false;  // uploaded: the unit carried a plan upload
+    int buf = 0;                                            // its snapshot buffer / event pair
+  };
+  int serve_loop(ServeState& st);
+  int admit(ServeState& st, Job* j);
+  int launch_unit(ServeState& st, Unit& u);
+  int enqueue_snapshot(ServeState& st, const Unit& u);
+  int finish_unit(const Unit& u, ServeState& st);
+  int accumulate_stamps(const Unit& u);
   int launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_from_ctrl, bool advance);
   int upload_plan(const StepPlan& p);
   void prof_begin(hipEvent_t* ev);

@@ -861,6 +861,7 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
 }
 
 int Engine::upload_plan(const StepPlan& p) {
+  static_assert(sizeof(Int4) == sizeof(int4) && alignof(Int4) == alignof(int4), "StepPlan rows / segs are the kernels' int4");
   const int R = (int)p.rows.size();
   if (!p.tok_from_ctrl) RT_HIP(hipMemcpyAsync(d_tok_, p.tok.data(), R * 4, hipMemcpyHostToDevice, stream_));
   RT_HIP(hipMemcpyAsync(d_rows_, p.rows.data(), R * sizeof(int4), hipMemcpyHostToDevice, stream_));
@@ -939,7 +940,7 @@ int Engine::infer(const rwkvtts_input* in, int n, int head_rows, float* logits, 
   StepPlan p;
   p.head_rows = head_rows;
   int budget = chunk_;
-  std::vector<std::pair<int, int>> out_map;  // (input index, logits row index)
+  std::vector<int> last_only;  // inputs whose one logits row is their last token's
   for (int i = 0; i < n; ++i) {
     consumed[i] = 0;
     has_logits[i] = 0;
@@ -949,27 +950,14 @@ int Engine::infer(const rwkvtts_input* in, int n, int head_rows, float* logits, 
       RT_CHECK(in[j].slot != b.slot, RWKVTTS_EINVAL, "two inputs share a slot");
     const int take = std::min(b.n_tokens, budget);
     if (take <= 0) continue;
-    const int r0 = (int)p.rows.size();
-    for (int t = 0; t < take; ++t) {
+    for (int t = 0; t < take; ++t)
       RT_CHECK(b.tokens[t] < (uint32_t)dims.n_vocab, RWKVTTS_EINVAL, "token id >= n_vocab");
-      int flags = (t == 0 ? kRowFirst : 0) | (t == take - 1 ? kRowLast : 0);
-      p.rows.push_back(make_int4(b.slot, flags, t == 0 ? -1 : r0 + t - 1, 0));
-      p.tok.push_back(b.tokens[t]);
-      if (b.option == RWKVTTS_OPT_FULL) {
-        p.lg_rows.push_back(r0 + t);
-        p.lg_slot.push_back(b.slot);
-      }
-    }
-    p.segs.push_back(make_int4(b.slot, r0, take, 0));
+    const bool full = b.option == RWKVTTS_OPT_FULL, last = b.option == RWKVTTS_OPT_LAST && take == b.n_tokens;
+    append_token_rows(p, b.slot, b.tokens, take, full ? kLogitsAll : last ? kLogitsLast : kLogitsNone);
     consumed[i] = take;
     budget -= take;
-    if (b.option == RWKVTTS_OPT_LAST && take == b.n_tokens) {
-      p.lg_rows.push_back(r0 + take - 1);
-      p.lg_slot.push_back(b.slot);
-      out_map.push_back({i, (int)p.lg_rows.size() - 1});
-    } else if (b.option == RWKVTTS_OPT_FULL) {
-      has_logits[i] = 1;
-    }
+    if (last) last_only.push_back(i);
+    has_logits[i] = full;
   }
   if (p.rows.empty()) return RWKVTTS_OK;
   RT_OK(run_step(p, true));
@@ -984,7 +972,7 @@ int Engine::infer(const rwkvtts_input* in, int n, int head_rows, float* logits, 
                             (size_t)head_rows * 4, n_lg, hipMemcpyDeviceToHost, stream_));
   }
   RT_HIP(hipStreamSynchronize(stream_));
-  for (auto& om : out_map) has_logits[om.first] = 1;
+  for (int i : last_only) has_logits[i] = 1;
   RT_OK(flush_prof());
   return dump_stamps();
 }
@@ -1182,23 +1170,9 @@ int Engine::sample(const float* logits, int n_rows, int row_len, const rwkvtts_s
 }
 
 // ------------------------------------------------------------------------------------------
-// Continuous-batching scheduler (DynamicBatchManager semantics, src/dynamic_batch_manager.rs)
+// Continuous-batching scheduler (DynamicBatchManager semantics, src/dynamic_batch_manager.rs):
+// the rules are sched.h's, here they meet the GPU
 // ------------------------------------------------------------------------------------------
-struct Active {
-  Job* job;
-  int slot;
-  std::vector<uint32_t> prompt;
-  int prefilled = 0;
-  int advances = 0;  // phase-controller invocations so far
-  int total = 0;     // advances after which the request is certainly done (its step limit)
-  bool zero_shot = false;
-  // token progress (Job::user): semantic tokens handed to the sink so far, and per unit buffer the
-  // end of the range of this slot's d_sem_ that the unit copied to h_prog_
-  const rwkvtts_token_sink* sink = nullptr;
-  int delivered = 0;
-  int copied_hi[2] = {0, 0};
-};
-
 namespace {
 
 const rwkvtts_token_sink* sink_of(const Job* j) {
@@ -1209,6 +1183,37 @@ const rwkvtts_token_sink* sink_of(const Job* j) {
 void sink_fail(const Job* j, int first) {
   if (const rwkvtts_token_sink* s = sink_of(j)) s->fn(s->user, nullptr, 0, nullptr, first, 0, 1, j->res->status);
 }
+// This job ends with status rc and no tokens. first >= 0: its stream ends there (done = 1, the
+// status); first < 0: its sink has had its last call already.
+void fail_job(JobSource& src, Job* j, int rc, int first) {
+  j->res->status = rc;
+  j->res->n_global = j->res->n_semantic = 0;
+  if (first >= 0) sink_fail(j, first);
+  src.finish(j);
+}
+
+// end stamp of a timeline slot: the latest of its max-reduced workgroup ends
+unsigned long long tl_end_stamp(const unsigned long long* q) {
+  unsigned long long e = 0;
+  for (int j = 2; j < kTlStride; ++j) e = std::max(e, q[j]);
+  return e;
+}
+
+// the start / end events of the two unit buffers, destroyed on every way out of serve
+struct UnitEvents {
+  hipEvent_t ev0[2] = {nullptr, nullptr}, ev1[2] = {nullptr, nullptr};
+  int create() {
+    for (int i = 0; i < 2; ++i) {
+      RT_HIP(hipEventCreate(&ev0[i]));
+      RT_HIP(hipEventCreate(&ev1[i]));
+    }
+    return RWKVTTS_OK;
+  }
+  ~UnitEvents() {
+    for (hipEvent_t e : {ev0[0], ev1[0], ev0[1], ev1[1]})
+      if (e) (void)hipEventDestroy(e);
+  }
+};
 
 // generate_batch: a fixed list of requests
 class ListSource : public JobSource {
@@ -1242,47 +1247,6 @@ class ListSource : public JobSource {
 };
 }  // namespace
 
-bool Engine::validate(const rwkvtts_request& q, std::string& why) const {
-  auto ids_ok = [&](const int32_t* p, int n, int lo, int hi, const char* what) {
-    if (n < 0 || (n > 0 && !p)) {
-      why = std::string(what) + ": bad array";
-      return false;
-    }
-    for (int i = 0; i < n; ++i)
-      if (p[i] < lo || p[i] >= hi) {
-        why = std::string(what) + ": id " + std::to_string(p[i]) + " out of range";
-        return false;
-      }
-    return true;
-  };
-  const int V = dims.n_vocab;
-  if (!ids_ok(q.text_tokens, q.n_text, 0, V, "text_tokens")) return false;
-  if (!ids_ok(q.property_tokens, q.n_property, 0, V, "property_tokens")) return false;
-  if ((q.ref_global && q.n_ref_global < 0) || (q.ref_semantic && q.n_ref_semantic < 0)) {
-    why = "reference token counts must be >= 0";
-    return false;
-  }
-  if (q.max_tokens < 0 || q.fixed_semantic < 0) {
-    why = "max_tokens / fixed_semantic must be >= 0";
-    return false;
-  }
-  const bool zero_shot = q.ref_global != nullptr && q.ref_semantic != nullptr;
-  if (V <= RWKVTTS_TAG_2 || (!zero_shot && V <= RWKVTTS_GLOBAL_TOKEN_OFFSET + 4095) ||
-      (zero_shot && q.n_ref_global > 0 && V <= RWKVTTS_GLOBAL_TOKEN_OFFSET + 4095)) {
-    why = "model vocabulary too small for the TTS tags / global tokens";
-    return false;
-  }
-  return true;
-}
-
-// Semantic-step limit and RNG seeds of a request, as the reference derives them.
-static int sem_limit_of(const rwkvtts_request& q) {
-  const bool zero_shot = q.ref_global != nullptr && q.ref_semantic != nullptr;
-  if (q.fixed_semantic > 0) return std::min(q.fixed_semantic, RWKVTTS_SEMANTIC_LIMIT);
-  if (zero_shot) return RWKVTTS_SEMANTIC_LIMIT;                  // zero_shot_inference.rs:128-142
-  return std::min(std::max(q.max_tokens, 0), RWKVTTS_SEMANTIC_LIMIT);  // normal_mode_inference.rs:316
-}
-
 int Engine::generate(const rwkvtts_request* reqs, int n, rwkvtts_result* res, const rwkvtts_token_sink* sinks) {
   stats = rwkvtts_stats{};
   max_active = 0;
@@ -1292,26 +1256,141 @@ int Engine::generate(const rwkvtts_request* reqs, int n, rwkvtts_result* res, co
   return rc;
 }
 
-// Waits for a unit's end event (polling: a blocking wait adds its wake-up latency to the GPU's
-// idle gap), accounts its time, and retires the slots its control-block snapshot shows done.
-int Engine::finish_unit(int b, bool prefill, std::vector<Active>& act, std::vector<int>& free_slots, JobSource& src,
-                        hipEvent_t* ev0, hipEvent_t* ev1) {
-  {
-    hipError_t q;
-    while ((q = hipEventQuery(ev1[b])) == hipErrorNotReady) __builtin_ia32_pause();
-    RT_HIP(q);
+// Each unit of work (a mixed step or a decode window) ends with a control-block snapshot into
+// its own pinned buffer and an end event. In steady decode (no admission possible, no prompt
+// rows, the plan uploaded earlier, no slot able to pass its step limit) the next window is
+// launched before the host reads the previous one's snapshot, so the GPU does not idle while
+// the host polls, retires and relaunches. A slot that finished inside the older window idles
+// (k_advance skips it) through the newer one; every later operation on it is stream-ordered.
+struct Engine::ServeState {
+  explicit ServeState(JobSource& s) : src(s) {}
+  JobSource& src;
+  std::vector<Active> act;      // the requests in state slots, sorted by slot before each unit
+  std::vector<int> free_slots;  // a stack, filled S-1..0
+  std::vector<Job*> fresh;      // taken from the source, neither in `act` nor finished yet
+  bool open = true;             // the source may still deliver jobs
+  Unit pending;                 // launched, its snapshot not read yet
+  StepPlan dp;                  // the decode plan (all active slots, tokens from the control blocks)
+  bool dp_valid = false;        // dp is on the device and matches `act`
+  UnitEvents ev;
+  std::random_device rd;
+};
+
+// One request into a free slot: its control block and state reset go onto the stream, ordered
+// before the slot's first step. A bad request fails alone; an error fails the engine.
+int Engine::admit(ServeState& st, Job* j) {
+  const rwkvtts_request& q = j->req;
+  j->res->status = 0;
+  j->res->n_global = j->res->n_semantic = 0;
+  std::string why;
+  if (!validate(q, why)) {  // dynamic_batch_manager.rs:466-469: this request fails alone
+    set_error("request rejected: " + why);
+    fail_job(st.src, j, RWKVTTS_EINVAL, 0);
+    return RWKVTTS_OK;
   }
-  float ms = 0;
-  hipEventElapsedTime(&ms, ev0[b], ev1[b]);
-  (prefill ? stats.prefill_ms : stats.decode_ms) += ms;
-  RT_OK(flush_prof());
-  if (graph_timing() && unit_graph_[b].first >= 0) {
-    const std::vector<std::string>& names = graph_names_[unit_graph_[b]];
-    const unsigned long long* h = h_gt_ + (size_t)b * kTlStride * kTlMax;
+  if (sink_of(j) && !h_prog_)
+    RT_HIP(hipHostMalloc((void**)&h_prog_, sizeof(int32_t) * 2 * (size_t)S_ * RWKVTTS_SEMANTIC_LIMIT,
+                         hipHostMallocDefault));
+  // test hook: RWKVTTS_TEST_FAIL_ADMIT=k fails this engine's k-th admission as a HIP error would
+  if (const char* fa = getenv("RWKVTTS_TEST_FAIL_ADMIT")) {
+    if (++admissions_ == atoi(fa)) {
+      set_error("injected admission failure (RWKVTTS_TEST_FAIL_ADMIT)");
+      return RWKVTTS_EHIP;
+    }
+  }
+  Admission ad = admission_of(q, q.has_seed ? 0 : (((uint64_t)st.rd() << 32) ^ st.rd()));
+  const int slot = st.free_slots.back();
+  st.free_slots.pop_back();
+  rwkvtts_rng rg, rs;
+  rwkvtts_rng_seed_from_u64(ad.gseed, &rg);
+  rwkvtts_rng_seed_from_u64(ad.sseed, &rs);
+  memcpy(ad.ctrl.gkey, rg.key, 32);
+  memcpy(ad.ctrl.skey, rs.key, 32);
+  RT_OK(slot_reset(slot, false));  // ordered before the slot's first step on stream_
+  // from per-slot host storage: admissions are not synchronised, so the source must outlive the
+  // stream-ordered copy (the slot's entry is rewritten only after the slot retires)
+  ctrl_stage_[slot] = ad.ctrl;
+  RT_HIP(hipMemcpyAsync(d_ctrl_ + slot, &ctrl_stage_[slot], sizeof(SlotCtrl), hipMemcpyHostToDevice, stream_));
+  Active a;
+  a.job = j;
+  a.slot = slot;
+  a.sink = sink_of(j);
+  a.zero_shot = ad.zero_shot;
+  a.prompt = std::move(ad.prompt);
+  a.total = ad.total;
+  st.act.push_back(std::move(a));
+  st.dp_valid = false;
+  return RWKVTTS_OK;
+}
+
+// Builds and launches the next unit: a mixed step while any slot has prompt tokens left, else a
+// decode window of the (cached) decode plan.
+int Engine::launch_unit(ServeState& st, Unit& u) {
+  std::vector<Active>& act = st.act;
+  u.valid = true;
+  u.uploaded = false;
+  u.prefill = std::any_of(act.begin(), act.end(), [](const Active& a) { return a.in_prompt(); });
+  u.buf = st.pending.valid ? st.pending.buf ^ 1 : 0;
+  RT_HIP(hipEventRecord(st.ev.ev0[u.buf], stream_));
+  if (u.prefill) {
+    RT_OK(run_step(mixed_plan(act, chunk_, dims.n_vocab), true));
+    st.dp_valid = false;
+    stats.prefill_steps++;
+    return RWKVTTS_OK;
+  }
+  if (!st.dp_valid) {
+    st.dp = decode_plan(act);
+    RT_OK(upload_plan(st.dp));
+    st.dp_valid = u.uploaded = true;
+  }
+  const int K = window_len(act, kLookahead, profiling || d_tl_);
+  if (d_tl_) RT_HIP(hipMemsetAsync(d_tl_, 0, (size_t)kTlStride * kTlMax * 8, stream_));
+  for (int k = 0; k < K; ++k) {
+    st.dp.head_rows = head_rows_of(act, dims.n_vocab);
+    RT_OK(run_step(st.dp, false));
+    for (auto& a : act) a.advances++;
+  }
+  stats.steps += K;
+  stats.decode_rows += (int64_t)st.dp.rows.size() * K;
+  max_active = std::max<int64_t>(max_active, (int64_t)st.dp.rows.size());
+  return RWKVTTS_OK;
+}
+
+// The unit's read-back, in stream order: the token progress of the sink-carrying slots, the
+// control-block snapshot, the in-graph stamps, the end event. Slots without a sink add nothing,
+// so a run without sinks enqueues what it always did.
+int Engine::enqueue_snapshot(ServeState& st, const Unit& u) {
+  const int b = u.buf;
+  for (auto& a : st.act) {
+    if (!a.sink) continue;
+    const ProgressRange r = progress_range(a.delivered, ctrl_stage_[a.slot].sem_limit, a.advances);
+    a.copied_hi[b] = r.hi;
+    if (r.hi <= r.lo) continue;
+    const size_t so = (size_t)a.slot * RWKVTTS_SEMANTIC_LIMIT + r.lo;
+    RT_HIP(hipMemcpyAsync(h_prog_ + (size_t)b * S_ * RWKVTTS_SEMANTIC_LIMIT + so, d_sem_ + so, sizeof(int32_t) * (r.hi - r.lo),
+                          hipMemcpyDeviceToHost, stream_));
+  }
+  RT_HIP(hipMemcpyAsync(h_ctrl_ + (size_t)b * (S_ + 1), d_ctrl_, sizeof(SlotCtrl) * (S_ + 1), hipMemcpyDeviceToHost, stream_));
+  unit_graph_[b] = {-1, -1};
+  if (graph_timing() && !u.prefill && last_graph_.first >= 0) {  // the window's last step's stamps
+    const size_t n = graph_names_[last_graph_].size();
+    RT_HIP(hipMemcpyAsync(h_gt_ + (size_t)b * kTlStride * kTlMax, d_gt_, n * kTlStride * 8, hipMemcpyDeviceToHost,
+                          stream_));
+    unit_graph_[b] = last_graph_;
+  }
+  RT_HIP(hipEventRecord(st.ev.ev1[b], stream_));
+  return RWKVTTS_OK;
+}
+
+// A finished unit's launch stamps: the in-graph timing into `prof` by launch name, the debug
+// timeline (semantic-phase decode steps only) into its running means.
+int Engine::accumulate_stamps(const Unit& u) {
+  if (graph_timing() && unit_graph_[u.buf].first >= 0) {
+    const std::vector<std::string>& names = graph_names_[unit_graph_[u.buf]];
+    const unsigned long long* h = h_gt_ + (size_t)u.buf * kTlStride * kTlMax;
     for (size_t i = 0; i < names.size(); ++i) {
       const unsigned long long* q = h + (size_t)kTlStride * i;
-      unsigned long long e = 0;
-      for (int j = 2; j < kTlStride; ++j) e = std::max(e, q[j]);
+      const unsigned long long e = tl_end_stamp(q);
       if (e <= q[0]) continue;
       auto it = std::find_if(prof.begin(), prof.end(), [&](const ProfEntry& x) { return x.name == names[i]; });
       if (it == prof.end()) {
@@ -1322,7 +1401,7 @@ int Engine::finish_unit(int b, bool prefill, std::vector<Active>& act, std::vect
       it->ms += (double)(e - q[0]) * 1e-5;  // 100 MHz ticks -> ms
     }
   }
-  if (d_tl_ && !prefill && stats.steps > 40) {  // semantic-phase steps only
+  if (d_tl_ && !u.prefill && stats.steps > 40) {
     std::vector<unsigned long long> h((size_t)kTlStride * kTlMax);
     RT_HIP(hipMemcpy(h.data(), d_tl_, h.size() * 8, hipMemcpyDeviceToHost));
     const int n = (int)tl_names_.size();
@@ -1330,13 +1409,29 @@ int Engine::finish_unit(int b, bool prefill, std::vector<Active>& act, std::vect
     tl_dur_.resize(n, 0.0);
     for (int i = 0; i < n; ++i) {
       const unsigned long long* q = h.data() + (size_t)kTlStride * i;
-      unsigned long long e = 0;
-      for (int j = 2; j < kTlStride; ++j) e = std::max(e, q[j]);
       tl_start_[i] += (double)(q[0] - h[0]) * 0.01;  // us
-      tl_dur_[i] += (double)(e - q[0]) * 0.01;
+      tl_dur_[i] += (double)(tl_end_stamp(q) - q[0]) * 0.01;
     }
     tl_steps_++;
   }
+  return RWKVTTS_OK;
+}
+
+// Waits for a unit's end event (polling: a blocking wait adds its wake-up latency to the GPU's
+// idle gap), accounts its time, and retires the slots its control-block snapshot shows done.
+int Engine::finish_unit(const Unit& u, ServeState& st) {
+  std::vector<Active>& act = st.act;
+  const int b = u.buf;
+  {
+    hipError_t q;
+    while ((q = hipEventQuery(st.ev.ev1[b])) == hipErrorNotReady) __builtin_ia32_pause();
+    RT_HIP(q);
+  }
+  float ms = 0;
+  hipEventElapsedTime(&ms, st.ev.ev0[b], st.ev.ev1[b]);
+  (u.prefill ? stats.prefill_ms : stats.decode_ms) += ms;
+  RT_OK(flush_prof());
+  RT_OK(accumulate_stamps(u));
   ++units_;
   // retire finished slots: every finished slot's tokens copied on the engine's stream (no
   // null-stream sync), one synchronisation, then the jobs are handed back
@@ -1347,24 +1442,22 @@ int Engine::finish_unit(int b, bool prefill, std::vector<Active>& act, std::vect
     set_error("persistent decode launch: a hand-off wait timed out (code " + std::to_string(code) + ")");
     return RWKVTTS_EHIP;
   }
+  auto retiring = [&](const Active& a) { return !a.in_prompt() && snap[a.slot].phase == kPhDone; };
   bool copied = false;
   for (auto& a : act) {
     const SlotCtrl& c = snap[a.slot];
-    if (a.prefilled < (int)a.prompt.size() || c.phase != kPhDone) continue;
-    rwkvtts_result& r = *a.job->res;
-    if (r.semantic_tokens && c.n_sem > 0) {
-      RT_HIP(hipMemcpyAsync(r.semantic_tokens, d_sem_ + (int64_t)a.slot * RWKVTTS_SEMANTIC_LIMIT,
-                            sizeof(int32_t) * c.n_sem, hipMemcpyDeviceToHost, stream_));
-      copied = true;
-    }
+    if (!retiring(a) || !a.job->res->semantic_tokens || c.n_sem <= 0) continue;
+    RT_HIP(hipMemcpyAsync(a.job->res->semantic_tokens, d_sem_ + (int64_t)a.slot * RWKVTTS_SEMANTIC_LIMIT,
+                          sizeof(int32_t) * c.n_sem, hipMemcpyDeviceToHost, stream_));
+    copied = true;
   }
   if (copied) RT_HIP(hipStreamSynchronize(stream_));
   // token progress (after the fault check: a faulted unit's tokens are never delivered): the new
-  // semantic ids of each sink-carrying slot came with this unit's snapshot (serve: the copy to
-  // h_prog_ sits before the unit's end event), so nothing is waited for here
+  // semantic ids of each sink-carrying slot came with this unit's snapshot (enqueue_snapshot: the
+  // copy to h_prog_ sits before the unit's end event), so nothing is waited for here
   // (the synchronisation above is the retiring slots', as before)
   for (auto& a : act) {
-    if (!a.sink || a.prefilled < (int)a.prompt.size()) continue;
+    if (!a.sink || a.in_prompt()) continue;
     const SlotCtrl& c = snap[a.slot];
     const bool done = c.phase == kPhDone;
     const int n = std::min(c.n_sem, a.copied_hi[b]);
@@ -1377,290 +1470,71 @@ int Engine::finish_unit(int b, bool prefill, std::vector<Active>& act, std::vect
     sk->fn(sk->user, c.global_out, c.n_global, h_prog_ + ((size_t)b * S_ + a.slot) * RWKVTTS_SEMANTIC_LIMIT + first,
            first, count, done ? 1 : 0, 0);
   }
-  src.progress(*this);
+  st.src.progress(*this);
   for (size_t i = 0; i < act.size();) {
-    Active& a = act[i];
-    const SlotCtrl& c = snap[a.slot];
-    if (a.prefilled < (int)a.prompt.size() || c.phase != kPhDone) {
+    if (!retiring(act[i])) {
       ++i;
       continue;
     }
-    rwkvtts_result& r = *a.job->res;
+    const SlotCtrl& c = snap[act[i].slot];
+    rwkvtts_result& r = *act[i].job->res;
     r.status = 0;
     r.n_global = c.n_global;
     memcpy(r.global_tokens, c.global_out, sizeof(int32_t) * RWKVTTS_N_GLOBAL);
     r.n_semantic = c.n_sem;
-    src.finish(a.job);
-    free_slots.push_back(a.slot);
+    st.src.finish(act[i].job);
+    st.free_slots.push_back(act[i].slot);
     act.erase(act.begin() + i);
   }
+  if (act.size() != st.dp.rows.size()) st.dp_valid = false;  // the decode plan has a row per active slot
   return RWKVTTS_OK;
+}
+
+// Admit, launch a unit, enqueue its read-back, finish units -- until the source is closed and
+// every admitted job has finished. Any error returns to serve's one tail.
+int Engine::serve_loop(ServeState& st) {
+  while (true) {
+    // admission: new requests take free slots between forward steps; a job leaves `fresh` once
+    // it is in `act` or has failed alone
+    if (st.open && !st.free_slots.empty()) {
+      st.open = st.src.next((int)st.free_slots.size(), st.act.empty(), st.fresh);
+      while (!st.fresh.empty()) {
+        RT_OK(admit(st, st.fresh.front()));
+        st.fresh.erase(st.fresh.begin());
+      }
+    }
+    if (st.act.empty()) {
+      if (!st.open) return RWKVTTS_OK;
+      continue;
+    }
+    std::sort(st.act.begin(), st.act.end(), [](const Active& x, const Active& y) { return x.slot < y.slot; });
+    Unit now;
+    RT_OK(launch_unit(st, now));
+    RT_OK(enqueue_snapshot(st, now));
+    // the older unit first (its retirements are stream-ordered after this one), then this one
+    // unless the next window may go out before its snapshot is read
+    if (st.pending.valid) {
+      const Unit old = st.pending;
+      st.pending.valid = false;
+      RT_OK(finish_unit(old, st));
+    }
+    const bool can_admit = st.open && !st.free_slots.empty();
+    if (may_run_ahead(st.act, now.prefill, now.uploaded, use_graphs_, profiling, d_tl_ != nullptr, can_admit))
+      st.pending = now;
+    else
+      RT_OK(finish_unit(now, st));
+  }
 }
 
 int Engine::serve(JobSource& src) {
   RT_HIP(hipSetDevice(device_));
-  std::vector<int> free_slots;
-  for (int s = S_ - 1; s >= 0; --s) free_slots.push_back(s);
-  std::vector<Active> act;
-  std::random_device rd;
-  // Each unit of work (a mixed step or a decode window) ends with a control-block snapshot into
-  // its own pinned buffer and an end event. In steady decode (no admission possible, no prompt
-  // rows, the plan uploaded earlier, no slot able to pass its step limit) the next window is
-  // launched before the host reads the previous one's snapshot, so the GPU does not idle while
-  // the host polls, retires and relaunches. A slot that finished inside the older window idles
-  // (k_advance skips it) through the newer one; every later operation on it is stream-ordered.
-  hipEvent_t ev0[2], ev1[2];
-  for (int i = 0; i < 2; ++i) {
-    RT_HIP(hipEventCreate(&ev0[i]));
-    RT_HIP(hipEventCreate(&ev1[i]));
-  }
-  struct Unit {
-    bool valid = false, prefill = false;
-    int buf = 0;
-  } pending;
-  bool open = true, decode_plan_valid = false;
-  StepPlan dp;  // the decode plan (all active slots, tokens from the control blocks)
-  std::vector<Job*> fresh;
-
-  auto admit = [&](Job* j) -> int {
-    const rwkvtts_request& q = j->req;
-    rwkvtts_result& r = *j->res;
-    r.status = 0;
-    r.n_global = r.n_semantic = 0;
-    std::string why;
-    if (!validate(q, why)) {  // dynamic_batch_manager.rs:466-469: this request fails alone
-      r.status = RWKVTTS_EINVAL;
-      set_error("request rejected: " + why);
-      sink_fail(j, 0);
-      src.finish(j);
-      return RWKVTTS_OK;
-    }
-    if (sink_of(j) && !h_prog_)
-      RT_HIP(hipHostMalloc((void**)&h_prog_, sizeof(int32_t) * 2 * (size_t)S_ * RWKVTTS_SEMANTIC_LIMIT,
-                           hipHostMallocDefault));
-    // test hook: RWKVTTS_TEST_FAIL_ADMIT=k fails this engine's k-th admission as a HIP error would
-    if (const char* fa = getenv("RWKVTTS_TEST_FAIL_ADMIT")) {
-      if (++admissions_ == atoi(fa)) {
-        set_error("injected admission failure (RWKVTTS_TEST_FAIL_ADMIT)");
-        return RWKVTTS_EHIP;
-      }
-    }
-    const int slot = free_slots.back();
-    free_slots.pop_back();
-    Active a;
-    a.job = j;
-    a.slot = slot;
-    a.sink = sink_of(j);
-    a.zero_shot = q.ref_global != nullptr && q.ref_semantic != nullptr;
-    for (int i = 0; i < q.n_property; ++i) a.prompt.push_back((uint32_t)q.property_tokens[i]);
-    a.prompt.push_back(RWKVTTS_TAG_2);
-    for (int i = 0; i < q.n_text; ++i) a.prompt.push_back((uint32_t)q.text_tokens[i]);
-    a.prompt.push_back(RWKVTTS_TAG_0);
-    SlotCtrl c;
-    memset(&c, 0, sizeof(c));
-    // RNG streams: normal_mode_inference.rs:138-174, zero_shot_inference.rs:204-216,
-    // dynamic_batch_manager.rs:491-499 (no seed -> from_entropy)
-    const uint64_t seed = q.has_seed ? q.seed : (((uint64_t)rd() << 32) ^ rd());
-    const bool indep = q.layered_set ? q.use_independent_seeds != 0 : true;
-    const uint64_t goff = q.layered_set ? q.global_seed_offset : 1000, soff = q.layered_set ? q.semantic_seed_offset : 2000;
-    uint64_t gseed = indep ? seed + goff : seed + 100, sseed = indep ? seed + soff : seed + 200;
-    if (a.zero_shot && !indep) sseed = 0;  // StdRng::seed_from_u64(0) handed to the zero-shot path
-    rwkvtts_rng rg, rs;
-    rwkvtts_rng_seed_from_u64(gseed, &rg);
-    rwkvtts_rng_seed_from_u64(sseed, &rs);
-    memcpy(c.gkey, rg.key, 32);
-    memcpy(c.skey, rs.key, 32);
-    c.top_k_g = q.greedy ? 1 : 20;
-    c.top_k_s = q.greedy ? 1 : 80;
-    c.fixed = q.fixed_semantic > 0;
-    c.sem_limit = sem_limit_of(q);
-    if (a.zero_shot) {
-      c.mode = 1;
-      c.phase = kPhSemantic;
-      for (int i = 0; i < q.n_ref_global; ++i) {
-        const int g = std::min(std::max(q.ref_global[i], 0), 4095);
-        a.prompt.push_back((uint32_t)(g + RWKVTTS_GLOBAL_TOKEN_OFFSET));
-        if (i < RWKVTTS_N_GLOBAL) c.global_out[c.n_global++] = g;
-      }
-      a.prompt.push_back(RWKVTTS_TAG_1);
-      const int tlen = q.n_text;
-      const int min_sem = std::min(std::max(tlen / 4, 8), 64);
-      const int est = (int)ceilf((float)tlen * 1.8f);
-      const int upper = (int)floorf((float)RWKVTTS_SEMANTIC_LIMIT * 0.9f);
-      c.hard_min = std::min(upper, std::max(min_sem, est));
-      a.total = std::max(c.sem_limit, 1);
-    } else {
-      c.mode = 0;
-      c.phase = kPhGlobal;
-      a.total = RWKVTTS_N_GLOBAL + 1 + c.sem_limit;
-    }
-    RT_OK(slot_reset(slot, false));  // ordered before the slot's first step on stream_
-    // from per-slot host storage: admissions are not synchronised, so the source must outlive the
-    // stream-ordered copy (the slot's entry is rewritten only after the slot retires)
-    ctrl_stage_[slot] = c;
-    RT_HIP(hipMemcpyAsync(d_ctrl_ + slot, &ctrl_stage_[slot], sizeof(c), hipMemcpyHostToDevice, stream_));
-    act.push_back(std::move(a));
-    decode_plan_valid = false;
-    return RWKVTTS_OK;
-  };
-
-  int rc = RWKVTTS_OK;
-  while (true) {
-    // ---- admission: new requests take free slots between forward steps
-    if (open && !free_slots.empty()) {
-      fresh.clear();
-      open = src.next((int)free_slots.size(), act.empty(), fresh);
-      size_t n_admitted = 0;
-      for (; n_admitted < fresh.size(); ++n_admitted)
-        if ((rc = admit(fresh[n_admitted])) != RWKVTTS_OK) break;
-      if (rc != RWKVTTS_OK) {
-        // the failing job and every later one were taken from the source but never reached
-        // `act`: they fail with the engine (the failure fan-out below covers `act` only)
-        for (size_t i = n_admitted; i < fresh.size(); ++i) {
-          Job* j = fresh[i];
-          if (std::any_of(act.begin(), act.end(), [&](const Active& a) { return a.job == j; })) continue;
-          j->res->status = rc;
-          j->res->n_global = j->res->n_semantic = 0;
-          sink_fail(j, 0);
-          src.finish(j);
-        }
-        break;
-      }
-    }
-    if (act.empty()) {
-      if (!open) break;
-      continue;
-    }
-    std::sort(act.begin(), act.end(), [](const Active& x, const Active& y) { return x.slot < y.slot; });
-    bool any_prefill = false;
-    for (auto& a : act) any_prefill |= a.prefilled < (int)a.prompt.size();
-    int K = 1;
-    bool all_global = true, uploaded = false;
-    const int b = pending.valid ? pending.buf ^ 1 : 0;  // this unit's snapshot buffer / events
-    RT_HIP(hipEventRecord(ev0[b], stream_));
-    if (any_prefill) {
-      // ---- mixed step: every decoding slot's row (token from its control block) plus prompt
-      // rows of the admitted slots, up to token_chunk_size rows; the decoding slots never stall
-      StepPlan p;
-      p.advance = true;
-      int budget = chunk_;
-      for (auto& a : act) {
-        if (a.prefilled < (int)a.prompt.size()) continue;
-        const int r = (int)p.rows.size();
-        p.rows.push_back(make_int4(a.slot, kRowFirst | kRowLast | kRowCtrl, -1, 0));
-        p.tok.push_back(0);
-        p.segs.push_back(make_int4(a.slot, r, 1, 0));
-        p.lg_rows.push_back(r);
-        p.lg_slot.push_back(a.slot);
-        all_global &= !a.zero_shot && a.advances <= RWKVTTS_N_GLOBAL;
-        a.advances++;
-        --budget;
-      }
-      budget = std::max(budget, 1);
-      for (auto& a : act) {
-        const int left = (int)a.prompt.size() - a.prefilled;
-        if (left <= 0 || budget <= 0) continue;
-        const int take = std::min(left, budget);
-        const int r0 = (int)p.rows.size();
-        for (int t = 0; t < take; ++t) {
-          const int flags = (t == 0 ? kRowFirst : 0) | (t == take - 1 ? kRowLast : 0);
-          p.rows.push_back(make_int4(a.slot, flags, t == 0 ? -1 : r0 + t - 1, 0));
-          p.tok.push_back(a.prompt[a.prefilled + t]);
-        }
-        p.segs.push_back(make_int4(a.slot, r0, take, 0));
-        a.prefilled += take;
-        budget -= take;
-        if (a.prefilled == (int)a.prompt.size()) {
-          p.lg_rows.push_back(r0 + take - 1);
-          p.lg_slot.push_back(a.slot);
-          all_global &= !a.zero_shot;
-          a.advances++;
-        }
-      }
-      p.head_rows = std::min(all_global ? 4096 : 8193, dims.n_vocab);
-      if ((rc = run_step(p, true)) != RWKVTTS_OK) break;
-      decode_plan_valid = false;
-      stats.prefill_steps++;
-    } else {
-      // ---- decode window: up to kLookahead steps queued back to back before the host reads
-      // the control blocks; no slot can pass its step limit inside the window (EOS may end a
-      // request earlier: its slot then idles through the rest of the window, k_advance skips it)
-      if (!decode_plan_valid) {
-        dp = StepPlan();
-        dp.tok_from_ctrl = true;
-        dp.advance = true;
-        for (auto& a : act) {
-          const int r = (int)dp.rows.size();
-          dp.rows.push_back(make_int4(a.slot, kRowFirst | kRowLast | kRowCtrl, -1, 0));
-          dp.segs.push_back(make_int4(a.slot, r, 1, 0));
-          dp.lg_rows.push_back(r);
-          dp.lg_slot.push_back(a.slot);
-        }
-        if ((rc = upload_plan(dp)) != RWKVTTS_OK) break;
-        decode_plan_valid = true;
-        uploaded = true;
-      }
-      K = (profiling || d_tl_) ? 1 : kLookahead;
-      for (auto& a : act) K = std::min(K, std::max(1, a.total - a.advances));
-      if (d_tl_) RT_HIP(hipMemsetAsync(d_tl_, 0, (size_t)kTlStride * kTlMax * 8, stream_));
-      for (int k = 0; k < K && rc == RWKVTTS_OK; ++k) {
-        // head rows: 4096 while every slot samples global tokens (or feeds g31), else 8193
-        all_global = true;
-        for (auto& a : act) all_global &= !a.zero_shot && a.advances <= RWKVTTS_N_GLOBAL;
-        dp.head_rows = std::min(all_global ? 4096 : 8193, dims.n_vocab);
-        rc = run_step(dp, false);
-        for (auto& a : act) a.advances++;
-      }
-      if (rc != RWKVTTS_OK) break;
-      stats.steps += K;
-      stats.decode_rows += (int64_t)dp.rows.size() * K;
-      max_active = std::max<int64_t>(max_active, (int64_t)dp.rows.size());
-    }
-    // token progress: the semantic ids this unit may have added to each sink-carrying slot, copied
-    // beside the snapshot (a slot holds at most one id per advance, and the host knows the ids it
-    // has handed out: [delivered, min(sem_limit, advances)) covers whatever the snapshot will show).
-    // Slots without a sink add nothing, so a run without sinks enqueues what it always did.
-    for (auto& a : act) {
-      if (!a.sink) continue;
-      const int lo = a.delivered, hi = std::min(ctrl_stage_[a.slot].sem_limit, a.advances);
-      a.copied_hi[b] = hi;
-      if (hi <= lo) continue;
-      const size_t so = (size_t)a.slot * RWKVTTS_SEMANTIC_LIMIT + lo;
-      RT_HIP(hipMemcpyAsync(h_prog_ + (size_t)b * S_ * RWKVTTS_SEMANTIC_LIMIT + so, d_sem_ + so, sizeof(int32_t) * (hi - lo),
-                            hipMemcpyDeviceToHost, stream_));
-    }
-    RT_HIP(hipMemcpyAsync(h_ctrl_ + (size_t)b * (S_ + 1), d_ctrl_, sizeof(SlotCtrl) * (S_ + 1), hipMemcpyDeviceToHost, stream_));
-    unit_graph_[b] = {-1, -1};
-    if (graph_timing() && !any_prefill && last_graph_.first >= 0) {  // the window's last step's stamps
-      const size_t n = graph_names_[last_graph_].size();
-      RT_HIP(hipMemcpyAsync(h_gt_ + (size_t)b * kTlStride * kTlMax, d_gt_, n * kTlStride * 8, hipMemcpyDeviceToHost,
-                            stream_));
-      unit_graph_[b] = last_graph_;
-    }
-    RT_HIP(hipEventRecord(ev1[b], stream_));
-    Unit now;
-    now.valid = true;
-    now.prefill = any_prefill;
-    now.buf = b;
-    // the older unit first (its retirements are stream-ordered after this one), then this one
-    // unless the next window may go out before its snapshot is read
-    if (pending.valid) {
-      const Unit u = pending;
-      pending.valid = false;
-      if ((rc = finish_unit(u.buf, u.prefill, act, free_slots, src, ev0, ev1)) != RWKVTTS_OK) break;
-      if (act.size() != dp.rows.size()) decode_plan_valid = false;
-    }
-    bool ahead = !any_prefill && !uploaded && use_graphs_ && !profiling && !d_tl_ &&
-                 (!open || free_slots.empty());
-    for (auto& a : act) ahead &= a.total - a.advances >= 1;
-    if (ahead) {
-      pending = now;
-    } else {
-      if ((rc = finish_unit(now.buf, now.prefill, act, free_slots, src, ev0, ev1)) != RWKVTTS_OK) break;
-      if (act.size() != dp.rows.size()) decode_plan_valid = false;
-    }
-  }
-  if (pending.valid || rc != RWKVTTS_OK) (void)hipStreamSynchronize(stream_);
+  ServeState st(src);
+  for (int s = S_ - 1; s >= 0; --s) st.free_slots.push_back(s);
+  RT_OK(st.ev.create());
+  const int rc = serve_loop(st);
+  // the one way out: whatever the loop returned, the stream is drained, a persistent fault is
+  // recovered from, and every job taken from the source and not finished fails with the engine
+  if (st.pending.valid || rc != RWKVTTS_OK) (void)hipStreamSynchronize(stream_);
   if (persist_fault_) {  // a timed-out hand-off: the engine recovers and keeps serving
     const int code = persist_fault_;
     persist_fault_ = 0;
@@ -1680,17 +1554,9 @@ int Engine::serve(JobSource& src) {
               "); the unit's requests failed, the engine was reset" +
               (degrade ? " and now runs the separate launches (second timeout)" : ""));
   }
-  for (int i = 0; i < 2; ++i) {
-    hipEventDestroy(ev0[i]);
-    hipEventDestroy(ev1[i]);
-  }
-  if (rc != RWKVTTS_OK) {  // engine failure: every job still in flight fails with it
-    for (auto& a : act) {
-      a.job->res->status = rc;
-      a.job->res->n_global = a.job->res->n_semantic = 0;
-      if (a.sink) sink_fail(a.job, a.delivered);  // the stream ends: done = 1, the engine's status
-      src.finish(a.job);
-    }
+  if (rc != RWKVTTS_OK) {
+    for (Job* j : st.fresh) fail_job(src, j, rc, 0);  // the failing admission and the ones after it
+    for (auto& a : st.act) fail_job(src, a.job, rc, a.sink ? a.delivered : -1);
     return rc;
   }
   return dump_stamps();

@@ -4,15 +4,13 @@
 #include <string.h>
 
 #include "common.h"
+#include "slot_ctrl.h"  // the row flags kRowFirst / kRowLast / kRowCtrl
 
 namespace rwkvtts {
 
 constexpr int kMaxPerThread = 8;     // C <= 2048 with 256-thread rows
 constexpr int kMaxLoraTotal = 512;   // Dw + Da + Dv + Dg
 constexpr int kMaxParts = 8;         // split-K slabs a WKV row sums (r, k, v, LoRA hidden)
-constexpr int kRowFirst = 1;         // row flags
-constexpr int kRowLast = 2;
-constexpr int kRowCtrl = 4;          // the row's token is its slot's SlotCtrl::next_token (decode)
 constexpr int kXPlanes = 0;  // gemm X: bf16 hi/lo planes
 constexpr int kXRelu2 = 1;   // gemm X: relu(sum of f32 partial slabs)^2
 

@@ -2,43 +2,13 @@
 // (src/normal_mode_inference.rs:222-391, src/zero_shot_inference.rs:128-309).
 #pragma once
 #include "common.h"
+#include "slot_ctrl.h"
 
 namespace rwkvtts {
 
 constexpr int kSampleMaxN = 16384;       // row length held in LDS (longer rows: global scratch)
 constexpr int kSampleMaxSorted = 4096;   // survivors sortable for top-p in LDS
 constexpr int kSampleMaxRowLen = 1 << 24;  // generic sampler API row limit
-
-enum SlotPhase : int32_t { kPhGlobal = 0, kPhGFeed = 1, kPhSemantic = 2, kPhDone = 3 };
-
-// Per-slot control block living in device memory.
-struct SlotCtrl {
-  int32_t mode;        // 0 normal, 1 zero-shot
-  int32_t phase;       // SlotPhase
-  int32_t n_global;
-  int32_t n_sem;
-  int32_t sem_limit;
-  int32_t hard_min;    // zero-shot: EOS forbidden while n_sem < hard_min
-  int32_t fixed;       // benchmark: EOS always masked
-  int32_t top_k_g, top_k_s;
-  int32_t next_token;  // token fed at the next step
-  int32_t win_bits;    // zero-shot EOS window (bit i = non-EOS, newest at bit 0)
-  int32_t win_len;
-  int32_t status;
-  int32_t pad0;
-  uint32_t gkey[8];
-  uint32_t skey[8];
-  uint64_t gdraw;
-  uint64_t sdraw;
-  int32_t global_out[32];
-  // ChaCha12 keystream block cache of each stream (k_advance): 16 consecutive draws share one
-  // block, so 15 of 16 draws are a word read instead of a ChaCha12 block on the critical path.
-  // *_blk_id = block index + 1 (0: empty -- the host zero-fills a new request's block)
-  uint64_t gblk_id;
-  uint64_t sblk_id;
-  uint32_t gblk[16];
-  uint32_t sblk[16];
-};
 
 struct SampleRowArgs {
   const float* logits;  // [rows][ld]

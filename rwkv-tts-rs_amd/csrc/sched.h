@@ -1,0 +1,256 @@
+// sched.h -- the continuous-batching scheduler's rules (DynamicBatchManager semantics,
+// src/dynamic_batch_manager.rs) as plain functions of host data: what a request's prompt, control
+// block and step limit are, which rows a forward step carries, how long a decode window is.
+// Engine::serve (engine.hip) applies them; nothing here touches the GPU (plain C++17, no HIP
+// header), so tests/native/sched_main.cpp checks them on a CPU.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/rwkvtts.h"
+#include "slot_ctrl.h"
+
+namespace rwkvtts {
+
+struct Job;  // engine.h: one request in flight through Engine::serve
+
+// four ints as the kernels read them (HIP's int4; engine.hip asserts size and alignment)
+struct alignas(16) Int4 {
+  int32_t x, y, z, w;
+};
+
+// One forward step description (host side).
+struct StepPlan {
+  std::vector<uint32_t> tok;   // per row
+  std::vector<Int4> rows;      // slot, flags, prev_row, 0
+  std::vector<Int4> segs;      // slot, row_begin, n_rows, 0
+  std::vector<int> lg_rows;    // rows whose logits are produced
+  std::vector<int> lg_slot;    // slot of each logits row (advance)
+  int head_rows = 0;
+  bool tok_from_ctrl = false;  // decode: token = ctrl[slot].next_token
+  bool advance = false;        // run the phase controller on the logits rows
+};
+
+// A request decoding in a state slot.
+struct Active {
+  Job* job = nullptr;
+  int slot = 0;
+  std::vector<uint32_t> prompt;
+  int prefilled = 0;
+  int advances = 0;  // phase-controller invocations so far
+  int total = 0;     // advances after which the request is certainly done (its step limit)
+  bool zero_shot = false;
+  // token progress (Job::user): semantic tokens handed to the sink so far, and per unit buffer the
+  // end of the range of this slot's d_sem_ that the unit copied to h_prog_
+  const rwkvtts_token_sink* sink = nullptr;
+  int delivered = 0;
+  int copied_hi[2] = {0, 0};
+  bool in_prompt() const { return prefilled < (int)prompt.size(); }
+};
+
+inline bool is_zero_shot(const rwkvtts_request& q) { return q.ref_global != nullptr && q.ref_semantic != nullptr; }
+
+// Checks a request before admission; fills `why` and returns false for a bad one.
+inline bool validate(const rwkvtts_request& q, int n_vocab, std::string& why) {
+  auto ids_ok = [&](const int32_t* p, int n, int lo, int hi, const char* what) {
+    if (n < 0 || (n > 0 && !p)) {
+      why = std::string(what) + ": bad array";
+      return false;
+    }
+    for (int i = 0; i < n; ++i)
+      if (p[i] < lo || p[i] >= hi) {
+        why = std::string(what) + ": id " + std::to_string(p[i]) + " out of range";
+        return false;
+      }
+    return true;
+  };
+  const int V = n_vocab;
+  if (!ids_ok(q.text_tokens, q.n_text, 0, V, "text_tokens")) return false;
+  if (!ids_ok(q.property_tokens, q.n_property, 0, V, "property_tokens")) return false;
+  if ((q.ref_global && q.n_ref_global < 0) || (q.ref_semantic && q.n_ref_semantic < 0)) {
+    why = "reference token counts must be >= 0";
+    return false;
+  }
+  if (q.max_tokens < 0 || q.fixed_semantic < 0) {
+    why = "max_tokens / fixed_semantic must be >= 0";
+    return false;
+  }
+  const bool zero_shot = is_zero_shot(q);
+  if (V <= RWKVTTS_TAG_2 || (!zero_shot && V <= RWKVTTS_GLOBAL_TOKEN_OFFSET + 4095) ||
+      (zero_shot && q.n_ref_global > 0 && V <= RWKVTTS_GLOBAL_TOKEN_OFFSET + 4095)) {
+    why = "model vocabulary too small for the TTS tags / global tokens";
+    return false;
+  }
+  return true;
+}
+
+// Semantic-step limit of a request, as the reference derives it.
+inline int sem_limit_of(const rwkvtts_request& q) {
+  if (q.fixed_semantic > 0) return std::min(q.fixed_semantic, RWKVTTS_SEMANTIC_LIMIT);
+  if (is_zero_shot(q)) return RWKVTTS_SEMANTIC_LIMIT;                  // zero_shot_inference.rs:128-142
+  return std::min(std::max(q.max_tokens, 0), RWKVTTS_SEMANTIC_LIMIT);  // normal_mode_inference.rs:316
+}
+
+// What admission derives from the request alone.
+struct Admission {
+  std::vector<uint32_t> prompt;
+  SlotCtrl ctrl;         // the slot's initial control block, gkey / skey still zero
+  uint64_t gseed, sseed;  // the engine derives gkey / skey from them (StdRng::seed_from_u64)
+  bool zero_shot;
+  int total;             // Active::total
+};
+
+// entropy: the seed of a request without one (dynamic_batch_manager.rs:491-499, from_entropy)
+inline Admission admission_of(const rwkvtts_request& q, uint64_t entropy) {
+  Admission a;
+  a.zero_shot = is_zero_shot(q);
+  for (int i = 0; i < q.n_property; ++i) a.prompt.push_back((uint32_t)q.property_tokens[i]);
+  a.prompt.push_back(RWKVTTS_TAG_2);
+  for (int i = 0; i < q.n_text; ++i) a.prompt.push_back((uint32_t)q.text_tokens[i]);
+  a.prompt.push_back(RWKVTTS_TAG_0);
+  SlotCtrl& c = a.ctrl;
+  memset(&c, 0, sizeof(c));
+  // RNG streams: normal_mode_inference.rs:138-174, zero_shot_inference.rs:204-216,
+  // dynamic_batch_manager.rs:491-499 (no seed -> from_entropy)
+  const uint64_t seed = q.has_seed ? q.seed : entropy;
+  const bool indep = q.layered_set ? q.use_independent_seeds != 0 : true;
+  const uint64_t goff = q.layered_set ? q.global_seed_offset : 1000, soff = q.layered_set ? q.semantic_seed_offset : 2000;
+  a.gseed = indep ? seed + goff : seed + 100;
+  a.sseed = indep ? seed + soff : seed + 200;
+  if (a.zero_shot && !indep) a.sseed = 0;  // StdRng::seed_from_u64(0) handed to the zero-shot path
+  c.top_k_g = q.greedy ? 1 : 20;
+  c.top_k_s = q.greedy ? 1 : 80;
+  c.fixed = q.fixed_semantic > 0;
+  c.sem_limit = sem_limit_of(q);
+  if (a.zero_shot) {
+    c.mode = 1;
+    c.phase = kPhSemantic;
+    for (int i = 0; i < q.n_ref_global; ++i) {
+      const int g = std::min(std::max(q.ref_global[i], 0), 4095);
+      a.prompt.push_back((uint32_t)(g + RWKVTTS_GLOBAL_TOKEN_OFFSET));
+      if (i < RWKVTTS_N_GLOBAL) c.global_out[c.n_global++] = g;
+    }
+    a.prompt.push_back(RWKVTTS_TAG_1);
+    const int tlen = q.n_text;
+    const int min_sem = std::min(std::max(tlen / 4, 8), 64);
+    const int est = (int)ceilf((float)tlen * 1.8f);
+    const int upper = (int)floorf((float)RWKVTTS_SEMANTIC_LIMIT * 0.9f);
+    c.hard_min = std::min(upper, std::max(min_sem, est));
+    a.total = std::max(c.sem_limit, 1);
+  } else {
+    c.mode = 0;
+    c.phase = kPhGlobal;
+    a.total = RWKVTTS_N_GLOBAL + 1 + c.sem_limit;
+  }
+  return a;
+}
+
+// ---- the row tables of a step: one segment per slot, its rows consecutive
+// a decoding slot's row: the token comes from its control block, the logits go to the controller
+inline void append_decode_row(StepPlan& p, int slot) {
+  const int r = (int)p.rows.size();
+  p.rows.push_back({slot, kRowFirst | kRowLast | kRowCtrl, -1, 0});
+  if (!p.tok_from_ctrl) p.tok.push_back(0);
+  p.segs.push_back({slot, r, 1, 0});
+  p.lg_rows.push_back(r);
+  p.lg_slot.push_back(slot);
+}
+
+enum LogitRows { kLogitsNone, kLogitsLast, kLogitsAll };
+
+// `take` > 0 tokens of a slot, each row after the first chained to the one before it
+inline void append_token_rows(StepPlan& p, int slot, const uint32_t* tok, int take, LogitRows lg) {
+  const int r0 = (int)p.rows.size();
+  for (int t = 0; t < take; ++t) {
+    const int flags = (t == 0 ? kRowFirst : 0) | (t == take - 1 ? kRowLast : 0);
+    p.rows.push_back({slot, flags, t == 0 ? -1 : r0 + t - 1, 0});
+    p.tok.push_back(tok[t]);
+    if (lg == kLogitsAll || (lg == kLogitsLast && t == take - 1)) {
+      p.lg_rows.push_back(r0 + t);
+      p.lg_slot.push_back(slot);
+    }
+  }
+  p.segs.push_back({slot, r0, take, 0});
+}
+
+// Head rows of a step: 4096 while every slot that gets a logits row (its prompt is in) samples
+// global tokens (normal_mode_inference.rs:236-240: from [0, 4096)) or feeds g31, else 8193 (:332:
+// semantic ids from [0, 8192]). Evaluated before the step's advances are counted.
+inline int head_rows_of(const std::vector<Active>& act, int n_vocab) {
+  bool all_global = true;
+  for (const Active& a : act)
+    if (!a.in_prompt()) all_global &= !a.zero_shot && a.advances <= RWKVTTS_N_GLOBAL;
+  return std::min(all_global ? 4096 : 8193, n_vocab);
+}
+
+// Mixed step: every decoding slot's row (token from its control block) plus prompt rows of the
+// admitted slots, up to `chunk` rows; the decoding slots never stall. `act` is sorted by slot.
+inline StepPlan mixed_plan(std::vector<Active>& act, int chunk, int n_vocab) {
+  StepPlan p;
+  p.advance = true;
+  int budget = chunk;
+  for (const Active& a : act) {
+    if (a.in_prompt()) continue;
+    append_decode_row(p, a.slot);
+    --budget;
+  }
+  budget = std::max(budget, 1);
+  for (Active& a : act) {
+    const int left = (int)a.prompt.size() - a.prefilled;
+    if (left <= 0 || budget <= 0) continue;
+    const int take = std::min(left, budget);
+    append_token_rows(p, a.slot, a.prompt.data() + a.prefilled, take, take == left ? kLogitsLast : kLogitsNone);
+    a.prefilled += take;
+    budget -= take;
+  }
+  p.head_rows = head_rows_of(act, n_vocab);
+  for (Active& a : act) a.advances += !a.in_prompt();  // one advance per logits row
+  return p;
+}
+
+// Decode plan: one row per active slot, tokens from the control blocks.
+inline StepPlan decode_plan(const std::vector<Active>& act) {
+  StepPlan p;
+  p.tok_from_ctrl = true;
+  p.advance = true;
+  for (const Active& a : act) append_decode_row(p, a.slot);
+  return p;
+}
+
+// Decode window: up to `lookahead` steps queued back to back before the host reads the control
+// blocks; no slot can pass its step limit inside the window (EOS may end a request earlier: its
+// slot then idles through the rest of the window, k_advance skips it). single: profiling or the
+// debug timeline, one step per window.
+inline int window_len(const std::vector<Active>& act, int lookahead, bool single) {
+  int K = single ? 1 : lookahead;
+  for (const Active& a : act) K = std::min(K, std::max(1, a.total - a.advances));
+  return K;
+}
+
+// Whether the next window may go out before this unit's snapshot is read: steady decode only --
+// no prompt rows in the unit, its plan uploaded earlier, graph replay without profiling or the
+// timeline, no admission possible (can_admit: the source is open and a slot is free) and no slot
+// able to pass its step limit.
+inline bool may_run_ahead(const std::vector<Active>& act, bool any_prefill, bool uploaded, bool graphs, bool profiling,
+                          bool timeline, bool can_admit) {
+  bool ahead = !any_prefill && !uploaded && graphs && !profiling && !timeline && !can_admit;
+  for (const Active& a : act) ahead &= a.total - a.advances >= 1;
+  return ahead;
+}
+
+// Token progress: the semantic ids a unit may have added to a slot. A slot holds at most one id
+// per advance, and the host knows the ids it has handed out: [delivered, min(sem_limit, advances))
+// covers whatever the unit's snapshot will show. Empty when hi <= lo.
+struct ProgressRange {
+  int lo, hi;
+};
+inline ProgressRange progress_range(int delivered, int sem_limit, int advances) {
+  return {delivered, std::min(sem_limit, advances)};
+}
+
+}  // namespace rwkvtts

@@ -186,6 +186,27 @@ def test_staggered_admission_equals_serial():
         assert st["prefill_steps"] >= 4  # admissions happened while slots were decoding
         for r, gs in zip(reqs, got):
             assert gs == _oracle(om, r)
+        # the schedule itself (seeded requests from a list: it does not depend on timing), as the
+        # scheduler before the serve-loop split produced it in two runs
+        assert (st["steps"], st["prefill_steps"], st["decode_rows"]) == (190, 6, 485)
+    finally:
+        rt.close()
+
+
+def test_mixed_step_budget_floor():
+    """token_chunk_size 2 with 3 slots: once two slots decode, their rows use the whole chunk and the
+    admitted slot's prompt still advances one row per step (the mixed step's budget floor), so a
+    step carries 3 rows; every result equals its serial run."""
+    blob = W.synth_blob(W.DIMS_TINY, seed=99)
+    import oracle
+    om = oracle.Model(blob)
+    rt = rwkvtts.SharedRwkvRuntime(blob, max_slots=3, token_chunk_size=2, use_graphs=True)
+    try:
+        reqs = [make_request(synth_text(520 + i, n=3 + 2 * i), seed=80 + i, max_tokens=4 + 2 * i) for i in range(6)]
+        got = rt.generate_batch(reqs)
+        assert rt.stats()["prefill_steps"] > 0
+        for r, gs in zip(reqs, got):
+            assert gs == _oracle(om, r)
     finally:
         rt.close()
 
