@@ -246,6 +246,10 @@ int rwkvtts_sample(rwkvtts_engine* e, const float* logits, int n_rows, int row_l
  * (dynamic_batch_manager.rs:512-515) and property-token construction (properties_util.rs:76-98). */
 #define RWKVTTS_MODE_AUTO 0      /* zero-shot iff both ref token sets present (dbm.rs:526-540) */
 typedef struct {
+  float temperature, top_p;
+  int32_t top_k;
+} rwkvtts_phase_sampling;
+typedef struct {
   const int32_t* text_tokens;
   int32_t n_text;
   const int32_t* property_tokens;
@@ -269,7 +273,21 @@ typedef struct {
                                     zero-shot StdRng(0) (dynamic_batch_manager.rs:491-494) */
   uint64_t global_seed_offset;
   uint64_t semantic_seed_offset;
+  /* Per-request sampling of the two phases. The reference fixes (temperature, top_p, top_k) per
+   * phase -- (1.0, 0.95, 20) global, (1.0, 0.95, 80) semantic, normal_mode_inference.rs:114-127 --
+   * whatever the request says; a zero-filled request keeps exactly that. sampling_set bit 0:
+   * global_sampling holds, bit 1: semantic_sampling holds (zero-shot has no global phase:
+   * global_sampling is accepted there and unused). A set phase needs temperature in [0.1, 4.0],
+   * top_p in [0, 1] and top_k >= 0 (0 or >= the row length: no top-k; top_p >= 1: no top-p);
+   * anything else, unknown bits, or `greedy` together with sampling_set fails the request alone.
+   * Cost per decode step: temperature 1 with 1 <= top_k <= 256 is the
+   * certified fast path; temperature != 1 adds the exact sequential softmax sum (no certificate
+   * covers powf); top_k 0 or > 256 takes the general path (a sort over the row). */
+  int32_t sampling_set;
+  rwkvtts_phase_sampling global_sampling, semantic_sampling;
 } rwkvtts_request;
+#define RWKVTTS_SAMPLING_GLOBAL 1
+#define RWKVTTS_SAMPLING_SEMANTIC 2
 
 typedef struct {
   int32_t status;         /* 0 ok; <0 this request failed -> (vec![], vec![]) as dbm.rs:466-469
@@ -418,6 +436,12 @@ int rwkvtts_profile_entry(rwkvtts_engine* e, int idx, char* name, int name_cap, 
  * Outputs out_tok / out_used / out_phase are [n_steps][n_rows]. */
 int rwkvtts_debug_advance(rwkvtts_engine* e, const float* logits, int n_rows, const void* rows, int exact,
                           int n_steps, int32_t* out_tok, int32_t* out_used, int32_t* out_phase);
+/* The same with per-row sampling parameters: `rows` points to n_rows records of 88 bytes, the 72
+ * above followed by uint32 struct_size (= 88), float temperature, float top_p and 4 bytes of
+ * padding. top_k may be 0 here (no top-k); temperature in [0.1, 4.0], top_p in [0, 1]. A row with
+ * (1.0, 0.95) gives what rwkvtts_debug_advance gives for its first 72 bytes. */
+int rwkvtts_debug_advance_ex(rwkvtts_engine* e, const float* logits, int n_rows, const void* rows, int exact,
+                             int n_steps, int32_t* out_tok, int32_t* out_used, int32_t* out_phase);
 
 /* ---- codec: BiCodecDetokenize via ORT (lightweight_tts_pipeline.rs:606-622,706-730) ----- */
 typedef struct rwkvtts_codec rwkvtts_codec;

@@ -125,6 +125,17 @@ int rwkvtts_debug_advance(rwkvtts_engine* e, const float* logits, int n_rows, co
   })
 }
 
+// The same with per-row temperature / top-p (engine.h DebugAdvanceRowEx); top_k may be 0.
+int rwkvtts_debug_advance_ex(rwkvtts_engine* e, const float* logits, int n_rows, const void* rows, int exact,
+                             int n_steps, int32_t* out_tok, int32_t* out_used, int32_t* out_phase) {
+  RT_CHECK(e && logits && rows && out_tok && out_used && out_phase, RWKVTTS_EINVAL, "debug_advance_ex: bad arguments");
+  LOCK(e);
+  GUARD({
+    return e->eng.debug_advance_ex(logits, n_rows, (const DebugAdvanceRowEx*)rows, exact, n_steps, out_tok, out_used,
+                                   out_phase);
+  })
+}
+
 int rwkvtts_generate_batch(rwkvtts_engine* e, const rwkvtts_request* reqs, int n,
                            rwkvtts_result* results) {
   RT_CHECK(e && reqs && results && n >= 0, RWKVTTS_EINVAL, "generate_batch: bad arguments");

@@ -25,6 +25,15 @@ struct DebugAdvanceRow {
   uint32_t key[8];   // ChaCha12 key of the phase's stream
   uint64_t draw;     // index of the next u32 draw
 };
+// rwkvtts_debug_advance_ex: the row above plus its phase's temperature and top-p
+struct DebugAdvanceRowEx {
+  DebugAdvanceRow row;
+  uint32_t struct_size;
+  float temperature;
+  float top_p;
+  uint32_t pad;
+};
+static_assert(sizeof(DebugAdvanceRow) == 72 && sizeof(DebugAdvanceRowEx) == 88, "test-hook row layouts");
 
 struct LayerW {
   const float *ln1_w, *ln1_b, *ln2_w, *ln2_b;
@@ -92,6 +101,9 @@ class Engine {
   // per-row controller states, for n_steps consecutive launches on the same rows.
   int debug_advance(const float* logits, int n_rows, const struct DebugAdvanceRow* rows, int exact, int n_steps,
                     int32_t* out_tok, int32_t* out_used, int32_t* out_phase);
+  // rwkvtts_debug_advance_ex: rows carry their own temperature / top-p, top_k may be 0
+  int debug_advance_ex(const float* logits, int n_rows, const struct DebugAdvanceRowEx* rows, int exact, int n_steps,
+                       int32_t* out_tok, int32_t* out_used, int32_t* out_phase);
   // Continuous batching until `src` is closed and every admitted job has finished.
   int serve(JobSource& src);
   // Checks a request before admission; fills `why` and returns false for a bad one.
@@ -136,7 +148,8 @@ class Engine {
   int enqueue_snapshot(ServeState& st, const Unit& u);
   int finish_unit(const Unit& u, ServeState& st);
   int accumulate_stamps(const Unit& u);
-  int launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_from_ctrl, bool advance);
+  int launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_from_ctrl, bool advance,
+                     bool sampling_params = false);
   int upload_plan(const StepPlan& p);
   void prof_begin(hipEvent_t* ev);
   void prof_end(const char* name, hipEvent_t ev);

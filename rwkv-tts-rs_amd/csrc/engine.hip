@@ -565,7 +565,8 @@ int Engine::flush_prof() {
 // prefill steps with more rows than this take the relu^2-plane route for the FFN value GEMM
 static constexpr int kPlaneRows = 64;
 
-int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_from_ctrl, bool advance) {
+int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_from_ctrl, bool advance,
+                           bool sampling_params) {
   const int C = dims.n_embd, F = dims.n_ffn, Lc = dims.n_layer;
   const int nb = (R + 255) / 256;
   // decode steps (tokens from the control blocks, one row per slot) keep each slot's shift
@@ -848,6 +849,7 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
       a.sem_out = d_sem_;
       a.n_rows = n_lg;
       a.stamps = dbg_astamps_;
+      a.params = sampling_params ? 1 : 0;
       timed("advance", "sample_advance", [&](unsigned long long* tl) {
         a.tl = tl;
         launch_advance(a, stream_, exact_sampler_ ? 0 : 1);
@@ -900,7 +902,7 @@ int Engine::run_step(const StepPlan& p, bool upload) {
   if (upload) RT_OK(upload_plan(p));
   const int n_seg = (int)p.segs.size(), n_lg = (int)p.lg_rows.size();
   if (p.tok_from_ctrl && use_graphs_ && !profiling) {
-    auto key = std::make_pair(R, p.head_rows * 2 + (p.advance ? 1 : 0));
+    auto key = std::make_pair(R, p.head_rows * 4 + (p.sampling_params ? 2 : 0) + (p.advance ? 1 : 0));
     auto it = graphs_.find(key);
     if (it == graphs_.end()) {
       // the one-launch step's argument table is uploaded before the capture (no synchronous copy
@@ -911,7 +913,7 @@ int Engine::run_step(const StepPlan& p, bool upload) {
       std::unique_lock<std::mutex> cap_lock(capture_mu);
       hipGraph_t graph;
       RT_HIP(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-      int rc = launch_forward(R, n_seg, n_lg, p.head_rows, true, p.advance);
+      int rc = launch_forward(R, n_seg, n_lg, p.head_rows, true, p.advance, p.sampling_params);
       hipError_t ce = hipStreamEndCapture(stream_, &graph);
       RT_OK(rc);
       RT_HIP(ce);
@@ -926,7 +928,7 @@ int Engine::run_step(const StepPlan& p, bool upload) {
     return RWKVTTS_OK;
   }
   last_graph_ = {-1, -1};
-  RT_OK(launch_forward(R, n_seg, n_lg, p.head_rows, p.tok_from_ctrl, p.advance));
+  RT_OK(launch_forward(R, n_seg, n_lg, p.head_rows, p.tok_from_ctrl, p.advance, p.sampling_params));
   return RWKVTTS_OK;
 }
 
@@ -986,14 +988,27 @@ int Engine::infer(const rwkvtts_input* in, int n, int head_rows, float* logits, 
 // out_used = draws the step consumed, out_phase = the phase after the step.
 int Engine::debug_advance(const float* logits, int n_rows, const DebugAdvanceRow* rows, int exact, int n_steps,
                           int32_t* out_tok, int32_t* out_used, int32_t* out_phase) {
+  RT_CHECK(n_rows > 0 && n_rows <= 4096, RWKVTTS_EINVAL, "debug_advance: bad sizes");
+  std::vector<DebugAdvanceRowEx> ex(n_rows);
+  for (int i = 0; i < n_rows; ++i) {
+    RT_CHECK(rows[i].top_k > 0, RWKVTTS_EINVAL, "debug_advance: bad row");
+    ex[i] = DebugAdvanceRowEx{rows[i], (uint32_t)sizeof(DebugAdvanceRowEx), 1.0f, 0.95f, 0u};
+  }
+  return debug_advance_ex(logits, n_rows, ex.data(), exact, n_steps, out_tok, out_used, out_phase);
+}
+
+int Engine::debug_advance_ex(const float* logits, int n_rows, const DebugAdvanceRowEx* rows, int exact, int n_steps,
+                             int32_t* out_tok, int32_t* out_used, int32_t* out_phase) {
   RT_HIP(hipSetDevice(device_));
   RT_CHECK(n_rows > 0 && n_rows <= 4096 && n_steps > 0 && n_steps <= 64, RWKVTTS_EINVAL, "debug_advance: bad sizes");
   constexpr int LD = RWKVTTS_EOS_TOKEN + 1;
   std::vector<SlotCtrl> c(n_rows);
   for (int i = 0; i < n_rows; ++i) {
-    const DebugAdvanceRow& r = rows[i];
-    RT_CHECK((r.phase == kPhGlobal || r.phase == kPhSemantic) && r.top_k > 0 && r.n_sem >= 0 &&
-                 r.n_sem + n_steps <= RWKVTTS_SEMANTIC_LIMIT && (r.mode == 0 || r.mode == 1),
+    const DebugAdvanceRow& r = rows[i].row;
+    RT_CHECK((r.phase == kPhGlobal || r.phase == kPhSemantic) && r.top_k >= 0 && r.n_sem >= 0 &&
+                 r.n_sem + n_steps <= RWKVTTS_SEMANTIC_LIMIT && (r.mode == 0 || r.mode == 1) &&
+                 rows[i].struct_size == sizeof(DebugAdvanceRowEx) && rows[i].temperature >= 0.1f &&
+                 rows[i].temperature <= 4.0f && rows[i].top_p >= 0.0f && rows[i].top_p <= 1.0f,
              RWKVTTS_EINVAL, "debug_advance: bad row");
     SlotCtrl& x = c[i];
     memset(&x, 0, sizeof(x));
@@ -1004,6 +1019,8 @@ int Engine::debug_advance(const float* logits, int n_rows, const DebugAdvanceRow
     x.hard_min = r.hard_min;
     x.fixed = r.fixed;
     x.top_k_g = x.top_k_s = r.top_k;
+    x.temp_g = x.temp_s = rows[i].temperature;
+    x.top_p_g = x.top_p_s = rows[i].top_p;
     x.win_bits = r.win_bits;
     x.win_len = r.win_len;
     memcpy(x.gkey, r.key, 32);
@@ -1045,6 +1062,8 @@ int Engine::debug_advance(const float* logits, int n_rows, const DebugAdvanceRow
     a.ctrl = d_c;
     a.sem_out = d_sem;
     a.n_rows = n_rows;
+    for (int i = 0; i < n_rows; ++i)
+      a.params |= rows[i].temperature != 1.0f || rows[i].top_p != 0.95f || rows[i].row.top_k < 1 || rows[i].row.top_k > kFastTopK;
     std::vector<SlotCtrl> prev = c, now(n_rows);
     for (int s = 0; s < n_steps && rc == RWKVTTS_OK; ++s) {
       launch_advance(a, stream_, exact ? 0 : 1);
@@ -1316,6 +1335,7 @@ int Engine::admit(ServeState& st, Job* j) {
   a.slot = slot;
   a.sink = sink_of(j);
   a.zero_shot = ad.zero_shot;
+  a.own_sampling = ad.own_sampling;
   a.prompt = std::move(ad.prompt);
   a.total = ad.total;
   st.act.push_back(std::move(a));

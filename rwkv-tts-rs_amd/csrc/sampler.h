@@ -39,6 +39,11 @@ struct AdvanceArgs {
   unsigned long long* tl;  // debug timeline slot (null in production)
   int cert;              // set by launch_advance: 1 certified fast path allowed (sample_cert)
   uint64_t* stamps;      // debug: [rows][16] s_memtime phase stamps (RWKVTTS_DEBUG_STAMPS adv=; null in production)
+  // 0: every row's slot samples with the reference's (temperature 1.0, top_p 0.95) and a top-k in
+  // [1, kFastTopK] -- k_advance, the two values compiled in; 1: some slot carries its own
+  // (SlotCtrl::temp_* / top_p_*) or another top-k -- k_advance_params reads them per row and
+  // carries every path. Both give a row of the first kind the same token.
+  int params;
 };
 
 size_t wide_scratch_bytes(int n);

@@ -14,8 +14,13 @@
 //  * rand 0.8 StdRng draw k == ChaCha12(key, block k/16)[k%16]; f32 = (u32 >> 8) * 2^-24.
 // Rows up to kSampleMaxN run with the row in LDS; longer rows (the full 77,923-token vocabulary)
 // run the same code with the row, sort keys and index list in a global scratch (k_sample_rows_wide),
-// so every top-k / top-p combination of the reference is accepted. temperature != 1 uses a
-// double-precision powf (not glibc's).
+// so every top-k / top-p combination of the reference is accepted. temperature != 1 raises the
+// survivors to 1 / T with glibc 2.35 powf restated (exact_math.h glibc_powf, bit-identical on the
+// sampler's domain 0 < p <= 1, 0.1 <= T <= 4), on the fast path and the general path alike; such a
+// row never takes the certified path (its certificate covers neither powf nor the second
+// normalisation). An LDS row (n <= kSampleMaxN) without a top-k cut and with top_p < 1 sorts its
+// probabilities as values only (sort_desc_u32) when more than kSampleMaxSorted are positive; more
+// than kSampleMaxVals elements in such a row remain RWKVTTS_EUNSUPPORTED.
 #include "sampler.h"
 #include "exact_math.h"
 
@@ -465,7 +470,7 @@ struct NoOther {
 // `other` runs on waves 1.. while wave 0 walks the chunk maps (the walk is serial; the other
 // waves would idle). It may not use workgroup barriers.
 template <int NT, typename Other = NoOther>
-__device__ float exact_seq_sum_chunks(const SampleSmem& sm, int n, uint64_t* stamps = nullptr, const Other& other = Other()) {
+__device__ __attribute__((always_inline)) float exact_seq_sum_chunks(const SampleSmem& sm, int n, uint64_t* stamps = nullptr, const Other& other = Other()) {
   constexpr int NS = NT / 64;  // sub-chunks per chunk (64 chunks, one per lane of wave 0)
   constexpr int NE = NT >= 1024 ? 64 : 128;  // serial-add register batch
   const int tid = threadIdx.x;
@@ -666,7 +671,7 @@ __device__ inline PMap pcompose(PMap a, PMap b) {  // a, then b
   return PMap{min(n0, 0x2000000u), min(n1, 0x2000000u)};
 }
 template <int NT, typename Other = NoOther>
-__device__ float exact_seq_sum_runs(const SampleSmem& sm, int n, uint64_t* stamps = nullptr, const Other& other = Other()) {
+__device__ __attribute__((always_inline)) float exact_seq_sum_runs(const SampleSmem& sm, int n, uint64_t* stamps = nullptr, const Other& other = Other()) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   int* rstart = sm.runs;
   int* rend = sm.runs + kRuns;
@@ -837,8 +842,10 @@ __device__ float exact_seq_sum_runs(const SampleSmem& sm, int n, uint64_t* stamp
   return sm.fred[16];
 }
 
+// (always inlined, like the two forms above: an out-of-line instance takes the SampleSmem by
+// reference, which puts the struct into scratch memory in every kernel that calls it)
 template <int NT, typename Other = NoOther>
-__device__ float exact_seq_sum(const SampleSmem& sm, int n, uint64_t* stamps = nullptr, const Other& other = Other()) {
+__device__ __attribute__((always_inline)) float exact_seq_sum(const SampleSmem& sm, int n, uint64_t* stamps = nullptr, const Other& other = Other()) {
   if (n <= kSampleMaxN) return exact_seq_sum_runs<NT>(sm, n, stamps, other);
   return exact_seq_sum_chunks<NT>(sm, n, stamps, other);
 }
@@ -861,11 +868,38 @@ __device__ void bitonic_desc(uint64_t* keys, int M) {
   }
 }
 
+// Descending sort of n (any count) 32-bit values in LDS by the whole workgroup: the bitonic
+// network in its one-direction form (each merge starts with the flip stage q <-> q ^ (k - 1), the
+// rest are half-cleaners q <-> q | j; every comparator leaves the larger value at the lower
+// index), padded to a power of two with virtual minimal elements past n, which no comparator
+// moves -- a pair whose upper index is >= n is skipped.
+template <int NT>
+__device__ void sort_desc_u32(uint32_t* v, int n) {
+  int M = 1;
+  while (M < n) M <<= 1;
+  for (int k = 2; k <= M; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const bool flip = j == (k >> 1);
+      for (int t = threadIdx.x; t < (M >> 1); t += NT) {
+        const int q = ((t & ~(j - 1)) << 1) | (t & (j - 1));  // bit j clear
+        const int ixj = flip ? (q ^ (2 * j - 1)) : (q | j);
+        if (ixj < n) {
+          const uint32_t A = v[q], B = v[ixj];
+          if (A < B) { v[q] = B; v[ixj] = A; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 __device__ inline uint64_t pkey(float p, int i) {
   return ((uint64_t)__builtin_bit_cast(uint32_t, p) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)i);
 }
 
-constexpr int kFastK = 256;     // largest top-k of the fast path
+// values an LDS row's keys + dscan + list regions hold when sorted without keys (carve())
+constexpr int kSampleMaxVals = (kSampleMaxSorted * 8 + 16 * 8 + kSampleMaxSorted * 4) / 4;
+constexpr int kFastK = kFastTopK;  // largest top-k of the fast path
 constexpr int kFastCap = 1024;  // candidate capacity (sm.keys[0, kFastCap)); ranked keys at 2048
 static_assert(kSampleMaxSorted >= 2048 + kFastCap, "fast-path key regions");
 
@@ -899,9 +933,12 @@ __device__ inline float draw_r(const uint32_t* key, uint64_t draw, bool fixed42)
 // cutoff, zeroing below it, the equal-to-cutoff adjustment with the index-order survivor sum),
 // multinomial over the survivors in index order (:174-207). Every other element has p = 0 after
 // top-k and adds exactly nothing to any sequential sum, so results equal the full path's.
+// tinv > 0: the temperature step (:156-171) on the survivors before the multinomial, in the
+// reference's order -- p = powf(p, tinv) (glibc's, exact_math.h), the index-order sum s2 of the
+// results, the division when s2 > 0. tinv == 0 (temperature 1): the reference skips the step.
 template <int NT>
 __device__ __attribute__((always_inline)) int sample_fast(const SampleSmem& sm, int nc, float sum, float top_p,
-                                                          int top_k, const uint32_t* key, uint64_t draw,
+                                                          int top_k, float tinv, const uint32_t* key, uint64_t draw,
                                                           bool fixed42, float* dbg, uint64_t* stamps) {
   const int tid = threadIdx.x;
   uint64_t* pk = sm.keys + 2048;
@@ -971,6 +1008,92 @@ __device__ __attribute__((always_inline)) int sample_fast(const SampleSmem& sm, 
   __syncthreads();
   STAMP(7);
   STAMP(8);
+  if (tinv > 0.0f) {
+    // (4) the equal-to-cutoff adjustment, as below, then (5) and (6) with p rewritten in place
+    if (tid < 64) {
+      const int found = sm.ired[2], ceq = sm.ired[3];
+      int adj_on = 0;
+      float adj = 0.0f;
+      if (top_p < 1.0f && found && top_p > 0.0f) {
+        float s1 = 0.0f;
+        for (int q0 = 0; q0 < m; q0 += 64) {
+          const float v = q0 + tid < m ? sm.p[sm.list[q0 + tid]] : 0.0f;
+          const int cnt = min(64, m - q0);
+          for (int i = 0; i < cnt; ++i) s1 += readlane_f(v, i);
+        }
+        if (s1 < top_p && ceq > 0) {
+          adj = (top_p - s1) / (float)ceq;
+          adj_on = 1;
+        }
+      }
+      if (tid == 0) {
+        sm.ired[4] = adj_on;
+        sm.fred[18] = adj;
+      }
+    }
+    __syncthreads();
+    {
+      const bool adj_on = sm.ired[4] != 0;
+      const float adj = sm.fred[18], cutoff = sm.fred[17];
+      const uint64_t* et = sm.etab;  // filled by the softmax step
+      auto tab = [et](int i) { return et[i]; };
+      for (int t = tid; t < m; t += NT) {
+        const int it = sm.list[t];
+        float v = sm.p[it];
+        if (adj_on && v == cutoff) v = cutoff + adj;
+        if (v > 0.0f) v = glibc_powf_t(v, tinv, tab);
+        sm.p[it] = v;
+      }
+    }
+    __syncthreads();
+    if (tid < 64) {  // s2: index-order sequential sum (:163)
+      float s2 = 0.0f;
+      for (int q0 = 0; q0 < m; q0 += 64) {
+        const float v = q0 + tid < m ? sm.p[sm.list[q0 + tid]] : 0.0f;
+        const int cnt = min(64, m - q0);
+        for (int i = 0; i < cnt; ++i) s2 += readlane_f(v, i);
+      }
+      if (tid == 0) sm.fred[19] = s2;
+    }
+    __syncthreads();
+    const float s2 = sm.fred[19];
+    if (s2 > 0.0f)
+      for (int t = tid; t < m; t += NT) {
+        const int it = sm.list[t];
+        sm.p[it] = sm.p[it] / s2;
+      }
+    __syncthreads();
+    if (tid < 64) {  // multinomial; powf may have underflowed survivors to 0 (:183-189 skips them)
+      const float r = sm.fred[21];
+      int ret = -1;
+      if (r <= 0.0f) {
+        ret = 0;
+      } else {
+        float cum = 0.0f;
+        int last_pos = -1;
+        for (int q0 = 0; q0 < m && ret < 0; q0 += 64) {
+          const bool in = q0 + tid < m;
+          const int idx_l = in ? sm.list[q0 + tid] : 0;
+          const float v = in ? sm.p[idx_l] : 0.0f;
+          float tot;
+          const float pre = prefix64(cum, v, &tot);
+          const uint64_t hit = __ballot(in && r <= pre);
+          const uint64_t posm = __ballot(in && v > 0.0f);
+          if (posm) last_pos = readlane_i(idx_l, 63 - __builtin_clzll(posm));
+          if (hit) ret = readlane_i(idx_l, __builtin_ctzll(hit));
+          cum = tot;
+        }
+        if (ret < 0) ret = max(last_pos, 0);
+      }
+      if (tid == 0) {
+        sm.ired[5] = ret;
+        if (dbg) { dbg[0] = sum; dbg[1] = r; }
+      }
+    }
+    __syncthreads();
+    STAMP(9);
+    return sm.ired[5];
+  }
   if (tid < 64) {
     const int found = sm.ired[2], ceq = sm.ired[3];
     const float cutoff = sm.fred[17];
@@ -1141,7 +1264,10 @@ __device__ __attribute__((always_inline)) int sample_cert(const SampleSmem& sm, 
 
 // The sampler. p holds the (masked) logits on entry. Returns the index in every thread.
 // status: 0 ok, RWKVTTS_EUNSUPPORTED for the documented limitation.
-template <int NT>
+// kValSort: the value-only sort of a row with more than kSampleMaxSorted positive probabilities at
+// top-p (false: that row is RWKVTTS_EUNSUPPORTED, as every such LDS row was; k_advance, whose rows
+// have 1 <= top-k <= kFastK and never get there, is compiled without it).
+template <int NT, bool kValSort = true>
 __device__ __attribute__((always_inline)) int sample_block(const SampleSmem& sm, int n, float temperature, float top_p,
                             int top_k, const uint32_t* key, uint64_t draw, bool fixed42,
                             float* dbg, int* status, uint64_t* stamps = nullptr, bool cert = true,
@@ -1171,11 +1297,12 @@ __device__ __attribute__((always_inline)) int sample_block(const SampleSmem& sm,
     for (; i < n; i += NT) sm.p[i] = glibc_expf_t(sm.p[i] - mx, tab);
   }
   }
-  // Fast path (top-k <= kFastK, no temperature step): while wave 0 walks the exact sum, the
+  // Fast path (top-k <= kFastK): while wave 0 walks the exact sum, the
   // other waves collect the top-k candidates on the unnormalised e = exp(l - max), so that after
   // the sum only the candidates are divided, ranked and sampled. See sample_fast_ok below.
   static_assert(NT <= 512, "fred[8 + wave] per candidate wave");
-  const bool want_fast = top_k > 0 && top_k < n && top_k <= kFastK && !(temperature != 1.0f && temperature > 0.0f);
+  const bool temp_on = temperature != 1.0f && temperature > 0.0f;
+  const bool want_fast = top_k > 0 && top_k < n && top_k <= kFastK;
   if (tid == 0 && !prepped) {
     sm.ired[30] = 0;  // sub-group arrival counter of the candidate waves
     sm.ired[31] = 0;  // candidate count
@@ -1243,12 +1370,12 @@ __device__ __attribute__((always_inline)) int sample_block(const SampleSmem& sm,
   if (prepped) {
     const int nc = sm.ired[31];
     const float L = sm.fred[20];
-    if (want_fast && !dbg && cert && n <= kSampleMaxN && L > 0.0f && nc >= top_k && nc <= kFastCap) {
+    if (want_fast && !temp_on && !dbg && cert && n <= kSampleMaxN && L > 0.0f && nc >= top_k && nc <= kFastCap) {
       const int ret = sample_cert<NT>(sm, n, nc, sm.dscan[12], sm.fred[21], top_p, top_k, sm.dscan[13], stamps);
       STAMP(11);
       if (ret >= 0) return ret;
     }
-  } else if (want_fast && !dbg && cert && n <= kSampleMaxN) {
+  } else if (want_fast && !temp_on && !dbg && cert && n <= kSampleMaxN) {
     if (tid < 64) {
       double e = 0.0;
       for (int i = tid; i < n; i += 64) e += (double)sm.p[i];
@@ -1276,7 +1403,8 @@ __device__ __attribute__((always_inline)) int sample_block(const SampleSmem& sm,
   if (want_fast) {
     const int nc = sm.ired[31];
     const float L = sm.fred[20];
-    if (sample_fast_ok(sum, L, nc, top_k)) return sample_fast<NT>(sm, nc, sum, top_p, top_k, key, draw, fixed42, dbg, stamps);
+    if (sample_fast_ok(sum, L, nc, top_k))
+      return sample_fast<NT>(sm, nc, sum, top_p, top_k, temp_on ? 1.0f / temperature : 0.0f, key, draw, fixed42, dbg, stamps);
   }
   if (sum > 0.0f)
     for (int i = tid; i < n; i += NT) sm.p[i] = sm.p[i] / sum;
@@ -1393,24 +1521,37 @@ __device__ __attribute__((always_inline)) int sample_block(const SampleSmem& sm,
   STAMP(6);
   // (4) top-p (:108-153)
   if (top_p < 1.0f) {
+    const uint32_t* vals = nullptr;  // set: the sorted probabilities as values (no keys)
     if (n_sorted < 0 || n_sorted > npos) {
       // survivors not yet sorted (or fewer positives than k): sort the positive ones
       if (npos > sm.cap) {
-        *status = RWKVTTS_EUNSUPPORTED;
-        return 0;
+        // more than the key region sorts. The cumulative below depends on the sorted VALUES alone
+        // (equal probabilities in any order give the same partial sums and the same cutoff), and
+        // an LDS row's keys, dscan and list regions, contiguous in carve(), hold kSampleMaxVals of
+        // them: dscan is dead after the exact sum, list is rebuilt by compact_positive below
+        if (!kValSort || sm.cap != kSampleMaxSorted || n > kSampleMaxVals) {
+          *status = RWKVTTS_EUNSUPPORTED;
+          return 0;
+        }
+        vals = (const uint32_t*)sm.keys;
+        uint32_t* vw = (uint32_t*)sm.keys;
+        for (int q = tid; q < n; q += NT) vw[q] = __builtin_bit_cast(uint32_t, sm.p[q]);  // p >= 0: bits order as values
+        __syncthreads();
+        sort_desc_u32<NT>(vw, n);
+      } else {
+        int M = 1;
+        while (M < npos) M <<= 1;
+        for (int q = tid; q < M; q += NT) sm.keys[q] = q < npos ? pkey(sm.p[sm.list[q]], sm.list[q]) : 0ull;
+        __syncthreads();
+        bitonic_desc<NT>(sm.keys, M);
       }
-      int M = 1;
-      while (M < npos) M <<= 1;
-      for (int q = tid; q < M; q += NT) sm.keys[q] = q < npos ? pkey(sm.p[sm.list[q]], sm.list[q]) : 0ull;
-      __syncthreads();
-      bitonic_desc<NT>(sm.keys, M);
     }
     if (tid < 64) {  // sequential cumulative in sorted order (wave-uniform, keys staged in lanes)
       float cum = 0.0f, cutoff = 0.0f;
       int found = 0;
       for (int q0 = 0; q0 < npos && !found; q0 += 64) {
         const bool in = q0 + tid < npos;
-        const float pv_l = in ? __builtin_bit_cast(float, (uint32_t)(sm.keys[q0 + tid] >> 32)) : 0.0f;
+        const float pv_l = in ? __builtin_bit_cast(float, vals ? vals[q0 + tid] : (uint32_t)(sm.keys[q0 + tid] >> 32)) : 0.0f;
         float tot;
         const float pre = prefix64(cum, pv_l, &tot);
         const uint64_t hit = __ballot(in && pre >= top_p);
@@ -1465,11 +1606,13 @@ __device__ __attribute__((always_inline)) int sample_block(const SampleSmem& sm,
   }
   STAMP(7);
   // (5) temperature (:156-171)
-  if (temperature != 1.0f && temperature > 0.0f) {
+  if (temp_on) {
     const float tinv = 1.0f / temperature;
+    const uint64_t* et = sm.etab;  // filled by the softmax step
+    auto tab = [et](int i) { return et[i]; };
     for (int i = tid; i < n; i += NT) {
       const float v = sm.p[i];
-      if (v > 0.0f) sm.p[i] = (float)exp2(log2((double)v) * (double)tinv);
+      if (v > 0.0f) sm.p[i] = glibc_powf_t(v, tinv, tab);
     }
     __syncthreads();
     npos = compact_positive<NT>(sm, n);
@@ -1847,6 +1990,7 @@ __device__ __attribute__((always_inline)) void advance_prep(const float* raw, co
   STAMP(10);
 }
 
+template <bool kParams>
 __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a, char* smem) {
   constexpr int NT = kSampleThreads;
   const int row = blockIdx.x;
@@ -1877,6 +2021,10 @@ __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a
   const SampleSmem sm = carve<NT>(smem, NS);
   const bool eos_masked = !glob && (c->fixed || (c->mode == 1 && c->n_sem < c->hard_min));
   const int n = glob ? 4096 : NS, top_k = glob ? c->top_k_g : c->top_k_s;
+  // the phase's temperature and top-p: the reference's (1.0, 0.95) as literals (k_advance: the
+  // sampler's temperature and top_p >= 1 branches fold away), or the slot's own (k_advance_params)
+  const float temp = !kParams ? 1.0f : (glob ? c->temp_g : c->temp_s);
+  const float top_p = !kParams ? 0.95f : (glob ? c->top_p_g : c->top_p_s);
   const uint32_t* key = glob ? c->gkey : c->skey;
   const uint64_t draw = glob ? c->gdraw : c->sdraw;
   // attempt 1 (zero-shot only): EOS drawn while the window rule does not stop the request ->
@@ -1887,7 +2035,7 @@ __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a
   for (int attempt = 0; attempt < 2; ++attempt) {
     if (glob) advance_prep<NT, 4096, PT>(raw, sm, false, top_k, key, draw + attempt, c->gblk, &c->gblk_id, stamps);
     else advance_prep<NT, NS, PT>(raw, sm, masked, top_k, key, draw + attempt, c->sblk, &c->sblk_id, stamps);
-    id = sample_block<NT>(sm, n, 1.0f, 0.95f, top_k, key, draw + attempt, false, nullptr, &status, stamps,
+    id = sample_block<NT, kParams>(sm, n, temp, top_p, top_k, key, draw + attempt, false, nullptr, &status, stamps,
                           a.cert != 0, true);
     used = attempt + 1;
     if (glob || id != RWKVTTS_EOS_TOKEN) break;
@@ -1935,15 +2083,23 @@ __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a
 __global__ __launch_bounds__(kSampleThreads, 2) void k_advance(AdvanceArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   tl_begin(a.tl);
-  advance_body(a, smem);
+  advance_body<false>(a, smem);
+  tl_end(a.tl);
+}
+// the same step for launches in which some slot has sampling parameters of its own
+__global__ __launch_bounds__(kSampleThreads, 2) void k_advance_params(AdvanceArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  tl_begin(a.tl);
+  advance_body<true>(a, smem);
   tl_end(a.tl);
 }
 
 int launch_advance(const AdvanceArgs& a0, hipStream_t st, int cert) {
   AdvanceArgs a = a0;
   a.cert = cert;  // 0: always walk the exact sequential sum (RWKVTTS_FORM_EXACT_SAMPLER)
-  RT_LAUNCH(k_advance, dim3(a.n_rows), dim3(kSampleThreads), smem_bytes<kSampleThreads>(RWKVTTS_EOS_TOKEN + 1),
-                     st, a);
+  const size_t lds = smem_bytes<kSampleThreads>(RWKVTTS_EOS_TOKEN + 1);
+  if (a.params) RT_LAUNCH(k_advance_params, dim3(a.n_rows), dim3(kSampleThreads), lds, st, a);
+  else RT_LAUNCH(k_advance, dim3(a.n_rows), dim3(kSampleThreads), lds, st, a);
   return a.n_rows;
 }
 

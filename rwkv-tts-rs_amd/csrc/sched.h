@@ -34,6 +34,9 @@ struct StepPlan {
   int head_rows = 0;
   bool tok_from_ctrl = false;  // decode: token = ctrl[slot].next_token
   bool advance = false;        // run the phase controller on the logits rows
+  // some active request samples with parameters of its own (Active::own_sampling): the step's
+  // controller reads every row's from its control block (AdvanceArgs::params)
+  bool sampling_params = false;
 };
 
 // A request decoding in a state slot.
@@ -45,6 +48,7 @@ struct Active {
   int advances = 0;  // phase-controller invocations so far
   int total = 0;     // advances after which the request is certainly done (its step limit)
   bool zero_shot = false;
+  bool own_sampling = false;  // Admission::own_sampling
   // token progress (Job::user): semantic tokens handed to the sink so far, and per unit buffer the
   // end of the range of this slot's d_sem_ that the unit copied to h_prog_
   const rwkvtts_token_sink* sink = nullptr;
@@ -86,6 +90,24 @@ inline bool validate(const rwkvtts_request& q, int n_vocab, std::string& why) {
     why = "model vocabulary too small for the TTS tags / global tokens";
     return false;
   }
+  if (q.sampling_set & ~(RWKVTTS_SAMPLING_GLOBAL | RWKVTTS_SAMPLING_SEMANTIC)) {
+    why = "sampling_set: unknown bits";
+    return false;
+  }
+  if (q.sampling_set && q.greedy) {
+    why = "greedy and sampling_set exclude each other";
+    return false;
+  }
+  auto phase_ok = [&](const rwkvtts_phase_sampling& s, const char* what) {
+    // (comparisons are false for NaN: a non-finite value fails its range)
+    if (!(s.temperature >= 0.1f && s.temperature <= 4.0f)) why = std::string(what) + ": temperature must be in [0.1, 4.0]";
+    else if (!(s.top_p >= 0.0f && s.top_p <= 1.0f)) why = std::string(what) + ": top_p must be in [0, 1]";
+    else if (s.top_k < 0) why = std::string(what) + ": top_k must be >= 0";
+    else return true;
+    return false;
+  };
+  if ((q.sampling_set & RWKVTTS_SAMPLING_GLOBAL) && !phase_ok(q.global_sampling, "global_sampling")) return false;
+  if ((q.sampling_set & RWKVTTS_SAMPLING_SEMANTIC) && !phase_ok(q.semantic_sampling, "semantic_sampling")) return false;
   return true;
 }
 
@@ -103,7 +125,17 @@ struct Admission {
   uint64_t gseed, sseed;  // the engine derives gkey / skey from them (StdRng::seed_from_u64)
   bool zero_shot;
   int total;             // Active::total
+  // a phase's temperature or top-p differs from the reference's (1.0, 0.95), or its top-k is
+  // outside the fast path's [1, kFastTopK]: steps with this request run the controller that reads
+  // the parameters from the control block and carries the general path for every top-k
+  bool own_sampling;
 };
+
+inline bool any_own_sampling(const std::vector<Active>& act) {
+  bool any = false;
+  for (const Active& a : act) any |= a.own_sampling;
+  return any;
+}
 
 // entropy: the seed of a request without one (dynamic_batch_manager.rs:491-499, from_entropy)
 inline Admission admission_of(const rwkvtts_request& q, uint64_t entropy) {
@@ -125,6 +157,20 @@ inline Admission admission_of(const rwkvtts_request& q, uint64_t entropy) {
   if (a.zero_shot && !indep) a.sseed = 0;  // StdRng::seed_from_u64(0) handed to the zero-shot path
   c.top_k_g = q.greedy ? 1 : 20;
   c.top_k_s = q.greedy ? 1 : 80;
+  c.temp_g = c.temp_s = 1.0f;  // normal_mode_inference.rs:114-127, unless the request sets a phase
+  c.top_p_g = c.top_p_s = 0.95f;
+  if (q.sampling_set & RWKVTTS_SAMPLING_GLOBAL) {
+    c.temp_g = q.global_sampling.temperature;
+    c.top_p_g = q.global_sampling.top_p;
+    c.top_k_g = q.global_sampling.top_k;
+  }
+  if (q.sampling_set & RWKVTTS_SAMPLING_SEMANTIC) {
+    c.temp_s = q.semantic_sampling.temperature;
+    c.top_p_s = q.semantic_sampling.top_p;
+    c.top_k_s = q.semantic_sampling.top_k;
+  }
+  a.own_sampling = c.temp_g != 1.0f || c.temp_s != 1.0f || c.top_p_g != 0.95f || c.top_p_s != 0.95f ||
+                   c.top_k_g < 1 || c.top_k_g > kFastTopK || c.top_k_s < 1 || c.top_k_s > kFastTopK;
   c.fixed = q.fixed_semantic > 0;
   c.sem_limit = sem_limit_of(q);
   if (a.zero_shot) {
@@ -209,6 +255,7 @@ inline StepPlan mixed_plan(std::vector<Active>& act, int chunk, int n_vocab) {
     budget -= take;
   }
   p.head_rows = head_rows_of(act, n_vocab);
+  p.sampling_params = any_own_sampling(act);
   for (Active& a : act) a.advances += !a.in_prompt();  // one advance per logits row
   return p;
 }
@@ -218,6 +265,7 @@ inline StepPlan decode_plan(const std::vector<Active>& act) {
   StepPlan p;
   p.tok_from_ctrl = true;
   p.advance = true;
+  p.sampling_params = any_own_sampling(act);
   for (const Active& a : act) append_decode_row(p, a.slot);
   return p;
 }

@@ -9,6 +9,11 @@ constexpr int kRowFirst = 1;  // row flags
 constexpr int kRowLast = 2;
 constexpr int kRowCtrl = 4;   // the row's token is its slot's SlotCtrl::next_token (decode)
 
+// largest top-k of the sampler's fast path (sampler.hip kFastK): a slot whose phases keep the
+// reference's (temperature 1.0, top_p 0.95) and a top-k in [1, kFastTopK] is served by k_advance
+// with the two values compiled in, any other by k_advance_params (sched.h Admission::own_sampling)
+constexpr int kFastTopK = 256;
+
 enum SlotPhase : int32_t { kPhGlobal = 0, kPhGFeed = 1, kPhSemantic = 2, kPhDone = 3 };
 
 // Per-slot control block living in device memory.
@@ -38,6 +43,11 @@ struct SlotCtrl {
   uint64_t sblk_id;
   uint32_t gblk[16];
   uint32_t sblk[16];
+  // Sampling parameters of the two phases (top_k_g / top_k_s above are their top-k; 0: no top-k).
+  // The reference fixes (1.0, 0.95) (normal_mode_inference.rs:114-127); a request may set others.
+  float temp_g, temp_s;
+  float top_p_g, top_p_s;
 };
+static_assert(sizeof(SlotCtrl) % 8 == 0, "control blocks are copied as an array; next_token is read at a 4-byte stride");
 
 }  // namespace rwkvtts

@@ -145,3 +145,8 @@ extern "C" void rwkvtts_rng_seed_from_u64(uint64_t state, rwkvtts_rng* r) {
 #include "exact_math.h"
 // Host self-test hook: the exact expf the GPU sampler runs (tests/test_expf_exact.py).
 extern "C" float rwkvtts_debug_expf(float x) { return rwkvtts::glibc_expf(x); }
+// Host self-test hook: the exact powf of the sampler's temperature step, out[i] = powf(x[i], y[i])
+// (tests/test_powf_exact.py).
+extern "C" void rwkvtts_debug_powf(const float* x, const float* y, int n, float* out) {
+  for (int i = 0; i < n; ++i) out[i] = rwkvtts::glibc_powf(x[i], y[i]);
+}

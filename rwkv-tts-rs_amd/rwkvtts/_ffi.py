@@ -84,6 +84,13 @@ class SampleArgs(ctypes.Structure):
                 ("top_k", ctypes.c_int32), ("forbid_token", ctypes.c_int32)]
 
 
+class PhaseSampling(ctypes.Structure):
+    _fields_ = [("temperature", ctypes.c_float), ("top_p", ctypes.c_float), ("top_k", ctypes.c_int32)]
+
+
+SAMPLING_GLOBAL, SAMPLING_SEMANTIC = 1, 2
+
+
 class Request(ctypes.Structure):
     _fields_ = [("text_tokens", ctypes.POINTER(ctypes.c_int32)), ("n_text", ctypes.c_int32),
                 ("property_tokens", ctypes.POINTER(ctypes.c_int32)), ("n_property", ctypes.c_int32),
@@ -93,7 +100,9 @@ class Request(ctypes.Structure):
                 ("max_tokens", ctypes.c_int32), ("fixed_semantic", ctypes.c_int32),
                 ("greedy", ctypes.c_int32), ("layered_set", ctypes.c_int32),
                 ("use_independent_seeds", ctypes.c_int32), ("global_seed_offset", ctypes.c_uint64),
-                ("semantic_seed_offset", ctypes.c_uint64)]
+                ("semantic_seed_offset", ctypes.c_uint64),
+                ("sampling_set", ctypes.c_int32), ("global_sampling", PhaseSampling),
+                ("semantic_sampling", PhaseSampling)]
 
 
 class Result(ctypes.Structure):
@@ -221,6 +230,9 @@ EXPORTS = {
     "rwkvtts_debug_advance": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p]),
+    "rwkvtts_debug_advance_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p]),
     "rwkvtts_profile_entry": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,
                                              ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]),
     "rwkvtts_codec_blob_bytes": (ctypes.c_int64, [ctypes.POINTER(CodecDims)]),

@@ -14,6 +14,10 @@ The same four entry points take `tempo` (no reference counterpart: the reference
 is the `speed` property token, which a cloned voice does not get): None / 1.0 leaves the PCM as it
 is; any other value in 0.25 .. 4.0 (above 1 is faster speech) stretches the 16 kHz PCM on the GPU
 without changing its pitch (audio.TimeStretcher), before any resampling, exact over stream chunks.
+LightweightTtsPipelineArgs.global_sampling / semantic_sampling (no reference counterpart: the
+reference carries temperature / top_p / top_k and samples with fixed values) set the token
+generator's temperature, top-p and top-k per phase (runtime.PhaseSampling); a value outside its
+range raises ValueError in the same four entry points before anything is generated.
 
 The voice store lookup by voice_id inside the pipeline (`VoiceFeatureManager::new("./raf")`,
 :751) goes through `voices.VoiceFeatureManager` on `raf_dir` (the server passes the
@@ -27,7 +31,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from .properties import convert_standard_properties_to_tokens
-from .runtime import LayeredRandomnessConfig, SamplerArgs, TtsBatchRequest
+from .runtime import LayeredRandomnessConfig, PhaseSampling, SamplerArgs, TtsBatchRequest
 
 SAMPLE_RATE = 16000
 
@@ -52,6 +56,23 @@ class LightweightTtsPipelineArgs:  # :18-65 (Default)
     voice_id: Optional[str] = None
     voice_global_tokens: Optional[List[int]] = None
     voice_semantic_tokens: Optional[List[int]] = None
+    # no reference counterpart: the sampling of the global / semantic phase (runtime.PhaseSampling;
+    # None: the reference's fixed (1.0, 0.95, 20 | 80)). temperature / top_p / top_k above stay
+    # ignored, as in the reference.
+    global_sampling: Optional[PhaseSampling] = None
+    semantic_sampling: Optional[PhaseSampling] = None
+
+
+def check_sampling(args) -> None:
+    """ValueError for a global_sampling / semantic_sampling (of pipeline args or SamplerArgs) outside
+    the engine's ranges, before anything is generated."""
+    for what in ("global_sampling", "semantic_sampling"):
+        ph = getattr(args, what, None)
+        if ph is None:
+            continue
+        if not isinstance(ph, PhaseSampling):
+            raise ValueError(f"{what} must be a PhaseSampling")
+        ph.check(what)
 
 
 class SpeechChunk(np.ndarray):
@@ -188,7 +209,8 @@ class LightweightTtsPipeline:
         props, rg, rs = self._prompt_parts(args)
         sargs = SamplerArgs(temperature=args.temperature, top_p=args.top_p, top_k=args.top_k,
                             max_tokens=args.max_tokens, seed=args.seed, voice_fidelity=0.8,
-                            layered_randomness=LayeredRandomnessConfig(), token_chunk_size=512)
+                            layered_randomness=LayeredRandomnessConfig(), token_chunk_size=512,
+                            global_sampling=args.global_sampling, semantic_sampling=args.semantic_sampling)
         return TtsBatchRequest(self.manager._tokens(text), props, rg, rs, sargs, args.voice_id)
 
     def generate_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
@@ -196,7 +218,9 @@ class LightweightTtsPipeline:
         """sample_rate None / 16000: the vocoder's 16 kHz PCM. Any other rate: that PCM resampled on
         the GPU (resampler()); the failed-request second of silence is sample_rate zeros.
         tempo None / 1.0: nothing. Any other: the 16 kHz PCM time-stretched on the GPU (stretcher())
-        before the resampler; the failed-request second of silence is not stretched."""
+        before the resampler; the failed-request second of silence is not stretched.
+        args.global_sampling / semantic_sampling outside their ranges raise ValueError, like tempo."""
+        check_sampling(args)
         stages, rate = self._stages(sample_rate, tempo)
         try:
             req = self._request(args)
@@ -235,6 +259,7 @@ class LightweightTtsPipeline:
         sinc_len / 2 = 128 input samples of look-ahead. t0, t1 and n_known stay in frames."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
+        check_sampling(args)
         try:
             req = self._request(args)
         except ValueError:  # untokenisable text: the request fails -> one second of silence
@@ -247,6 +272,8 @@ class LightweightTtsPipeline:
         was submitted)."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
+        if req is not None:
+            check_sampling(req.args)
         stages, rate = self._stages(sample_rate, tempo)
         streams = [stream() for _, stream in stages]
         H = self.codec.halo()
@@ -285,6 +312,8 @@ class LightweightTtsPipeline:
         """sample_rate other than None / 16000: the whole batch is resampled in one resample_batch
         call (a failed item stays an empty array). tempo other than None / 1.0: the whole batch is
         first stretched in one stretch_batch call, one tempo for the call."""
+        for a in batch_args:
+            check_sampling(a)
         stages, _ = self._stages(sample_rate, tempo)
         reqs, idx = [], []
         for i, a in enumerate(batch_args):

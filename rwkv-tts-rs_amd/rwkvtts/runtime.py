@@ -106,6 +106,15 @@ def request_struct(r: "TtsBatchRequest"):
     q.use_independent_seeds = 1 if lr.use_independent_seeds else 0
     q.global_seed_offset = int(lr.global_seed_offset) & 0xFFFFFFFFFFFFFFFF
     q.semantic_seed_offset = int(lr.semantic_seed_offset) & 0xFFFFFFFFFFFFFFFF
+    q.sampling_set = 0
+    for bit, ph, dst, k_default in ((_ffi.SAMPLING_GLOBAL, r.args.global_sampling, q.global_sampling, 20),
+                                    (_ffi.SAMPLING_SEMANTIC, r.args.semantic_sampling, q.semantic_sampling, 80)):
+        if ph is None:
+            continue
+        q.sampling_set |= bit
+        dst.temperature = float(ph.temperature)
+        dst.top_p = float(ph.top_p)
+        dst.top_k = k_default if ph.top_k is None else int(ph.top_k)
     return q, keep
 
 
@@ -374,7 +383,31 @@ class LayeredRandomnessConfig:  # src/rwkv_sampler.rs:251-275
 
 
 @dataclasses.dataclass
+class PhaseSampling:
+    """Sampling parameters of one phase (global or semantic tokens) of a request. temperature in
+    [0.1, 4.0], top_p in [0, 1] (1: no top-p), top_k >= 0 (0: no top-k; None: the phase's own 20
+    global / 80 semantic). No reference counterpart: the reference fixes (1.0, 0.95, 20 | 80)."""
+    temperature: float = 1.0
+    top_p: float = 0.95
+    top_k: Optional[int] = None
+
+    def check(self, what: str = "sampling") -> "PhaseSampling":
+        """Raises ValueError for a value the engine would refuse (sched.h validate)."""
+        t, p, k = self.temperature, self.top_p, self.top_k
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not 0.1 <= t <= 4.0:
+            raise ValueError(f"{what}: temperature must be a number in [0.1, 4.0]")
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
+            raise ValueError(f"{what}: top_p must be a number in [0, 1]")
+        if k is not None and (isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < 2 ** 31):
+            raise ValueError(f"{what}: top_k must be an integer >= 0")
+        return self
+
+
+@dataclasses.dataclass
 class SamplerArgs:  # src/rwkv_sampler.rs:234-290
+    """temperature, top_p and top_k are carried and ignored, as in the reference
+    (normal_mode_inference.rs:114-127 fixes the parameters per phase). global_sampling /
+    semantic_sampling (None: the reference's values) are what the decode step honours."""
     temperature: float = 1.0
     top_p: float = 0.85
     top_k: int = 0
@@ -383,6 +416,8 @@ class SamplerArgs:  # src/rwkv_sampler.rs:234-290
     voice_fidelity: float = 0.8
     layered_randomness: LayeredRandomnessConfig = dataclasses.field(default_factory=LayeredRandomnessConfig)
     token_chunk_size: int = 512
+    global_sampling: Optional[PhaseSampling] = None
+    semantic_sampling: Optional[PhaseSampling] = None
 
 
 @dataclasses.dataclass

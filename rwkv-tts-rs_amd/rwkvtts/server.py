@@ -25,6 +25,12 @@
   continuous rate applied to the finished 16 kHz PCM by a pitch-preserving time stretch on the GPU
   (audio.TimeStretcher), before any resampling, and works for every voice. Without the field (or
   with 1.0) the routes are unchanged.
+* `global_sampling` / `semantic_sampling` in the body of both TTS routes (no reference
+  counterpart): each an object with any of `temperature` (0.1 .. 4.0), `top_p` (0 .. 1) and `top_k`
+  (an integer >= 0, 0: no top-k) for that phase of the token generator (runtime.PhaseSampling; a
+  key left out keeps the phase's own 1.0 / 0.95 / 20 global, 80 semantic); anything else a 400. The
+  top-level `temperature` and `top_p` keep doing nothing, as in the reference, which parses them
+  and then samples with fixed values (normal_mode_inference.rs:114-127).
 * `handle_tts_stream(body, pipeline, voice_dir)` (no reference counterpart): the same request as a
   WAV stream, POST /api/tts/stream -- audio while the request is still decoding, at a fixed scale
   (no peak normalisation: that needs the whole utterance).
@@ -39,6 +45,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from .pipeline import LightweightTtsPipelineArgs
+from .runtime import PhaseSampling
 
 
 def convert_samples_to_wav(samples, sample_rate: int = 16000) -> bytes:
@@ -146,6 +153,17 @@ def _tts_args(body, voice_dir: str):
           or not TEMPO_MIN <= tempo <= TEMPO_MAX):  # (NaN fails the comparison)
         return (400, {"success": False, "error": f"不支持的语速倍率: {tempo} (支持: "
                                                  f"{TEMPO_MIN} - {TEMPO_MAX})"}), None, None
+    sampling = {}
+    for what in ("global_sampling", "semantic_sampling"):
+        o = body.get(what)
+        if o is None:
+            continue
+        try:
+            if not isinstance(o, dict) or set(o) - {"temperature", "top_p", "top_k"}:
+                raise ValueError(f"{what}: an object with any of temperature, top_p, top_k")
+            sampling[what] = PhaseSampling(**{k: v for k, v in o.items() if v is not None}).check(what)
+        except ValueError as e:
+            return (400, {"success": False, "error": f"不支持的采样参数: {e}"}), None, None
     voice_id = body.get("voice_id")
     voice = None
     prompt_from_voice = None
@@ -165,7 +183,7 @@ def _tts_args(body, voice_dir: str):
         emotion=body.get("emotion") or "NEUTRAL", pitch=map_pitch(body.get("pitch")),
         speed=map_speed(body.get("speed")), prompt_text=prompt_text,
         voice_global_tokens=list(voice["global_tokens"]) if voice else None,
-        voice_semantic_tokens=list(voice["semantic_tokens"]) if voice else None)
+        voice_semantic_tokens=list(voice["semantic_tokens"]) if voice else None, **sampling)
     kw = {}
     if rate != 16000:
         kw["sample_rate"] = rate

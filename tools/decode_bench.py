@@ -1,6 +1,9 @@
 """Decode-loop microbenchmark: 32 requests (0.4B synthetic bf16), fixed S semantic tokens, graph
 replay. Prints decode ms/step from the engine's own HIP events and a token checksum (a kernel
-change that keeps the arithmetic must keep the checksum). Usage: decode_bench.py [S] [reps].
+change that keeps the arithmetic must keep the checksum). Usage: decode_bench.py [S] [reps]
+[--temperature T] [--top-p P] [--top-k K] [--sampling-slots N]: the semantic phase's sampling
+parameters (runtime.PhaseSampling; an option left out keeps the phase's own value) for the first N
+requests (default: all of them); without any of the three, no request carries parameters.
 Env: DB_B requests (default 32), DB_F16=1 fp16 weights, DB_ZS=1 zero-shot prompts (32 reference
 global tokens + 128 reference semantic tokens per request), DB_QUANT=int8|nf4 (every layer quantised,
 the server's --quant-layers 24 --quant-type ...), DB_FORMS=n (rwkvtts_engine_desc.forms: RWKVTTS_FORM_* bits)."""
@@ -14,8 +17,20 @@ sys.path.insert(0, os.path.join(ROOT, "rwkv-tts-rs_amd"))
 import rwkvtts  # noqa: E402
 from rwkvtts import weights as W  # noqa: E402
 
-S = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-reps = int(sys.argv[2]) if len(sys.argv) > 2 else 2
+import argparse  # noqa: E402
+ap = argparse.ArgumentParser()
+ap.add_argument("S", nargs="?", type=int, default=64)
+ap.add_argument("reps", nargs="?", type=int, default=2)
+ap.add_argument("--temperature", type=float, default=None)
+ap.add_argument("--top-p", type=float, default=None)
+ap.add_argument("--top-k", type=int, default=None)
+ap.add_argument("--sampling-slots", type=int, default=None)
+opt = ap.parse_args()
+S, reps = opt.S, opt.reps
+sampling = None
+if opt.temperature is not None or opt.top_p is not None or opt.top_k is not None:
+    sampling = rwkvtts.PhaseSampling(**{k: v for k, v in (("temperature", opt.temperature), ("top_p", opt.top_p),
+                                                           ("top_k", opt.top_k)) if v is not None}).check("semantic")
 f16 = os.environ.get("DB_F16", "0") == "1"
 B = int(os.environ.get("DB_B", "32"))
 zs = os.environ.get("DB_ZS", "0") == "1"
@@ -36,6 +51,8 @@ for i in range(B):
     reqs.append(rwkvtts.TtsBatchRequest(text_tokens=rs.randint(12293, 77822, size=24).tolist(),
                                         property_tokens=[] if zs else [77823, 77838, 77869, 77845, 77830, 77826],
                                         args=rwkvtts.SamplerArgs(seed=i), fixed_semantic=S, **ref))
+    if sampling is not None and i < (B if opt.sampling_slots is None else opt.sampling_slots):
+        reqs[-1].args.semantic_sampling = sampling
 for r in range(reps):
     t0 = time.perf_counter()
     out = rt.generate_batch(reqs)
@@ -43,7 +60,7 @@ for r in range(reps):
     st = rt.stats()
     h = hashlib.sha1(repr(out).encode()).hexdigest()[:12]
     us = st['decode_ms'] / max(st['steps'], 1) * 1000
-    print(f"rep {r}: B={B} f16={int(f16)} zs={int(zs)} quant={qt} decode {us:.1f} us/step over {st['steps']} steps "
+    print(f"rep {r}: B={B} f16={int(f16)} zs={int(zs)} quant={qt} sampling={sampling} decode {us:.1f} us/step over {st['steps']} steps "
           f"({B * 320 / us * 1e6:.0f} samples/s decode-only), "
           f"prefill {st['prefill_ms']:.2f} ms, wall {wall * 1000:.1f} ms, tokens {h}", flush=True)
 rt.close()
