@@ -285,6 +285,17 @@ typedef struct {
    * covers powf); top_k 0 or > 256 takes the general path (a sort over the row). */
   int32_t sampling_set;
   rwkvtts_phase_sampling global_sampling, semantic_sampling;
+  /* Pinned voice (no reference counterpart: a normal-mode request of the reference always samples
+   * its own 32 global tokens). 1: ref_global holds exactly RWKVTTS_N_GLOBAL ids in [0, 4096) and
+   * ref_semantic is NULL; anything else fails the request alone (RWKVTTS_EINVAL). The request is
+   * normal mode with the global phase replaced by the given tokens: its prompt is property
+   * tokens, TAG_2, text, TAG_0, g_0 + 8196 .. g_31 + 8196, TAG_1 -- what a normal request feeds
+   * itself while decoding (normal_mode_inference.rs:277-278) -- the property tokens are kept, EOS
+   * ends it (no hard minimum, no window, no re-draw), the semantic stream is seeded as for a normal
+   * request and the global stream is unused. So a pinned request with the globals G a normal
+   * request sampled returns that request's (G, S), bit for bit. max_tokens == 0 (without
+   * fixed_semantic) gives status 0, the 32 globals and no semantic tokens. 0: as before. */
+  int32_t pinned_voice;
 } rwkvtts_request;
 #define RWKVTTS_SAMPLING_GLOBAL 1
 #define RWKVTTS_SAMPLING_SEMANTIC 2
@@ -700,6 +711,66 @@ typedef struct {
 int rwkvtts_tsm_windows(rwkvtts_tsm* t, rwkvtts_tsm_window_t* w, int n);
 /* HIP-event time of the last launch pair (both kernels, no copies), in ms; 0 before the first. */
 int rwkvtts_tsm_kernel_ms(rwkvtts_tsm* t, double* ms);
+
+/* ---- join: the PCM of a long text's segments into one signal, each segment's silent edges cut to
+ * a kept margin and faded, a controlled pause after it, on the GPU (no reference counterpart: the
+ * reference synthesises one request per text and stops at 2048 semantic tokens) ------------------
+ * Rate-agnostic; the pipeline applies it to the vocoder's 16 kHz PCM, before the stretch and the
+ * resampler. The arithmetic contract (integer bounds, one rounded f32 multiply per faded sample,
+ * every other sample a copy):
+ *   desc      threshold (f32, finite, >= 0; 0 = 0.01, the reference's silence_threshold), keep
+ *             (samples, >= 0), fade (samples, 0 .. 4096), trim (0 or 1)
+ *   job       n_seg segments x_s[0, n_s), each followed by gap_s >= 0 zero samples; n_s == 0 allowed
+ *   bounds    trim == 0: a_s = 0, b_s = n_s, no fades. trim == 1: a sample is loud iff
+ *             fabsf(x) > threshold (false for NaN); no loud sample: a_s = b_s = 0 (an empty piece);
+ *             otherwise, lo and hi the first and last loud index, a_s = max(0, lo - keep) and
+ *             b_s = min(n_s, hi + 1 + keep): integers, whatever the reduction tree
+ *   ramp      r[k] = (float)((k + 0.5) / fade), in double, k in [0, fade)
+ *   piece     (trim == 1) len_s = b_s - a_s, f_s = min(fade, len_s / 2); p[i] = x[a_s + i] * r[i]
+ *             for i < f_s, p[i] = x[a_s + i] * r[len_s - 1 - i] for i >= len_s - f_s (one rounded
+ *             f32 multiply each), every other sample x[a_s + i] bit for bit. Both edges fade whether
+ *             or not a cut was made there. trim == 0: the piece is the segment.
+ *   layout    off_0 = 0, off_{s+1} = off_s + len_s + gap_s (64-bit); the piece at off_s, then gap_s
+ *             samples of +0.0f; n_out = off_{n_seg}
+ * A piece depends on its own segment only, so the join of a job equals the joins of its segments
+ * one by one, back to back, bitwise: a stream may emit segment by segment. */
+typedef struct {
+  uint32_t struct_size;
+  float threshold;
+  int32_t keep;
+  int32_t fade;
+  int32_t trim;
+} rwkvtts_join_desc;
+/* The ramp table (host only): out[fade] (nothing is written for fade 0). Anything outside the
+ * ranges above (a NaN or infinite threshold included) is RWKVTTS_EINVAL, here and in every call
+ * that takes a desc. */
+int rwkvtts_join_ramp(const rwkvtts_join_desc* desc, float* out);
+/* sum n_s + sum gap_s: the capacity of a job's output, reached when nothing is cut (host only);
+ * -1 for a negative length or gap, n_seg outside 0 .. 4096 or a segment above 2^30 samples. */
+int64_t rwkvtts_join_capacity(const int64_t* n, const int64_t* gap, int32_t n_seg);
+typedef struct rwkvtts_join rwkvtts_join;
+/* table == NULL: the ramp of rwkvtts_join_ramp; otherwise the caller's [fade] table (copied). */
+int rwkvtts_join_create(int device, const rwkvtts_join_desc* desc, const float* table, rwkvtts_join** out);
+int rwkvtts_join_destroy(rwkvtts_join* j);
+typedef struct {
+  uint32_t struct_size;
+  int32_t n_seg;            /* 0 .. 4096 */
+  const float* const* seg;  /* [n_seg] host pointers (NULL allowed where n is 0) */
+  const int64_t* n;         /* [n_seg] samples per segment, each 0 .. 2^30 */
+  const int64_t* gap;       /* [n_seg] zero samples after each segment */
+  float* out;               /* capacity rwkvtts_join_capacity(n, gap, n_seg); [n_out, capacity) is +0 */
+  int64_t* a;               /* out: [n_seg] a_s (NULL: not wanted) */
+  int64_t* b;               /* out: [n_seg] b_s (NULL: not wanted) */
+  int64_t n_out;            /* out */
+} rwkvtts_join_job;
+/* n jobs (1 .. 1024, ragged) in one pass of three launches -- bounds (per-segment integer min / max
+ * over workgroups; not launched for trim 0), layout (the prefix over a job's segments), write (a
+ * lane per output sample: copy, fade or zero). Host buffers. n_out and every (a_s, b_s) are read
+ * back before the call's one synchronisation. Nothing is launched and nothing written unless every
+ * job passes the checks above. Calls on one handle serialise on its lock. */
+int rwkvtts_join_jobs(rwkvtts_join* j, rwkvtts_join_job* jobs, int n);
+/* HIP-event time of the last call's kernels (no copies), in ms; 0 before the first. */
+int rwkvtts_join_kernel_ms(rwkvtts_join* j, double* ms);
 
 #ifdef __cplusplus
 }

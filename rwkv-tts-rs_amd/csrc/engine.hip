@@ -1307,6 +1307,13 @@ int Engine::admit(ServeState& st, Job* j) {
     fail_job(st.src, j, RWKVTTS_EINVAL, 0);
     return RWKVTTS_OK;
   }
+  if (pinned_without_tokens(q)) {  // nothing to decode: the given voice, no semantic tokens, no slot
+    j->res->n_global = RWKVTTS_N_GLOBAL;
+    memcpy(j->res->global_tokens, q.ref_global, sizeof(int32_t) * RWKVTTS_N_GLOBAL);
+    if (const rwkvtts_token_sink* s = sink_of(j)) s->fn(s->user, q.ref_global, RWKVTTS_N_GLOBAL, nullptr, 0, 0, 1, 0);
+    st.src.finish(j);
+    return RWKVTTS_OK;
+  }
   if (sink_of(j) && !h_prog_)
     RT_HIP(hipHostMalloc((void**)&h_prog_, sizeof(int32_t) * 2 * (size_t)S_ * RWKVTTS_SEMANTIC_LIMIT,
                          hipHostMallocDefault));
@@ -1335,6 +1342,7 @@ int Engine::admit(ServeState& st, Job* j) {
   a.slot = slot;
   a.sink = sink_of(j);
   a.zero_shot = ad.zero_shot;
+  a.pinned = ad.pinned;
   a.own_sampling = ad.own_sampling;
   a.prompt = std::move(ad.prompt);
   a.total = ad.total;

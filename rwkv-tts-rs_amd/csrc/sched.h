@@ -48,6 +48,7 @@ struct Active {
   int advances = 0;  // phase-controller invocations so far
   int total = 0;     // advances after which the request is certainly done (its step limit)
   bool zero_shot = false;
+  bool pinned = false;        // Admission::pinned: normal mode, the 32 global tokens given
   bool own_sampling = false;  // Admission::own_sampling
   // token progress (Job::user): semantic tokens handed to the sink so far, and per unit buffer the
   // end of the range of this slot's d_sem_ that the unit copied to h_prog_
@@ -58,6 +59,8 @@ struct Active {
 };
 
 inline bool is_zero_shot(const rwkvtts_request& q) { return q.ref_global != nullptr && q.ref_semantic != nullptr; }
+// pinned voice: a normal-mode request whose global phase is replaced by the 32 ids of ref_global
+inline bool is_pinned(const rwkvtts_request& q) { return q.pinned_voice != 0; }
 
 // Checks a request before admission; fills `why` and returns false for a bad one.
 inline bool validate(const rwkvtts_request& q, int n_vocab, std::string& why) {
@@ -83,6 +86,14 @@ inline bool validate(const rwkvtts_request& q, int n_vocab, std::string& why) {
   if (q.max_tokens < 0 || q.fixed_semantic < 0) {
     why = "max_tokens / fixed_semantic must be >= 0";
     return false;
+  }
+  if (q.pinned_voice != 0) {
+    if (q.pinned_voice != 1) why = "pinned_voice must be 0 or 1";
+    else if (q.ref_semantic) why = "pinned_voice: ref_semantic must be NULL";
+    else if (!q.ref_global || q.n_ref_global != RWKVTTS_N_GLOBAL)
+      why = "pinned_voice: ref_global must hold exactly " + std::to_string(RWKVTTS_N_GLOBAL) + " ids";
+    else if (!ids_ok(q.ref_global, q.n_ref_global, 0, 4096, "pinned_voice: ref_global")) return false;
+    if (!why.empty()) return false;
   }
   const bool zero_shot = is_zero_shot(q);
   if (V <= RWKVTTS_TAG_2 || (!zero_shot && V <= RWKVTTS_GLOBAL_TOKEN_OFFSET + 4095) ||
@@ -118,12 +129,17 @@ inline int sem_limit_of(const rwkvtts_request& q) {
   return std::min(std::max(q.max_tokens, 0), RWKVTTS_SEMANTIC_LIMIT);  // normal_mode_inference.rs:316
 }
 
+// A valid pinned request that emits nothing (max_tokens == 0 without fixed_semantic): it ends at
+// admission with status 0, its 32 global tokens and no semantic tokens, and takes no state slot.
+inline bool pinned_without_tokens(const rwkvtts_request& q) { return is_pinned(q) && sem_limit_of(q) == 0; }
+
 // What admission derives from the request alone.
 struct Admission {
   std::vector<uint32_t> prompt;
   SlotCtrl ctrl;         // the slot's initial control block, gkey / skey still zero
   uint64_t gseed, sseed;  // the engine derives gkey / skey from them (StdRng::seed_from_u64)
   bool zero_shot;
+  bool pinned;           // is_pinned: decodes as normal mode from its first logits row on
   int total;             // Active::total
   // a phase's temperature or top-p differs from the reference's (1.0, 0.95), or its top-k is
   // outside the fast path's [1, kFastTopK]: steps with this request run the controller that reads
@@ -141,6 +157,7 @@ inline bool any_own_sampling(const std::vector<Active>& act) {
 inline Admission admission_of(const rwkvtts_request& q, uint64_t entropy) {
   Admission a;
   a.zero_shot = is_zero_shot(q);
+  a.pinned = is_pinned(q);
   for (int i = 0; i < q.n_property; ++i) a.prompt.push_back((uint32_t)q.property_tokens[i]);
   a.prompt.push_back(RWKVTTS_TAG_2);
   for (int i = 0; i < q.n_text; ++i) a.prompt.push_back((uint32_t)q.text_tokens[i]);
@@ -188,6 +205,19 @@ inline Admission admission_of(const rwkvtts_request& q, uint64_t entropy) {
     const int upper = (int)floorf((float)RWKVTTS_SEMANTIC_LIMIT * 0.9f);
     c.hard_min = std::min(upper, std::max(min_sem, est));
     a.total = std::max(c.sem_limit, 1);
+  } else if (a.pinned) {
+    // what a normal request has fed itself when its semantic phase starts (kPhGFeed, then TAG_1,
+    // normal_mode_inference.rs:277-278): mode 0 stops at EOS, the semantic draw counter starts at
+    // 0 as it does there, the global stream is never drawn from. sem_limit == 0 is not admitted
+    // (pinned_without_tokens): the first logits row would emit a token.
+    c.mode = 0;
+    c.phase = kPhSemantic;
+    for (int i = 0; i < RWKVTTS_N_GLOBAL; ++i) {
+      a.prompt.push_back((uint32_t)(q.ref_global[i] + RWKVTTS_GLOBAL_TOKEN_OFFSET));
+      c.global_out[c.n_global++] = q.ref_global[i];
+    }
+    a.prompt.push_back(RWKVTTS_TAG_1);
+    a.total = c.sem_limit;
   } else {
     c.mode = 0;
     c.phase = kPhGlobal;
@@ -226,11 +256,12 @@ inline void append_token_rows(StepPlan& p, int slot, const uint32_t* tok, int ta
 
 // Head rows of a step: 4096 while every slot that gets a logits row (its prompt is in) samples
 // global tokens (normal_mode_inference.rs:236-240: from [0, 4096)) or feeds g31, else 8193 (:332:
-// semantic ids from [0, 8192]). Evaluated before the step's advances are counted.
+// semantic ids from [0, 8192]; a zero-shot or pinned slot from its first logits row on).
+// Evaluated before the step's advances are counted.
 inline int head_rows_of(const std::vector<Active>& act, int n_vocab) {
   bool all_global = true;
   for (const Active& a : act)
-    if (!a.in_prompt()) all_global &= !a.zero_shot && a.advances <= RWKVTTS_N_GLOBAL;
+    if (!a.in_prompt()) all_global &= !a.zero_shot && !a.pinned && a.advances <= RWKVTTS_N_GLOBAL;
   return std::min(all_global ? 4096 : 8193, n_vocab);
 }
 

@@ -12,3 +12,7 @@ from . import weights  # noqa: F401
 # DynamicBatchManager.stream_tts, LightweightTtsPipeline.stream_speech, server.handle_tts_stream
 from .codec import BiCodecDetokenizer, codec_halo, window_plan  # noqa: F401
 from .pipeline import LightweightTtsPipeline, LightweightTtsPipelineArgs, SpeechChunk  # noqa: F401
+# long-form synthesis: TtsBatchRequest.pinned_voice, segment.split_text, audio.Joiner,
+# LightweightTtsPipeline.generate_long_speech / stream_long_speech, long_form in the HTTP bodies
+from .pipeline import LongSpeech  # noqa: F401
+from .segment import Pauses, Segment, split_text  # noqa: F401

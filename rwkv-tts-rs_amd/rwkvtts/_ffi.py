@@ -102,7 +102,7 @@ class Request(ctypes.Structure):
                 ("use_independent_seeds", ctypes.c_int32), ("global_seed_offset", ctypes.c_uint64),
                 ("semantic_seed_offset", ctypes.c_uint64),
                 ("sampling_set", ctypes.c_int32), ("global_sampling", PhaseSampling),
-                ("semantic_sampling", PhaseSampling)]
+                ("semantic_sampling", PhaseSampling), ("pinned_voice", ctypes.c_int32)]
 
 
 class Result(ctypes.Structure):
@@ -185,6 +185,17 @@ class TsmWindow(ctypes.Structure):
                 ("n_in", ctypes.c_int64), ("final", ctypes.c_int32), ("tempo", ctypes.c_double),
                 ("block_first", ctypes.c_int64), ("s_prev", ctypes.c_int64), ("out_count", ctypes.c_int64),
                 ("out", ctypes.c_void_p), ("s_last", ctypes.c_int64)]
+
+
+class JoinDesc(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("threshold", ctypes.c_float), ("keep", ctypes.c_int32),
+                ("fade", ctypes.c_int32), ("trim", ctypes.c_int32)]
+
+
+class JoinJob(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_seg", ctypes.c_int32), ("seg", ctypes.c_void_p),
+                ("n", ctypes.c_void_p), ("gap", ctypes.c_void_p), ("out", ctypes.c_void_p), ("a", ctypes.c_void_p),
+                ("b", ctypes.c_void_p), ("n_out", ctypes.c_int64)]
 
 
 # Every symbol include/rwkvtts.h declares (checked by tests/test_abi.py against the header).
@@ -292,6 +303,14 @@ EXPORTS = {
                                          ctypes.c_int, ctypes.c_void_p]),
     "rwkvtts_tsm_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TsmWindow), ctypes.c_int]),
     "rwkvtts_tsm_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    # join: ramp and capacity (host only), ragged jobs of segments in one pass
+    "rwkvtts_join_ramp": (ctypes.c_int, [ctypes.POINTER(JoinDesc), ctypes.c_void_p]),
+    "rwkvtts_join_capacity": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
+    "rwkvtts_join_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(JoinDesc), ctypes.c_void_p,
+                                           ctypes.POINTER(ctypes.c_void_p)]),
+    "rwkvtts_join_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "rwkvtts_join_jobs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(JoinJob), ctypes.c_int]),
+    "rwkvtts_join_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None

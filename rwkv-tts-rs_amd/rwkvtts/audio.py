@@ -24,6 +24,11 @@ and the clip / silence helpers it uses), feeding the HIP mel kernel (features.py
   one-shot, batched with a tempo per signal, and exact over stream chunks. Its arithmetic contract
   (include/rwkvtts.h) has no division and no square root; the kernels are pinned
   bitwise to its numpy restatement (tests/tsm_ref.py).
+* `Joiner` (no reference counterpart: the reference synthesises one request per text): the PCM of a
+  long text's segments joined into one signal as HIP kernels (csrc/join.hip) -- silent edges cut to a
+  kept margin and faded, a pause of zeros after each segment. Integer bounds, one rounded multiply per
+  faded sample, every other sample copied (include/rwkvtts.h); pinned bitwise to its
+  numpy restatement (tests/join_ref.py).
 """
 import ctypes
 import struct
@@ -455,6 +460,85 @@ class TimeStretchStream(_ExactStream):
 
     def _first_needed(self, n_known):
         return self.t.plan(self.tempo, n_known, False, self._block_next, self._s_prev)[1]
+
+
+# ---- join on the GPU -------------------------------------------------------------------------
+def _join_ramp(fade: int) -> np.ndarray:
+    """r[k] = (float)((k + 0.5) / fade), in double: the table both sides read."""
+    return ((np.arange(fade, dtype=np.float64) + 0.5) / float(max(fade, 1))).astype(F32)
+
+
+class Joiner(_NativeStage):
+    """The PCM of a long text's segments joined into one signal as HIP kernels (csrc/join.hip; the
+    arithmetic contract is in include/rwkvtts.h): with trim, each segment is cut to
+    `keep` samples around its first and last sample above `threshold` and both its edges are faded
+    over `fade` samples; a gap of zeros follows each segment. Rate-agnostic: the pipeline applies it
+    at 16 kHz, before the stretch and the resampler. A piece depends on its own segment only, so the
+    join of a job is bitwise the joins of its segments one by one, back to back.
+
+    threshold (finite, >= 0; 0 means the default 0.01 as in the C desc), keep >= 0, fade 0 .. 4096.
+    The kernels read the table `_join_ramp` builds, so both sides read one table.
+
+    evaluator: a callable (joiner, jobs) -> [(ndarray, [(a, b)])] standing in for the native call,
+    jobs being [([segment], [gap])]; no GPU object is created then."""
+    _NAME = "join"
+
+    def __init__(self, device: int = 0, threshold: float = 0.01, keep: int = 800, fade: int = 80, trim: bool = True,
+                 evaluator=None):
+        self.device = int(device)
+        self._desc = _ffi.JoinDesc(struct_size=ctypes.sizeof(_ffi.JoinDesc), threshold=float(threshold),
+                                   keep=int(keep), fade=int(fade), trim=1 if trim else 0)
+        super().__init__(evaluator)
+        self.keep, self.fade, self.trim = int(keep), int(fade), bool(trim)
+        self.threshold = float(F32(threshold)) or float(F32(0.01))
+        probe = np.zeros(max(self.fade, 1) if 0 <= self.fade <= 4096 else 1, dtype=F32)
+        _native("join_ramp", ctypes.byref(self._desc), probe.ctypes.data_as(ctypes.c_void_p))  # (refuses a bad description)
+        self.table = _join_ramp(self.fade)
+        self._create(self.table if self.fade else np.zeros(1, dtype=F32))
+
+    @staticmethod
+    def capacity(lengths, gaps) -> int:
+        """sum n_s + sum gap_s (rwkvtts_join_capacity)."""
+        n = np.ascontiguousarray(lengths, dtype=np.int64)
+        g = np.ascontiguousarray(gaps, dtype=np.int64)
+        if n.size != g.size:
+            raise ValueError("join: one gap per segment")
+        cap = int(_ffi.lib().rwkvtts_join_capacity(n.ctypes.data_as(ctypes.c_void_p), g.ctypes.data_as(ctypes.c_void_p),
+                                                   int(n.size)))
+        if cap < 0:
+            raise _ffi.RwkvTtsError(_ffi.EINVAL, "join_capacity")
+        return cap
+
+    def join_batch(self, jobs) -> list:
+        """[([segment], [gap])] -> [(joined PCM, [(a_s, b_s)])], ragged, all jobs in one pass."""
+        jobs = [([np.ascontiguousarray(x, dtype=F32).reshape(-1) for x in segs], [int(g) for g in gaps])
+                for segs, gaps in jobs]
+        for segs, gaps in jobs:
+            if len(segs) != len(gaps):
+                raise ValueError("join: one gap per segment")
+        if self._evaluator is not None:
+            return [(np.ascontiguousarray(y, dtype=F32), [(int(a), int(b)) for a, b in ab])
+                    for y, ab in self._evaluator(self, jobs)]
+        if not jobs:
+            return []
+        js = (_ffi.JoinJob * len(jobs))()
+        keep = []
+        for j, (segs, gaps) in zip(js, jobs):
+            n = np.array([x.size for x in segs], dtype=np.int64)
+            g = np.array(gaps, dtype=np.int64)
+            ptr = (ctypes.c_void_p * max(len(segs), 1))(*[x.ctypes.data for x in segs])
+            out = np.empty(self.capacity(n, g), dtype=F32)
+            a, b = np.zeros(len(segs), dtype=np.int64), np.zeros(len(segs), dtype=np.int64)
+            j.struct_size, j.n_seg = ctypes.sizeof(_ffi.JoinJob), len(segs)
+            j.seg, j.n, j.gap = ctypes.addressof(ptr), n.ctypes.data, g.ctypes.data
+            j.out, j.a, j.b = out.ctypes.data, a.ctypes.data, b.ctypes.data
+            keep.append((n, g, ptr, out, a, b))
+        self._call("join_jobs", js, len(jobs))
+        return [(out[:int(j.n_out)].copy(), list(zip(a.tolist(), b.tolist()))) for j, (_, _, _, out, a, b) in zip(js, keep)]
+
+    def join(self, segments, gaps):
+        """One job -> (joined PCM, [(a_s, b_s)])."""
+        return self.join_batch([(segments, gaps)])[0]
 
 
 # ---- normalisation / trimming ------------------------------------------------------------

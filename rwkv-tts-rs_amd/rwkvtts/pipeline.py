@@ -19,6 +19,12 @@ reference carries temperature / top_p / top_k and samples with fixed values) set
 generator's temperature, top-p and top-k per phase (runtime.PhaseSampling); a value outside its
 range raises ValueError in the same four entry points before anything is generated.
 
+generate_long_speech / stream_long_speech (no reference counterpart: a request of the reference ends
+at 2048 semantic tokens, 41 s, without an error) take a text of any length: segment.split_text cuts
+it, the segments decode side by side with one voice (segment 0 a normal request, the others pinned
+to its 32 global tokens: TtsBatchRequest.pinned_voice, LightweightTtsPipelineArgs.pin_voice), and
+audio.Joiner joins their PCM on the GPU before the stretch and the resampler.
+
 The voice store lookup by voice_id inside the pipeline (`VoiceFeatureManager::new("./raf")`,
 :751) goes through `voices.VoiceFeatureManager` on `raf_dir` (the server passes the
 tokens directly instead).
@@ -61,6 +67,23 @@ class LightweightTtsPipelineArgs:  # :18-65 (Default)
     # ignored, as in the reference.
     global_sampling: Optional[PhaseSampling] = None
     semantic_sampling: Optional[PhaseSampling] = None
+    # no reference counterpart: with voice_global_tokens set and voice_semantic_tokens None, a
+    # normal-mode request whose 32 global tokens are those (rwkvtts_request.pinned_voice): the same
+    # voice again, still with its property tokens. Without it that combination ignores the tokens.
+    pin_voice: bool = False
+
+
+def check_voice_pin(args) -> None:
+    """ValueError for a pin_voice without exactly 32 voice_global_tokens in [0, 4096) or with
+    voice_semantic_tokens, before anything is generated."""
+    if not getattr(args, "pin_voice", False):
+        return
+    g = args.voice_global_tokens
+    if args.voice_semantic_tokens is not None:
+        raise ValueError("pin_voice: voice_semantic_tokens must be None (both token sets clone a voice)")
+    if g is None or len(g) != 32 or any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 0 <= x < 4096
+                                        for x in g):
+        raise ValueError("pin_voice: voice_global_tokens must be 32 integers in [0, 4096)")
 
 
 def check_sampling(args) -> None:
@@ -73,6 +96,7 @@ def check_sampling(args) -> None:
         if not isinstance(ph, PhaseSampling):
             raise ValueError(f"{what} must be a PhaseSampling")
         ph.check(what)
+    check_voice_pin(args)
 
 
 class SpeechChunk(np.ndarray):
@@ -86,6 +110,23 @@ class SpeechChunk(np.ndarray):
     def make(cls, pcm, t0, t1, n_known, done):
         c = np.ascontiguousarray(pcm, dtype=np.float32).view(cls)
         c.t0, c.t1, c.n_known, c.done = int(t0), int(t1), int(n_known), bool(done)
+        return c
+
+
+class LongSpeech(np.ndarray):
+    """The result of generate_long_speech, and one item of stream_long_speech: float32 PCM (an
+    ndarray) that also carries global_tokens (the voice every segment spoke with; None if none is
+    known) and segments, one record per segment it holds: text, status, n_semantic, truncated (the
+    segment emitted as many semantic tokens as its limit allows: it was probably cut off), pause_ms,
+    and a, b (the samples [a, b) of the segment's 16 kHz PCM that the join kept)."""
+    global_tokens = None
+    segments = ()
+
+    @classmethod
+    def make(cls, pcm, global_tokens, segments):
+        c = np.ascontiguousarray(pcm, dtype=np.float32).view(cls)
+        c.global_tokens = None if global_tokens is None else list(global_tokens)
+        c.segments = list(segments)
         return c
 
 
@@ -121,7 +162,8 @@ class LightweightTtsPipeline:
         self.reference_tokenizer = reference_tokenizer
         self._resamplers = {}  # output rate -> audio.Resampler (created on first use, kept)
         self._stretcher = None  # audio.TimeStretcher (created on the first tempo other than 1.0, kept)
-        self._stage_cache_lock = threading.Lock()  # guards both (the server's worker threads share the pipeline)
+        self._joiners = {}  # (trim, keep, fade) -> audio.Joiner (created on first use, kept)
+        self._stage_cache_lock = threading.Lock()  # guards all three (the server's worker threads share the pipeline)
 
     # ---- output rates other than 16 kHz (no reference counterpart: the reference emits 16 kHz only)
     def resampler(self, sample_rate: Optional[int]):
@@ -153,6 +195,18 @@ class LightweightTtsPipeline:
                 from .audio import TimeStretcher
                 self._stretcher = TimeStretcher(device=getattr(self.codec, "device", 0))
         return self._stretcher
+
+    # ---- long texts (no reference counterpart: the reference stops at 2048 semantic tokens)
+    def joiner(self, trim: bool = True, keep: int = 800, fade: int = 80):
+        """The pipeline's Joiner for these parameters, on the codec's GPU."""
+        key = (bool(trim), int(keep), int(fade))
+        with self._stage_cache_lock:
+            j = self._joiners.get(key)
+            if j is None:
+                from .audio import Joiner
+                j = self._joiners[key] = Joiner(device=getattr(self.codec, "device", 0), trim=key[0], keep=key[1],
+                                                fade=key[2])
+        return j
 
     def _stages(self, sample_rate: Optional[int], tempo: Optional[float]):  # -> (stages, output rate)
         rs = self.resampler(sample_rate)
@@ -202,6 +256,8 @@ class LightweightTtsPipeline:
         if args.zero_shot:
             g, s = self.process_reference_audio(args.ref_audio_path)
             return [], g, s
+        if args.pin_voice and args.voice_global_tokens is not None:  # a pinned voice keeps its property tokens
+            return self.generate_property_tokens(args), [int(x) for x in args.voice_global_tokens], None
         return self.generate_property_tokens(args), None, None
 
     def _request(self, args: LightweightTtsPipelineArgs) -> TtsBatchRequest:
@@ -211,7 +267,8 @@ class LightweightTtsPipeline:
                             max_tokens=args.max_tokens, seed=args.seed, voice_fidelity=0.8,
                             layered_randomness=LayeredRandomnessConfig(), token_chunk_size=512,
                             global_sampling=args.global_sampling, semantic_sampling=args.semantic_sampling)
-        return TtsBatchRequest(self.manager._tokens(text), props, rg, rs, sargs, args.voice_id)
+        return TtsBatchRequest(self.manager._tokens(text), props, rg, rs, sargs, args.voice_id,
+                               pinned_voice=rg is not None and rs is None)
 
     def generate_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
                         tempo: Optional[float] = None) -> np.ndarray:
@@ -330,3 +387,137 @@ class LightweightTtsPipeline:
         for batch, _ in stages:
             pcm = batch(pcm)
         return pcm
+
+    # ---- long-form synthesis (no reference counterpart: a request of the reference ends at 2048
+    # semantic tokens, 41 s of audio, without an error) ------------------------------------------
+    def _long_submit(self, args: LightweightTtsPipelineArgs, segment_tokens: int, pauses):
+        """Segments the text and submits every segment. -> (segments, tickets, limit), or None for a
+        text that cannot be tokenised or whose first segment failed before its voice was known
+        (nothing is left in flight then). tickets[i] is None for a segment that was not submitted.
+
+        A cloned voice (voice_id, both voice token sets, zero_shot) submits every segment at once as
+        the zero-shot request _request builds; pin_voice submits every segment pinned from the
+        start. Otherwise segment 0 is the request generate_speech would build, submitted as a
+        stream; as soon as its 32 global tokens are known, segments 1 .. N-1 go out at once, each
+        the same request with its own text, pinned to those tokens. Segment i is seeded with
+        args.seed + i when args.seed is given."""
+        from .segment import Pauses, Segment, split_text
+        text = self.process_text_zero_shot(args.text, args.prompt_text) if args.zero_shot else self.process_text(args.text)
+        try:
+            segs = split_text(text, self.manager._tokens, segment_tokens, pauses or Pauses())
+            if len(segs) <= 1:  # one segment is generate_speech's request, surrounding whitespace included
+                segs = [Segment(text, list(self.manager._tokens(text)), 0, "end")]
+            base = self._request(dataclasses.replace(args, text=""))
+        except ValueError:  # untokenisable text
+            return None
+
+        def request(i, pin=None):
+            r = dataclasses.replace(base, text_tokens=list(segs[i].tokens), args=dataclasses.replace(
+                base.args, seed=None if args.seed is None else int(args.seed) + i))
+            if pin is not None:
+                r.ref_global_tokens, r.ref_semantic_tokens, r.pinned_voice = list(pin), None, True
+            return r
+
+        limit = 2048 if base.ref_semantic_tokens is not None else min(max(int(args.max_tokens), 0), 2048)
+        if base.ref_global_tokens is not None:  # the voice is known: cloned (zero-shot) or pinned
+            return segs, [self.manager.submit(request(i)) for i in range(len(segs))], limit
+        t0 = self.manager.submit(request(0), stream=True)
+        voice, have = None, 0
+        try:
+            while voice is None:
+                voice, sem, done, status = self.manager.wait_tokens(t0, have)
+                have = len(sem)
+                if done:
+                    break
+        except BaseException:
+            self.manager.wait_status(t0)
+            raise
+        if voice is None or len(voice) != 32:  # segment 0 failed in normal mode: no voice to go on with
+            self.manager.wait_status(t0)
+            return None
+        return segs, [t0] + [self.manager.submit(request(i, voice)) for i in range(1, len(segs))], limit
+
+    @staticmethod
+    def _long_record(seg, result, status, limit):
+        g, s = result
+        return {"text": seg.text, "status": int(status), "n_semantic": len(s), "truncated": bool(s) and len(s) >= limit,
+                "pause_ms": int(seg.pause_ms), "a": 0, "b": 0}
+
+    def generate_long_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
+                             tempo: Optional[float] = None, segment_tokens: int = 64, pauses=None,
+                             trim: bool = True, keep: int = 800, fade: int = 80) -> "LongSpeech":
+        """generate_speech for a text of any length: the text is cut into segments of at most
+        segment_tokens text tokens (segment.split_text), the segments decode side by side in the
+        manager's slots and engines with one voice (_long_submit), and their PCM is joined on the
+        GPU (audio.Joiner: with trim, each segment cut to `keep` samples around its audible part
+        and faded over `fade` samples; pause_ms * 16 zero samples after it), then stretched and
+        resampled as generate_speech does. One decode_audio_batch, one join.
+
+        A failed segment contributes only its gap and its status. If segment 0 fails in normal mode,
+        or every segment fails, the result is generate_speech's second of silence. A text of one
+        segment with trim=False gives bitwise generate_speech(args, ...). segment_tokens, pauses,
+        keep and fade are unmeasured defaults."""
+        check_sampling(args)
+        stages, rate = self._stages(sample_rate, tempo)
+        joiner = self.joiner(trim, keep, fade)
+        plan = self._long_submit(args, segment_tokens, pauses)
+        if plan is None:
+            return LongSpeech.make(np.zeros(rate, dtype=np.float32), None, [])  # :828-830
+        segs, tickets, limit = plan
+        results = [self.manager.wait_status(t) for t in tickets]
+        recs = [self._long_record(sg, r, st, limit) for sg, (r, st) in zip(segs, results)]
+        voice = next((list(r[0]) for r, st in results if st == 0 and r[0]), None)
+        if not any(st == 0 and (r[0] or r[1]) for r, st in results):
+            return LongSpeech.make(np.zeros(rate, dtype=np.float32), voice, recs)
+        pcm = self.codec.decode_audio_batch([r if st == 0 else ([], []) for r, st in results])
+        out, ab = joiner.join(pcm, [sg.pause_ms * (SAMPLE_RATE // 1000) for sg in segs])
+        for rec, (a, b) in zip(recs, ab):
+            rec["a"], rec["b"] = a, b
+        for batch, _ in stages:
+            out = batch([out])[0]
+        return LongSpeech.make(out, voice, recs)
+
+    def stream_long_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
+                           tempo: Optional[float] = None, segment_tokens: int = 64, pauses=None,
+                           trim: bool = True, keep: int = 800, fade: int = 80):
+        """generate_long_speech as a generator of LongSpeech items, one per segment, in order: segment
+        i is emitted once it and every segment before it are done -- decoded, joined alone with its
+        gap (a piece depends on its own segment only), and fed through the stages' exact streams,
+        with `final` on the last segment. The concatenation of the items is bitwise
+        generate_long_speech for the same arguments and seed; the first audio arrives when segment 0
+        has finished. An item may be empty (a failed segment without a gap; stretched blocks or
+        resampled outputs still waiting for the next segment's samples). Failed segments before the
+        first good one are held back until it arrives, so a text whose every segment fails yields
+        the one second of silence alone. Streaming inside a segment is out of scope."""
+        check_sampling(args)
+        stages, rate = self._stages(sample_rate, tempo)
+        joiner = self.joiner(trim, keep, fade)
+        plan = self._long_submit(args, segment_tokens, pauses)
+        if plan is None:
+            yield LongSpeech.make(np.zeros(rate, dtype=np.float32), None, [])
+            return
+        segs, tickets, limit = plan
+        streams = [stream() for _, stream in stages]
+        held, started, voice, waited = [], False, None, 0
+        try:
+            for i, (sg, t) in enumerate(zip(segs, tickets)):
+                r, st = self.manager.wait_status(t)
+                waited = i + 1
+                rec = self._long_record(sg, r, st, limit)
+                good = st == 0 and bool(r[0] or r[1])
+                if good and voice is None and r[0]:
+                    voice = list(r[0])
+                pcm = self.codec.decode_audio_batch([r if st == 0 else ([], [])])[0]
+                piece, ((rec["a"], rec["b"]),) = joiner.join([pcm], [sg.pause_ms * (SAMPLE_RATE // 1000)])
+                last = i + 1 == len(segs)
+                if not started and not good:
+                    held.append((piece, rec))
+                    continue
+                for k, (p, rc) in enumerate(held + [(piece, rec)]):
+                    yield LongSpeech.make(feed_stages(streams, p, last and k == len(held)), voice, [rc])
+                held, started = [], True
+            if not started:
+                yield LongSpeech.make(np.zeros(rate, dtype=np.float32), voice, [rc for _, rc in held])
+        finally:
+            for t in tickets[waited:]:  # (a stream left early: the tickets are released once the requests finish)
+                self.manager.wait_status(t)

@@ -115,6 +115,7 @@ def request_struct(r: "TtsBatchRequest"):
         dst.temperature = float(ph.temperature)
         dst.top_p = float(ph.top_p)
         dst.top_k = k_default if ph.top_k is None else int(ph.top_k)
+    q.pinned_voice = 1 if r.pinned_voice else 0
     return q, keep
 
 
@@ -430,6 +431,9 @@ class TtsBatchRequest:  # src/rwkv_sampler.rs:222-231 (text already tokenised)
     voice_id: Optional[str] = None
     fixed_semantic: int = 0   # benchmark mode: EOS masked, exactly this many tokens
     greedy: bool = False      # config-1 plumbing check (top_k = 1)
+    # no reference counterpart (rwkvtts.h rwkvtts_request.pinned_voice): a normal-mode request whose
+    # 32 global tokens are ref_global_tokens (ref_semantic_tokens None); the property tokens are kept
+    pinned_voice: bool = False
 
 
 @dataclasses.dataclass

@@ -31,6 +31,17 @@
   key left out keeps the phase's own 1.0 / 0.95 / 20 global, 80 semantic); anything else a 400. The
   top-level `temperature` and `top_p` keep doing nothing, as in the reference, which parses them
   and then samples with fixed values (normal_mode_inference.rs:114-127).
+* `long_form`, `segment_tokens` and `voice_tokens` in the body of both TTS routes (no reference
+  counterpart: a request of the reference ends at 2048 semantic tokens, 41 s of audio, without an
+  error). `long_form`: a JSON bool; true routes the request to pipeline.generate_long_speech /
+  stream_long_speech, which cut the text into segments, synthesise them side by side with one voice
+  and join them. `segment_tokens`: an integer in [SEGMENT_TOKENS_MIN, SEGMENT_TOKENS_MAX] =
+  [8, 256], the segmenter's budget; it needs `long_form`. `voice_tokens`: 32 integers in [0, 4096),
+  the global tokens of a voice heard before (a `long_form` response returns them): the request
+  speaks with that voice and keeps its property tokens (pin_voice), with or without `long_form`; it
+  excludes `voice_id`. Anything else is a 400. A `long_form` JSON response adds `voice_tokens` and
+  `segments` (text, status, n_semantic, truncated, pause_ms, a, b per segment). Without the keys the
+  routes are unchanged.
 * `handle_tts_stream(body, pipeline, voice_dir)` (no reference counterpart): the same request as a
   WAV stream, POST /api/tts/stream -- audio while the request is still decoding, at a fixed scale
   (no peak normalisation: that needs the whole utterance).
@@ -78,6 +89,9 @@ SAMPLE_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
 # `tempo` of the same bodies (no reference counterpart): the range in which the time stretch still
 # sounds like speech; the kernel itself takes 0.25 .. 4.0
 TEMPO_MIN, TEMPO_MAX = 0.5, 2.0
+# `segment_tokens` of the same bodies (no reference counterpart): text tokens per segment of a
+# `long_form` request; the default, 64, is pipeline.generate_long_speech's
+SEGMENT_TOKENS_MIN, SEGMENT_TOKENS_MAX = 8, 256
 
 
 def map_speed(speed) -> str:
@@ -132,7 +146,9 @@ def _tts_args(body, voice_dir: str):
     ((status, payload), None, None) for a body the handler refuses. keywords: what the pipeline call
     takes beyond the args, each only when the body sets it to something other than its default --
     sample_rate (one of SAMPLE_RATES, not 16000) and tempo (TEMPO_MIN .. TEMPO_MAX, not 1.0) -- so a
-    body without them makes exactly the call it always made."""
+    body without them makes exactly the call it always made. A true `long_form` adds
+    long_form=True, which the handler takes out and answers by calling the long-form entry point,
+    and segment_tokens when the body sets it."""
     if isinstance(body, (bytes, str)):
         try:
             body = json.loads(body)
@@ -164,6 +180,24 @@ def _tts_args(body, voice_dir: str):
             sampling[what] = PhaseSampling(**{k: v for k, v in o.items() if v is not None}).check(what)
         except ValueError as e:
             return (400, {"success": False, "error": f"不支持的采样参数: {e}"}), None, None
+    long_form = body.get("long_form")
+    if long_form is not None and not isinstance(long_form, bool):
+        return (400, {"success": False, "error": f"不支持的长文本开关: {long_form} (支持: true, false)"}), None, None
+    seg_tokens = body.get("segment_tokens")
+    if seg_tokens is not None:
+        if (isinstance(seg_tokens, bool) or not isinstance(seg_tokens, int)
+                or not SEGMENT_TOKENS_MIN <= seg_tokens <= SEGMENT_TOKENS_MAX):
+            return (400, {"success": False, "error": f"不支持的分段长度: {seg_tokens} (支持: "
+                                                     f"{SEGMENT_TOKENS_MIN} - {SEGMENT_TOKENS_MAX})"}), None, None
+        if not long_form:
+            return (400, {"success": False, "error": "segment_tokens 需要 long_form 为 true"}), None, None
+    voice_tokens = body.get("voice_tokens")
+    if voice_tokens is not None:
+        if (not isinstance(voice_tokens, list) or len(voice_tokens) != 32
+                or any(isinstance(x, bool) or not isinstance(x, int) or not 0 <= x < 4096 for x in voice_tokens)):
+            return (400, {"success": False, "error": "不支持的音色标记: voice_tokens 需要 32 个 [0, 4096) 内的整数"}), None, None
+        if body.get("voice_id"):
+            return (400, {"success": False, "error": "voice_tokens 与 voice_id 不能同时使用"}), None, None
     voice_id = body.get("voice_id")
     voice = None
     prompt_from_voice = None
@@ -182,9 +216,14 @@ def _tts_args(body, voice_dir: str):
         age=body.get("age") or "youth-adult", gender=body.get("gender") or "male",
         emotion=body.get("emotion") or "NEUTRAL", pitch=map_pitch(body.get("pitch")),
         speed=map_speed(body.get("speed")), prompt_text=prompt_text,
-        voice_global_tokens=list(voice["global_tokens"]) if voice else None,
-        voice_semantic_tokens=list(voice["semantic_tokens"]) if voice else None, **sampling)
+        voice_global_tokens=list(voice["global_tokens"]) if voice else voice_tokens,
+        voice_semantic_tokens=list(voice["semantic_tokens"]) if voice else None,
+        pin_voice=voice_tokens is not None, **sampling)
     kw = {}
+    if long_form:
+        kw["long_form"] = True
+        if seg_tokens is not None:
+            kw["segment_tokens"] = seg_tokens
     if rate != 16000:
         kw["sample_rate"] = rate
     if float(tempo) != 1.0:
@@ -198,15 +237,20 @@ def handle_tts_json(body, pipeline, voice_dir: str = "assets/raf") -> Tuple[int,
     if err:
         return err
     rate = kw.get("sample_rate", 16000)
+    long_form = kw.pop("long_form", False)
     try:
-        audio = pipeline.generate_speech(args, **kw)
+        audio = pipeline.generate_long_speech(args, **kw) if long_form else pipeline.generate_speech(args, **kw)
     except Exception as e:  # noqa: BLE001 -- rendered as the reference's 500 body
         return 500, {"success": False, "error": f"生成TTS音频失败: {e}"}
     wav = convert_samples_to_wav(audio, rate)
     b64 = base64.standard_b64encode(wav).decode("ascii")
     total = time.perf_counter() - t0
-    return 200, {"success": True, "message": "TTS生成成功", "audio_base64": b64,
-                 "duration_ms": int(total * 1000), "rtf": calculate_rtf(audio, total, rate)}
+    out = {"success": True, "message": "TTS生成成功", "audio_base64": b64,
+           "duration_ms": int(total * 1000), "rtf": calculate_rtf(audio, total, rate)}
+    if long_form:
+        out["voice_tokens"] = audio.global_tokens
+        out["segments"] = list(audio.segments)
+    return 200, out
 
 
 def streaming_wav_header(sample_rate: int = 16000) -> bytes:
@@ -246,7 +290,10 @@ def handle_tts_stream(body, pipeline, voice_dir: str = "assets/raf", chunk_frame
         return err[0], iter([json.dumps(err[1], ensure_ascii=False).encode("utf-8")])
     rate = kw.get("sample_rate", 16000)
     try:
-        chunks = pipeline.stream_speech(args, chunk_frames=chunk_frames, **kw)
+        if kw.pop("long_form", False):  # one item per segment: the first audio when segment 0 is done
+            chunks = pipeline.stream_long_speech(args, **kw)
+        else:
+            chunks = pipeline.stream_speech(args, chunk_frames=chunk_frames, **kw)
         first = next(chunks, None)  # before the status line goes out: a failure is still a 500
     except Exception as e:  # noqa: BLE001 -- rendered as the reference's 500 body
         payload = {"success": False, "error": f"生成TTS音频失败: {e}"}
