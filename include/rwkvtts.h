@@ -772,6 +772,105 @@ int rwkvtts_join_jobs(rwkvtts_join* j, rwkvtts_join_job* jobs, int n);
 /* HIP-event time of the last call's kernels (no copies), in ms; 0 before the first. */
 int rwkvtts_join_kernel_ms(rwkvtts_join* j, double* ms);
 
+/* ---- level: a look-ahead loudness leveller with a peak ceiling on the GPU, the `loudness` of the
+ * pipeline (no reference counterpart: the reference peak-normalises a finished WAV to 0.8, which sets
+ * no loudness and cannot be streamed) -----------------------------------------------------------
+ * Runs on the 16 kHz PCM, after the stretch and before the resampler. One causal definition with a
+ * bounded look-ahead, so a stream's pieces are bitwise the one-shot result. The arithmetic contract
+ * (every output bit is defined by IEEE f32 operations: rounded add, subtract and multiply, never
+ * fused, and correctly rounded divide and square root; no log, no pow):
+ *   B, L, A   block length, FIR length, look-ahead in blocks; H the memory in blocks (0: unbounded)
+ *   T2        the target, an f32 mean square per signal: (float)10^((loudness_dB + 0.691) / 10), in
+ *             double (rwkvtts_level_target)
+ *   table     h[0, L) then r[0, B), f32. h: the first L samples of the impulse response of the two
+ *             BS.1770 K-weighting biquads re-derived for 16 kHz, in double, rounded to f32. Bilinear
+ *             design, K = tan(pi * f0 / fs). Shelf (f0 = 1681.974450955533, G = 3.999843853973347 dB,
+ *             Q = 0.7071752369554196): Vh = 10^(G/20), Vb = Vh^0.4996667741545416,
+ *             a0 = 1 + K/Q + K*K, b = [(Vh + Vb*K/Q + K*K), 2(K*K - Vh), (Vh - Vb*K/Q + K*K)] / a0,
+ *             a = [1, 2(K*K - 1)/a0, (1 - K/Q + K*K)/a0]. High-pass (f0 = 38.13547087602444,
+ *             Q = 0.5003270373238773): b = [1, -2, 1], a of the same form. Each biquad is run in
+ *             direct form I on the unit impulse, shelf first, every step one double operation:
+ *             y[n] = (((b0*x[n] + b1*x[n-1]) + b2*x[n-2]) - a1*y[n-1]) - a2*y[n-2].
+ *             r[i] = (float)((double)(i + 1) / (double)B).
+ *   measure   z[n] = sum_k h[k] * x[n-k]: a sequential f32 sum in ascending k from +0, one rounded
+ *             multiply then one rounded add per tap; x below sample 0 is +0. Block j covers samples
+ *             [jB, (j+1)B); z and x at or past the signal's end are +0 (the last block may be
+ *             partial). E_j from 64 partials: p[l] = sum of z[i]*z[i] over the block's i = l (mod 64),
+ *             ascending from +0 (one rounded multiply, one rounded add), then p[l] += p[l+s] for
+ *             l < s, s = 32, 16, 8, 4, 2, 1; E_j = p[0]. pk_j = max |x| over the block.
+ *             P_j = ((((+0 + E_{j-3}) + E_{j-2}) + E_{j-1}) + E_j) / (float)(4B); E below block 0 is +0.
+ *   gain      a serial scan: before g_j, every block k <= min(j + A, last) not yet entered enters in
+ *             ascending k: if P_k >= gate then, while N < H or H == 0, S = S + P_k and N = N + 1,
+ *             otherwise S = (S - S / (float)H) + P_k. From S = +0, N = 0.
+ *             g_j = 1 if N == 0, else sqrt(T2 / (S / (float)N)); then g_j = g_min if g_j < g_min;
+ *             then g_j = g_max if g_j > g_max; then, with p = max(pk_j, pk_{j+1}) (0 for a block
+ *             that does not exist): if g_j * p > C then g_j = C / p. The peak cap wins over g_min.
+ *   apply     sample i of block j: y = x * (g_{j-1} + (g_j - g_{j-1}) * r[i]), g_{-1} = g_0.
+ * So n_out = n; silence comes back bit for bit (g = 1, and x * 1 = x); and |y| <= C * (1 + 2^-20):
+ * both ends of block j's ramp were capped against pk_j, and at most five roundings follow. A
+ * non-finite sample leaves the outputs from its block on unspecified; nothing is read or written
+ * out of bounds. Every default below is untuned: the repository has no real checkpoint. */
+typedef struct {
+  uint32_t struct_size;
+  int32_t block;     /* B: a multiple of 64, 64 .. 4800; 0 = 1600 (100 ms) */
+  int32_t taps;      /* L: a multiple of 64, 64 .. 2048; 0 = 1024 */
+  int32_t lookahead; /* A: 1 .. 16; 0 = 4 */
+  float gate;        /* finite, > 0; 0 = 1e-5 (-50 dB) */
+  float ceiling;     /* C: finite, > 0; 0 = 0.891 */
+  float g_min;       /* finite, > 0; 0 = 0.1 */
+  float g_max;       /* finite, >= g_min; 0 = 10, the cap of the reference's WAV normalisation */
+  int32_t horizon;   /* H: 0 .. 2^24; 0 = unbounded */
+} rwkvtts_level_desc;
+/* The library's own table builder (host only): out[L + B]. Anything outside the ranges above (NaN
+ * included) is RWKVTTS_EINVAL, here and in every call that takes a desc. */
+int rwkvtts_level_table(const rwkvtts_level_desc* desc, float* out);
+/* T2 of a loudness in dB (host only): (float)pow(10, (loudness_db + 0.691) / 10). */
+float rwkvtts_level_target(double loudness_db);
+/* Streaming plan (host only, a pure function). With samples [0, n_known) of a signal known and
+ * blocks [0, block_first) done:
+ * *out_ready_end = B * max(0, floor(n_known / B) - A): block j is exact once blocks up to j + A are
+ * complete. With final (n_known is the signal's length) it is n_known.
+ * *in_first_needed = max(0, min(block_first * B, (block_first + A - 3) * B - (L - 1))): the cursor
+ * block's own samples, and the FIR history of the first block whose energy has yet to enter --
+ * samples before it are never read again. Either pointer may be NULL. Monotone in both. */
+int rwkvtts_level_plan(const rwkvtts_level_desc* desc, int64_t n_known, int final, int64_t block_first,
+                       int64_t* out_ready_end, int64_t* in_first_needed);
+typedef struct rwkvtts_level rwkvtts_level;
+/* table == NULL: the table of rwkvtts_level_table; otherwise the caller's [L + B] table (copied). */
+int rwkvtts_level_create(int device, const rwkvtts_level_desc* desc, const float* table, rwkvtts_level** out);
+int rwkvtts_level_destroy(rwkvtts_level* v);
+/* n signals (ragged), each with its own target t2[i] (finite, > 0), in one launch triple (measure,
+ * gain, apply). Host buffers; out[i] has capacity n_in[i]. n_in[i] == 0 writes nothing. Calls on one
+ * handle serialise on its lock. */
+int rwkvtts_level_batch(rwkvtts_level* v, const float* const* in, const int64_t* n_in, const float* t2, int n,
+                        float* const* out);
+typedef struct {
+  uint32_t struct_size;
+  const float* in;     /* points at sample in_first of the signal */
+  int64_t in_first;
+  int64_t n_in;
+  int32_t final;       /* 1: in_first + n_in is the signal's length */
+  float t2;
+  int64_t block_first; /* outputs [block_first * B, block_first * B + out_count) */
+  float s_prev;        /* the state after block block_first - 1: S, N and g of that block, as the */
+  int64_t n_prev;      /* last call returned them; S = 0, N = 0 (g ignored) for block_first 0 */
+  float g_prev;
+  int64_t out_count;   /* whole blocks, or up to the signal's end with final */
+  float* out;          /* capacity out_count */
+  float s_last;        /* out: the state after the last block written (the state given if */
+  int64_t n_last;      /* out_count is 0) */
+  float g_last;
+} rwkvtts_level_window;
+/* n windows (of any signals, any targets) in one launch triple: outputs [block_first * B,
+ * + out_count) of the whole-signal result, bitwise, whatever follows the known samples.
+ * RWKVTTS_EINVAL before anything is launched (and nothing written, the state included) if a window
+ * asks for more than rwkvtts_level_plan allows: block_first * B + out_count >
+ * out_ready_end(in_first + n_in, final), in_first > in_first_needed(block_first), an out_count that
+ * ends inside a block before the signal's end, or a state that no scan can have left. */
+int rwkvtts_level_windows(rwkvtts_level* v, rwkvtts_level_window* w, int n);
+/* HIP-event time of the last launch triple (all three kernels, no copies), in ms; 0 before the first. */
+int rwkvtts_level_kernel_ms(rwkvtts_level* v, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

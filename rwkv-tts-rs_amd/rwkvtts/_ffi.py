@@ -198,6 +198,20 @@ class JoinJob(ctypes.Structure):
                 ("b", ctypes.c_void_p), ("n_out", ctypes.c_int64)]
 
 
+class LevelDesc(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("block", ctypes.c_int32), ("taps", ctypes.c_int32),
+                ("lookahead", ctypes.c_int32), ("gate", ctypes.c_float), ("ceiling", ctypes.c_float),
+                ("g_min", ctypes.c_float), ("g_max", ctypes.c_float), ("horizon", ctypes.c_int32)]
+
+
+class LevelWindow(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("in_", ctypes.c_void_p), ("in_first", ctypes.c_int64),
+                ("n_in", ctypes.c_int64), ("final", ctypes.c_int32), ("t2", ctypes.c_float),
+                ("block_first", ctypes.c_int64), ("s_prev", ctypes.c_float), ("n_prev", ctypes.c_int64),
+                ("g_prev", ctypes.c_float), ("out_count", ctypes.c_int64), ("out", ctypes.c_void_p),
+                ("s_last", ctypes.c_float), ("n_last", ctypes.c_int64), ("g_last", ctypes.c_float)]
+
+
 # Every symbol include/rwkvtts.h declares (checked by tests/test_abi.py against the header).
 EXPORTS = {
     "rwkvtts_synth_weights": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p]),
@@ -311,6 +325,18 @@ EXPORTS = {
     "rwkvtts_join_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "rwkvtts_join_jobs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(JoinJob), ctypes.c_int]),
     "rwkvtts_join_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    # level: table, target and plan (host only), batched / exact stream windows
+    "rwkvtts_level_table": (ctypes.c_int, [ctypes.POINTER(LevelDesc), ctypes.c_void_p]),
+    "rwkvtts_level_target": (ctypes.c_float, [ctypes.c_double]),
+    "rwkvtts_level_plan": (ctypes.c_int, [ctypes.POINTER(LevelDesc), ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "rwkvtts_level_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(LevelDesc), ctypes.c_void_p,
+                                            ctypes.POINTER(ctypes.c_void_p)]),
+    "rwkvtts_level_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "rwkvtts_level_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_int, ctypes.c_void_p]),
+    "rwkvtts_level_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(LevelWindow), ctypes.c_int]),
+    "rwkvtts_level_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None

@@ -29,6 +29,12 @@ and the clip / silence helpers it uses), feeding the HIP mel kernel (features.py
   kept margin and faded, a pause of zeros after each segment. Integer bounds, one rounded multiply per
   faded sample, every other sample copied (include/rwkvtts.h); pinned bitwise to its
   numpy restatement (tests/join_ref.py).
+* `Leveller` (no reference counterpart: the reference peak-normalises a finished WAV to 0.8): a
+  look-ahead loudness leveller with a peak ceiling as HIP kernels (csrc/level.hip) -- K-weighted
+  momentary power per block, a gated running mean, a clamped and peak-capped gain ramped per block --
+  one-shot, batched with a target per signal, and exact over stream chunks. Its arithmetic contract
+  (include/rwkvtts.h) is f32 add, subtract, multiply and correctly rounded divide and
+  square root; pinned bitwise to its numpy restatement (tests/level_ref.py).
 """
 import ctypes
 import struct
@@ -539,6 +545,163 @@ class Joiner(_NativeStage):
     def join(self, segments, gaps):
         """One job -> (joined PCM, [(a_s, b_s)])."""
         return self.join_batch([(segments, gaps)])[0]
+
+
+# ---- loudness levelling on the GPU -----------------------------------------------------------
+def _level_biquads(fs: float):
+    """The two BS.1770 K-weighting biquads at rate fs -> ((b, a) of the shelf, (b, a) of the high-pass):
+    the bilinear design of include/rwkvtts.h, one double operation at a time, in its order."""
+    import math
+    out = []
+    for f0, Q, G in ((1681.974450955533, 0.7071752369554196, 3.999843853973347),
+                     (38.13547087602444, 0.5003270373238773, None)):
+        K = math.tan(math.pi * f0 / fs)
+        KQ, KK = K / Q, K * K
+        a0 = (1.0 + KQ) + KK
+        if G is not None:
+            Vh = math.pow(10.0, G / 20.0)
+            Vb = math.pow(Vh, 0.4996667741545416)
+            b = (((Vh + Vb * KQ) + KK) / a0, (2.0 * (KK - Vh)) / a0, ((Vh - Vb * KQ) + KK) / a0)
+        else:
+            b = (1.0, -2.0, 1.0)
+        out.append((b, (1.0, (2.0 * (KK - 1.0)) / a0, ((1.0 - KQ) + KK) / a0)))
+    return out
+
+
+def _level_table(taps: int, block: int, fs: float = 16000.0) -> np.ndarray:
+    """h[0, taps) -- the impulse response of the two biquads in direct form I, shelf first, in double,
+    rounded to f32 -- then r[i] = (float)((i + 1) / block): the table both sides read."""
+    v = [1.0] + [0.0] * (taps - 1)
+    for b, a in _level_biquads(fs):
+        y, x1, x2, y1, y2 = [], 0.0, 0.0, 0.0, 0.0
+        for x in v:
+            t = b[0] * x
+            t = t + b[1] * x1
+            t = t + b[2] * x2
+            t = t - a[1] * y1
+            t = t - a[2] * y2
+            x2, x1, y2, y1 = x1, x, y1, t
+            y.append(t)
+        v = y
+    r = np.arange(1, block + 1, dtype=np.float64) / float(block)
+    return np.concatenate([np.array(v, dtype=np.float64), r]).astype(F32)
+
+
+def level_target(loudness: float) -> np.float32:
+    """T2, the f32 mean square of a loudness in dB: 10^((loudness + 0.691) / 10), taken in double
+    (rwkvtts_level_target, host only)."""
+    return F32(_ffi.lib().rwkvtts_level_target(float(loudness)))
+
+
+class Leveller(_NativeStage):
+    """A look-ahead loudness leveller with a built-in peak ceiling as HIP kernels (csrc/level.hip; the
+    arithmetic contract is in include/rwkvtts.h): the K-weighted momentary power of
+    blocks of `block` samples (a `taps`-long FIR), a gated running mean of it that sees `lookahead`
+    blocks ahead, a gain sqrt(target / mean) clamped to [g_min, g_max] and capped so that no sample
+    passes `ceiling`, ramped linearly over each block. One causal definition, so a stream's pieces
+    are bitwise the one-shot result; n_out = n. The pipeline applies it at 16 kHz, after the stretch
+    and before the resampler. A loudness is a target in dB per signal (-23, -16, ..).
+
+    0 means the default as in the C desc: block 1600 (100 ms), taps 1024, lookahead 4, gate 1e-5,
+    ceiling 0.891, g_min 0.1, g_max 10, horizon 0 (unbounded memory). Every default is untuned: the
+    repository has no real checkpoint. The kernels read the table `_level_table` builds.
+
+    evaluator: a callable (leveller, items) -> [(ndarray, S, N, g)] standing in for the native window
+    call, items being [(samples from in_first on, in_first, final, t2, block_first, S, N, g_prev,
+    out_count)]; no GPU object is created then (the host-only plan / table entry points are still the
+    library's)."""
+    _NAME = "level"
+
+    def __init__(self, device: int = 0, block: int = 1600, taps: int = 1024, lookahead: int = 4, gate: float = 1e-5,
+                 ceiling: float = 0.891, g_min: float = 0.1, g_max: float = 10.0, horizon: int = 0, evaluator=None):
+        self.device = int(device)
+        self._desc = _ffi.LevelDesc(struct_size=ctypes.sizeof(_ffi.LevelDesc), block=int(block), taps=int(taps),
+                                    lookahead=int(lookahead), gate=float(gate), ceiling=float(ceiling),
+                                    g_min=float(g_min), g_max=float(g_max), horizon=int(horizon))
+        super().__init__(evaluator)
+        self.plan(0, False)  # (refuses a bad description before anything is built)
+        self.block, self.taps, self.lookahead = int(block) or 1600, int(taps) or 1024, int(lookahead) or 4
+        self.gate, self.ceiling = F32(gate) or F32(1e-5), F32(ceiling) or F32(0.891)
+        self.g_min, self.g_max, self.horizon = F32(g_min) or F32(0.1), F32(g_max) or F32(10.0), int(horizon)
+        self.table = _level_table(self.taps, self.block)
+        self._create(self.table)
+
+    # ---- host-only plan ----
+    def plan(self, n_known: int, final: bool, block_first: int = 0):
+        """(out_ready_end, in_first_needed) of rwkvtts_level_plan."""
+        end, first = ctypes.c_int64(), ctypes.c_int64()
+        _native("level_plan", ctypes.byref(self._desc), int(n_known), 1 if final else 0, int(block_first),
+                ctypes.byref(end), ctypes.byref(first))
+        return end.value, first.value
+
+    # ---- the kernels ----
+    def level_windows(self, items) -> list:
+        """[(samples from in_first on, in_first, final, t2, block_first, S, N, g_prev, out_count)] ->
+        [(outputs [block_first * block, + out_count) of the whole-signal result, S, N, g)], the state
+        after each window's last block, all windows in one launch triple. Raises
+        RwkvTtsError(EINVAL), with nothing computed, if a window asks for more than plan() allows."""
+        items = [(np.ascontiguousarray(x, dtype=F32).reshape(-1), int(a), bool(f), float(F32(t)), int(b), float(F32(s)),
+                  int(n), float(F32(g)), int(c)) for x, a, f, t, b, s, n, g, c in items]
+        if self._evaluator is not None:
+            return [(np.ascontiguousarray(y, dtype=F32), F32(s), int(n), F32(g)) for y, s, n, g in self._evaluator(self, items)]
+        ws, outs = self._windows("level_windows", _ffi.LevelWindow, items, t2=3, block_first=4, s_prev=5, n_prev=6,
+                                 g_prev=7)
+        return [(o, F32(w.s_last), int(w.n_last), F32(w.g_last)) for o, w in zip(outs, ws)]
+
+    def level_batch(self, signals, loudness) -> list:
+        """[signal], [loudness in dB] -> [levelled signal], ragged, a target per signal, in one launch
+        triple; an empty signal gives an empty one."""
+        xs = [np.ascontiguousarray(x, dtype=F32).reshape(-1) for x in signals]
+        ts = [level_target(v) for v in loudness]
+        if len(xs) != len(ts):
+            raise ValueError("level_batch: one loudness per signal")
+        if self._evaluator is not None:
+            return [y for y, _, _, _ in self.level_windows([(x, 0, True, t, 0, 0.0, 0, 1.0, x.size)
+                                                            for x, t in zip(xs, ts)])]
+        if not xs:
+            return []
+        outs, ins, lens, ous = self._ragged(xs, [x.size for x in xs])
+        self._call("level_batch", ins, lens, (ctypes.c_float * len(ts))(*[float(t) for t in ts]), len(xs), ous)
+        return outs
+
+    def level(self, x, loudness: float) -> np.ndarray:
+        return self.level_batch([x], [loudness])[0]
+
+    def stream(self, loudness: float) -> "LevelStream":
+        return LevelStream(self, loudness)
+
+
+class LevelStream(_ExactStream):
+    """Leveller.stream(loudness): feed(pcm_chunk, final=False) -> the blocks that became exact with
+    it. The concatenation of what feed returns is bitwise Leveller.level(the concatenated input,
+    loudness), however the input was cut. A block goes out once the `lookahead` blocks after it are
+    complete, so the output lags the input by up to lookahead + 1 blocks (0.5 s at the defaults); the
+    kept tail is what rwkvtts_level_plan asks for, fewer than (lookahead + 4) * block + taps samples."""
+
+    def __init__(self, leveller: Leveller, loudness: float):
+        super().__init__()
+        self.v = leveller
+        self.t2 = level_target(loudness)
+        if not (np.isfinite(self.t2) and self.t2 > 0):
+            raise ValueError("loudness gives no finite positive target")
+        self._block_next = 0                       # blocks [0, _block_next) went out
+        self._state = (F32(0.0), 0, F32(1.0))      # (S, N, g) after block _block_next - 1
+
+    def _emit(self, n_known, final):
+        B = self.v.block
+        end, _ = self.v.plan(n_known, final, self._block_next)
+        count = end - self._block_next * B
+        if count <= 0:
+            return np.zeros(0, dtype=F32)
+        S, N, g = self._state
+        out, S, N, g = self.v.level_windows([(self._tail, self._tail_first, final, self.t2, self._block_next, S, N, g,
+                                              count)])[0]
+        self._state = (S, N, g)
+        self._block_next += -(-count // B)
+        return out
+
+    def _first_needed(self, n_known):
+        return self.v.plan(n_known, False, self._block_next)[1]
 
 
 # ---- normalisation / trimming ------------------------------------------------------------

@@ -14,6 +14,10 @@ The same four entry points take `tempo` (no reference counterpart: the reference
 is the `speed` property token, which a cloned voice does not get): None / 1.0 leaves the PCM as it
 is; any other value in 0.25 .. 4.0 (above 1 is faster speech) stretches the 16 kHz PCM on the GPU
 without changing its pitch (audio.TimeStretcher), before any resampling, exact over stream chunks.
+They and the long-form pair take `loudness` (no reference counterpart: the reference peak-normalises a
+finished WAV): None leaves the PCM at the vocoder's scale; a target in dB, -40 .. -10, levels the
+16 kHz PCM on the GPU to that K-weighted loudness under a peak ceiling (audio.Leveller, DESIGN.md
+section 24), after the stretch and before the resampler, exact over stream chunks.
 LightweightTtsPipelineArgs.global_sampling / semantic_sampling (no reference counterpart: the
 reference carries temperature / top_p / top_k and samples with fixed values) set the token
 generator's temperature, top-p and top-k per phase (runtime.PhaseSampling); a value outside its
@@ -130,13 +134,16 @@ class LongSpeech(np.ndarray):
         return c
 
 
-def audio_stages(stretcher, tempo, resampler) -> list:
+def audio_stages(stretcher, tempo, resampler, leveller=None, loudness=None) -> list:
     """The stages behind the vocoder in the order they apply -- the stretch at 16 kHz, then the
-    resampler; None is no stage -- each as (batch, stream): batch([pcm]) -> [pcm] in one native call
-    (one tempo for the call), stream() -> an object whose feed(pcm, final) is exact over chunks."""
+    leveller, then the resampler; None is no stage -- each as (batch, stream): batch([pcm]) -> [pcm]
+    in one native call (one tempo, one loudness for the call), stream() -> an object whose
+    feed(pcm, final) is exact over chunks."""
     stages = []
     if stretcher is not None:
         stages.append((lambda pcm: stretcher.stretch_batch(pcm, [tempo] * len(pcm)), lambda: stretcher.stream(tempo)))
+    if leveller is not None:
+        stages.append((lambda pcm: leveller.level_batch(pcm, [loudness] * len(pcm)), lambda: leveller.stream(loudness)))
     if resampler is not None:
         stages.append((resampler.resample_batch, resampler.stream))
     return stages
@@ -163,7 +170,8 @@ class LightweightTtsPipeline:
         self._resamplers = {}  # output rate -> audio.Resampler (created on first use, kept)
         self._stretcher = None  # audio.TimeStretcher (created on the first tempo other than 1.0, kept)
         self._joiners = {}  # (trim, keep, fade) -> audio.Joiner (created on first use, kept)
-        self._stage_cache_lock = threading.Lock()  # guards all three (the server's worker threads share the pipeline)
+        self._levellers = {}  # horizon -> audio.Leveller (created on the first loudness, kept)
+        self._stage_cache_lock = threading.Lock()  # guards all four (the server's worker threads share the pipeline)
 
     # ---- output rates other than 16 kHz (no reference counterpart: the reference emits 16 kHz only)
     def resampler(self, sample_rate: Optional[int]):
@@ -208,9 +216,30 @@ class LightweightTtsPipeline:
                                                 fade=key[2])
         return j
 
-    def _stages(self, sample_rate: Optional[int], tempo: Optional[float]):  # -> (stages, output rate)
+    # ---- loudness (no reference counterpart: the reference peak-normalises a finished WAV)
+    def leveller(self, loudness: Optional[float], horizon: int = 0):
+        """None for None (nothing is created: the PCM keeps the vocoder's scale); otherwise the
+        pipeline's Leveller for this horizon (its other parameters are the untuned defaults of
+        audio.Leveller), on the codec's GPU. The loudness is a target in dB per call, not a part of
+        the object. A loudness outside -40 .. -10 raises ValueError before anything is generated."""
+        if loudness is None:
+            return None
+        if isinstance(loudness, bool) or not -40.0 <= float(loudness) <= -10.0:  # (NaN fails)
+            raise ValueError("loudness must be in [-40, -10] dB")
+        key = int(horizon)
+        with self._stage_cache_lock:
+            v = self._levellers.get(key)
+            if v is None:
+                from .audio import Leveller
+                v = self._levellers[key] = Leveller(device=getattr(self.codec, "device", 0), horizon=key)
+        return v
+
+    def _stages(self, sample_rate: Optional[int], tempo: Optional[float],
+                loudness: Optional[float] = None):  # -> (stages, output rate)
         rs = self.resampler(sample_rate)
-        return audio_stages(self.stretcher(tempo), tempo, rs), rs.sr_out if rs else SAMPLE_RATE
+        lv = self.leveller(loudness)
+        return (audio_stages(self.stretcher(tempo), tempo, rs, lv, None if lv is None else float(loudness)),
+                rs.sr_out if rs else SAMPLE_RATE)
 
     # ---- text / attribute handling (:148-193)
     @staticmethod
@@ -271,14 +300,17 @@ class LightweightTtsPipeline:
                                pinned_voice=rg is not None and rs is None)
 
     def generate_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
-                        tempo: Optional[float] = None) -> np.ndarray:
+                        tempo: Optional[float] = None, loudness: Optional[float] = None) -> np.ndarray:
         """sample_rate None / 16000: the vocoder's 16 kHz PCM. Any other rate: that PCM resampled on
         the GPU (resampler()); the failed-request second of silence is sample_rate zeros.
         tempo None / 1.0: nothing. Any other: the 16 kHz PCM time-stretched on the GPU (stretcher())
         before the resampler; the failed-request second of silence is not stretched.
+        loudness None: nothing. A target in dB, -40 .. -10 (-23, -16, ..): the 16 kHz PCM levelled on
+        the GPU (leveller()) after the stretch and before the resampler; the failed-request second of
+        silence is not levelled.
         args.global_sampling / semantic_sampling outside their ranges raise ValueError, like tempo."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo)
+        stages, rate = self._stages(sample_rate, tempo, loudness)
         try:
             req = self._request(args)
         except ValueError:  # untokenisable text: the request fails -> empty result
@@ -292,7 +324,8 @@ class LightweightTtsPipeline:
         return pcm
 
     def stream_speech(self, args: LightweightTtsPipelineArgs, chunk_frames: int = 16,
-                      sample_rate: Optional[int] = None, tempo: Optional[float] = None):
+                      sample_rate: Optional[int] = None, tempo: Optional[float] = None,
+                      loudness: Optional[float] = None):
         """generate_speech as a generator of float32 PCM chunks (SpeechChunk: an ndarray that also
         carries t0, t1, n_known, done), each decoded while the request is still generating tokens.
 
@@ -313,7 +346,12 @@ class LightweightTtsPipeline:
         Resampler.stream()), each exact over chunks, so the concatenation is bitwise
         generate_speech(args, tempo=..., sample_rate=...). An item then holds what became exact with
         its frames: whole stretched blocks (it may be empty), resampled outputs short of the
-        sinc_len / 2 = 128 input samples of look-ahead. t0, t1 and n_known stay in frames."""
+        sinc_len / 2 = 128 input samples of look-ahead. t0, t1 and n_known stay in frames.
+
+        loudness (a target in dB, -40 .. -10): Leveller.stream(loudness) sits between the two, and the
+        concatenation is bitwise generate_speech(args, loudness=...). A levelled item lags its frames
+        by up to lookahead + 1 blocks, 0.5 s at the defaults: a block goes out once the four blocks
+        after it are complete."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         check_sampling(args)
@@ -321,17 +359,19 @@ class LightweightTtsPipeline:
             req = self._request(args)
         except ValueError:  # untokenisable text: the request fails -> one second of silence
             req = None
-        return self.stream_request(req, chunk_frames, sample_rate=sample_rate, tempo=tempo)
+        self.leveller(loudness)  # (refuses a bad loudness here, not at the first next())
+        return self.stream_request(req, chunk_frames, sample_rate=sample_rate, tempo=tempo, loudness=loudness)
 
     def stream_request(self, req: Optional[TtsBatchRequest], chunk_frames: int = 16,
-                       sample_rate: Optional[int] = None, tempo: Optional[float] = None):
+                       sample_rate: Optional[int] = None, tempo: Optional[float] = None,
+                       loudness: Optional[float] = None):
         """stream_speech for a request that is already built (None: a request that failed before it
         was submitted)."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         if req is not None:
             check_sampling(req.args)
-        stages, rate = self._stages(sample_rate, tempo)
+        stages, rate = self._stages(sample_rate, tempo, loudness)
         streams = [stream() for _, stream in stages]
         H = self.codec.halo()
         g, sem, t0, yielded, status = None, [], 0, False, 0
@@ -365,13 +405,15 @@ class LightweightTtsPipeline:
                 it.close()  # (a stream left early: the ticket is released once the request has finished)
 
     def generate_speech_batch(self, batch_args: Sequence[LightweightTtsPipelineArgs],
-                              sample_rate: Optional[int] = None, tempo: Optional[float] = None) -> List[np.ndarray]:
+                              sample_rate: Optional[int] = None, tempo: Optional[float] = None,
+                              loudness: Optional[float] = None) -> List[np.ndarray]:
         """sample_rate other than None / 16000: the whole batch is resampled in one resample_batch
         call (a failed item stays an empty array). tempo other than None / 1.0: the whole batch is
-        first stretched in one stretch_batch call, one tempo for the call."""
+        first stretched in one stretch_batch call, one tempo for the call. loudness other than None:
+        the whole batch is levelled in one level_batch call between the two, one target for the call."""
         for a in batch_args:
             check_sampling(a)
-        stages, _ = self._stages(sample_rate, tempo)
+        stages, _ = self._stages(sample_rate, tempo, loudness)
         reqs, idx = [], []
         for i, a in enumerate(batch_args):
             try:
@@ -445,7 +487,8 @@ class LightweightTtsPipeline:
 
     def generate_long_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
                              tempo: Optional[float] = None, segment_tokens: int = 64, pauses=None,
-                             trim: bool = True, keep: int = 800, fade: int = 80) -> "LongSpeech":
+                             trim: bool = True, keep: int = 800, fade: int = 80,
+                             loudness: Optional[float] = None) -> "LongSpeech":
         """generate_speech for a text of any length: the text is cut into segments of at most
         segment_tokens text tokens (segment.split_text), the segments decode side by side in the
         manager's slots and engines with one voice (_long_submit), and their PCM is joined on the
@@ -456,9 +499,11 @@ class LightweightTtsPipeline:
         A failed segment contributes only its gap and its status. If segment 0 fails in normal mode,
         or every segment fails, the result is generate_speech's second of silence. A text of one
         segment with trim=False gives bitwise generate_speech(args, ...). segment_tokens, pauses,
-        keep and fade are unmeasured defaults."""
+        keep and fade are unmeasured defaults. loudness levels the joined
+        signal as one (generate_speech), so the segments, decoded as independent requests, come out
+        at one level; the second of silence is not levelled."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo)
+        stages, rate = self._stages(sample_rate, tempo, loudness)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)
         if plan is None:
@@ -479,7 +524,7 @@ class LightweightTtsPipeline:
 
     def stream_long_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
                            tempo: Optional[float] = None, segment_tokens: int = 64, pauses=None,
-                           trim: bool = True, keep: int = 800, fade: int = 80):
+                           trim: bool = True, keep: int = 800, fade: int = 80, loudness: Optional[float] = None):
         """generate_long_speech as a generator of LongSpeech items, one per segment, in order: segment
         i is emitted once it and every segment before it are done -- decoded, joined alone with its
         gap (a piece depends on its own segment only), and fed through the stages' exact streams,
@@ -488,9 +533,10 @@ class LightweightTtsPipeline:
         has finished. An item may be empty (a failed segment without a gap; stretched blocks or
         resampled outputs still waiting for the next segment's samples). Failed segments before the
         first good one are held back until it arrives, so a text whose every segment fails yields
-        the one second of silence alone. Streaming inside a segment is out of scope."""
+        the one second of silence alone. Streaming inside a segment is out of scope. With loudness
+        an item also waits for the leveller's look-ahead (up to 0.5 s of the next segment)."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo)
+        stages, rate = self._stages(sample_rate, tempo, loudness)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)
         if plan is None:

@@ -42,6 +42,13 @@
   excludes `voice_id`. Anything else is a 400. A `long_form` JSON response adds `voice_tokens` and
   `segments` (text, status, n_semantic, truncated, pause_ms, a, b per segment). Without the keys the
   routes are unchanged.
+* `loudness` in the body of both TTS routes (no reference counterpart: the reference peak-normalises
+  the finished WAV to 0.8, which sets no loudness and which a stream cannot do): a JSON number in
+  [LOUDNESS_MIN, LOUDNESS_MAX] = [-40, -10] dB, anything else a 400. The 16 kHz PCM is levelled on the
+  GPU to that K-weighted loudness under a peak ceiling (audio.Leveller), after the stretch and before
+  the resampler. /api/tts then writes its WAV at scale 1.0 (`levelled_samples_to_wav`: no peak rule,
+  which would undo the target), so its samples are byte for byte the PCM /api/tts/stream sends for
+  the same body and seed. Without the field the routes are unchanged.
 * `handle_tts_stream(body, pipeline, voice_dir)` (no reference counterpart): the same request as a
   WAV stream, POST /api/tts/stream -- audio while the request is still decoding, at a fixed scale
   (no peak normalisation: that needs the whole utterance).
@@ -69,13 +76,23 @@ def convert_samples_to_wav(samples, sample_rate: int = 16000) -> bytes:
     scale = np.float32(scale)
     y = np.clip(x * scale, np.float32(-1.0), np.float32(1.0)) * np.float32(32767.0)
     pcm = np.trunc(y).astype("<i2")  # Rust `as i16`: truncation toward zero
-    n = x.size
+    return _wav_header(x.size, sample_rate) + pcm.tobytes()
+
+
+def _wav_header(n: int, sample_rate: int) -> bytes:
     hdr = b"RIFF" + int(36 + n * 2).to_bytes(4, "little", signed=False) + b"WAVE"
     hdr += b"fmt " + (16).to_bytes(4, "little") + (1).to_bytes(2, "little") + (1).to_bytes(2, "little")
     hdr += int(sample_rate).to_bytes(4, "little") + int(sample_rate * 2).to_bytes(4, "little")
     hdr += (2).to_bytes(2, "little") + (16).to_bytes(2, "little")
-    hdr += b"data" + int(n * 2).to_bytes(8, "little")  # (samples.len() * 2).to_le_bytes(): usize
-    return hdr + pcm.tobytes()
+    return hdr + b"data" + int(n * 2).to_bytes(8, "little")  # (samples.len() * 2).to_le_bytes(): usize
+
+
+def levelled_samples_to_wav(samples, sample_rate: int = 16000) -> bytes:
+    """convert_samples_to_wav's header over samples_to_pcm16: scale 1.0, no peak rule. For PCM that
+    the leveller has already set to a loudness under its own peak ceiling: the peak rule would undo
+    the target. The data bytes are what /api/tts/stream sends for the same body and seed."""
+    x = np.asarray(samples, dtype=np.float32)
+    return _wav_header(x.size, sample_rate) + samples_to_pcm16(x)
 
 
 def calculate_rtf(audio, processing_seconds: float, sample_rate: int = 16000) -> float:
@@ -92,6 +109,9 @@ TEMPO_MIN, TEMPO_MAX = 0.5, 2.0
 # `segment_tokens` of the same bodies (no reference counterpart): text tokens per segment of a
 # `long_form` request; the default, 64, is pipeline.generate_long_speech's
 SEGMENT_TOKENS_MIN, SEGMENT_TOKENS_MAX = 8, 256
+# `loudness` of the same bodies (no reference counterpart): the leveller's target in dB (LUFS-like:
+# K-weighted, -23 broadcast, -16 streaming); the pipeline's range
+LOUDNESS_MIN, LOUDNESS_MAX = -40.0, -10.0
 
 
 def map_speed(speed) -> str:
@@ -145,7 +165,8 @@ def _tts_args(body, voice_dir: str):
     """The request body of /api/tts -> (None, LightweightTtsPipelineArgs, keywords), or
     ((status, payload), None, None) for a body the handler refuses. keywords: what the pipeline call
     takes beyond the args, each only when the body sets it to something other than its default --
-    sample_rate (one of SAMPLE_RATES, not 16000) and tempo (TEMPO_MIN .. TEMPO_MAX, not 1.0) -- so a
+    sample_rate (one of SAMPLE_RATES, not 16000), tempo (TEMPO_MIN .. TEMPO_MAX, not 1.0) and loudness
+    (LOUDNESS_MIN .. LOUDNESS_MAX; there is no default value that means "off" but its absence) -- so a
     body without them makes exactly the call it always made. A true `long_form` adds
     long_form=True, which the handler takes out and answers by calling the long-form entry point,
     and segment_tokens when the body sets it."""
@@ -169,6 +190,11 @@ def _tts_args(body, voice_dir: str):
           or not TEMPO_MIN <= tempo <= TEMPO_MAX):  # (NaN fails the comparison)
         return (400, {"success": False, "error": f"不支持的语速倍率: {tempo} (支持: "
                                                  f"{TEMPO_MIN} - {TEMPO_MAX})"}), None, None
+    loudness = body.get("loudness")
+    if loudness is not None and (isinstance(loudness, bool) or not isinstance(loudness, (int, float))
+                                 or not LOUDNESS_MIN <= loudness <= LOUDNESS_MAX):  # (NaN fails the comparison)
+        return (400, {"success": False, "error": f"不支持的响度目标: {loudness} (支持: "
+                                                 f"{LOUDNESS_MIN} - {LOUDNESS_MAX} dB)"}), None, None
     sampling = {}
     for what in ("global_sampling", "semantic_sampling"):
         o = body.get(what)
@@ -228,6 +254,8 @@ def _tts_args(body, voice_dir: str):
         kw["sample_rate"] = rate
     if float(tempo) != 1.0:
         kw["tempo"] = float(tempo)
+    if loudness is not None:
+        kw["loudness"] = float(loudness)
     return None, args, kw
 
 
@@ -242,8 +270,9 @@ def handle_tts_json(body, pipeline, voice_dir: str = "assets/raf") -> Tuple[int,
         audio = pipeline.generate_long_speech(args, **kw) if long_form else pipeline.generate_speech(args, **kw)
     except Exception as e:  # noqa: BLE001 -- rendered as the reference's 500 body
         return 500, {"success": False, "error": f"生成TTS音频失败: {e}"}
-    wav = convert_samples_to_wav(audio, rate)
-    b64 = base64.standard_b64encode(wav).decode("ascii")
+    # (levelled PCM goes out at scale 1.0, as the stream route sends it: the peak rule would undo the target)
+    wav = levelled_samples_to_wav(audio, rate) if "loudness" in kw else convert_samples_to_wav(audio, rate)
+    b64 =base64.standard_b64encode(wav).decode("ascii")
     total = time.perf_counter() - t0
     out = {"success": True, "message": "TTS生成成功", "audio_base64": b64,
            "duration_ms": int(total * 1000), "rtf": calculate_rtf(audio, total, rate)}
@@ -280,7 +309,9 @@ def handle_tts_stream(body, pipeline, voice_dir: str = "assets/raf", chunk_frame
     samples already lie in (-1, 1). There is NO peak normalisation, unlike /api/tts
     (convert_samples_to_wav): the peak rule needs the whole utterance, which a stream does not have
     when its first sample goes out -- the same request is therefore quieter or louder here than in
-    /api/tts's WAV, by that rule's factor. Clamping and truncation are convert_samples_to_wav's.
+    /api/tts's WAV, by that rule's factor, unless the body sets `loudness`: then both routes send the
+    leveller's PCM at scale 1.0, byte for byte the same samples (the stream's lag 0.5 s behind the
+    vocoder at the leveller's defaults). Clamping and truncation are convert_samples_to_wav's.
     An optional `sample_rate` (SAMPLE_RATES) streams that rate instead of 16 kHz: the chunks are
     resampled on the GPU by a resampler that is exact over chunks, and the header carries the rate.
     A refused body gives /api/tts's status and JSON body (as one bytes item); so does a failure
