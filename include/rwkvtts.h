@@ -871,6 +871,115 @@ int rwkvtts_level_windows(rwkvtts_level* v, rwkvtts_level_window* w, int n);
 /* HIP-event time of the last launch triple (all three kernels, no copies), in ms; 0 before the first. */
 int rwkvtts_level_kernel_ms(rwkvtts_level* v, double* ms);
 
+/* ---- pitch: a formant-preserving pitch shift (period estimation and pitch-synchronous overlap-add,
+ * TD-PSOLA) on the GPU, the `pitch_shift` of the pipeline (no reference counterpart: the reference's
+ * only pitch control is the `pitch` property token, which a cloned voice does not get) -------------
+ * Runs on the 16 kHz PCM, first of the stages: before the stretch, the leveller and the resampler.
+ * n_out = n. One causal definition with a bounded look-ahead, so a stream's pieces are bitwise the
+ * one-shot result. The arithmetic contract (every output bit is defined by IEEE f32 rounded add,
+ * subtract and multiply, never fused, and one correctly rounded f32 divide; every decision is an
+ * integer):
+ *   Ha, Wc    frame hop and comparison length; Lmin, Lmax the period range; P0 the hop where unvoiced
+ *   f         double, per signal, 0.5 .. 2.0 (2^(semitones / 12)); above 1 is a higher voice
+ *   table     rows P = Lmin .. Lmax back to back, row P of 2P floats at offset
+ *             (P - Lmin) * (P + Lmin - 1): w_P[i] = (float)(0.5 - 0.5 * cos(2 * pi * (i + 0.5) / (2P))),
+ *             in double, i in [0, 2P). Every w is > 0.
+ *   zeros     every read of x outside [0, n) is +0
+ *   period    frame j (j >= 0) starts at c = j * Ha. For every lag t in [Lmin - 1, Lmax + 1]:
+ *             d(t) = sum_i (x[c+i] - x[c+i+t])^2 and m(t) = sum_i (x[c+i]^2 + x[c+i+t]^2), i in
+ *             [0, Wc): each a sequential f32 sum in ascending i from +0 -- a d term is one rounded
+ *             subtract and one rounded multiply, an m term two rounded multiplies and one rounded add,
+ *             then one rounded add onto the sum. Lag t in [Lmin, Lmax] qualifies iff
+ *             d(t) <= d(t-1) and d(t) <= d(t+1) and d(t) <= theta * m(t) (one rounded multiply) and
+ *             m(t) > floor; every comparison with a NaN is false. P_j = the lowest qualifying lag
+ *             (the minimum of an integer key, whatever the reduction tree), 0 (unvoiced) if none.
+ *             P(t) = P_{floor(t / Ha)} for a sample position t >= 0. Frames wholly past the signal's
+ *             end read zeros only, so they are unvoiced.
+ *   marks     two serial integer walks from sample 0. Analysis: a_0 = 0, a_{k+1} = a_k + p_k with
+ *             p_k = P(a_k), or P0 where that is 0. Synthesis: s_0 = 0, s_{q+1} = s_q +
+ *             max(1, (int)floor((double)P(s_q) / f + 0.5)) (one double divide, one double add), or
+ *             + P0 where P(s_q) is 0. Synthesis mark q takes the analysis mark k(q) nearest to it,
+ *             |a_k - s_q| least, the lower k on a tie.
+ *   output    grain q is x[a_k - p_k + i] * w_{p_k}[i], i in [0, 2 p_k), k = k(q), placed at
+ *             s_q - p_k + i. Over the grains that cover output o, in ascending q, from num = den = +0:
+ *             num = num + w * x (one rounded multiply, one rounded add), den = den + w.
+ *             y[o] = num / den (correctly rounded), +0 where no grain covers o.
+ * So silence comes back bit for bit (no frame is voiced, num = +0, den > 0). Where every frame is
+ * unvoiced (a_k = s_k = k * P0), and at f = 1.0 (s_q = a_q), every grain that covers o reads x[o]
+ * itself: y = (sum w x) / (sum w) over G same-signed products, so |y - x| <= 2 G u |x| (1 + 2^-20) +
+ * G 2^-149 with u = 2^-24; G = 2 where all is unvoiced, under 4 ulp. A non-finite sample leaves the
+ * outputs from its first frame on unspecified; nothing is read or written out of bounds. Every
+ * default below is untuned and nobody has listened to the output: the repository has no real
+ * checkpoint. */
+typedef struct {
+  uint32_t struct_size;
+  int32_t hop;      /* Ha: 1 .. 4096; 0 = 160 (10 ms) */
+  int32_t window;   /* Wc: 1 .. 4096; 0 = 640 */
+  int32_t lag_min;  /* Lmin: 2 .. 1024; 0 = 32 (500 Hz) */
+  int32_t lag_max;  /* Lmax: Lmin .. 1024; 0 = 320 (50 Hz) */
+  int32_t unvoiced; /* P0: Lmin .. Lmax; 0 = 80 */
+  float theta;      /* in (0, 1]; 0 = 0.2 */
+  float floor;      /* finite, > 0; 0 = 1e-3 */
+} rwkvtts_pitch_desc;
+/* The library's own table builder (host only): out[(Lmax - Lmin + 1) * (Lmax + Lmin)]. Anything
+ * outside the ranges above (NaN included), and a factor outside 0.5 .. 2.0 (NaN included), is
+ * RWKVTTS_EINVAL, here and in every call that takes a desc or a factor. */
+int rwkvtts_pitch_table(const rwkvtts_pitch_desc* desc, float* out);
+/* Streaming plan (host only, a pure function). The state after outputs [0, e) is two marks:
+ * s = the largest synthesis mark <= max(0, e - Lmax), a = the largest analysis mark <=
+ * max(0, s - Lmax). Both walks go on from a mark by the periods alone, no grain of an earlier
+ * synthesis mark reaches output e (a grain is at most 2 Lmax long), and no earlier analysis mark is
+ * the nearest to a later synthesis mark (the next one, at most Lmax on, is nearer): two integers are
+ * the whole state, the periods being recomputed from the kept samples. With samples [0, n_known)
+ * known, outputs [0, out_first) done and (a_prev, s_prev) their state (a pair outside the ranges a
+ * walk can leave -- s_prev in (max(0, out_first - Lmax) - 2 Lmax, max(0, out_first - Lmax)], a_prev in
+ * (max(0, s_prev - Lmax) - Lmax, max(0, s_prev - Lmax)], neither negative -- is RWKVTTS_EINVAL):
+ * *out_ready_end = max(0, n_known - (Wc + 3 Lmax)): output o is covered by grains of synthesis marks
+ * below o + Lmax, whose analysis marks lie below o + 2 Lmax, whose frames start at or below that and
+ * read Wc + Lmax samples on; the grains read below o + 3 Lmax. With final (n_known is the signal's
+ * length) it is n_known.
+ * *in_first_needed = max(0, min(a_prev - Lmax, floor(a_prev / Ha) * Ha)): the earliest grain and the
+ * frame of a_prev -- samples before it are never read again; a stream keeps fewer than
+ * Wc + 9 Lmax + Ha samples once the ready outputs are out. Either pointer may be NULL. Monotone in
+ * n_known. */
+int rwkvtts_pitch_plan(const rwkvtts_pitch_desc* desc, int64_t n_known, int final, int64_t out_first, int64_t a_prev,
+                       int64_t s_prev, int64_t* out_ready_end, int64_t* in_first_needed);
+typedef struct rwkvtts_pitch rwkvtts_pitch;
+/* table == NULL: the table of rwkvtts_pitch_table; otherwise the caller's table (copied). */
+int rwkvtts_pitch_create(int device, const rwkvtts_pitch_desc* desc, const float* table, rwkvtts_pitch** out);
+int rwkvtts_pitch_destroy(rwkvtts_pitch* p);
+/* n signals (ragged, each at most 2^30 samples), each with its own factor, in one launch triple
+ * (period: a workgroup per frame; marks: a wave per signal; synthesis: a lane per output sample).
+ * Host buffers; out[i] has capacity n_in[i]. n_in[i] == 0 writes nothing. Calls on one handle
+ * serialise on its lock. */
+int rwkvtts_pitch_batch(rwkvtts_pitch* p, const float* const* in, const int64_t* n_in, const double* factor, int n,
+                        float* const* out);
+typedef struct {
+  uint32_t struct_size;
+  const float* in;    /* points at sample in_first of the signal */
+  int64_t in_first;
+  int64_t n_in;
+  int32_t final;      /* 1: in_first + n_in is the signal's length */
+  double factor;
+  int64_t out_first;  /* outputs [out_first, out_first + out_count) */
+  int64_t a_prev;     /* the state after outputs [0, out_first): 0, 0 for out_first 0, else the */
+  int64_t s_prev;     /* last call's a_last, s_last */
+  int64_t out_count;
+  float* out;         /* capacity out_count */
+  int64_t a_last;     /* out: the state after the last output written (the state given if */
+  int64_t s_last;     /* out_count is 0) */
+} rwkvtts_pitch_window;
+/* n windows (of any signals, any factors) in one launch triple: outputs [out_first, + out_count) of
+ * the whole-signal result, bitwise, whatever follows the known samples. RWKVTTS_EINVAL before
+ * anything is launched (and nothing written, the state included) if a window asks for more than
+ * rwkvtts_pitch_plan allows: out_first + out_count > out_ready_end(in_first + n_in, final),
+ * in_first > in_first_needed, or a state that no walk can have left. */
+int rwkvtts_pitch_windows(rwkvtts_pitch* p, rwkvtts_pitch_window* w, int n);
+/* HIP-event time of the last launch triple (all three kernels, no copies), in ms; 0 before the first. */
+int rwkvtts_pitch_kernel_ms(rwkvtts_pitch* p, double* ms);
+/* HIP-event time of the last call's marks kernel alone, the serial part, in ms; 0 before the first. */
+int rwkvtts_pitch_walk_ms(rwkvtts_pitch* p, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

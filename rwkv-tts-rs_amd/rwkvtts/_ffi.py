@@ -212,6 +212,20 @@ class LevelWindow(ctypes.Structure):
                 ("s_last", ctypes.c_float), ("n_last", ctypes.c_int64), ("g_last", ctypes.c_float)]
 
 
+class PitchDesc(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("hop", ctypes.c_int32), ("window", ctypes.c_int32),
+                ("lag_min", ctypes.c_int32), ("lag_max", ctypes.c_int32), ("unvoiced", ctypes.c_int32),
+                ("theta", ctypes.c_float), ("floor", ctypes.c_float)]
+
+
+class PitchWindow(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("in_", ctypes.c_void_p), ("in_first", ctypes.c_int64),
+                ("n_in", ctypes.c_int64), ("final", ctypes.c_int32), ("factor", ctypes.c_double),
+                ("out_first", ctypes.c_int64), ("a_prev", ctypes.c_int64), ("s_prev", ctypes.c_int64),
+                ("out_count", ctypes.c_int64), ("out", ctypes.c_void_p), ("a_last", ctypes.c_int64),
+                ("s_last", ctypes.c_int64)]
+
+
 # Every symbol include/rwkvtts.h declares (checked by tests/test_abi.py against the header).
 EXPORTS = {
     "rwkvtts_synth_weights": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p]),
@@ -337,6 +351,19 @@ EXPORTS = {
                                            ctypes.c_int, ctypes.c_void_p]),
     "rwkvtts_level_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(LevelWindow), ctypes.c_int]),
     "rwkvtts_level_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    # pitch: table and plan (host only), batched / exact stream windows
+    "rwkvtts_pitch_table": (ctypes.c_int, [ctypes.POINTER(PitchDesc), ctypes.c_void_p]),
+    "rwkvtts_pitch_plan": (ctypes.c_int, [ctypes.POINTER(PitchDesc), ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                          ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                                          ctypes.POINTER(ctypes.c_int64)]),
+    "rwkvtts_pitch_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(PitchDesc), ctypes.c_void_p,
+                                            ctypes.POINTER(ctypes.c_void_p)]),
+    "rwkvtts_pitch_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "rwkvtts_pitch_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_int, ctypes.c_void_p]),
+    "rwkvtts_pitch_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PitchWindow), ctypes.c_int]),
+    "rwkvtts_pitch_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    "rwkvtts_pitch_walk_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None

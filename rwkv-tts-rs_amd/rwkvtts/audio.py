@@ -704,6 +704,149 @@ class LevelStream(_ExactStream):
         return self.v.plan(n_known, False, self._block_next)[1]
 
 
+# ---- pitch shift on the GPU ------------------------------------------------------------------
+def pitch_factor(semitones: float) -> float:
+    """f = 2^(semitones / 12), in double: what the native side takes per signal."""
+    return 2.0 ** (float(semitones) / 12.0)
+
+
+def _pitch_table(lag_min: int, lag_max: int) -> np.ndarray:
+    """Rows P = lag_min .. lag_max back to back, row P at (P - lag_min) * (P + lag_min - 1):
+    w_P[i] = (float)(0.5 - 0.5 * cos(2 * pi * (i + 0.5) / (2P))), in double: the table both sides read."""
+    rows = []
+    for P in range(lag_min, lag_max + 1):
+        i = np.arange(2 * P, dtype=np.float64)
+        rows.append((0.5 - 0.5 * np.cos((2.0 * np.pi * (i + 0.5)) / float(2 * P))).astype(F32))
+    return np.concatenate(rows)
+
+
+class PitchShifter(_NativeStage):
+    """A formant-preserving pitch shift (period estimation and pitch-synchronous overlap-add,
+    TD-PSOLA) as HIP kernels (csrc/pitch.hip; the arithmetic contract is in include/rwkvtts.h,
+    DESIGN.md §25): per frame of `hop` samples the period is the lowest lag in lag_min .. lag_max at
+    which the squared difference over `window` samples has a local minimum below theta times the
+    energy (no such lag: unvoiced); two-period Hann grains around pitch marks one period apart are
+    laid down again period / factor apart and normalised by the summed windows. The fundamental moves
+    by the factor, the grains (and so the spectral envelope) stay, unvoiced sound and silence pass,
+    n_out = n. One causal definition, so a stream's pieces are bitwise the one-shot result. The
+    pipeline applies it at 16 kHz, first of the stages. A shift is in semitones per signal, -12 .. 12.
+
+    0 means the default as in the C desc: hop 160, window 640, lag_min 32, lag_max 320 (50 .. 500 Hz),
+    unvoiced 80, theta 0.2, floor 1e-3. Every default is untuned and nobody has listened to the
+    output: the repository has no real checkpoint. The kernels read the table `_pitch_table` builds.
+
+    evaluator: a callable (shifter, items) -> [(ndarray, a_last, s_last)] standing in for the native
+    window call, items being [(samples from in_first on, in_first, final, factor, out_first, a_prev,
+    s_prev, out_count)]; no GPU object is created then (the host-only plan / table entry points are
+    still the library's)."""
+    _NAME = "pitch"
+
+    def __init__(self, device: int = 0, hop: int = 160, window: int = 640, lag_min: int = 32, lag_max: int = 320,
+                 unvoiced: int = 80, theta: float = 0.2, floor: float = 1e-3, evaluator=None):
+        self.device = int(device)
+        self._desc = _ffi.PitchDesc(struct_size=ctypes.sizeof(_ffi.PitchDesc), hop=int(hop), window=int(window),
+                                    lag_min=int(lag_min), lag_max=int(lag_max), unvoiced=int(unvoiced),
+                                    theta=float(theta), floor=float(floor))
+        super().__init__(evaluator)
+        self.plan(0, False)  # (refuses a bad description before anything is built)
+        self.hop, self.window = int(hop) or 160, int(window) or 640
+        self.lag_min, self.lag_max, self.unvoiced = int(lag_min) or 32, int(lag_max) or 320, int(unvoiced) or 80
+        self.theta, self.floor = F32(theta) or F32(0.2), F32(floor) or F32(1e-3)
+        self.lookahead = self.window + 3 * self.lag_max  # samples an output waits for
+        self.table = _pitch_table(self.lag_min, self.lag_max)
+        self._create(self.table)
+
+    @staticmethod
+    def factor(semitones: float) -> float:
+        f = pitch_factor(semitones)
+        if not 0.5 <= f <= 2.0:  # (NaN fails)
+            raise ValueError("a pitch shift must be in [-12, 12] semitones")
+        return f
+
+    # ---- host-only plan ----
+    def plan(self, n_known: int, final: bool, out_first: int = 0, a_prev: int = 0, s_prev: int = 0):
+        """(out_ready_end, in_first_needed) of rwkvtts_pitch_plan."""
+        end, first = ctypes.c_int64(), ctypes.c_int64()
+        _native("pitch_plan", ctypes.byref(self._desc), int(n_known), 1 if final else 0, int(out_first), int(a_prev),
+                int(s_prev), ctypes.byref(end), ctypes.byref(first))
+        return end.value, first.value
+
+    # ---- the kernels ----
+    def shift_windows(self, items) -> list:
+        """[(samples from in_first on, in_first, final, factor, out_first, a_prev, s_prev, out_count)]
+        -> [(outputs [out_first, + out_count) of the whole-signal result, a_last, s_last)], the state
+        after each window's last output, all windows in one launch triple. Raises
+        RwkvTtsError(EINVAL), with nothing computed, if a window asks for more than plan() allows."""
+        items = [(np.ascontiguousarray(x, dtype=F32).reshape(-1), int(a), bool(fin), float(f), int(o), int(ap), int(sp),
+                  int(c)) for x, a, fin, f, o, ap, sp, c in items]
+        if self._evaluator is not None:
+            for x, a, fin, f, o, ap, sp, c in items:  # the native call's own refusals, from the host-only plan
+                if not 0.5 <= f <= 2.0:
+                    raise _ffi.RwkvTtsError(_ffi.EINVAL, "pitch_windows")
+                end, first = self.plan(a + x.size, fin, o, ap, sp)
+                if c < 0 or (c > 0 and (o + c > end or a > first)):
+                    raise _ffi.RwkvTtsError(_ffi.EINVAL, "pitch_windows")
+            return [(np.ascontiguousarray(y, dtype=F32), int(al), int(sl)) for y, al, sl in self._evaluator(self, items)]
+        ws, outs = self._windows("pitch_windows", _ffi.PitchWindow, items, factor=3, out_first=4, a_prev=5, s_prev=6)
+        return [(o, int(w.a_last), int(w.s_last)) for o, w in zip(outs, ws)]
+
+    def shift_batch(self, signals, semitones) -> list:
+        """[signal], [semitones] -> [shifted signal], ragged, a shift per signal, in one launch triple;
+        an empty signal gives an empty one."""
+        xs = [np.ascontiguousarray(x, dtype=F32).reshape(-1) for x in signals]
+        fs = [self.factor(s) for s in semitones]
+        if len(xs) != len(fs):
+            raise ValueError("shift_batch: one shift per signal")
+        if self._evaluator is not None:
+            return [y for y, _, _ in self.shift_windows([(x, 0, True, f, 0, 0, 0, x.size) for x, f in zip(xs, fs)])]
+        if not xs:
+            return []
+        outs, ins, lens, ous = self._ragged(xs, [x.size for x in xs])
+        self._call("pitch_batch", ins, lens, (ctypes.c_double * len(fs))(*fs), len(xs), ous)
+        return outs
+
+    def shift(self, x, semitones: float) -> np.ndarray:
+        return self.shift_batch([x], [semitones])[0]
+
+    def stream(self, semitones: float) -> "PitchStream":
+        return PitchStream(self, semitones)
+
+    def walk_ms(self) -> float:
+        """HIP-event time of the last call's marks kernel alone (the serial walk)."""
+        ms = ctypes.c_double()
+        _native("pitch_walk_ms", self._h, ctypes.byref(ms))
+        return ms.value
+
+
+class PitchStream(_ExactStream):
+    """PitchShifter.stream(semitones): feed(pcm_chunk, final=False) -> the outputs that became exact
+    with it. The concatenation of what feed returns is bitwise PitchShifter.shift(the concatenated
+    input, semitones), however the input was cut. An output goes out once window + 3 * lag_max samples
+    after it are known (0.1 s at the defaults); the kept tail is what rwkvtts_pitch_plan asks for,
+    fewer than window + 9 * lag_max + hop samples."""
+
+    def __init__(self, shifter: PitchShifter, semitones: float):
+        super().__init__()
+        self.p = shifter
+        self.f = shifter.factor(semitones)
+        self._out_next = 0       # outputs [0, _out_next) went out
+        self._state = (0, 0)     # (a, s) after them
+
+    def _emit(self, n_known, final):
+        a, s = self._state
+        end, _ = self.p.plan(n_known, final, self._out_next, a, s)
+        count = end - self._out_next
+        if count <= 0:
+            return np.zeros(0, dtype=F32)
+        out, a, s = self.p.shift_windows([(self._tail, self._tail_first, final, self.f, self._out_next, a, s, count)])[0]
+        self._state = (a, s)
+        self._out_next += count
+        return out
+
+    def _first_needed(self, n_known):
+        return self.p.plan(n_known, False, self._out_next, *self._state)[1]
+
+
 # ---- normalisation / trimming ------------------------------------------------------------
 def audio_volume_normalize(audio, coeff: float = 0.2) -> np.ndarray:
     x = np.asarray(audio, dtype=F32).copy()

@@ -18,6 +18,11 @@ They and the long-form pair take `loudness` (no reference counterpart: the refer
 finished WAV): None leaves the PCM at the vocoder's scale; a target in dB, -40 .. -10, levels the
 16 kHz PCM on the GPU to that K-weighted loudness under a peak ceiling (audio.Leveller, DESIGN.md
 section 24), after the stretch and before the resampler, exact over stream chunks.
+All five also take `pitch_shift` (no reference counterpart: the reference's only pitch control is the
+`pitch` property token, which a cloned voice does not get): None / 0 leaves the PCM as it is; a shift
+in semitones, -12 .. 12, moves the fundamental of the 16 kHz PCM on the GPU and keeps its spectral
+envelope and its length (audio.PitchShifter), first of the stages -- before the
+stretch, and in long-form after the join -- exact over stream chunks.
 LightweightTtsPipelineArgs.global_sampling / semantic_sampling (no reference counterpart: the
 reference carries temperature / top_p / top_k and samples with fixed values) set the token
 generator's temperature, top-p and top-k per phase (runtime.PhaseSampling); a value outside its
@@ -134,12 +139,14 @@ class LongSpeech(np.ndarray):
         return c
 
 
-def audio_stages(stretcher, tempo, resampler, leveller=None, loudness=None) -> list:
-    """The stages behind the vocoder in the order they apply -- the stretch at 16 kHz, then the
-    leveller, then the resampler; None is no stage -- each as (batch, stream): batch([pcm]) -> [pcm]
-    in one native call (one tempo, one loudness for the call), stream() -> an object whose
-    feed(pcm, final) is exact over chunks."""
+def audio_stages(stretcher, tempo, resampler, leveller=None, loudness=None, shifter=None, pitch_shift=None) -> list:
+    """The stages behind the vocoder in the order they apply -- the pitch shift at 16 kHz, then the
+    stretch, then the leveller, then the resampler; None is no stage -- each as (batch, stream):
+    batch([pcm]) -> [pcm] in one native call (one shift, one tempo, one loudness for the call),
+    stream() -> an object whose feed(pcm, final) is exact over chunks."""
     stages = []
+    if shifter is not None:
+        stages.append((lambda pcm: shifter.shift_batch(pcm, [pitch_shift] * len(pcm)), lambda: shifter.stream(pitch_shift)))
     if stretcher is not None:
         stages.append((lambda pcm: stretcher.stretch_batch(pcm, [tempo] * len(pcm)), lambda: stretcher.stream(tempo)))
     if leveller is not None:
@@ -171,7 +178,8 @@ class LightweightTtsPipeline:
         self._stretcher = None  # audio.TimeStretcher (created on the first tempo other than 1.0, kept)
         self._joiners = {}  # (trim, keep, fade) -> audio.Joiner (created on first use, kept)
         self._levellers = {}  # horizon -> audio.Leveller (created on the first loudness, kept)
-        self._stage_cache_lock = threading.Lock()  # guards all four (the server's worker threads share the pipeline)
+        self._shifter = None  # audio.PitchShifter (created on the first pitch_shift other than 0, kept)
+        self._stage_cache_lock = threading.Lock()  # guards all five (the server's worker threads share the pipeline)
 
     # ---- output rates other than 16 kHz (no reference counterpart: the reference emits 16 kHz only)
     def resampler(self, sample_rate: Optional[int]):
@@ -234,11 +242,31 @@ class LightweightTtsPipeline:
                 v = self._levellers[key] = Leveller(device=getattr(self.codec, "device", 0), horizon=key)
         return v
 
-    def _stages(self, sample_rate: Optional[int], tempo: Optional[float],
-                loudness: Optional[float] = None):  # -> (stages, output rate)
+    # ---- pitch (no reference counterpart: the reference has the `pitch` property token only)
+    def shifter(self, pitch_shift: Optional[float]):
+        """None for None / 0 (nothing is created: the PCM is the vocoder's); otherwise the pipeline's
+        one PitchShifter (the untuned defaults of audio.PitchShifter), on the codec's GPU. The shift
+        is in semitones per call, not a part of the object. A shift outside -12 .. 12 raises
+        ValueError before anything is generated."""
+        if pitch_shift is None:
+            return None
+        if isinstance(pitch_shift, bool) or not -12.0 <= float(pitch_shift) <= 12.0:  # (NaN fails)
+            raise ValueError("pitch_shift must be in [-12, 12] semitones")
+        if float(pitch_shift) == 0.0:
+            return None
+        with self._stage_cache_lock:
+            if self._shifter is None:
+                from .audio import PitchShifter
+                self._shifter = PitchShifter(device=getattr(self.codec, "device", 0))
+        return self._shifter
+
+    def _stages(self, sample_rate: Optional[int], tempo: Optional[float], loudness: Optional[float] = None,
+                pitch_shift: Optional[float] = None):  # -> (stages, output rate)
         rs = self.resampler(sample_rate)
         lv = self.leveller(loudness)
-        return (audio_stages(self.stretcher(tempo), tempo, rs, lv, None if lv is None else float(loudness)),
+        sh = self.shifter(pitch_shift)
+        return (audio_stages(self.stretcher(tempo), tempo, rs, lv, None if lv is None else float(loudness),
+                             sh, None if sh is None else float(pitch_shift)),
                 rs.sr_out if rs else SAMPLE_RATE)
 
     # ---- text / attribute handling (:148-193)
@@ -300,7 +328,8 @@ class LightweightTtsPipeline:
                                pinned_voice=rg is not None and rs is None)
 
     def generate_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
-                        tempo: Optional[float] = None, loudness: Optional[float] = None) -> np.ndarray:
+                        tempo: Optional[float] = None, loudness: Optional[float] = None,
+                        pitch_shift: Optional[float] = None) -> np.ndarray:
         """sample_rate None / 16000: the vocoder's 16 kHz PCM. Any other rate: that PCM resampled on
         the GPU (resampler()); the failed-request second of silence is sample_rate zeros.
         tempo None / 1.0: nothing. Any other: the 16 kHz PCM time-stretched on the GPU (stretcher())
@@ -308,9 +337,12 @@ class LightweightTtsPipeline:
         loudness None: nothing. A target in dB, -40 .. -10 (-23, -16, ..): the 16 kHz PCM levelled on
         the GPU (leveller()) after the stretch and before the resampler; the failed-request second of
         silence is not levelled.
+        pitch_shift None / 0: nothing. A shift in semitones, -12 .. 12: the 16 kHz PCM's fundamental
+        moved on the GPU (shifter()) before the stretch, its envelope and length kept; independent of
+        args.pitch, which stays the property token.
         args.global_sampling / semantic_sampling outside their ranges raise ValueError, like tempo."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo, loudness)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift)
         try:
             req = self._request(args)
         except ValueError:  # untokenisable text: the request fails -> empty result
@@ -325,7 +357,7 @@ class LightweightTtsPipeline:
 
     def stream_speech(self, args: LightweightTtsPipelineArgs, chunk_frames: int = 16,
                       sample_rate: Optional[int] = None, tempo: Optional[float] = None,
-                      loudness: Optional[float] = None):
+                      loudness: Optional[float] = None, pitch_shift: Optional[float] = None):
         """generate_speech as a generator of float32 PCM chunks (SpeechChunk: an ndarray that also
         carries t0, t1, n_known, done), each decoded while the request is still generating tokens.
 
@@ -351,7 +383,11 @@ class LightweightTtsPipeline:
         loudness (a target in dB, -40 .. -10): Leveller.stream(loudness) sits between the two, and the
         concatenation is bitwise generate_speech(args, loudness=...). A levelled item lags its frames
         by up to lookahead + 1 blocks, 0.5 s at the defaults: a block goes out once the four blocks
-        after it are complete."""
+        after it are complete.
+
+        pitch_shift (semitones, -12 .. 12, not 0): PitchShifter.stream(pitch_shift) comes first, and
+        the concatenation is bitwise generate_speech(args, pitch_shift=...). A shifted item lags its
+        frames by the shifter's look-ahead, 0.1 s at the defaults."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         check_sampling(args)
@@ -360,18 +396,22 @@ class LightweightTtsPipeline:
         except ValueError:  # untokenisable text: the request fails -> one second of silence
             req = None
         self.leveller(loudness)  # (refuses a bad loudness here, not at the first next())
-        return self.stream_request(req, chunk_frames, sample_rate=sample_rate, tempo=tempo, loudness=loudness)
+        if pitch_shift is None:
+            return self.stream_request(req, chunk_frames, sample_rate=sample_rate, tempo=tempo, loudness=loudness)
+        self.shifter(pitch_shift)  # (the same for a bad shift)
+        return self.stream_request(req, chunk_frames, sample_rate=sample_rate, tempo=tempo, loudness=loudness,
+                                   pitch_shift=pitch_shift)
 
     def stream_request(self, req: Optional[TtsBatchRequest], chunk_frames: int = 16,
                        sample_rate: Optional[int] = None, tempo: Optional[float] = None,
-                       loudness: Optional[float] = None):
+                       loudness: Optional[float] = None, pitch_shift: Optional[float] = None):
         """stream_speech for a request that is already built (None: a request that failed before it
         was submitted)."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         if req is not None:
             check_sampling(req.args)
-        stages, rate = self._stages(sample_rate, tempo, loudness)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift)
         streams = [stream() for _, stream in stages]
         H = self.codec.halo()
         g, sem, t0, yielded, status = None, [], 0, False, 0
@@ -406,14 +446,17 @@ class LightweightTtsPipeline:
 
     def generate_speech_batch(self, batch_args: Sequence[LightweightTtsPipelineArgs],
                               sample_rate: Optional[int] = None, tempo: Optional[float] = None,
-                              loudness: Optional[float] = None) -> List[np.ndarray]:
+                              loudness: Optional[float] = None,
+                              pitch_shift: Optional[float] = None) -> List[np.ndarray]:
         """sample_rate other than None / 16000: the whole batch is resampled in one resample_batch
         call (a failed item stays an empty array). tempo other than None / 1.0: the whole batch is
         first stretched in one stretch_batch call, one tempo for the call. loudness other than None:
-        the whole batch is levelled in one level_batch call between the two, one target for the call."""
+        the whole batch is levelled in one level_batch call between the two, one target for the call.
+        pitch_shift other than None / 0: the whole batch is shifted in one shift_batch call before
+        all of them, one shift for the call."""
         for a in batch_args:
             check_sampling(a)
-        stages, _ = self._stages(sample_rate, tempo, loudness)
+        stages, _ = self._stages(sample_rate, tempo, loudness, pitch_shift)
         reqs, idx = [], []
         for i, a in enumerate(batch_args):
             try:
@@ -488,7 +531,8 @@ class LightweightTtsPipeline:
     def generate_long_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
                              tempo: Optional[float] = None, segment_tokens: int = 64, pauses=None,
                              trim: bool = True, keep: int = 800, fade: int = 80,
-                             loudness: Optional[float] = None) -> "LongSpeech":
+                             loudness: Optional[float] = None,
+                             pitch_shift: Optional[float] = None) -> "LongSpeech":
         """generate_speech for a text of any length: the text is cut into segments of at most
         segment_tokens text tokens (segment.split_text), the segments decode side by side in the
         manager's slots and engines with one voice (_long_submit), and their PCM is joined on the
@@ -501,9 +545,10 @@ class LightweightTtsPipeline:
         segment with trim=False gives bitwise generate_speech(args, ...). segment_tokens, pauses,
         keep and fade are unmeasured defaults. loudness levels the joined
         signal as one (generate_speech), so the segments, decoded as independent requests, come out
-        at one level; the second of silence is not levelled."""
+        at one level; the second of silence is not levelled. pitch_shift shifts the joined signal as
+        one, after the join and before the stretch."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo, loudness)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)
         if plan is None:
@@ -524,7 +569,8 @@ class LightweightTtsPipeline:
 
     def stream_long_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
                            tempo: Optional[float] = None, segment_tokens: int = 64, pauses=None,
-                           trim: bool = True, keep: int = 800, fade: int = 80, loudness: Optional[float] = None):
+                           trim: bool = True, keep: int = 800, fade: int = 80, loudness: Optional[float] = None,
+                           pitch_shift: Optional[float] = None):
         """generate_long_speech as a generator of LongSpeech items, one per segment, in order: segment
         i is emitted once it and every segment before it are done -- decoded, joined alone with its
         gap (a piece depends on its own segment only), and fed through the stages' exact streams,
@@ -534,9 +580,10 @@ class LightweightTtsPipeline:
         resampled outputs still waiting for the next segment's samples). Failed segments before the
         first good one are held back until it arrives, so a text whose every segment fails yields
         the one second of silence alone. Streaming inside a segment is out of scope. With loudness
-        an item also waits for the leveller's look-ahead (up to 0.5 s of the next segment)."""
+        an item also waits for the leveller's look-ahead (up to 0.5 s of the next segment), with
+        pitch_shift for the shifter's (0.1 s)."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo, loudness)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)
         if plan is None:

@@ -49,6 +49,13 @@
   the resampler. /api/tts then writes its WAV at scale 1.0 (`levelled_samples_to_wav`: no peak rule,
   which would undo the target), so its samples are byte for byte the PCM /api/tts/stream sends for
   the same body and seed. Without the field the routes are unchanged.
+* `pitch_shift` in the body of both TTS routes (no reference counterpart): a JSON number in
+  [PITCH_SHIFT_MIN, PITCH_SHIFT_MAX] = [-12, 12] semitones, anything else a 400; above 0 is a higher
+  voice. It is not `pitch`: `pitch` keeps the reference's meaning, the model's five-class property
+  token, which a request with a `voice_id` does not get at all; `pitch_shift` is a continuous shift
+  of the finished 16 kHz PCM's fundamental on the GPU that keeps the spectral envelope and the
+  length (audio.PitchShifter), before the stretch, and works for every voice. Without the field (or
+  with 0) the routes are unchanged.
 * `handle_tts_stream(body, pipeline, voice_dir)` (no reference counterpart): the same request as a
   WAV stream, POST /api/tts/stream -- audio while the request is still decoding, at a fixed scale
   (no peak normalisation: that needs the whole utterance).
@@ -112,6 +119,9 @@ SEGMENT_TOKENS_MIN, SEGMENT_TOKENS_MAX = 8, 256
 # `loudness` of the same bodies (no reference counterpart): the leveller's target in dB (LUFS-like:
 # K-weighted, -23 broadcast, -16 streaming); the pipeline's range
 LOUDNESS_MIN, LOUDNESS_MAX = -40.0, -10.0
+# `pitch_shift` of the same bodies (no reference counterpart): semitones, an octave either way -- the
+# kernel's own range
+PITCH_SHIFT_MIN, PITCH_SHIFT_MAX = -12.0, 12.0
 
 
 def map_speed(speed) -> str:
@@ -165,8 +175,9 @@ def _tts_args(body, voice_dir: str):
     """The request body of /api/tts -> (None, LightweightTtsPipelineArgs, keywords), or
     ((status, payload), None, None) for a body the handler refuses. keywords: what the pipeline call
     takes beyond the args, each only when the body sets it to something other than its default --
-    sample_rate (one of SAMPLE_RATES, not 16000), tempo (TEMPO_MIN .. TEMPO_MAX, not 1.0) and loudness
-    (LOUDNESS_MIN .. LOUDNESS_MAX; there is no default value that means "off" but its absence) -- so a
+    sample_rate (one of SAMPLE_RATES, not 16000), tempo (TEMPO_MIN .. TEMPO_MAX, not 1.0), loudness
+    (LOUDNESS_MIN .. LOUDNESS_MAX; there is no default value that means "off" but its absence) and
+    pitch_shift (PITCH_SHIFT_MIN .. PITCH_SHIFT_MAX, not 0) -- so a
     body without them makes exactly the call it always made. A true `long_form` adds
     long_form=True, which the handler takes out and answers by calling the long-form entry point,
     and segment_tokens when the body sets it."""
@@ -195,6 +206,13 @@ def _tts_args(body, voice_dir: str):
                                  or not LOUDNESS_MIN <= loudness <= LOUDNESS_MAX):  # (NaN fails the comparison)
         return (400, {"success": False, "error": f"不支持的响度目标: {loudness} (支持: "
                                                  f"{LOUDNESS_MIN} - {LOUDNESS_MAX} dB)"}), None, None
+    shift = body.get("pitch_shift")
+    if shift is None:
+        shift = 0.0
+    elif (isinstance(shift, bool) or not isinstance(shift, (int, float))
+          or not PITCH_SHIFT_MIN <= shift <= PITCH_SHIFT_MAX):  # (NaN fails the comparison)
+        return (400, {"success": False, "error": f"不支持的音高偏移: {shift} (支持: "
+                                                 f"{PITCH_SHIFT_MIN} - {PITCH_SHIFT_MAX} 半音)"}), None, None
     sampling = {}
     for what in ("global_sampling", "semantic_sampling"):
         o = body.get(what)
@@ -256,6 +274,8 @@ def _tts_args(body, voice_dir: str):
         kw["tempo"] = float(tempo)
     if loudness is not None:
         kw["loudness"] = float(loudness)
+    if float(shift) != 0.0:
+        kw["pitch_shift"] = float(shift)
     return None, args, kw
 
 

@@ -35,4 +35,4 @@ def main(files):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1:] or ["lm_kernels.hip", "sampler.hip", "codec.hip", "mel.hip", "resample.hip", "tsm.hip", "join.hip", "level.hip", "engine.hip"]))
+    sys.exit(main(sys.argv[1:] or ["lm_kernels.hip", "sampler.hip", "codec.hip", "mel.hip", "resample.hip", "tsm.hip", "join.hip", "level.hip", "pitch.hip", "engine.hip"]))
