@@ -176,6 +176,7 @@ typedef struct {
 #define RWKVTTS_FORM_SEPARATE_LNOUT 16u /* one-row steps: ln_out launch, not folded into the head GEMM */
 #define RWKVTTS_FORM_SEPARATE_EMBED 32u /* decode steps: k_embed launch, not folded into layer 0's LayerNorm */
 #define RWKVTTS_FORM_EXACT_SAMPLER 64u /* k_advance: always the exact sequential-sum walk (no certificate) */
+#define RWKVTTS_FORM_VALUE_TILE_32X64 128u /* k_ffn_persist, 17..32 rows: 32 x 64 value tiles, not 16 x 128 */
 
 #define RWKVTTS_QUANT_NONE 0
 #define RWKVTTS_QUANT_INT8 1 /* 128-element blocks along K: f16 (min, max), u8 q; w = min + q (max - min)/255 */
@@ -453,6 +454,11 @@ int rwkvtts_debug_advance(rwkvtts_engine* e, const float* logits, int n_rows, co
  * (1.0, 0.95) gives what rwkvtts_debug_advance gives for its first 72 bytes. */
 int rwkvtts_debug_advance_ex(rwkvtts_engine* e, const float* logits, int n_rows, const void* rows, int exact,
                              int n_steps, int32_t* out_tok, int32_t* out_used, int32_t* out_phase);
+
+/* Test hook, not part of the drop-in surface: rows [0, n_rows) x head_rows of the logits that the
+ * engine's last forward step left on the device (n_rows <= the engine's row capacity; a decode step
+ * of R slots wrote rows [0, R)). `out` is a HOST buffer of n_rows x head_rows floats. */
+int rwkvtts_debug_last_logits(rwkvtts_engine* e, int n_rows, int head_rows, float* out);
 
 /* ---- codec: BiCodecDetokenize via ORT (lightweight_tts_pipeline.rs:606-622,706-730) ----- */
 typedef struct rwkvtts_codec rwkvtts_codec;

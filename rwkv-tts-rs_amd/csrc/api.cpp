@@ -136,6 +136,14 @@ int rwkvtts_debug_advance_ex(rwkvtts_engine* e, const float* logits, int n_rows,
   })
 }
 
+// Test hook (not part of the drop-in surface): rows [0, n_rows) x head_rows of the logits the engine's
+// last forward step left on the device (the head GEMM's split-K slabs summed in order)
+int rwkvtts_debug_last_logits(rwkvtts_engine* e, int n_rows, int head_rows, float* out) {
+  RT_CHECK(e && out, RWKVTTS_EINVAL, "debug_last_logits: bad arguments");
+  LOCK(e);
+  GUARD({ return e->eng.debug_last_logits(n_rows, head_rows, out); })
+}
+
 int rwkvtts_generate_batch(rwkvtts_engine* e, const rwkvtts_request* reqs, int n,
                            rwkvtts_result* results) {
   RT_CHECK(e && reqs && results && n >= 0, RWKVTTS_EINVAL, "generate_batch: bad arguments");

@@ -104,6 +104,9 @@ class Engine {
   // rwkvtts_debug_advance_ex: rows carry their own temperature / top-p, top_k may be 0
   int debug_advance_ex(const float* logits, int n_rows, const struct DebugAdvanceRowEx* rows, int exact, int n_steps,
                        int32_t* out_tok, int32_t* out_used, int32_t* out_phase);
+  // Test hook (rwkvtts_debug_last_logits): rows [0, n_rows) of the logits the last forward step left on
+  // the device (its head GEMM's split-K slabs summed in order, as infer returns them)
+  int debug_last_logits(int n_rows, int head_rows, float* out);
   // Continuous batching until `src` is closed and every admitted job has finished.
   int serve(JobSource& src);
   // Checks a request before admission; fills `why` and returns false for a bad one.
@@ -210,6 +213,9 @@ class Engine {
   // decode steps' FFN / attention half as one persistent launch (k_ffn_persist / k_att_persist);
   // RWKVTTS_FORM_SEPARATE_FFN / _ATT turn them off
   bool ffn_persist_ = true;
+  // k_ffn_persist at 17..32 rows: the value role's 32-row x 64-column tile instead of 16 x 128
+  // (RWKVTTS_FORM_VALUE_TILE_32X64; the default is 16 x 128)
+  bool value_32x64_ = false;
   int* ffn_sync_ = nullptr; // its hand-off counters: [L][kFfnSyncInts] (give-up code: d_ctrl_[S_])
   bool att_persist_ = true;
   int* att_sync_ = nullptr; // its hand-off counters: [L][kAttSyncInts]

@@ -173,7 +173,8 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
   // decode-step forms (rwkvtts_engine_desc.forms; 0 = the shipping forms, every bit bitwise-equal)
   constexpr uint32_t kKnownForms = RWKVTTS_FORM_SEPARATE_ATT | RWKVTTS_FORM_SEPARATE_FFN | RWKVTTS_FORM_LN_ROWS |
                                    RWKVTTS_FORM_SLAB_HANDOFF | RWKVTTS_FORM_SEPARATE_LNOUT |
-                                   RWKVTTS_FORM_SEPARATE_EMBED | RWKVTTS_FORM_EXACT_SAMPLER;
+                                   RWKVTTS_FORM_SEPARATE_EMBED | RWKVTTS_FORM_EXACT_SAMPLER |
+                                   RWKVTTS_FORM_VALUE_TILE_32X64;
   RT_CHECK((desc.forms & ~kKnownForms) == 0, RWKVTTS_EINVAL, "engine desc: unknown forms bits");
   att_persist_ = !(desc.forms & RWKVTTS_FORM_SEPARATE_ATT);
   ffn_persist_ = !(desc.forms & RWKVTTS_FORM_SEPARATE_FFN);
@@ -182,6 +183,7 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
   lnrow_ = !(desc.forms & RWKVTTS_FORM_SEPARATE_LNOUT);
   no_emb_fuse_ = (desc.forms & RWKVTTS_FORM_SEPARATE_EMBED) != 0;
   exact_sampler_ = (desc.forms & RWKVTTS_FORM_EXACT_SAMPLER) != 0;
+  value_32x64_ = (desc.forms & RWKVTTS_FORM_VALUE_TILE_32X64) != 0;
   if ((ffn_persist_ || att_persist_) && !claim_persistent(desc.device, this, &lock_fd_)) ffn_persist_ = att_persist_ = false;
   // debug instrumentation (tools/: stamps of one layer's launches, the launch timeline), off in
   // production: RWKVTTS_DEBUG_STAMPS="kind=path[;kind=path...]", kind one of gemm (layer-5 rkv /
@@ -799,7 +801,7 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
         return launch_ffn_persist(f, gk, gv, ffn_sync_ + (size_t)l * kFfnSyncInts,
                                   ffn_sync_ + (size_t)((l + Lc - 1) % Lc) * kFfnSyncInts, (int*)(d_ctrl_ + S_), R,
                                   stream_, l == kStampLayer ? dbg_fstamps_ : nullptr, fuse_ln1_,
-                                  gran_live ? d_gran_ : nullptr, d_epoch_);
+                                  gran_live ? d_gran_ : nullptr, d_epoch_, value_32x64_);
       }));
     if (!persisted) {
       timed("ln_ffn", "ln_mix_ffn", [&](unsigned long long* tl) { f.tl = tl; launch_ln_mix(f, R, stream_); });
@@ -977,6 +979,22 @@ int Engine::infer(const rwkvtts_input* in, int n, int head_rows, float* logits, 
   for (int i : last_only) has_logits[i] = 1;
   RT_OK(flush_prof());
   return dump_stamps();
+}
+
+int Engine::debug_last_logits(int n_rows, int head_rows, float* out) {
+  RT_HIP(hipSetDevice(device_));
+  RT_CHECK(n_rows > 0 && n_rows <= Rmax_ && head_rows > 0 && head_rows <= dims.n_vocab, RWKVTTS_EINVAL,
+           "debug_last_logits: rows out of range");
+  RT_HIP(hipStreamSynchronize(stream_));
+  if (splitH_ > 1) {
+    const int64_t tot = (int64_t)n_rows * head_rows;
+    hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream_, logits_,
+                       (int64_t)Rmax_ * Vpad_, splitH_, Vpad_, n_rows, head_rows);
+  }
+  RT_HIP(hipMemcpy2DAsync(out, (size_t)head_rows * 4, logits_, (size_t)Vpad_ * 4, (size_t)head_rows * 4, n_rows,
+                          hipMemcpyDeviceToHost, stream_));
+  RT_HIP(hipStreamSynchronize(stream_));
+  return RWKVTTS_OK;
 }
 
 // ------------------------------------------------------------------------------------------

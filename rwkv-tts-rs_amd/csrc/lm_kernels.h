@@ -155,7 +155,8 @@ int launch_gemm(const GemmArgs& a, hipStream_t st);
 // a one-row step's head GEMM with ln_out folded in (k_gemm2_lnrow); false if not covered
 bool launch_gemm_lnrow(const GemmArgs& a, const LnMixArgs& lo, hipStream_t st);
 // The FFN half of a decode step (LN2 + mix, key GEMM, relu^2, value GEMM) as ONE persistent launch
-// with in-launch hand-offs (k_ffn_persist); false if the shapes are not covered.
+// with in-launch hand-offs (k_ffn_persist); false if the shapes are not covered. value_tile_32x64: steps
+// of 17..32 rows keep the value role's 32-row x 64-column tile instead of 16 x 128 (the same bits).
 constexpr int kFfnSyncInts = 24 * 64;  // counter block per layer: (8 LN replicas + 16 K-slices) x 256 B
 // row-fused form (no LayerNorm rows): key workgroups done (the shift writer waits), in LN replica 1's
 // counter. (A 25th counter staggered every later device allocation: 2 % slower decode at 32 rows.)
@@ -196,6 +197,7 @@ struct FfnSync {     // (both persistent launches; a field marked FFN / attentio
   int key_per_slice; // FFN: key workgroups per value K-slice (key_group x key splits)
   int n_wkv;         // attention: WKV workgroups
   int n_val;         // FFN: value workgroups
+  int val16;         // FFN: the value workgroups run 16-row x 128-column tiles (kRoleFfnValue16), not 32 x 64
   int rkv_tiles;     // attention: column tiles of the rkv launch (its grid is tiles x splits)
   int head_target;   // attention: rkv workgroups per head (3 tiles x splits)
   int lora_target;   // attention: LoRA-down workgroups (tiles x splits)
@@ -247,7 +249,8 @@ bool launch_att_persist(const LnMixArgs& ln, const GemmArgs& rkv, const WkvArgs&
 inline int64_t att_gran_count(int C) { return (int64_t)C; }
 bool launch_ffn_persist(const LnMixArgs& ln, const GemmArgs& key, const GemmArgs& val, int* cnt, int* cnt_prev,
                         int* err, int R, hipStream_t st, uint64_t* stamps = nullptr,
-                        bool fused_ln = false, uint64_t* gran = nullptr, const int* epoch = nullptr);
+                        bool fused_ln = false, uint64_t* gran = nullptr, const int* epoch = nullptr,
+                        bool value_tile_32x64 = false);
 // granules the row-fused FFN form's key -> value hand-off needs (FfnSync::gran)
 inline int64_t ffn_gran_count(int key_splits, int F) { return (int64_t)key_splits * F; }
 // Fills a.tw / a.tinfo / a.n_tinfo when the segments' packed weights are contiguous in 64-column

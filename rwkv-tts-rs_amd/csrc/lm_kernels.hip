@@ -723,6 +723,7 @@ __device__ inline u32x4_ ld_sc1_b128(__amdgpu_buffer_rsrc_t r, int off_bytes) {
 //   kRolePlain      --                           plain loads, before the weights     --                    k_gemm2
 //   kRoleFfnKey     the LN rows (a replica)      planes, sc1                         its K-slice counter   k_ffn_persist
 //   kRoleFfnValue   its K-slice's key slabs      the NX key slabs, sc1               --                    k_ffn_persist
+//   kRoleFfnValue16 as kRoleFfnValue             16 rows of the NX key slabs, sc1    --                    k_ffn_persist
 //   kRoleRkv        the LN rows (a replica)      planes, sc1                         head / LoRA counter   k_att_persist
 //   kRoleWo         WKV of its two heads         z planes, sc1                       --                    k_att_persist
 //   kRoleRkvRow     -- (one row, layers > 0)     LN1 + its tile's mix here, row 0    as kRoleRkv, rkv-done k_att_persist FUSED
@@ -736,8 +737,14 @@ __device__ inline u32x4_ ld_sc1_b128(__amdgpu_buffer_rsrc_t r, int off_bytes) {
 // rows' arithmetic bit for bit) and stage only their K-slice's mix as row 0 of the X image -- no
 // LayerNorm rows, no hand-off before the GEMM. The values are `int` template arguments of the kernels'
 // instantiations.
+// kRoleFfnValue16 (17..32 rows): the value role with a 16-row x 128-column tile instead of 32 x 64 -- each
+// workgroup stages half the key-slab bytes (the read behind its wait) and each wave runs two 16-column
+// tiles (columns 64 j + 16 wave .., as k_gemm_wide) off the one staged X slice. 1-D grid: block 8 j + xcd
+// = row group j & 1 of column pair (j >> 1) % ntiles of K-slice xcd + 8 ((j >> 1) / ntiles), so the two
+// row groups that request the same weight fragments sit on adjacent blocks of the K-slice's XCD. Every
+// output element takes kRoleFfnValue's staging arithmetic and MFMA sequence: the slabs are bit-identical.
 constexpr int kRolePlain = 0, kRoleFfnKey = 1, kRoleFfnValue = 2, kRoleRkv = 3, kRoleWo = 4, kRoleRkvRow = 5,
-              kRoleKeyRow = 6, kRoleValueGran = 7, kRoleWoGran = 8, kRoleHeadLn = 10;
+              kRoleKeyRow = 6, kRoleValueGran = 7, kRoleWoGran = 8, kRoleFfnValue16 = 9, kRoleHeadLn = 10;
 // by: the split index of an xmap-0 grid (blockIdx.y for a plain launch).
 template <int MT, int KSTEPS, int XMODE, bool F16, int NX, int MS, bool QW, int ROLE, class GA>
 __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int bx, const int by,
@@ -754,7 +761,15 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
   int64_t e_sstride = a.split_stride;
   int e_ldo = a.ldo, e_M = a.M;
   int tile = bx, split = by;
-  if (a.xmap == 2) {  // consumer-aligned 1-D grid (GemmArgs::xalign)
+  constexpr int NT = ROLE == kRoleFfnValue16 ? 2 : 1;  // 16-column tiles per wave, 64 columns apart
+  int rgrp = 0;  // kRoleFfnValue16: the workgroup's 16-row group
+  if constexpr (ROLE == kRoleFfnValue16) {
+    static_assert(MT == 1 && XMODE == kXRelu2 && MS == 0 && !QW, "16-row value role: one row tile, relu^2 X");
+    const int j = bx >> 3, jp = j >> 1;
+    rgrp = j & 1;
+    split = (bx & 7) + 8 * (jp / a.ntiles);
+    tile = jp % a.ntiles;
+  } else if (a.xmap == 2) {  // consumer-aligned 1-D grid (GemmArgs::xalign)
     const int b = bx, xcd = b & 7, j = b >> 3;
     split = j % a.k_split;
     const int lt = j / a.k_split;
@@ -808,7 +823,7 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
   }
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int g = lane >> 4, li = lane & 15;
-  const int col0 = (tile - tstart) * 64 + wave * 16;
+  const int col0 = (tile - tstart) * (NT * 64) + wave * 16;
   const int kbeg = split * KS;
   // row groups: a workgroup runs row groups blockIdx.z, blockIdx.z + gridDim.z, ... (prefill
   // steps; decode steps have one) with its weight fragments loaded once, and requests the next
@@ -817,7 +832,7 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
   // (quantised launches keep one row group per workgroup: the loop's live registers spill there)
   int rg = a.xmap ? 0 : (int)blockIdx.z;
   const int nrg = (a.xmap || QW) ? rg + 1 : (e_M + ROWS - 1) / ROWS;
-  int row0 = rg * ROWS;
+  int row0 = (rg + rgrp) * ROWS;
   int xrow0 = row0;  // the row group load_x requests
   // X slice (activations of the previous launch, L2-resident) and weight stream (packed
   // fragment blocks, 1 KB per wave instruction). X is requested first: staging waits only for X
@@ -832,6 +847,7 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
   if (nb >= nblk) nb = nblk - 1;
   const bf16_t* wp = Wm + (((int64_t)nb * (a.K >> 5) + (kbeg >> 5)) * 64 + lane) * 8;
   short8 b[KSTEPS];
+  short8 b2[NT > 1 ? KSTEPS : 1];  // (NT 2) the wave's second column tile, 64 columns on
   // quantised tiles: codes in the same fragment order (column tiles back to back from the
   // launch's first quantised tile), one scale word per (column, K-block) and step
   uint2 bq8[QW ? KSTEPS : 1];
@@ -926,6 +942,12 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
     }
 #pragma unroll
   for (int t = 0; t < KSTEPS; ++t) b[t] = __builtin_nontemporal_load((const short8*)(wp + t * 512));
+  if constexpr (NT > 1) {
+    const int nb2 = min((col0 + 64) >> 4, nblk - 1);
+    const bf16_t* wp2 = Wm + (((int64_t)nb2 * (a.K >> 5) + (kbeg >> 5)) * 64 + lane) * 8;
+#pragma unroll
+    for (int t = 0; t < KSTEPS; ++t) b2[t] = __builtin_nontemporal_load((const short8*)(wp2 + t * 512));
+  }
   };
   if constexpr (ROLE == kRoleFfnKey || ROLE == kRoleRkv) {
     // the weight stream does not depend on the LayerNorm: in flight during the wait
@@ -1077,7 +1099,7 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
     }
     __syncthreads();
     sync_stamp(sy, 1);
-  } else if constexpr (ROLE == kRoleFfnValue) {
+  } else if constexpr (ROLE == kRoleFfnValue || ROLE == kRoleFfnValue16) {
     hold_until(sy.d_v);
     load_w();
     sync_wait(sy.cnt + kSyncStride * (kLnReplicas + split), sy.key_per_slice, sy.err, kGiveUpKey);
@@ -1160,6 +1182,9 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
   float4_ acc_h[MT], acc_l[MT];
 #pragma unroll
   for (int m = 0; m < MT; ++m) acc_h[m] = acc_l[m] = (float4_){0.f, 0.f, 0.f, 0.f};
+  float4_ acc_h2[MT], acc_l2[MT];  // (NT 2) the second column tile's chains
+#pragma unroll
+  for (int m = 0; m < MT; ++m) acc_h2[m] = acc_l2[m] = (float4_){0.f, 0.f, 0.f, 0.f};
   if constexpr (QW) {
     if (qf) {
       // dequantise 8 weights per step, split w = hi + lo, three MFMAs per product (x_hi w_hi,
@@ -1227,13 +1252,26 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
         acc_l[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, al), __builtin_bit_cast(bf16x8, b[t]),
                                                            acc_l[m], 0, 0, 0);
       }
+      if constexpr (NT > 1) {  // the second column tile off the same X fragments
+        if constexpr (F16) {
+          acc_h2[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, b2[t]),
+                                                             acc_h2[m], 0, 0, 0);
+          acc_l2[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, al), __builtin_bit_cast(f16x8, b2[t]),
+                                                             acc_l2[m], 0, 0, 0);
+        } else {
+          acc_h2[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ah), __builtin_bit_cast(bf16x8, b2[t]),
+                                                              acc_h2[m], 0, 0, 0);
+          acc_l2[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, al), __builtin_bit_cast(bf16x8, b2[t]),
+                                                              acc_l2[m], 0, 0, 0);
+        }
+      }
     }
   }
   }
   // 5) store (D layout: col = lane&15, row = 4*(lane>>4) + j)
   const int col = col0 + li;
-  auto result = [&](int m, int j) {
-    float v = acc_h[m][j] + acc_l[m][j];
+  auto result = [&](int m, int j, int n = 0) {  // n: the wave's column tile (NT 2)
+    float v = n ? acc_h2[m][j] + acc_l2[m][j] : acc_h[m][j] + acc_l[m][j];
     if constexpr (F16 && QW) {
       if (qf) v *= __builtin_amdgcn_ldexpf(1.0f, -a.q_shift);
     }
@@ -1250,19 +1288,21 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
   } else if (a.wt) {
     // write-through: the tile is staged in LDS so every lane stores whole 16-byte pieces (a
     // 4-byte sc1 store is one fabric write each)
-    constexpr int LDT = 68;
+    constexpr int LDT = NT * 64 + 4;
     float* st = (float*)smem;
     __syncthreads();  // every wave is done reading its X fragments
 #pragma unroll
-    for (int m = 0; m < MT; ++m)
+    for (int n = 0; n < NT; ++n)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) st[(m * 16 + 4 * g + j) * LDT + wave * 16 + li] = result(m, j);
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) st[(m * 16 + 4 * g + j) * LDT + n * 64 + wave * 16 + li] = result(m, j, n);
     __syncthreads();
-    const int tcol = (tile - tstart) * 64;  // first column of this tile within the segment
+    const int tcol = (tile - tstart) * (NT * 64);  // first column of this tile within the segment
     const auto rs = wt_rsrc(e_out);
 #pragma unroll
-    for (int q = threadIdx.x; q < ROWS * 16; q += 256) {
-      const int r = q >> 4, c4 = (q & 15) * 4, row = row0 + r;
+    for (int q = threadIdx.x; q < ROWS * NT * 16; q += 256) {
+      const int r = q / (NT * 16), c4 = (q % (NT * 16)) * 4, row = row0 + r;
       if (row >= e_M || tcol + c4 >= Nn) continue;
       const int64_t o = (int64_t)split * e_sstride + col_off + tcol + c4 + (int64_t)row * e_ldo;
       const float4_ v = *(const float4_*)(st + r * LDT + c4);
@@ -1272,15 +1312,19 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
         for (int e = 0; e < 4 && tcol + c4 + e < Nn; ++e) store_wt(rs, (int)((o + e) * 4), v[e]);
       }
     }
-  } else if (col < Nn) {
-    float* out = e_out + split * e_sstride + col_off + col;
+  } else {
 #pragma unroll
-    for (int m = 0; m < MT; ++m)
+    for (int n = 0; n < NT; ++n) {
+      if (col + n * 64 >= Nn) continue;
+      float* out = e_out + split * e_sstride + col_off + col + n * 64;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int row = row0 + m * 16 + 4 * g + j;
-        if (row < e_M) out[(int64_t)row * e_ldo] = result(m, j);
-      }
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int row = row0 + m * 16 + 4 * g + j;
+          if (row < e_M) out[(int64_t)row * e_ldo] = result(m, j, n);
+        }
+    }
   }
   if (QW || rg_next >= nrg) break;
   rg = rg_next;
@@ -1479,7 +1523,8 @@ bool launch_gemm_lnrow(const GemmArgs& a, const LnMixArgs& lo, hipStream_t st) {
 //                                      counted into their value K-slice's counter;
 //   blocks [+n_key, +n_key + 256)      value GEMM workgroups (XCD-aware order): weights at
 //                                      dispatch, wait for the K-slice's key slabs, relu^2 staging
-//                                      from sc1 loads, MFMA, partial slab out.
+//                                      from sc1 loads, MFMA, partial slab out. 17..32 rows: 16-row x
+//                                      128-column tiles (kRoleFfnValue16), the same 256 workgroups.
 // Every dependency points to a lower block index, so in-order dispatch keeps every waited-on
 // producer resident or finished (no deadlock with other kernels on the GPU). Every output is the
 // three-launch path's, bit for bit (same bodies, same orders). Block 0 zeroes the counters of
@@ -1519,7 +1564,8 @@ __global__ __launch_bounds__(256, RWKVTTS_FFN_WPC) void k_ffn_persist(LnMixArgs 
       if (sy.gran) gemm2_body<1, 8, kXRelu2, F16, 4, 0, false, kRoleValueGran>(va, b, 0, sy);  // (one row: 16-row tile)
       else gemm2_body<2, 8, kXRelu2, F16, 4, 0, false, kRoleFfnValue>(va, b, 0, sy);
     } else {
-      gemm2_body<2, 8, kXRelu2, F16, 4, 0, false, kRoleFfnValue>(va, b, 0, sy);
+      if (sy.val16) gemm2_body<1, 8, kXRelu2, F16, 4, 0, false, kRoleFfnValue16>(va, b, 0, sy);
+      else gemm2_body<2, 8, kXRelu2, F16, 4, 0, false, kRoleFfnValue>(va, b, 0, sy);
     }
   } else if constexpr (FUSED) {  // the shift writer
     if (threadIdx.x < sy.n_prev) sy.cnt_prev[threadIdx.x * kSyncStride] = 0;
@@ -1899,7 +1945,7 @@ constexpr int kHold1Wo = 400, kHold1Value = 100;
 
 bool launch_ffn_persist(const LnMixArgs& ln, const GemmArgs& key, const GemmArgs& val, int* cnt, int* cnt_prev,
                         int* err, int R, hipStream_t st, uint64_t* stamps, bool fused_ln, uint64_t* gran,
-                        const int* epoch) {
+                        const int* epoch, bool value_tile_32x64) {
   if (ln.C != 1024 || !ln.shift || ln.n_mix != 1 || ln.n_part != 8 || ln.emb || R < 1 || R > 32 ||
       key.xmode != kXPlanes || val.xmode != kXRelu2 || val.x_nsplit != 4 || key.kslice != 256 ||
       val.kslice != 256 || key.M != R || val.M != R || key.nseg != 1 || val.nseg != 1 || key.q_fmt || val.q_fmt ||
@@ -1933,6 +1979,13 @@ bool launch_ffn_persist(const LnMixArgs& ln, const GemmArgs& key, const GemmArgs
   sy.key_group = key.xalign;
   sy.key_per_slice = key.xalign * key.k_split;
   sy.n_val = vt * val.k_split;
+  // 17..32 rows: the value role's 16-row x 128-column tiles (kRoleFfnValue16), two row groups x vt / 2
+  // column pairs x the K-slices -- the same workgroup count. Up to 16 rows the second row group would
+  // be empty: the 32 x 64 role stays (its one-row tile reads no more, and all 256 workgroups stream weights)
+  if (!fused && R > 16 && !value_tile_32x64 && vt % 2 == 0) {
+    sy.val16 = 1;
+    va.ntiles = vt / 2;
+  }
   sy.stamps = stamps;
   sy.d_k = fused ? 0 : kHoldKey;
   sy.d_v = fused ? kHold1Value : 0;

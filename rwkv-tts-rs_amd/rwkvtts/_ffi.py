@@ -62,6 +62,7 @@ class EngineDesc(ctypes.Structure):
 # back to the launches it replaces (bitwise-equal outputs; verification and A/B timing only)
 FORM_SEPARATE_ATT, FORM_SEPARATE_FFN, FORM_LN_ROWS, FORM_SLAB_HANDOFF = 1, 2, 4, 8
 FORM_SEPARATE_LNOUT, FORM_SEPARATE_EMBED, FORM_EXACT_SAMPLER = 16, 32, 64
+FORM_VALUE_TILE_32X64 = 128  # k_ffn_persist at 17..32 rows: the 32 x 64 value tile, not 16 x 128
 # codec weight paths and forms (RWKVTTS_CODEC_WEIGHTS_* / RWKVTTS_CODEC_FORM_*)
 CODEC_WEIGHTS_AUTO, CODEC_WEIGHTS_BF16, CODEC_WEIGHTS_HILO = 0, 1, 2
 CODEC_FORM_SEPARATE_RESUNIT, CODEC_FORM_CHANNEL_LAST = 1, 2
@@ -272,6 +273,8 @@ EXPORTS = {
     "rwkvtts_debug_advance_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                                 ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_void_p]),
+    # test hook (tests/test_gpu_value_tile.py): the logits the last forward step left on the device
+    "rwkvtts_debug_last_logits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "rwkvtts_profile_entry": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,
                                              ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]),
     "rwkvtts_codec_blob_bytes": (ctypes.c_int64, [ctypes.POINTER(CodecDims)]),

@@ -257,6 +257,15 @@ class SharedRwkvRuntime:
                 outputs.append(np.zeros(0, dtype=np.float32))
         return remaining, outputs
 
+    @_locked
+    def last_logits(self, n_rows: int, head_rows: Optional[int] = None) -> np.ndarray:
+        """Test hook: rows [0, n_rows) of the logits the last forward step left on the device."""
+        head_rows = head_rows or self.dims["n_vocab"]
+        out = np.empty((n_rows, head_rows), dtype=np.float32)
+        check(lib().rwkvtts_debug_last_logits(self._h, n_rows, head_rows, out.ctypes.data_as(ctypes.c_void_p)),
+              "debug_last_logits")
+        return out
+
     # ---- device sampler ----
     @_locked
     def sample(self, logits: np.ndarray, temperature=1.0, top_p=0.85, top_k=0, forbid_token=None,

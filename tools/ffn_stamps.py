@@ -51,4 +51,8 @@ for r, (b, e) in roles.items():
         v = x[:, k][a[b:e, k] > 0]
         if v.size:
             line.append(f"{names[k]} {v.min():6.2f}/{np.median(v):6.2f}/{v.max():6.2f}")
+    both = (a[b:e, 1] > 0) & (a[b:e, 2] > 0)  # per block: wait done -> work done
+    if both.any():
+        w = x[both, 2] - x[both, 1]
+        line.append(f"work {w.min():6.2f}/{np.median(w):6.2f}/{w.max():6.2f}")
     print(f"{r:6s} " + "  ".join(line))
