@@ -154,8 +154,8 @@ typedef struct {
                                reference's per-request RnnInput token_chunk_size, 512 at
                                lightweight_tts_pipeline.rs:799; outputs are chunk-invariant) */
   int32_t use_graphs;       /* capture decode steps in hipGraphs */
-  int32_t wkv_variant;      /* 0 auto; 1 k_wkv4 (2 waves per (slot, head)); 2 k_wkv6 (4 waves).
-                               0.4B LoRA ranks only; both are tested against the oracle */
+  int32_t wkv_variant;      /* ignored: every value selects the one WKV kernel the shape has; kept
+                               for layout compatibility */
   /* web-rwkv ModelBuilder::quant(HashMap<layer, Quant>) as the server builds it from
    * --quant-layers / --quant-type (bin/server.rs:1029-1071, src/shared_runtime.rs:156-160):
    * layers [0, quant_layers) store their r / k / v / o and FFN key / value matrices quantised

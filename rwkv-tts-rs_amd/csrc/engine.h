@@ -179,9 +179,7 @@ class Engine {
   int* d_drop_ = nullptr;
   int test_drops_left_ = 0;
 
-  void state_permute(const float* std_block, float* dev_block);
-  void state_unpermute(const float* dev_block, float* std_block);
-  int state_perm_ = 0;  // WKV state block layout (wkv_perm_layout; engine.hip perm_index)
+  int state_perm_ = 0;  // WKV state block layout (wkv_perm_layout): 0 row-major, 2 engine.hip perm_index
   // launch classes of a forward step: the bit positions of the per-class masks below
   enum LaunchClass { kClsRkv, kClsWo, kClsKey, kClsValue, kClsHead, kClsWkv, kClsLnAtt, kClsLnFfn };
   // XCD-aware grids per launch class

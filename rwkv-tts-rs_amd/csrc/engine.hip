@@ -169,7 +169,7 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
   splitH_ = pick(C, 512);  // head: 129 col tiles x 2
   RT_CHECK(C % 128 == 0 && F % 128 == 0, RWKVTTS_EUNSUPPORTED, "K dims must be multiples of 128");
   RT_CHECK(splitA_ <= kMaxParts, RWKVTTS_EUNSUPPORTED, "n_embd too large for the WKV partial sum (raise kMaxParts)");
-  state_perm_ = wkv_perm_layout(dims.d_decay, dims.d_aaa, dims.d_mv, dims.d_gate, splitA_, S_, desc.wkv_variant);
+  state_perm_ = wkv_perm_layout(dims.d_decay, dims.d_aaa, dims.d_mv, dims.d_gate, splitA_);
   // decode-step forms (rwkvtts_engine_desc.forms; 0 = the shipping forms, every bit bitwise-equal)
   constexpr uint32_t kKnownForms = RWKVTTS_FORM_SEPARATE_ATT | RWKVTTS_FORM_SEPARATE_FFN | RWKVTTS_FORM_LN_ROWS |
                                    RWKVTTS_FORM_SLAB_HANDOFF | RWKVTTS_FORM_SEPARATE_LNOUT |
@@ -257,8 +257,6 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
     bf16_t* dst = lora_pack_ + (size_t)l * C * Dtot_;
     if (state_perm_ == 2)  // k_wkv6 (0.4B LoRA ranks): its coalesced register order
       launch_pack_lora6(w.w2t, w.a2t, w.v2t, w.g2t, C, dst, stream_);
-    else if (state_perm_ == 1)  // k_wkv4
-      launch_pack_lora4(w.w2t, w.a2t, w.v2t, w.g2t, C, dst, stream_);
     else
       launch_pack_lora(w.w2t, w.a2t, w.v2t, w.g2t, C, dims.d_decay, dims.d_aaa, dims.d_mv, dims.d_gate, dst, stream_);
     RT_HIP(hipGetLastError());
@@ -438,25 +436,21 @@ int Engine::slot_reset(int slot, bool sync) {
   return RWKVTTS_OK;
 }
 
-// Coalesced state layouts of one (slot, layer, head) block, in the WKV kernel's register order:
-// layout 1 (k_wkv4): thread t = 2 i + (j >> 5) owns row i, half j >> 5; its q-th float4 (columns
-// 32 hf + 4 q .. + 3) lives at float4 index q * 128 + t. Layout 2 (k_wkv6): t = 4 i + (j >> 4),
-// q-th float4 at q * 256 + t. Either way each wave-wide load / store is 1 KB contiguous.
-static inline int64_t perm_index(int kind, int i, int j) {
-  if (kind == 1) {
-    const int t = 2 * i + (j >> 5), q = (j & 31) >> 2, e = j & 3;
-    return ((int64_t)q * 128 + t) * 4 + e;
-  }
+// Coalesced state layout of one (slot, layer, head) block (state_perm_ == 2), in k_wkv6's register
+// order: thread t = 4 i + (j >> 4) owns row i, quarter j >> 4; its q-th float4 (columns
+// 16 (j >> 4) + 4 q .. + 3) lives at float4 index q * 256 + t, so each wave-wide load / store is
+// 1 KB contiguous.
+static inline int64_t perm_index(int i, int j) {
   const int t = 4 * i + (j >> 4), q = (j & 15) >> 2, e = j & 3;
   return ((int64_t)q * 256 + t) * 4 + e;
 }
-void Engine::state_permute(const float* std_block, float* dev_block) {
+static void state_permute(const float* std_block, float* dev_block) {
   for (int i = 0; i < 64; ++i)
-    for (int j = 0; j < 64; ++j) dev_block[perm_index(state_perm_, i, j)] = std_block[i * 64 + j];
+    for (int j = 0; j < 64; ++j) dev_block[perm_index(i, j)] = std_block[i * 64 + j];
 }
-void Engine::state_unpermute(const float* dev_block, float* std_block) {
+static void state_unpermute(const float* dev_block, float* std_block) {
   for (int i = 0; i < 64; ++i)
-    for (int j = 0; j < 64; ++j) std_block[i * 64 + j] = dev_block[perm_index(state_perm_, i, j)];
+    for (int j = 0; j < 64; ++j) std_block[i * 64 + j] = dev_block[perm_index(i, j)];
 }
 
 int Engine::slot_read(int slot, float* out) {

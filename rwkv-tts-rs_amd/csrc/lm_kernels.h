@@ -119,8 +119,8 @@ struct WkvArgs {
   int n_part;
   int ldp;
   int64_t part_stride;
-  const bf16_t *w2t, *a2t, *v2t, *g2t;  // LoRA-up rows [C][D] (k_wkv1)
-  const bf16_t* lup;   // LoRA-up rows packed for k_wkv (launch_pack_lora) or k_wkv4 (launch_pack_lora4)
+  const bf16_t *w2t, *a2t, *v2t, *g2t;  // LoRA-up rows [C][D] (k_wkv2)
+  const bf16_t* lup;   // LoRA-up rows packed for k_wkv (launch_pack_lora) or k_wkv6 (launch_pack_lora6)
   const float *w0, *a0, *v0, *k_k, *k_a, *r_k, *lnx_w, *lnx_b;
   float* state;
   int64_t slot_stride;
@@ -134,10 +134,10 @@ struct WkvArgs {
   int layer, C, Dw, Da, Dv, Dg;
   int n_slots;         // state slots (bounds the speculative slot = segment index)
   int n_seg;           // segments in this step 
-  int perm;            // state block layout (wkv_perm_layout): 0 row-major, 1 k_wkv4, 2 k_wkv6
-  int xmap;            // k_wkv4 / k_wkv6: 1-D grid, head h's workgroups on one XCD (H % 8 == 0)
+  int perm;            // state block layout (wkv_perm_layout): 0 row-major, 2 k_wkv6
+  int xmap;            // k_wkv6: 1-D grid, head h's workgroups on one XCD (H % 8 == 0)
   int allow_xmap;      // set by the caller
-  int wt;              // k_wkv4 / k_wkv6: write-through (sc1) state stores
+  int wt;              // k_wkv6: write-through (sc1) state stores
   int f16;             // fp16 model: LoRA-up rows and the z planes are f16
   uint64_t* stamps;    // debug: 8 s_memtime stamps per workgroup (null in production)
   int multi_row;       // some segment has > 1 row (prefill / mixed step): a separate kernel
@@ -258,10 +258,9 @@ inline int64_t ffn_gran_count(int key_splits, int F) { return (int64_t)key_split
 // the table applies (otherwise the kernel looks the segment up).
 bool gemm_tile_table(GemmArgs& a, int64_t x_mix_stride);
 int launch_wkv(const WkvArgs& a, int n_seg, int H, hipStream_t st);
-// Which coalesced WKV state layout launch_wkv expects for these LoRA ranks / slab count: 0 none
-// (row-major S[i][j], generic kernels), 1 k_wkv4 (two waves per block), 2 k_wkv6 (four waves).
-// variant: rwkvtts_engine_desc.wkv_variant (0 auto by slot count).
-int wkv_perm_layout(int Dw, int Da, int Dv, int Dg, int n_part, int max_slots, int variant);
+// The WKV state layout launch_wkv expects for these LoRA ranks / slab count (WkvArgs::perm): 2 where
+// the shape has k_wkv6's coalesced layout, else 0 (row-major S[i][j], generic kernels).
+int wkv_perm_layout(int Dw, int Da, int Dv, int Dg, int n_part);
 // relu(sum of nx f32 slabs [nx][R][ld])^2 -> bf16 hi/lo planes [R][F] (bf16 prefill steps)
 void launch_relu2_planes(const float* part, int nx, int64_t pstride, int ld, int F, int R, bf16_t* hi, bf16_t* lo,
                          hipStream_t st);
@@ -278,9 +277,7 @@ constexpr int kQ8Block = 128, kQ4Block = 64;
 inline size_t quant_code_bytes(int qt, int N, int K) { return (size_t)N * K / (qt == 1 ? 1 : 2); }
 inline size_t quant_scale_bytes(int qt, int N, int K) { return qt == 1 ? (size_t)N * (K / kQ8Block) * 4 : (size_t)N * (K / kQ4Block) * 2; }
 void launch_quant_pack(const uint16_t* W, int N, int K, int f16, int qt, uint8_t* codes, void* scales, hipStream_t st);
-// Repack one layer's LoRA-up rows (0.4B ranks 64/64/32/128) into k_wkv4's coalesced order.
-void launch_pack_lora4(const bf16_t* w2t, const bf16_t* a2t, const bf16_t* v2t, const bf16_t* g2t, int C,
-                       bf16_t* out, hipStream_t st);
+// Repack one layer's LoRA-up rows (0.4B ranks 64/64/32/128) into k_wkv6's coalesced order.
 void launch_pack_lora6(const bf16_t* w2t, const bf16_t* a2t, const bf16_t* v2t, const bf16_t* g2t, int C,
                        bf16_t* out, hipStream_t st);
 // Repack one layer's w2t | a2t | v2t | g2t ([C][D] each) into the per-thread order of k_wkv.

@@ -2156,31 +2156,6 @@ __global__ void k_pack_lora(const bf16_t* w2t, const bf16_t* a2t, const bf16_t* 
   }
 }
 
-// LoRA-up rows in k_wkv4's register order: per head h, entry u (w 0..3 | a 4..7 | v 8..9 |
-// g 10..17, 8 bf16 each) of thread t = 2 i + hf (channel 64 h + i, half hf) at uint4 index
-// (h * 18 + u) * 128 + t, so each wave-wide load is 1 KB contiguous.
-__global__ void k_pack_lora4(const bf16_t* w2t, const bf16_t* a2t, const bf16_t* v2t, const bf16_t* g2t, int C,
-                             bf16_t* out) {
-  const int64_t total = (int64_t)(C / 64) * 18 * 128;
-  for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total;
-       idx += (int64_t)gridDim.x * blockDim.x) {
-    const int t = (int)(idx % 128), u = (int)((idx / 128) % 18), h = (int)(idx / (128 * 18));
-    const int c = h * 64 + (t >> 1), hf = t & 1;
-    const bf16_t* src;
-    if (u < 4) src = w2t + (int64_t)c * 64 + hf * 32 + u * 8;
-    else if (u < 8) src = a2t + (int64_t)c * 64 + hf * 32 + (u - 4) * 8;
-    else if (u < 10) src = v2t + (int64_t)c * 32 + hf * 16 + (u - 8) * 8;
-    else src = g2t + (int64_t)c * 128 + hf * 64 + (u - 10) * 8;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) out[idx * 8 + e] = src[e];
-  }
-}
-
-void launch_pack_lora4(const bf16_t* w2t, const bf16_t* a2t, const bf16_t* v2t, const bf16_t* g2t, int C,
-                       bf16_t* out, hipStream_t st) {
-  RT_LAUNCH(k_pack_lora4, dim3(256), dim3(256), 0, st, w2t, a2t, v2t, g2t, C, out);
-}
-
 // k_wkv6's register order: thread t = 4 i + qq holds quarter qq of channel c = 64 h + i's rows
 // (w 16 | a 16 | v 8 | g 32 values = 9 entries of 8); entry u of thread t at uint4 u * 256 + t.
 __global__ void k_pack_lora6(const bf16_t* w2t, const bf16_t* a2t, const bf16_t* v2t, const bf16_t* g2t, int C,
@@ -2400,14 +2375,19 @@ __global__ __launch_bounds__(128) void k_wkv2(WkvArgs a) {
 }
 
 // ------------------------------------------------------------------------------------
-// wkv4: the 0.4B shape (LoRA ranks 64/64/32/128, 4 split-K slabs) cut down to the instruction
-// stream the arithmetic needs. The decode WKV is VALU-issue-bound (one wave per SIMD, every
-// wave a straight ~2k-instruction program), so this variant removes work rather than adding
-// parallelism: the weight format is a template (no runtime f16/bf16 select), the LoRA hidden
-// is summed from float4 slab loads by 72 threads, LoRA-up dot products and the state update run
-// on packed f32 pairs (v_pk_fma_f32), sigmoid / tanh / exp use the hardware exp2 (|rel err|
-// ~1e-7, far inside the logits tolerance), and the slot / row speculation of k_wkv2 is kept.
-// Thread t = (channel i = t >> 1, half hf = t & 1) owns state row S[i][32 hf .. 32 hf + 31].
+// wkv6: the 0.4B shape (LoRA ranks 64/64/32/128, 4 split-K slabs) on four waves per (segment,
+// head). Thread t = (channel i = t >> 2, quarter qq = t & 3) owns state row
+// S[i][16 qq .. 16 qq + 15] and a quarter of channel c's LoRA-up dot products; two waves share
+// every SIMD (the dependent chains of one hide behind the other's) and quarter sums are two quad
+// shuffles. The decode WKV is VALU-issue-bound, so the instruction stream is cut to what the
+// arithmetic needs: the weight format is a template argument (no runtime f16 / bf16 select), the
+// LoRA hidden is summed from float4 slab loads by 72 threads, LoRA-up dot products and the state
+// update run on packed f32 pairs (v_pk_fma_f32), and sigmoid / tanh / exp use the hardware exp2
+// (|rel err| ~1e-7, far inside the logits tolerance). The segment's slot and first row are
+// speculated as the segment index (the decode layout), so their loads issue before the segment
+// descriptor arrives; a wrong guess reloads.
+// State blocks: thread t's q-th float4 at float4 index q * 256 + t (engine.hip perm_index);
+// LoRA-up rows: entry u of thread t at uint4 index u * 256 + t (launch_pack_lora6).
 // ------------------------------------------------------------------------------------
 __device__ inline float fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 __device__ inline float fsigm(float x) { return __builtin_amdgcn_rcpf(1.0f + fexp(-x)); }
@@ -2424,217 +2404,6 @@ __device__ inline float2_ w2f(uint32_t u) {  // two packed 16-bit weights -> f32
   }
 }
 
-template <bool F16>
-__global__ __launch_bounds__(128) void k_wkv4(WkvArgs a) {
-  constexpr int N = 64, DW = 64, DA = 64, DV = 32, DG = 128, DALL = DW + DA + DV + DG, NP = 4;
-  __shared__ __attribute__((aligned(16))) float s_hid[DALL];
-  __shared__ __attribute__((aligned(16))) float s_vec[5][N];  // w, kk (unnormalised), a, k, r
-  __shared__ float s_red[4][2];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, i = t >> 1, hf = t & 1;
-  int seg_i = blockIdx.x, h = blockIdx.y;
-  if (a.xmap) {  // 1-D grid: head h's workgroups share one XCD (its LoRA-up rows stay in one L2)
-    const int b = blockIdx.x, xcd = b & 7, j = b >> 3;
-    h = xcd + 8 * (j / a.n_seg);
-    seg_i = j % a.n_seg;
-  }
-  const int C = a.C, c = h * N + i;
-  tl_begin(a.tl);
-  // debug phase stamps (RWKVTTS_DEBUG_STAMPS wkv=, one layer only; null in production): [0] realtime
-  // start, [1..6] core clock at phase ends, [7] realtime end
-  uint64_t* stp = (a.stamps && t == 0) ? a.stamps + ((int64_t)h * a.n_seg + seg_i) * 8 : nullptr;
-  if (stp) { stp[0] = __builtin_amdgcn_s_memrealtime(); stp[1] = __builtin_amdgcn_s_memtime(); }
-  bf16_t* e_zhi = a.z_hi;
-  bf16_t* e_zlo = a.z_lo;
-  int e_ldz = a.ldz;
-  const int4 sg = a.segs[seg_i];
-  uint4 lw[18];  // 8 bf16 per entry: w 0..3 | a 4..7 | v 8..9 | g 10..17
-  {  // packed per head by launch_pack_lora4: entry u of thread t at uint4 index u * 128 + t
-    const uint4* pl = (const uint4*)(a.lup + (int64_t)h * 18 * 128 * 8);
-#pragma unroll
-    for (int u = 0; u < 18; ++u) lw[u] = pl[u * 128 + t];
-  }
-  // ---- head-only loads: half of channel c's LoRA-up rows + parameters
-  const float w0 = a.w0[c], a0 = a.a0[c], v0 = a.v0[c], kkc = a.k_k[c], kac = a.k_a[c];
-  const float rkc = a.r_k[c], lnw = a.lnx_w[c], lnb = a.lnx_b[c];
-  // ---- segment-dependent loads, speculated for slot = row = segment index (decode layout)
-  const int spec = seg_i < a.n_slots ? seg_i : 0;
-  // state block layout (engine.hip perm_index): this thread's q-th float4 at index q * 128 + t
-  const int64_t soff = a.layer_off + (int64_t)h * N * N + (int64_t)t * 4;
-  float4_ S4[8];
-  auto load_state = [&](int slot) {
-    const float4_* Sp = (const float4_*)(a.state + (int64_t)slot * a.slot_stride + soff);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) S4[q] = Sp[q * 128];
-  };
-  const bool hid_thread = t < DALL / 4;
-  float4_ hp[NP];
-  float rp[NP], kp[NP], vp[NP], vf = 0.f;
-  auto load_parts = [&](int row) {
-    const float* prow = a.part + (int64_t)row * a.ldp;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      const float* pp = prow + p * a.part_stride;
-      hp[p] = *(const float4_*)(pp + 3 * C + (hid_thread ? 4 * t : 0));
-      rp[p] = pp[c];
-      kp[p] = pp[C + c];
-      vp[p] = pp[2 * C + c];
-    }
-    vf = a.layer > 0 ? a.v_first[(int64_t)row * a.ldv + c] : 0.f;
-  };
-  load_parts(spec);
-  // the state goes out last (vmcnt retires in issue order): the LoRA / mixing phase starts
-  // while it is still in flight (measured: the LoRA-up rows first, then the partials, is best
-  // here; k_wkv6 prefers partials first)
-  load_state(spec);
-  const int slot = sg.x, r_begin = sg.y, n_rows = sg.z;
-  if (r_begin != spec) load_parts(r_begin);
-  if (slot != spec) load_state(slot);
-  float4_* Srow = (float4_*)(a.state + (int64_t)slot * a.slot_stride + soff);
-  for (int rr = 0; rr < n_rows; ++rr) {
-    const int row = r_begin + rr;
-    if (rr > 0) load_parts(row);
-    // LoRA hidden: threads 0..71 each own 4 consecutive entries (one region: w | a | v | g)
-    if (hid_thread) {
-      float4_ x = hp[0];
-#pragma unroll
-      for (int p = 1; p < NP; ++p) x += hp[p];
-      float4_ y;
-      if (t < DW / 4) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = ftanh(x[e]);
-      } else if (t < (DW + DA + DV) / 4) {
-        y = x;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = fsigm(x[e]);
-      }
-      *(float4_*)(s_hid + 4 * t) = y;
-    }
-    float r = rp[0], k = kp[0], v = vp[0];
-#pragma unroll
-    for (int p = 1; p < NP; ++p) {
-      r += rp[p];
-      k += kp[p];
-      v += vp[p];
-    }
-    __syncthreads();
-    if (stp && rr == 0) stp[2] = __builtin_amdgcn_s_memtime() + (uint64_t)(r != r);
-    // ---- LoRA up on packed pairs: this thread's half of channel c's four dot products
-    float2_ l0 = {0.f, 0.f}, l1 = {0.f, 0.f}, l2 = {0.f, 0.f}, l3 = {0.f, 0.f};
-    auto dot = [&](float2_ acc, const uint4 q, const float* hsrc) {
-      const float4_ h0 = *(const float4_*)hsrc;
-      const float4_ h1 = *(const float4_*)(hsrc + 4);
-      acc += w2f<F16>(q.x) * (float2_){h0[0], h0[1]};
-      acc += w2f<F16>(q.y) * (float2_){h0[2], h0[3]};
-      acc += w2f<F16>(q.z) * (float2_){h1[0], h1[1]};
-      acc += w2f<F16>(q.w) * (float2_){h1[2], h1[3]};
-      return acc;
-    };
-#pragma unroll
-    for (int u = 0; u < 4; ++u) l0 = dot(l0, lw[u], s_hid + hf * (DW / 2) + u * 8);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) l1 = dot(l1, lw[4 + u], s_hid + DW + hf * (DA / 2) + u * 8);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) l2 = dot(l2, lw[8 + u], s_hid + DW + DA + hf * (DV / 2) + u * 8);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) l3 = dot(l3, lw[10 + u], s_hid + DW + DA + DV + hf * (DG / 2) + u * 8);
-    float lo0 = l0[0] + l0[1], lo1 = l1[0] + l1[1], lo2 = l2[0] + l2[1], lo3 = l3[0] + l3[1];
-    lo0 += dpp_mov<0xB1>(lo0);
-    lo1 += dpp_mov<0xB1>(lo1);
-    lo2 += dpp_mov<0xB1>(lo2);
-    lo3 += dpp_mov<0xB1>(lo3);
-    // ---- channel mixing terms (both threads of the pair compute channel c)
-    const float w = fexp(-0.60653066f * fsigm(w0 + lo0));
-    const float av = fsigm(a0 + lo1);
-    const float kk = k * kkc;
-    k = k * (1.0f + (av - 1.0f) * kac);
-    if (a.layer == 0) {
-      if (hf == 0) a.v_first[(int64_t)row * a.ldv + c] = v;
-    } else {
-      v = v + (vf - v) * fsigm(v0 + lo2);
-    }
-    {
-      const float ksq = wave_sum(hf == 0 ? kk * kk : 0.f);
-      const float bon = wave_sum(hf == 0 ? r * k * rkc : 0.f);
-      if (lane == 0) { s_red[0][wave] = ksq; s_red[1][wave] = bon; }
-    }
-    if (hf == 0) {
-      s_vec[0][i] = w; s_vec[1][i] = kk; s_vec[2][i] = av; s_vec[3][i] = k; s_vec[4][i] = r;
-    }
-    __syncthreads();
-    if (stp && rr == 0) stp[3] = __builtin_amdgcn_s_memtime();
-    const float inv = __builtin_amdgcn_rcpf(fmaxf(sqrtf(s_red[0][0] + s_red[0][1]), 1e-12f));
-    const float bonus = s_red[1][0] + s_red[1][1];
-    // ---- state half-row update on packed pairs: S = S*w - sa*(kk*inv*a) + v*k ; y = S.r
-    const float* vj = &s_vec[0][hf * 32];
-    float2_ sa2 = {0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const float4_ kq = *(const float4_*)(vj + N + q * 4);
-      sa2 += (float2_){S4[q][0], S4[q][1]} * (float2_){kq[0], kq[1]};
-      sa2 += (float2_){S4[q][2], S4[q][3]} * (float2_){kq[2], kq[3]};
-    }
-    float sa = (sa2[0] + sa2[1]) * inv;
-    sa += dpp_mov<0xB1>(sa);
-    float2_ y2 = {0.f, 0.f};
-    const float2_ sav = {sa * inv, sa * inv}, vv = {v, v};
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const float4_ wq = *(const float4_*)(vj + q * 4);
-      const float4_ kq = *(const float4_*)(vj + N + q * 4);
-      const float4_ aq = *(const float4_*)(vj + 2 * N + q * 4);
-      const float4_ k4 = *(const float4_*)(vj + 3 * N + q * 4);
-      const float4_ rq = *(const float4_*)(vj + 4 * N + q * 4);
-#pragma unroll
-      for (int e = 0; e < 4; e += 2) {
-        float2_ sv = (float2_){S4[q][e], S4[q][e + 1]} * (float2_){wq[e], wq[e + 1]};
-        sv -= sav * ((float2_){kq[e], kq[e + 1]} * (float2_){aq[e], aq[e + 1]});
-        sv += vv * (float2_){k4[e], k4[e + 1]};
-        S4[q][e] = sv[0];
-        S4[q][e + 1] = sv[1];
-        y2 += sv * (float2_){rq[e], rq[e + 1]};
-      }
-    }
-    if (stp && rr == 0) stp[4] = __builtin_amdgcn_s_memtime() + (uint64_t)(y2[0] != y2[0]);
-    if (rr + 1 == n_rows) {  // the segment's final state: stored before the GroupNorm tail
-      if (a.wt) {
-        const auto rs = wt_rsrc(a.state + (int64_t)slot * a.slot_stride + a.layer_off + (int64_t)h * N * N);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) store_wt(rs, (q * 128 + t) * 16, S4[q]);
-      } else {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) Srow[q * 128] = S4[q];
-      }
-    }
-    float y = y2[0] + y2[1];
-    y += dpp_mov<0xB1>(y);
-    {
-      const float s1 = wave_sum(hf == 0 ? y : 0.f);
-      const float s2 = wave_sum(hf == 0 ? y * y : 0.f);
-      if (lane == 0) { s_red[2][wave] = s1; s_red[3][wave] = s2; }
-    }
-    __syncthreads();
-    if (stp && rr == 0) stp[5] = __builtin_amdgcn_s_memtime();
-    const float mean = (s_red[2][0] + s_red[2][1]) * (1.0f / N);
-    const float var = fmaxf((s_red[3][0] + s_red[3][1]) * (1.0f / N) - mean * mean, 0.f);
-    if (hf == 0) {
-      const float gn = (y - mean) * __builtin_amdgcn_rsqf(var + 64e-5f) * lnw + lnb;
-      split_store((gn + bonus * v) * lo3, e_zhi, e_zlo, (int64_t)row * e_ldz + c, F16);
-    }
-    if (rr + 1 < n_rows) __syncthreads();
-  }
-  if (stp) { stp[6] = __builtin_amdgcn_s_memtime(); stp[7] = __builtin_amdgcn_s_memrealtime(); }
-  tl_end(a.tl);
-}
-
-// ------------------------------------------------------------------------------------
-// wkv6: k_wkv4 on four waves. Thread t = (channel i = t >> 2, quarter qq = t & 3) owns state
-// row S[i][16 qq .. 16 qq + 15] and a quarter of channel c's LoRA-up dot products, so each
-// thread executes half of k_wkv4's per-row arithmetic and two waves share every SIMD (the
-// dependent chains of one hide behind the other's). Quarter sums are two quad shuffles.
-// State blocks: thread t's q-th float4 at float4 index q * 256 + t (engine.hip perm_index,
-// layout 2); LoRA-up rows: entry u of thread t at uint4 index u * 256 + t (launch_pack_lora6).
-// ------------------------------------------------------------------------------------
 // wkv6_body's roles (decode rows only in k_att_persist). The hand-off roles request the LoRA-up rows
 // and the state (independent of this layer's rkv workgroups) at dispatch, read the partials by sc1
 // loads, and store the final state after their hand-off.
@@ -2660,7 +2429,8 @@ __device__ __attribute__((always_inline)) void wkv6_body(const WkvArgs& a, const
     seg_i = j % a.n_seg;
   }
   const int C = a.C, c = h * N + i;
-  // debug phase stamps (as k_wkv4: RWKVTTS_DEBUG_STAMPS wkv=, one layer only; null in production)
+  // debug phase stamps (RWKVTTS_DEBUG_STAMPS wkv=, one layer only; null in production): [0] realtime
+  // start, [1..6] core clock at phase ends, [7] realtime end
   uint64_t* stp = (a.stamps && t == 0) ? a.stamps + ((int64_t)h * a.n_seg + seg_i) * 8 : nullptr;
   if (stp) { stp[0] = __builtin_amdgcn_s_memrealtime(); stp[1] = __builtin_amdgcn_s_memtime(); }
   const int4 sg = a.segs[seg_i];
@@ -3278,33 +3048,22 @@ bool launch_att_persist(const LnMixArgs& ln, const GemmArgs& rkv, const WkvArgs&
   return true;
 }
 
-int wkv_perm_layout(int Dw, int Da, int Dv, int Dg, int n_part, int max_slots, int variant) {
-  if (!(Dw == 64 && Da == 64 && Dv == 32 && Dg == 128 && n_part == 4)) return 0;
-  if (variant == 1 || variant == 2) return variant;
-  // auto: k_wkv6 (measured, timeline of a graph-replayed 32-slot step: 4.85 vs 5.33 us per
-  // launch once its loads are issued in need order and the XCD-aware grid keeps a head's
-  // LoRA-up rows in one L2; 1 % faster at one slot as well)
-  (void)max_slots;
-  return 2;
+int wkv_perm_layout(int Dw, int Da, int Dv, int Dg, int n_part) {
+  return Dw == 64 && Da == 64 && Dv == 32 && Dg == 128 && n_part == 4 ? 2 : 0;
 }
 int launch_wkv(const WkvArgs& a, int n_seg, int H, hipStream_t st) {
   const dim3 grid(n_seg, H);
-  if (a.Dw == 64 && a.Da == 64 && a.Dv == 32 && a.Dg == 128 && a.n_part == 4 && (a.perm == 1 || a.perm == 2)) {
+  if (a.Dw == 64 && a.Da == 64 && a.Dv == 32 && a.Dg == 128 && a.n_part == 4 && a.perm == 2) {
     WkvArgs b = a;
     b.xmap = (H % 8 == 0 && a.allow_xmap) ? 1 : 0;
     b.n_seg = n_seg;
     const dim3 g = b.xmap ? dim3(n_seg * H) : grid;
-    if (a.perm == 2) {
-      if (a.multi_row) {
-        if (a.f16) RT_LAUNCH((k_wkv6<true, true>), g, dim3(256), 0, st, b);
-        else RT_LAUNCH((k_wkv6<false, true>), g, dim3(256), 0, st, b);
-      } else {
-        if (a.f16) RT_LAUNCH((k_wkv6<true>), g, dim3(256), 0, st, b);
-        else RT_LAUNCH((k_wkv6<false>), g, dim3(256), 0, st, b);
-      }
+    if (a.multi_row) {
+      if (a.f16) RT_LAUNCH((k_wkv6<true, true>), g, dim3(256), 0, st, b);
+      else RT_LAUNCH((k_wkv6<false, true>), g, dim3(256), 0, st, b);
     } else {
-      if (a.f16) RT_LAUNCH((k_wkv4<true>), g, dim3(128), 0, st, b);
-      else RT_LAUNCH((k_wkv4<false>), g, dim3(128), 0, st, b);
+      if (a.f16) RT_LAUNCH((k_wkv6<true>), g, dim3(256), 0, st, b);
+      else RT_LAUNCH((k_wkv6<false>), g, dim3(256), 0, st, b);
     }
     return n_seg * H;
   }

@@ -52,6 +52,7 @@ class Dims(ctypes.Structure):
 
 
 class EngineDesc(ctypes.Structure):
+    # wkv_variant: ignored by the engine, kept for layout compatibility (include/rwkvtts.h)
     _fields_ = [("device", ctypes.c_int32), ("max_slots", ctypes.c_int32),
                 ("token_chunk_size", ctypes.c_int32), ("use_graphs", ctypes.c_int32),
                 ("wkv_variant", ctypes.c_int32), ("quant_layers", ctypes.c_int32),

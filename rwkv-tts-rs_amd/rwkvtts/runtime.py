@@ -157,7 +157,9 @@ def quant_config(quant_layers: int, quant_type) -> tuple:
 class SharedRwkvRuntime:
     """One engine per GPU: weights resident in HBM, `max_concurrent_batches` state slots.
     quant_layers / quant_type: the server's --quant-layers / --quant-type (web-rwkv Quant).
-    forms: rwkvtts_engine_desc.forms (_ffi.FORM_*; 0 = the shipping decode forms)."""
+    forms: rwkvtts_engine_desc.forms (_ffi.FORM_*; 0 = the shipping decode forms).
+    wkv_variant: mirrors rwkvtts_engine_desc.wkv_variant; ignored (every value selects the one WKV
+    kernel the shape has)."""
 
     def __init__(self, weights: np.ndarray, device: int = 0, max_slots: int = 10,
                  token_chunk_size: int = 512, use_graphs: bool = True, weights_on_device: bool = False,
@@ -461,7 +463,8 @@ class DynamicBatchManager:
     thread may call generate_tts; the collector batches concurrent calls with the reference's
     collect window and routes each request to the least-loaded engine (one per device, one owner
     thread each), whose continuous batching decodes all its requests together. Per-request
-    outputs equal the serial single-engine run."""
+    outputs equal the serial single-engine run. wkv_variant mirrors
+    rwkvtts_engine_desc.wkv_variant and is ignored."""
 
     def __init__(self, weights: np.ndarray, config: Optional[DynamicBatchConfig] = None,
                  devices: Sequence[int] = (0,), max_slots: int = 32, token_chunk_size: int = 512,

@@ -12,7 +12,7 @@ Where they land (Engine::init's pick(); launch_wkv, launch_ln_mix, launch_gemm_t
 
   launch_wkv     units = ceil(rank total / 16), n_part = the rkv split. c128x: 5 units, 1 slab, and
                  ranks that are not k_wkv2's 16/16/16/32 -> k_wkv<8,4>. c768: 18 units, 3 slabs (the
-                 0.4B ranks, but not its 4 slabs, so not k_wkv6 / k_wkv4) -> k_wkv<20,4>. c2048:
+                 0.4B ranks, but not its 4 slabs, so not k_wkv6) -> k_wkv<20,4>. c2048:
                  32 units, 8 slabs -> k_wkv<32,8>.
   launch_ln_mix  C != 1024, so never k_ln1024. c128x and c768: k_ln_mix<1,0> (layer 0) and
                  k_ln_mix<1,-1> with 3 / 1 and 12 / 6 slabs (LN1 of layers > 0 and ln_out sum the
@@ -23,7 +23,7 @@ Where they land (Engine::init's pick(); launch_wkv, launch_ln_mix, launch_gemm_t
                  <= 64 rows on bf16 engines and at every row count on f16 engines (no relu^2 planes).
                  The planes-mode GEMMs (rkv, Wo, key, head) stay k_gemm2 with kslice 128 / 256.
   grids          the XCD-mapped 1-D grids (kXmapMask: value GEMM and WKV) exist in k_gemm2 and
-                 k_wkv6 / k_wkv4 only, so every launch above keeps the plain (tiles, k_split, mg) and
+                 k_wkv6 only, so every launch above keeps the plain (tiles, k_split, mg) and
                  (n_seg, H) grids, c768 with H = 12 and splits 3 / 6 / 12 that are no divisor or
                  multiple of 8. The key GEMM's XCD-aligned grid (kXalignMask, steps of <= 32 rows) pads
                  its tile groups to a multiple of 8: c128x has 3 groups of 2 tiles (-> 8), c768 12

@@ -1,8 +1,8 @@
 """The LM forward pass at ragged steps and tile edges, at the 0.4B widths (DIMS_MID, n_vocab 77923).
 
 Every step is ONE rt.infer call whose inputs all ask for every row's logits (OPT_FULL), on engines
-with use_graphs=False and max_slots=8: bf16 and f16, and for the 128-token engine also
-wkv_variant=1 (k_wkv4's row loop instead of k_wkv6 / wkv6_rows). Tokens are uniform random ids
+with use_graphs=False and max_slots=8: bf16 and f16, and for the 128-token engine also one created
+with wkv_variant=1 (id bf16_wkv4; the engine ignores the field). Tokens are uniform random ids
 below n_vocab from fixed seeds. Every case makes the three assertions of forward_check.check_case:
 float64 reference (logits < 2e-3, state < 1e-3: test_gpu_forward.py's bounds, now against an exact
 reference), bitwise equality with the segment run alone, bitwise equality with one token per call
@@ -48,7 +48,7 @@ What each case crosses (R = rows of the step, mg = ceil(R / 32) row groups):
   head edge, 3 rows: head_rows 1, 15, 17, 63, 65 (the first 64-column tile partly filled / just
     exceeded), 77923 (Vpad = 77936: the last of 1218 tiles holds 35 columns)
   hand-over: a ragged step, a step of one row per slot (R == n_seg: the one-row WKV kernel reads
-    the state wkv6_rows / k_wkv4's row loop wrote), a second ragged step, then every slot's state
+    the state wkv6_rows wrote), a second ragged step, then every slot's state
 """
 import functools
 
