@@ -479,6 +479,10 @@ typedef struct {
   int32_t up_kernels[4];  /* 16,11,8,4 */
 } rwkvtts_codec_dims;
 int64_t rwkvtts_codec_blob_bytes(const rwkvtts_codec_dims* d);
+/* rwkvtts_codec_create refuses, with RWKVTTS_EINVAL and before it touches a device, dims the decoder
+ * cannot run: a product of up_rates other than RWKVTTS_HOP (the PCM buffers hold 320 samples per
+ * frame), a ConvTranspose with k < s, odd k - s or more than 7 taps per phase (ceil(k / s)), channel
+ * counts that are no multiples of 64 (last stage: of 32, at most 112), prenet_dim above 512. */
 int rwkvtts_codec_synth_weights(const rwkvtts_codec_dims* d, uint64_t seed, float* out);
 int rwkvtts_codec_create(int device, const rwkvtts_codec_dims* d, const float* weights,
                          rwkvtts_codec** out);
@@ -538,6 +542,45 @@ int rwkvtts_codec_decode_windows(rwkvtts_codec* c, const rwkvtts_codec_window* w
 #define RWKVTTS_CODEC_FORM_SEPARATE_RESUNIT 1u /* 96-channel residual units as conv7 + conv1 launches */
 #define RWKVTTS_CODEC_FORM_CHANNEL_LAST 2u     /* WaveGenerator planes [t][c] instead of [c / 32][t][32] */
 int rwkvtts_codec_set_forms(rwkvtts_codec* c, uint32_t forms);
+/* ---- codec test hooks, not part of the drop-in surface -------------------------------------
+ * One record per k_conv launch of a decode, in launch order: what the launch computes and which
+ * k_conv instantiation, grid and LDS size the host chooses for it. The decode path takes its choice
+ * from the same function that fills these records. Tensor references are
+ * group * 1000000 + index * 100 + tensor of include/rwkvtts_codec_layout.h, -1 for none. */
+typedef struct {
+  uint32_t struct_size;
+  int32_t kind;             /* 0 conv, 1 ConvTranspose, 2 fused residual unit (conv7 -> Snake -> conv1) */
+  int32_t ci, co, k, dil, pad, s;
+  int32_t tin_mul;          /* input rows per frame; output rows per frame: tin_mul (* s for kind 1) */
+  int32_t tn, kt, wlo, nwv; /* k_conv<TN, KT, WLO, NWV, kind == 2> */
+  int32_t shm_bytes;
+  int32_t xmap, gx, gy;     /* XCD-mapped 1-D grid; time tiles; phases * column tiles */
+  int32_t grid[3];
+  int32_t act;              /* 1: exact GELU */
+  int32_t has_y, has_planes, has_res, has_rbias;
+  int32_t w, bias, gamma, y_alpha, mid_alpha, w1, bias1;
+} rwkvtts_codec_launch;
+/* The launches of a decode of n utterances of at most Tmax frames, for a decoder on the weight hi
+ * + lo path (weight_lo != 0) or not, with the given RWKVTTS_CODEC_FORM_* bits. Fills up to `cap`
+ * records of `out` (nullable) and returns the number of launches, or a negative RWKVTTS_E* code
+ * (dims that rwkvtts_codec_create refuses, or a launch for which no tile fits). Host only. */
+int rwkvtts_codec_debug_launch_plan(const rwkvtts_codec_dims* d, int weight_lo, uint32_t forms, int n, int Tmax,
+                                    rwkvtts_codec_launch* out, int cap);
+/* Arms launch `launch` (an index into the plan above; -1 disarms) of the NEXT decode call: around
+ * that launch the decode synchronises and copies out the launch's inputs (before) and outputs
+ * (after). The call after that runs unarmed again. A decode whose launch `launch` does not match
+ * the plan's record fails with RWKVTTS_EINVAL. */
+int rwkvtts_codec_debug_capture(rwkvtts_codec* c, int launch);
+/* The captured launch: its record, utterance count and rows per utterance (Tmax * tin_mul in,
+ * * s out for a ConvTranspose). */
+int rwkvtts_codec_debug_captured_launch(rwkvtts_codec* c, rwkvtts_codec_launch* rec, int32_t* n, int32_t* rows_in,
+                                        int32_t* rows_out);
+/* One captured array as logical [n][rows][C], channel blocking undone. what: 0 / 1 input hi / lo
+ * planes (bf16 bits, [n][rows_in][ci]); 2 residual (f32, [n][rows_out][co], before the launch);
+ * 3 y (f32); 4 / 5 output hi / lo planes (bf16 bits); 6 per-utterance bias (f32 [n][co]). Rows past
+ * an utterance's length hold whatever the buffers held. Returns the array's size in bytes (0: the
+ * launch has no such array) and copies it to `out` if cap_bytes suffices (out nullable). */
+int64_t rwkvtts_codec_debug_captured(rwkvtts_codec* c, int what, void* out, int64_t cap_bytes);
 /* Per-stage HIP-event timing of later decode calls (profiling on): name, launches, total ms. */
 int rwkvtts_codec_set_profiling(rwkvtts_codec* c, int on);
 int rwkvtts_codec_profile_count(rwkvtts_codec* c);

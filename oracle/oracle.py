@@ -159,13 +159,17 @@ class Model:
 
 
 def codec_decode(dims_struct, weights: np.ndarray, semantic, global_tokens, threads: int = 0) -> np.ndarray:
-    """f32 CPU restatement of the BiCodec decoder (codec.c) -> PCM [T * 320]."""
+    """f32 CPU restatement of the BiCodec decoder (codec.c) -> PCM [T * prod(up_rates)] (320 per
+    frame at every dims the GPU decoder admits; codec.c writes that many whatever the dims say)."""
     if threads:
         lib().oracle_set_threads(threads)
     s = np.ascontiguousarray(semantic, dtype=np.int64)
     g = np.ascontiguousarray(global_tokens, dtype=np.int64)
     w = np.ascontiguousarray(weights, dtype=np.float32)
-    pcm = np.empty(s.size * 320, dtype=np.float32)
+    hop = 1
+    for i in range(dims_struct.n_up):
+        hop *= int(dims_struct.up_rates[i])
+    pcm = np.empty(s.size * hop, dtype=np.float32)
     rc = lib().oracle_codec_decode(ctypes.byref(dims_struct), w.ctypes.data, s.ctypes.data, int(s.size),
                                    g.ctypes.data, pcm.ctypes.data)
     if rc != 0:

@@ -702,6 +702,231 @@ static int codec_window_plan(const rwkvtts_codec_dims* d, int t0, int t1, int n_
   return RWKVTTS_OK;
 }
 
+// The dims the decoder runs (nullptr) or why not. Codec::init asks before its first HIP call, and
+// rwkvtts_codec_debug_launch_plan before it plans: pcm holds RWKVTTS_HOP samples per frame and
+// k_conv_out writes prod(up_rates) of them, and k_conv has no instantiation for more than 7 taps.
+static const char* codec_dims_check(const rwkvtts_codec_dims& d) {
+  if (!(d.n_up >= 1 && d.n_up <= 4 && d.latent_dim == d.spk_dim && d.prenet_dim <= 512 && d.fsq_dims <= 16 &&
+        d.codebook_dim <= 64 && d.fsq_levels >= 2))
+    return "codec: unsupported dims";
+  if (!(d.codebook_size > 0 && d.codebook_dim > 0 && d.fsq_dims > 0 && d.n_global > 0 && d.latent_dim > 0 &&
+        d.prenet_dim > 0 && d.prenet_inter > 0 && d.prenet_layers >= 0 && d.prenet_layers <= 4096 &&
+        (d.dec_channels >> d.n_up) > 0))
+    return "codec: unsupported dims";
+  if (!(d.latent_dim % 64 == 0 && d.prenet_dim % 64 == 0 && d.prenet_inter % 64 == 0 &&
+        (d.dec_channels >> d.n_up) % 32 == 0 && (d.dec_channels >> d.n_up) <= 112))
+    return "codec: channel counts must be multiples of 64 (last stage: of 32, <= 112)";
+  int64_t hop = 1;
+  for (int i = 0; i < d.n_up; ++i) {
+    if (!(d.up_rates[i] >= 1 && d.up_rates[i] <= RWKVTTS_HOP && d.up_kernels[i] >= d.up_rates[i] &&
+          ((d.up_kernels[i] - d.up_rates[i]) % 2) == 0 && (d.up_kernels[i] + d.up_rates[i] - 1) / d.up_rates[i] <= 7))
+      return "codec: ConvTranspose needs k >= s, even k - s and <= 7 taps per phase";
+    hop *= d.up_rates[i];
+  }
+  if (hop != RWKVTTS_HOP) return "codec: the product of up_rates must be RWKVTTS_HOP (320 samples per frame)";
+  return nullptr;
+}
+
+// ---- the launch plan: which k_conv instantiation, LDS size and grid a launch gets ------------
+// Host only. Codec::conv() and Codec::resunit_fused() launch what these two functions choose, and
+// rwkvtts_codec_debug_launch_plan lists it (tests/test_codec_plan_cpu.py).
+struct ConvPlan {
+  int TN = 0, KT = 0, NWV = 0;
+  bool WLO = false, FUSE = false;
+  size_t shm = 0;
+  int xmap = 0, gx = 0, gy = 0;  // time tiles, phases * column tiles
+  unsigned grid[3] = {0, 0, 0};
+};
+// nullptr, or why the launch cannot run
+static const char* conv_plan(bool wlo, int n, int Tmax, int Ci, int tin_mul, int K, int Co, int mode, int dil, int s,
+                             ConvPlan* p) {
+  if (Ci % 32 != 0 || Co % 32 != 0) return "codec conv: channels must be multiples of 32";
+  // column tile: 64, or for the last stage's 96 channels 96 (pointwise) / 48 (taps): 32-wide
+  // tiles read two LDS fragments per four MFMAs
+  int TN = (Co % 64 == 0) ? 64 : ((Co % 96 == 0 && K == 1) ? 96 : (Co % 48 == 0 ? 48 : 32));
+  // pointwise (memory-bound) convs: 96-wide column tiles read the input window fewer times
+  // (conv1 @ 192 / 384 / 768: 6.9 / 4.1 / 2.2 -> 5.3 / 3.5 / 2.0 ms per batch with the XCD-aware
+  // order below; 192-wide tiles halve the occupancy and are slower)
+  if (K == 1 && Co % 96 == 0) TN = 96;
+  const int ntaps_max = mode == 1 ? (K + s - 1) / s : K;
+  const int span = (ntaps_max - 1) * (mode == 1 ? 1 : dil);
+  const int KT = ntaps_max <= 1 ? 1 : (ntaps_max <= 3 ? 3 : 7);
+  {  // 7-tap convs: 64-wide column tiles by default. 96-wide ones (where the double-buffered
+     // chunk fits: RWKVTTS_CONV7_TN=96) make the vocoder alone faster (residual conv7 33.4 ->
+     // 31.1 ms per batch) but their 155 KB of LDS leaves no room on the CU for a decode GEMM
+     // workgroup (34 KB): beside the next batch's token generator -- the serving shape, the
+     // bench -- every GEMM launch then waits for whole vocoder workgroups to retire. 64-wide
+     // tiles (124 KB) let them share the CU: decode step 0.883 -> 0.875 ms in the bench, +0.7 %
+     // samples/s (same-box A/B x2, tools/bench_ab.sh) for +1 ms of vocoder time. Tests
+     // bit-identical either way: the per-element accumulation order does not depend on TN.
+    // Round 4: the decode step's persistent workgroups (k_att_persist / k_ffn_persist) take
+    // 36.6 KB of LDS, which fits beside a 64-wide tile at dilation 1 only. 48-wide tiles leave
+    // room at every dilation: bench A/Bs (13 alternating pairs over three boxes,
+    // profiles/r04_conv7_tile_ab.txt) +0.1 to +1.2 % samples/s, within the boxes' run-to-run
+    // spread, for +1.5 ms of vocoder time; 64 stays.
+    // ConvTranspose: 96-wide tiles measured faster at 96 and 384 output channels (2.54 -> 2.14,
+    // 2.30 -> 2.10 ms per batch), slower at 192 (2.51 -> 2.62), equal at 768
+    if (mode == 1 && KT == 3 && (Co == 96 || Co == 384)) TN = 96;
+    // (Round 6: capping every conv launch's workgroups per CU, by padding its LDS request, so that a
+    // persistent decode workgroup always fits beside them -- with the pointwise convs in 64-wide
+    // tiles, the ConvTranspose ones too, the 7-tap ones in 48-wide tiles -- left the decode step
+    // beside the vocoder unchanged, 0.806-0.816 ms, and the vocoder alone 3-10 ms slower:
+    // profiles/r06e_coresidency_ab.txt, tools/experiments/r06_codec_coresidency.patch)
+  }
+  int nwv = conv_waves(KT);
+  const int wplanes = wlo ? 2 : 1;  // weight planes staged per chunk
+  auto chunk_rows = [&](int tn, int nw) { return 2 * ((32 * nw + span + 15) & ~15) + wplanes * ntaps_max * tn; };
+  auto shm_of = [&](int tn, int nw) {
+    return std::max(2 * (size_t)chunk_rows(tn, nw) * 64, (size_t)nw * 32 * (tn + 4) * sizeof(float));
+  };
+  auto fits = [&](int tn, int nw) {
+    return Co % tn == 0 && shm_of(tn, nw) <= 160 * 1024 && chunk_rows(tn, nw) / 16 <= 16 * nw;
+  };
+  if (wlo && (!fits(TN, nwv) || TN > 96)) {  // (no weight-lo kernel wider than 96 columns)
+    // the weight lo plane doubles the staged weights: the (tile width, waves) that fits and
+    // stages the fewest LDS rows per output element
+    int bt = 0, bw = 0;
+    double best = 0.0;
+    for (int nw : {conv_waves(KT), 4})
+      for (int tn : {96, 64, 48, 32}) {
+        if (!fits(tn, nw) || (nw != conv_waves(KT) && KT != 7)) continue;
+        const double sc = (double)(32 * nw * tn) / chunk_rows(tn, nw);
+        if (sc > best) { best = sc; bt = tn; bw = nw; }
+      }
+    if (bt <= 0) return "codec conv: no tile fits the LDS with weight lo planes";
+    TN = bt;
+    nwv = bw;
+  }
+  const int TM = 32 * nwv;
+  if (!(fits(TN, nwv) && ntaps_max <= 7 && Ci <= 4096)) return "codec conv: tile window too large";
+  p->TN = TN; p->KT = KT; p->NWV = nwv; p->WLO = wlo; p->FUSE = false;
+  p->shm = shm_of(TN, nwv);
+  const int phases = mode == 1 ? s : 1;
+  p->gx = (int)((Tmax * (int64_t)tin_mul + TM - 1) / TM);
+  p->gy = phases * (Co / TN);
+  p->grid[0] = (unsigned)p->gx; p->grid[1] = (unsigned)p->gy; p->grid[2] = (unsigned)n;
+  // XCD-aware order for the long-time-axis residual convs (conv7 and conv1 at >= 32 time tiles:
+  // a time tile's column tiles share one L2); the short prenet / conv_in / convT launches keep
+  // the default order (2x slower remapped)
+  // (the ConvTranspose launches in this order too: 1-8 % slower, the Infinity Cache serves their
+  // re-reads)
+  p->xmap = 0;
+  if (p->gy > 1 && p->gx >= 32 && mode == 0 && (K == 7 || K == 1)) {
+    p->xmap = 1;
+    p->grid[0] = (unsigned)(8 * ((p->gx + 7) / 8) * p->gy);
+    p->grid[1] = 1;
+  }
+  return nullptr;
+}
+
+// One residual unit (conv7 -> Snake -> conv1 -> + residual) as ONE launch when it fits: 96
+// channels (one column tile covers every channel the pointwise conv needs), bf16-exact weights
+// (the weight lo plane would not fit beside the 7-tap chunk). false: the two convs run.
+static bool resunit_plan(bool wlo, uint32_t forms, int n, int Tmax, int C, int tin_mul, int dil, ConvPlan* p) {
+  if ((forms & RWKVTTS_CODEC_FORM_SEPARATE_RESUNIT) || wlo || C != 96) return false;
+  const int span = 6 * dil;
+  int nwv = 0;
+  for (int nw : {8, 4}) {  // (4-wave units where 8 do not fit: 8 measured faster)
+    const int wr = (32 * nw + span + 15) & ~15;
+    const size_t chunk = 2 * (size_t)(2 * wr + 7 * 96) * 64;
+    const size_t fused = (size_t)3 * 2 * 32 * nw * 64 + 3 * 96 * 64;
+    const size_t epi = (size_t)nw * 32 * 100 * sizeof(float);
+    if (std::max(std::max(chunk, fused), epi) <= 160 * 1024 && (2 * wr + 7 * 96) / 16 <= conv_maxb(nw, true) * nw) {
+      nwv = nw;
+      break;
+    }
+  }
+  if (!nwv) return false;
+  const int TM = 32 * nwv, wr = (TM + span + 15) & ~15;
+  p->TN = 96; p->KT = 7; p->NWV = nwv; p->WLO = false; p->FUSE = true;
+  p->shm = std::max(std::max(2 * (size_t)(2 * wr + 7 * 96) * 64, (size_t)3 * 2 * TM * 64 + 3 * 96 * 64),
+                    (size_t)nwv * 32 * 100 * sizeof(float));
+  p->xmap = 0;
+  p->gx = (int)((Tmax * (int64_t)tin_mul + TM - 1) / TM);
+  p->gy = 1;
+  p->grid[0] = (unsigned)p->gx; p->grid[1] = 1; p->grid[2] = (unsigned)n;
+  return true;
+}
+
+// Every k_conv launch of one decode, in the order Codec::prenet() and Codec::wavegen() issue them
+// (a capture run checks the armed launch against its record here: Codec::capture_pre)
+static int codec_launch_plan(const rwkvtts_codec_dims& d, bool wlo, uint32_t forms, int n, int Tmax,
+                             std::vector<rwkvtts_codec_launch>* out) {
+  const char* why = codec_dims_check(d);
+  RT_CHECK(!why, RWKVTTS_EINVAL, why);
+  RT_CHECK(n > 0 && Tmax > 0, RWKVTTS_EINVAL, "codec launch plan: n and Tmax must be > 0");
+  auto ref = [](int g, int i, int t) { return g * 1000000 + i * 100 + t; };
+  auto rec_of = [&](int kind, int Ci, int tin_mul, int K, int Co, int dil, int pad, int s, const ConvPlan& p) {
+    rwkvtts_codec_launch r;
+    memset(&r, 0, sizeof(r));
+    r.struct_size = sizeof(r);
+    r.kind = kind; r.ci = Ci; r.co = Co; r.k = K; r.dil = dil; r.pad = pad; r.s = s; r.tin_mul = tin_mul;
+    r.tn = p.TN; r.kt = p.KT; r.wlo = p.WLO; r.nwv = p.NWV; r.shm_bytes = (int32_t)p.shm;
+    r.xmap = p.xmap; r.gx = p.gx; r.gy = p.gy;
+    for (int i = 0; i < 3; ++i) r.grid[i] = (int32_t)p.grid[i];
+    r.w = r.bias = r.gamma = r.y_alpha = r.mid_alpha = r.w1 = r.bias1 = -1;
+    return r;
+  };
+  const char* err = nullptr;
+  auto conv = [&](int Ci, int tin_mul, int K, int Co, int mode, int dil, int pad, int s) {
+    ConvPlan p;
+    if (!err) err = conv_plan(wlo, n, Tmax, Ci, tin_mul, K, Co, mode, dil, s, &p);
+    out->push_back(rec_of(mode, Ci, tin_mul, K, Co, dil, pad, s, p));
+    return &out->back();
+  };
+  const int L = d.latent_dim, P = d.prenet_dim, I = d.prenet_inter;
+  {
+    auto* r = conv(L, 1, 1, P, 0, 1, 0, 1);
+    r->w = ref(0, 0, CD_PRE_W); r->bias = ref(0, 0, CD_PRE_B); r->has_planes = 1;
+    r = conv(P, 1, 7, P, 0, 1, 3, 1);
+    r->w = ref(0, 0, CD_EMB_W); r->bias = ref(0, 0, CD_EMB_B); r->has_y = 1;
+  }
+  for (int l = 0; l < d.prenet_layers; ++l) {
+    auto* r = conv(P, 1, 1, I, 0, 1, 0, 1);
+    r->w = ref(1, l, CB_PW1_W); r->bias = ref(1, l, CB_PW1_B); r->has_planes = 1; r->act = 1;
+    r = conv(I, 1, 1, P, 0, 1, 0, 1);
+    r->w = ref(1, l, CB_PW2_W); r->bias = ref(1, l, CB_PW2_B); r->gamma = ref(1, l, CB_GAMMA); r->has_y = r->has_res = 1;
+  }
+  {
+    auto* r = conv(P, 1, 1, L, 0, 1, 0, 1);
+    r->w = ref(0, 0, CD_LIN_W); r->bias = ref(0, 0, CD_LIN_B); r->has_planes = r->has_rbias = 1;
+  }
+  int C = d.dec_channels, mul = 1;
+  {
+    auto* r = conv(L, 1, 7, C, 0, 1, 3, 1);
+    r->w = ref(0, 0, CD_CIN_W); r->bias = ref(0, 0, CD_CIN_B); r->has_planes = 1; r->y_alpha = ref(2, 0, CU_SNAKE);
+  }
+  static const int dils[3] = {1, 3, 9};
+  for (int ub = 0; ub < d.n_up; ++ub) {
+    const int Co = C / 2, s = d.up_rates[ub], K = d.up_kernels[ub];
+    auto* r = conv(C, mul, K, Co, 1, 1, 0, s);
+    r->w = ref(2, ub, CU_T_W); r->bias = ref(2, ub, CU_T_B); r->has_y = r->has_planes = 1; r->y_alpha = ref(2, ub, CU_R0_A1);
+    mul *= s;
+    C = Co;
+    for (int u = 0; u < 3; ++u) {
+      const int o = u * (CU_R1_A1 - CU_R0_A1);
+      const int next = u < 2 ? ref(2, ub, CU_R0_A1 + o + (CU_R1_A1 - CU_R0_A1))
+                             : (ub + 1 < d.n_up ? ref(2, ub + 1, CU_SNAKE) : ref(0, 0, CD_SOUT_A));
+      ConvPlan p;
+      if (resunit_plan(wlo, forms, n, Tmax, C, mul, dils[u], &p)) {
+        out->push_back(rec_of(2, C, mul, 7, C, dils[u], 3 * dils[u], 1, p));
+        r = &out->back();
+        r->w = ref(2, ub, CU_R0_W7 + o); r->bias = ref(2, ub, CU_R0_B7 + o); r->mid_alpha = ref(2, ub, CU_R0_A2 + o);
+        r->w1 = ref(2, ub, CU_R0_W1 + o); r->bias1 = ref(2, ub, CU_R0_B1 + o);
+        r->has_y = u < 2; r->has_res = r->has_planes = 1; r->y_alpha = next;
+        continue;
+      }
+      r = conv(C, mul, 7, C, 0, dils[u], 3 * dils[u], 1);
+      r->w = ref(2, ub, CU_R0_W7 + o); r->bias = ref(2, ub, CU_R0_B7 + o); r->has_planes = 1; r->y_alpha = ref(2, ub, CU_R0_A2 + o);
+      r = conv(C, mul, 1, C, 0, 1, 0, 1);
+      r->w = ref(2, ub, CU_R0_W1 + o); r->bias = ref(2, ub, CU_R0_B1 + o);
+      r->has_y = u < 2; r->has_res = r->has_planes = 1; r->y_alpha = next;
+    }
+  }
+  RT_CHECK(!err, RWKVTTS_EINVAL, err);
+  return RWKVTTS_OK;
+}
+
 struct Planes {  // activated activations as bf16 hi + lo (x = hi + lo)
   bf16_t* h = nullptr;
   bf16_t* l = nullptr;
@@ -772,16 +997,8 @@ class Codec {
   int init(int dev, const rwkvtts_codec_dims& dims, const float* host_w, int weight_path) {
     d = dims;
     device = dev;
-    RT_CHECK(d.n_up >= 1 && d.n_up <= 4 && d.latent_dim == d.spk_dim && d.prenet_dim <= 512 &&
-                 d.fsq_dims <= 16 && d.codebook_dim <= 64 && d.fsq_levels >= 2,
-             RWKVTTS_EINVAL, "codec: unsupported dims");
-    RT_CHECK(d.latent_dim % 64 == 0 && d.prenet_dim % 64 == 0 && d.prenet_inter % 64 == 0 &&
-                 (d.dec_channels >> d.n_up) % 32 == 0 && (d.dec_channels >> d.n_up) <= 112,
-             RWKVTTS_EINVAL, "codec: channel counts must be multiples of 64 (last stage: of 32, <= 112)");
-    for (int i = 0; i < d.n_up; ++i)
-      RT_CHECK(d.up_rates[i] >= 1 && d.up_kernels[i] >= d.up_rates[i] && ((d.up_kernels[i] - d.up_rates[i]) % 2) == 0 &&
-                   (d.up_kernels[i] + d.up_rates[i] - 1) / d.up_rates[i] <= 8,
-               RWKVTTS_EINVAL, "codec: ConvTranspose needs k >= s, even k - s and <= 8 taps per phase");
+    const char* why = codec_dims_check(d);
+    RT_CHECK(!why, RWKVTTS_EINVAL, why);
     RT_HIP(hipSetDevice(device));
     {  // lowest queue priority: the LM decode chain (engine.hip) goes first when both share the GPU
       int least = 0, greatest = 0;
@@ -896,6 +1113,76 @@ class Codec {
     prof.push_back({name, {1, (double)ms}});
   }
 
+  // ---- launch capture (test hook: rwkvtts_codec_debug_capture) ----
+  // launch_idx counts the k_conv launches of a decode call; the launch whose index is cap_arm has
+  // its inputs copied out before it runs and its outputs after (a stream synchronise each side).
+  int launch_idx = 0, cap_arm = -1;
+  struct Capture {
+    bool have = false;
+    rwkvtts_codec_launch rec{};
+    int n = 0, rows_in = 0, rows_out = 0;
+    std::vector<uint16_t> xh, xl, yh, yl;
+    std::vector<float> res, y, rbias;
+  } cap;
+  // planes of `rows` rows x C channels per utterance -> logical [n][rows][C]
+  int fetch_planes(const bf16_t* base, int64_t bs, int64_t cs, int n, int rows, int C, std::vector<uint16_t>* out) {
+    const size_t per = (size_t)rows * C;
+    out->assign((size_t)n * per, 0);
+    std::vector<uint16_t> tmp(per);
+    for (int req = 0; req < n; ++req) {
+      RT_HIP(hipMemcpy(tmp.data(), base + req * bs, per * sizeof(uint16_t), hipMemcpyDeviceToHost));
+      uint16_t* o = out->data() + req * per;
+      if (!cs) {
+        memcpy(o, tmp.data(), per * sizeof(uint16_t));
+        continue;
+      }
+      for (int r = 0; r < rows; ++r)
+        for (int c = 0; c < C; ++c) o[(size_t)r * C + c] = tmp[(size_t)(c >> 5) * cs + (size_t)r * 32 + (c & 31)];
+    }
+    return RWKVTTS_OK;
+  }
+  int fetch_f32(const float* base, int64_t bs, int n, int64_t per, std::vector<float>* out) {
+    out->assign((size_t)n * per, 0.f);
+    for (int req = 0; req < n; ++req)
+      RT_HIP(hipMemcpy(out->data() + (size_t)req * per, base + req * bs, per * sizeof(float), hipMemcpyDeviceToHost));
+    return RWKVTTS_OK;
+  }
+  int capture_pre(int li, const ConvArgs& a, const ConvPlan& pl, int n, int Tmax) {
+    std::vector<rwkvtts_codec_launch> plan;
+    int rc = codec_launch_plan(d, wlo, forms, n, Tmax, &plan);
+    if (rc) return rc;
+    RT_CHECK(li < (int)plan.size(), RWKVTTS_EINVAL, "codec capture: more launches than the plan lists");
+    const rwkvtts_codec_launch& r = plan[li];
+    const int kind = pl.FUSE ? 2 : a.mode;
+    RT_CHECK(r.kind == kind && r.ci == a.Ci && r.co == a.Co && r.k == a.K && r.dil == a.dil && r.pad == a.pad &&
+                 r.s == a.s && r.tin_mul == a.tin_mul && r.tn == pl.TN && r.kt == pl.KT && r.wlo == (int)pl.WLO &&
+                 r.nwv == pl.NWV && r.shm_bytes == (int32_t)pl.shm && r.xmap == pl.xmap && r.gx == pl.gx &&
+                 r.gy == pl.gy && r.act == a.act && r.has_y == (a.y != nullptr) && r.has_planes == (a.yh != nullptr) &&
+                 r.has_res == (a.res != nullptr) && r.has_rbias == (a.rbias != nullptr) &&
+                 (r.y_alpha >= 0) == (a.y_alpha != nullptr) && (r.gamma >= 0) == (a.gamma != nullptr),
+             RWKVTTS_EINVAL, "codec capture: the launch differs from its record in the plan");
+    cap = Capture{};
+    cap.rec = r;
+    cap.n = n;
+    cap.rows_in = Tmax * a.tin_mul;
+    cap.rows_out = cap.rows_in * (a.mode == 1 ? a.s : 1);
+    RT_HIP(hipStreamSynchronize(stream));
+    if ((rc = fetch_planes(a.xh, a.x_bs, a.x_cs, n, cap.rows_in, a.Ci, &cap.xh))) return rc;
+    if ((rc = fetch_planes(a.xl, a.x_bs, a.x_cs, n, cap.rows_in, a.Ci, &cap.xl))) return rc;
+    if (a.res && (rc = fetch_f32(a.res, a.y_bs, n, (int64_t)cap.rows_out * a.Co, &cap.res))) return rc;
+    if (a.rbias && (rc = fetch_f32(a.rbias, a.rb_bs, n, a.Co, &cap.rbias))) return rc;
+    return RWKVTTS_OK;
+  }
+  int capture_post(const ConvArgs& a) {
+    int rc;
+    RT_HIP(hipStreamSynchronize(stream));
+    if (a.y && (rc = fetch_f32(a.y, a.y_bs, cap.n, (int64_t)cap.rows_out * a.Co, &cap.y))) return rc;
+    if (a.yh && (rc = fetch_planes(a.yh, a.y_bs, a.y_cs, cap.n, cap.rows_out, a.Co, &cap.yh))) return rc;
+    if (a.yl && (rc = fetch_planes(a.yl, a.y_bs, a.y_cs, cap.n, cap.rows_out, a.Co, &cap.yl))) return rc;
+    cap.have = true;
+    return RWKVTTS_OK;
+  }
+
   // One implicit-GEMM conv launch. Output: f32 y and/or planes (snake(y_alpha) applied).
   struct ConvOut {
     float* y = nullptr;
@@ -911,85 +1198,25 @@ class Codec {
   std::string stage_name(const char* base, int C) { return profiling ? std::string(base) + "@" + std::to_string(C) : std::string(); }
   int conv(int n, int Tmax, const std::string& name, Planes x, int64_t bs, int Ci, int tin_mul, const bf16_t* w,
            int K, int Co, int mode, int dil, int pad, int s, const float* bias, const ConvOut& o) {
-    RT_CHECK(Ci % 32 == 0 && Co % 32 == 0, RWKVTTS_EINVAL, "codec conv: channels must be multiples of 32");
-    // column tile: 64, or for the last stage's 96 channels 96 (pointwise) / 48 (taps): 32-wide
-    // tiles read two LDS fragments per four MFMAs
-    int TN = (Co % 64 == 0) ? 64 : ((Co % 96 == 0 && K == 1) ? 96 : (Co % 48 == 0 ? 48 : 32));
-    // pointwise (memory-bound) convs: 96-wide column tiles read the input window fewer times
-    // (conv1 @ 192 / 384 / 768: 6.9 / 4.1 / 2.2 -> 5.3 / 3.5 / 2.0 ms per batch with the XCD-aware
-    // order below; 192-wide tiles halve the occupancy and are slower)
-    if (K == 1 && Co % 96 == 0) TN = 96;
-    const int ntaps_max = mode == 1 ? (K + s - 1) / s : K;
-    const int span = (ntaps_max - 1) * (mode == 1 ? 1 : dil);
-    const int KT = ntaps_max <= 1 ? 1 : (ntaps_max <= 3 ? 3 : 7);
-    {  // 7-tap convs: 64-wide column tiles by default. 96-wide ones (where the double-buffered
-       // chunk fits: RWKVTTS_CONV7_TN=96) make the vocoder alone faster (residual conv7 33.4 ->
-       // 31.1 ms per batch) but their 155 KB of LDS leaves no room on the CU for a decode GEMM
-       // workgroup (34 KB): beside the next batch's token generator -- the serving shape, the
-       // bench -- every GEMM launch then waits for whole vocoder workgroups to retire. 64-wide
-       // tiles (124 KB) let them share the CU: decode step 0.883 -> 0.875 ms in the bench, +0.7 %
-       // samples/s (same-box A/B x2, tools/bench_ab.sh) for +1 ms of vocoder time. Tests
-       // bit-identical either way: the per-element accumulation order does not depend on TN.
-      // Round 4: the decode step's persistent workgroups (k_att_persist / k_ffn_persist) take
-      // 36.6 KB of LDS, which fits beside a 64-wide tile at dilation 1 only. 48-wide tiles leave
-      // room at every dilation: bench A/Bs (13 alternating pairs over three boxes,
-      // profiles/r04_conv7_tile_ab.txt) +0.1 to +1.2 % samples/s, within the boxes' run-to-run
-      // spread, for +1.5 ms of vocoder time; 64 stays.
-      // ConvTranspose: 96-wide tiles measured faster at 96 and 384 output channels (2.54 -> 2.14,
-      // 2.30 -> 2.10 ms per batch), slower at 192 (2.51 -> 2.62), equal at 768
-      if (mode == 1 && KT == 3 && (Co == 96 || Co == 384)) TN = 96;
-      // (Round 6: capping every conv launch's workgroups per CU, by padding its LDS request, so that a
-      // persistent decode workgroup always fits beside them -- with the pointwise convs in 64-wide
-      // tiles, the ConvTranspose ones too, the 7-tap ones in 48-wide tiles -- left the decode step
-      // beside the vocoder unchanged, 0.806-0.816 ms, and the vocoder alone 3-10 ms slower:
-      // profiles/r06e_coresidency_ab.txt, tools/experiments/r06_codec_coresidency.patch)
-    }
-    int nwv = conv_waves(KT);
-    const int wplanes = wlo ? 2 : 1;  // weight planes staged per chunk
-    auto chunk_rows = [&](int tn, int nw) { return 2 * ((32 * nw + span + 15) & ~15) + wplanes * ntaps_max * tn; };
-    auto shm_of = [&](int tn, int nw) {
-      return std::max(2 * (size_t)chunk_rows(tn, nw) * 64, (size_t)nw * 32 * (tn + 4) * sizeof(float));
-    };
-    auto fits = [&](int tn, int nw) {
-      return Co % tn == 0 && shm_of(tn, nw) <= 160 * 1024 && chunk_rows(tn, nw) / 16 <= 16 * nw;
-    };
-    if (wlo && (!fits(TN, nwv) || TN > 96)) {  // (no weight-lo kernel wider than 96 columns)
-      // the weight lo plane doubles the staged weights: the (tile width, waves) that fits and
-      // stages the fewest LDS rows per output element
-      int bt = 0, bw = 0;
-      double best = 0.0;
-      for (int nw : {conv_waves(KT), 4})
-        for (int tn : {96, 64, 48, 32}) {
-          if (!fits(tn, nw) || (nw != conv_waves(KT) && KT != 7)) continue;
-          const double sc = (double)(32 * nw * tn) / chunk_rows(tn, nw);
-          if (sc > best) { best = sc; bt = tn; bw = nw; }
-        }
-      RT_CHECK(bt > 0, RWKVTTS_EINVAL, "codec conv: no tile fits the LDS with weight lo planes");
-      TN = bt;
-      nwv = bw;
-    }
-    const int TM = 32 * nwv;
-    const size_t shm = shm_of(TN, nwv);
-    RT_CHECK(fits(TN, nwv) && ntaps_max <= 7 && Ci <= 4096, RWKVTTS_EINVAL, "codec conv: tile window too large");
+    ConvPlan pl;
+    const char* why = conv_plan(wlo, n, Tmax, Ci, tin_mul, K, Co, mode, dil, s, &pl);
+    RT_CHECK(!why, RWKVTTS_EINVAL, why);
+    const int TN = pl.TN, KT = pl.KT, nwv = pl.NWV;
+    const size_t shm = pl.shm;
     ConvArgs a{};
     a.xh = x.h; a.xl = x.l; a.x_bs = bs; a.Ci = Ci; a.tin_mul = tin_mul; a.w = w; a.wl = wlb ? wlb + (w - wb) : nullptr; a.K = K; a.Co = Co;
     a.mode = mode; a.dil = dil; a.pad = pad; a.s = s; a.bias = bias; a.rbias = o.rbias; a.rb_bs = o.rb_bs;
     a.gamma = o.gamma; a.res = o.res; a.act = o.act; a.y = o.y; a.yh = o.p.h; a.yl = o.p.l;
     a.y_alpha = o.alpha; a.y_bs = o.y_bs >= 0 ? o.y_bs : bs; a.ntok = ntok_dev; a.zeros = zeros;
     a.x_cs = x.cs; a.y_cs = o.p.cs;
-    const int phases = mode == 1 ? s : 1;
-    dim3 grid((unsigned)((Tmax * (int64_t)tin_mul + TM - 1) / TM), (unsigned)(phases * (Co / TN)), (unsigned)n);
-    // XCD-aware order for the long-time-axis residual convs (conv7 and conv1 at >= 32 time tiles:
-    // a time tile's column tiles share one L2); the short prenet / conv_in / convT launches keep
-    // the default order (2x slower remapped)
-    // (the ConvTranspose launches in this order too: 1-8 % slower, the Infinity Cache serves their
-    // re-reads)
-    a.xmap = 0;
-    if (grid.y > 1 && grid.x >= 32 && mode == 0 && (K == 7 || K == 1)) {
-      a.xmap = 1;
-      a.gx = (int)grid.x;
-      a.gy = (int)grid.y;
-      grid = dim3((unsigned)(8 * ((grid.x + 7) / 8) * grid.y), 1, (unsigned)n);
+    a.xmap = pl.xmap;
+    a.gx = pl.gx;
+    a.gy = pl.gy;
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+    const int li = launch_idx++;  // (capture: a test hook; unarmed, this compare is all it costs)
+    if (li == cap_arm) {
+      const int rc = capture_pre(li, a, pl, n, Tmax);
+      if (rc) return rc;
     }
     pbeg();
     const int nthr = 64 * nwv;
@@ -1004,6 +1231,7 @@ class Codec {
     RT_CHECK(launched, RWKVTTS_EINVAL, "codec conv: no kernel for this tile shape");
     RT_HIP(hipGetLastError());
     pend(name.c_str());
+    if (li == cap_arm) return capture_post(a);
     return RWKVTTS_OK;
   }
 
@@ -1015,23 +1243,10 @@ class Codec {
                     const bf16_t* w7, const float* b7, int dil, const float* mid_alpha, const bf16_t* w1,
                     const float* b1, const ConvOut& o, bool* done) {
     *done = false;
-    if ((forms & RWKVTTS_CODEC_FORM_SEPARATE_RESUNIT) || wlo || C != 96) return RWKVTTS_OK;
-    const int span = 6 * dil;
-    int nwv = 0;
-    for (int nw : {8, 4}) {  // (4-wave units where 8 do not fit: 8 measured faster)
-      const int wr = (32 * nw + span + 15) & ~15;
-      const size_t chunk = 2 * (size_t)(2 * wr + 7 * 96) * 64;
-      const size_t fused = (size_t)3 * 2 * 32 * nw * 64 + 3 * 96 * 64;
-      const size_t epi = (size_t)nw * 32 * 100 * sizeof(float);
-      if (std::max(std::max(chunk, fused), epi) <= 160 * 1024 && (2 * wr + 7 * 96) / 16 <= conv_maxb(nw, true) * nw) {
-        nwv = nw;
-        break;
-      }
-    }
-    if (!nwv) return RWKVTTS_OK;
-    const int TM = 32 * nwv, wr = (TM + span + 15) & ~15;
-    const size_t shm = std::max(std::max(2 * (size_t)(2 * wr + 7 * 96) * 64, (size_t)3 * 2 * TM * 64 + 3 * 96 * 64),
-                                (size_t)nwv * 32 * 100 * sizeof(float));
+    ConvPlan pl;
+    if (!resunit_plan(wlo, forms, n, Tmax, C, tin_mul, dil, &pl)) return RWKVTTS_OK;
+    const int nwv = pl.NWV;
+    const size_t shm = pl.shm;
     ConvArgs a{};
     a.xh = x.h; a.xl = x.l; a.x_bs = bs; a.Ci = C; a.tin_mul = tin_mul; a.w = w7; a.wl = wlb ? wlb + (w7 - wb) : nullptr; a.K = 7; a.Co = C;
     a.mode = 0; a.dil = dil; a.pad = 3 * dil; a.s = 1; a.bias = b7; a.rbias = nullptr; a.rb_bs = 0;
@@ -1040,19 +1255,30 @@ class Codec {
     a.mid_alpha = mid_alpha; a.w1 = w1; a.bias1 = b1;
     a.x_cs = x.cs; a.y_cs = o.p.cs;
     a.xmap = 0;
-    dim3 grid((unsigned)((Tmax * (int64_t)tin_mul + TM - 1) / TM), 1, (unsigned)n);
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+    const int li = launch_idx++;
+    if (li == cap_arm) {
+      const int rc = capture_pre(li, a, pl, n, Tmax);
+      if (rc) return rc;
+    }
     pbeg();
     if (nwv == 8) k_conv<96, 7, false, 8, true><<<grid, 512, shm, stream>>>(a);
     else k_conv<96, 7, false, 4, true><<<grid, 256, shm, stream>>>(a);
     RT_HIP(hipGetLastError());
     pend(name.c_str());
     *done = true;
+    if (li == cap_arm) return capture_post(a);
     return RWKVTTS_OK;
   }
 
   // Decode n utterances; semantic[i] has T[i] codes, global[i] n_global codes; pcm[i] gets T[i]*320.
   int decode(const int64_t* const* semantic, const int* T, const int64_t* const* global, int n,
              float* const* out) {
+    struct Disarm {  // a capture covers one decode call, whatever its outcome
+      int& arm;
+      ~Disarm() { arm = -1; }
+    } disarm{cap_arm};
+    launch_idx = 0;
     RT_CHECK(n > 0, RWKVTTS_EINVAL, "codec decode: n must be > 0");
     int Tmax = 0;
     for (int i = 0; i < n; ++i) {
@@ -1096,6 +1322,10 @@ class Codec {
   // Every window is validated before anything is enqueued.
   int decode_windows(const rwkvtts_codec_window* const* w, int n) {
     RT_CHECK(n > 0, RWKVTTS_EINVAL, "codec decode_windows: n must be > 0");
+    // (the launch plan describes a whole-utterance decode: a window's prenet and WaveGenerator run
+    // different lengths)
+    RT_CHECK(cap_arm < 0, RWKVTTS_EINVAL, "codec decode_windows: a launch capture is armed (whole decodes only)");
+    launch_idx = 0;
     int n_codes = 1;
     for (int i = 0; i < d.fsq_dims; ++i) n_codes *= d.fsq_levels;
     std::vector<int> c0(n), c1(n), w0(n), w1(n);
@@ -1535,6 +1765,62 @@ int rwkvtts_codec_set_forms(rwkvtts_codec* c, uint32_t forms) {
            "codec_set_forms: unknown forms bits");
   c->c.forms = forms;
   return RWKVTTS_OK;
+}
+
+int rwkvtts_codec_debug_launch_plan(const rwkvtts_codec_dims* d, int weight_lo, uint32_t forms, int n, int Tmax,
+                                    rwkvtts_codec_launch* out, int cap) {
+  RT_CHECK(d && (out || cap <= 0), RWKVTTS_EINVAL, "codec_debug_launch_plan: null argument");
+  try {
+    std::vector<rwkvtts_codec_launch> plan;
+    const int rc = codec_launch_plan(*d, weight_lo != 0, forms, n, Tmax, &plan);
+    if (rc) return rc;
+    for (int i = 0; i < (int)plan.size() && i < cap; ++i) out[i] = plan[i];
+    return (int)plan.size();
+  } catch (const std::exception& ex) {
+    set_error(ex.what());
+    return RWKVTTS_ENOMEM;
+  }
+}
+
+int rwkvtts_codec_debug_capture(rwkvtts_codec* c, int launch) {
+  RT_CHECK(c && launch >= -1, RWKVTTS_EINVAL, "codec_debug_capture: bad arguments");
+  c->c.cap_arm = launch;
+  c->c.cap = Codec::Capture{};
+  return RWKVTTS_OK;
+}
+
+int rwkvtts_codec_debug_captured_launch(rwkvtts_codec* c, rwkvtts_codec_launch* rec, int32_t* n, int32_t* rows_in,
+                                        int32_t* rows_out) {
+  RT_CHECK(c && rec && n && rows_in && rows_out, RWKVTTS_EINVAL, "codec_debug_captured_launch: null argument");
+  RT_CHECK(c->c.cap.have, RWKVTTS_EINVAL, "codec_debug_captured_launch: no launch was captured");
+  *rec = c->c.cap.rec;
+  *n = c->c.cap.n;
+  *rows_in = c->c.cap.rows_in;
+  *rows_out = c->c.cap.rows_out;
+  return RWKVTTS_OK;
+}
+
+int64_t rwkvtts_codec_debug_captured(rwkvtts_codec* c, int what, void* out, int64_t cap_bytes) {
+  RT_CHECK(c && c->c.cap.have && what >= 0 && what <= 6, RWKVTTS_EINVAL,
+           "codec_debug_captured: no launch was captured, or an unknown array");
+  const Codec::Capture& k = c->c.cap;
+  const void* src = nullptr;
+  int64_t bytes = 0;
+  auto pick = [&](const auto& v) {
+    src = v.data();
+    bytes = (int64_t)(v.size() * sizeof(v[0]));
+  };
+  switch (what) {
+    case 0: pick(k.xh); break;
+    case 1: pick(k.xl); break;
+    case 2: pick(k.res); break;
+    case 3: pick(k.y); break;
+    case 4: pick(k.yh); break;
+    case 5: pick(k.yl); break;
+    default: pick(k.rbias); break;
+  }
+  if (out && bytes > 0 && cap_bytes >= bytes) memcpy(out, src, (size_t)bytes);
+  return bytes;
 }
 
 int rwkvtts_codec_set_profiling(rwkvtts_codec* c, int on) {

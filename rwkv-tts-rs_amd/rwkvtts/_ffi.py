@@ -163,6 +163,15 @@ class CodecWindow(ctypes.Structure):
                 ("global_", ctypes.c_void_p), ("pcm", ctypes.c_void_p)]
 
 
+class CodecLaunch(ctypes.Structure):
+    """rwkvtts_codec_launch: one k_conv launch of a decode (rwkvtts_codec_debug_launch_plan)."""
+    _fields_ = [("struct_size", ctypes.c_uint32)] + [(n, ctypes.c_int32) for n in (
+        "kind", "ci", "co", "k", "dil", "pad", "s", "tin_mul", "tn", "kt", "wlo", "nwv", "shm_bytes",
+        "xmap", "gx", "gy")] + [("grid", ctypes.c_int32 * 3)] + [(n, ctypes.c_int32) for n in (
+            "act", "has_y", "has_planes", "has_res", "has_rbias",
+            "w", "bias", "gamma", "y_alpha", "mid_alpha", "w1", "bias1")]
+
+
 RESAMPLE_ALIGN_RUBATO, RESAMPLE_ALIGN_ZERO = 0, 1
 
 
@@ -296,6 +305,18 @@ EXPORTS = {
     "rwkvtts_codec_window_plan": (ctypes.c_int, [ctypes.POINTER(CodecDims), ctypes.c_int32, ctypes.c_int32,
                                                  ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(CodecPlan)]),
     "rwkvtts_codec_decode_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CodecWindow), ctypes.c_int]),
+    # test hooks (tests/test_codec_plan_cpu.py, tests/test_gpu_codec_dims.py): the launch plan (host
+    # only) and one launch's captured inputs and outputs
+    "rwkvtts_codec_debug_launch_plan": (ctypes.c_int, [ctypes.POINTER(CodecDims), ctypes.c_int, ctypes.c_uint32,
+                                                       ctypes.c_int, ctypes.c_int, ctypes.POINTER(CodecLaunch),
+                                                       ctypes.c_int]),
+    "rwkvtts_codec_debug_capture": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "rwkvtts_codec_debug_captured_launch": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CodecLaunch),
+                                                           ctypes.POINTER(ctypes.c_int32),
+                                                           ctypes.POINTER(ctypes.c_int32),
+                                                           ctypes.POINTER(ctypes.c_int32)]),
+    "rwkvtts_codec_debug_captured": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                      ctypes.c_int64]),
     "rwkvtts_codec_set_profiling": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "rwkvtts_codec_profile_count": (ctypes.c_int, [ctypes.c_void_p]),
     "rwkvtts_codec_profile_entry": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,

@@ -76,6 +76,26 @@ def window_plan(d: dict, t0: int, t1: int, n_known: int, final: bool) -> dict:
     return {"ctx": (p.ctx0, p.ctx1), "wave": (p.wave0, p.wave1)}
 
 
+def launch_plan(d: dict, wlo: bool, forms: int, n: int, Tmax: int) -> List[dict]:
+    """Every k_conv launch of a decode of n utterances of at most Tmax frames, in launch order, one
+    dict per launch with the fields of rwkvtts_codec_launch (rwkvtts_codec_debug_launch_plan; host
+    only -- the decode takes its tile, grid and LDS choice from the same function)."""
+    cd = make_codec_dims(d)
+    cnt = lib().rwkvtts_codec_debug_launch_plan(ctypes.byref(cd), 1 if wlo else 0, int(forms), n, Tmax, None, 0)
+    if cnt < 0:
+        raise _ffi.RwkvTtsError(cnt, "codec_debug_launch_plan")
+    recs = (_ffi.CodecLaunch * cnt)()
+    check(min(0, lib().rwkvtts_codec_debug_launch_plan(ctypes.byref(cd), 1 if wlo else 0, int(forms), n, Tmax,
+                                                       recs, cnt)), "codec_debug_launch_plan")
+    return [_launch_dict(r) for r in recs]
+
+
+def _launch_dict(r) -> dict:
+    out = {n: getattr(r, n) for n, _ in _ffi.CodecLaunch._fields_ if n not in ("struct_size", "grid")}
+    out["grid"] = tuple(r.grid)
+    return out
+
+
 class BiCodecDetokenizer:
     """One decoder per GPU (replaces the 4-session ORT pool of src/onnx_session_pool.rs:204-279)."""
 
@@ -179,6 +199,36 @@ class BiCodecDetokenizer:
         with self._lock:
             check(lib().rwkvtts_codec_decode_windows(self._h, ws, n), "codec_decode_windows")
         return outs
+
+    # ---- test hook: one launch's inputs and outputs ----
+    def capture_launch(self, k: int, batch: Sequence[tuple]):
+        """Decode `batch` ([(global_tokens, semantic_tokens)]) with launch k of launch_plan() captured
+        (rwkvtts_codec_debug_capture). Returns (pcm list, capture): capture["rec"] the launch's record,
+        "x_hi" / "x_lo" uint16 [n][rows_in][ci] (bf16 bits), "res" / "y" float32 [n][rows_out][co],
+        "y_hi" / "y_lo" uint16, "rbias" float32 [n][co]; an array the launch does not have is None."""
+        check(lib().rwkvtts_codec_debug_capture(self._h, int(k)), "codec_debug_capture")
+        pcm = self.decode_audio_batch(batch)  # (the decode call disarms the capture, whatever its outcome)
+        rec = _ffi.CodecLaunch()
+        n, ri, ro = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        check(lib().rwkvtts_codec_debug_captured_launch(self._h, ctypes.byref(rec), ctypes.byref(n), ctypes.byref(ri),
+                                                        ctypes.byref(ro)), "codec_debug_captured_launch")
+        cap = {"rec": _launch_dict(rec), "n": n.value, "rows_in": ri.value, "rows_out": ro.value}
+        shapes = {"x_hi": (0, np.uint16, (ri.value, rec.ci)), "x_lo": (1, np.uint16, (ri.value, rec.ci)),
+                  "res": (2, np.float32, (ro.value, rec.co)), "y": (3, np.float32, (ro.value, rec.co)),
+                  "y_hi": (4, np.uint16, (ro.value, rec.co)), "y_lo": (5, np.uint16, (ro.value, rec.co)),
+                  "rbias": (6, np.float32, (rec.co,))}
+        for name, (what, dt, shp) in shapes.items():
+            nbytes = lib().rwkvtts_codec_debug_captured(self._h, what, None, 0)
+            if nbytes < 0:
+                raise _ffi.RwkvTtsError(int(nbytes), "codec_debug_captured")
+            if nbytes == 0:
+                cap[name] = None
+                continue
+            a = np.empty((n.value,) + shp, dtype=dt)
+            assert a.nbytes == nbytes, (name, a.nbytes, nbytes)
+            lib().rwkvtts_codec_debug_captured(self._h, what, a.ctypes.data_as(ctypes.c_void_p), a.nbytes)
+            cap[name] = a
+        return pcm, cap
 
     # ---- profiling (per-stage HIP-event timing) ----
     def set_profiling(self, on: bool):

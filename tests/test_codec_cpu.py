@@ -83,3 +83,51 @@ def test_raf_fixture_tokens_in_codec_range():
         assert len(r["global_tokens"]) == 32
         assert all(0 <= t < 4096 for t in r["global_tokens"])
         assert all(0 <= t < 8192 for t in r["semantic_tokens"])
+
+
+def _create_rc(d):
+    """rwkvtts_codec_create on dims d: its status, and that no decoder came back. The dims check runs
+    before the first HIP call, so a refusal needs no device."""
+    import ctypes
+    h = ctypes.c_void_p()
+    w = np.zeros(64, np.float32)
+    rc = _ffi.lib().rwkvtts_codec_create(0, ctypes.byref(codec.make_codec_dims(d)), w.ctypes.data_as(ctypes.c_void_p),
+                                         ctypes.byref(h))
+    assert rc != 0 and not h.value
+    return rc, _ffi.lib().rwkvtts_last_error().decode()
+
+
+@pytest.mark.parametrize("mod,why", [
+    (dict(up_rates=(8, 5, 4, 1), up_kernels=(16, 11, 8, 1)), "RWKVTTS_HOP"),    # hop 160
+    (dict(up_rates=(8, 5, 4, 4), up_kernels=(16, 11, 8, 8)), "RWKVTTS_HOP"),    # hop 640
+    (dict(up_kernels=(16, 11, 8, 16)), "7 taps"),                               # 8 taps per phase at stride 2
+])
+def test_create_refuses_dims_the_decoder_cannot_run(mod, why):
+    """pcm holds 320 samples per frame and k_conv_out writes prod(up_rates) of them; k_conv has no
+    instantiation for 8 taps. Both were admitted by create before (the second failed at the first
+    decode, the first wrote past pcm): EINVAL now, before any HIP call."""
+    for base in (codec.CODEC_DIMS_TINY, codec.CODEC_DIMS_FULL):
+        rc, msg = _create_rc(dict(base, **mod))
+        assert rc == _ffi.EINVAL and why in msg, (rc, msg)
+        with pytest.raises(_ffi.RwkvTtsError) as e:
+            codec.launch_plan(dict(base, **mod), False, 0, 1, 4)
+        assert e.value.code == _ffi.EINVAL
+
+
+def test_halo_and_window_plan_do_not_need_a_runnable_decoder():
+    """rwkvtts_codec_halo / _window_plan are pure arithmetic: they keep answering for such dims."""
+    d = dict(codec.CODEC_DIMS_TINY, up_rates=(8, 5, 4, 4), up_kernels=(16, 11, 8, 8))
+    hp, hw = codec.codec_halo(d)
+    assert hp == 9 and hw > 0
+    assert codec.window_plan(d, 0, 4, 4, True)["wave"] == (0, 4)
+
+
+def test_oracle_sizes_its_output_from_the_dims(oracle_mod):
+    """oracle/codec.c writes T * prod(up_rates) samples; codec_decode allocates that many (it assumed
+    320 before, so hop-640 dims wrote past the buffer)."""
+    for rates, kernels, hop in (((8, 5, 4, 4), (16, 11, 8, 8), 640), ((8, 5, 4, 1), (16, 11, 8, 1), 160)):
+        d = dict(codec.CODEC_DIMS_TINY, up_rates=rates, up_kernels=kernels)
+        w = codec.synth_codec_blob(d)
+        rs = np.random.default_rng(3)
+        pcm = oracle_mod.codec_decode(codec.make_codec_dims(d), w, rs.integers(0, 8192, 3), rs.integers(0, 4096, 32))
+        assert pcm.shape == (3 * hop,) and np.isfinite(pcm).all() and np.abs(pcm).max() < 1.0
