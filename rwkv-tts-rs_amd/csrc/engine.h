@@ -191,7 +191,7 @@ class Engine {
   static constexpr int xmap(LaunchClass c) { return (kXmapMask >> c) & 1; }
   static constexpr int wt(LaunchClass c) { return (kWtMask >> c) & 1; }
   static constexpr int xalign(LaunchClass c) { return (kXalignMask >> c) & 1; }
-  // the layer whose launches carry the debug stamps (RWKVTTS_DEBUG_STAMPS gemm / ffn / att / wkv)
+  // the layer whose launches carry the debug stamps (RWKVTTS_DEBUG_STAMPS ffn / att / wkv)
   static constexpr int kStampLayer = 5;
   // The decode-step forms (rwkvtts_engine_desc.forms, RWKVTTS_FORM_*; the defaults are the shipping
   // forms, each measured faster than the launches it replaces):
@@ -335,8 +335,6 @@ class Engine {
   std::string dbg_astamp2_path_;
   uint64_t* dbg_fstamps_ = nullptr;  // ffn: layer-5 k_ffn_persist block stamps
   std::string dbg_fstamp_path_;
-  uint64_t* dbg_gstamps_ = nullptr;  // gemm: layer-5 rkv / ffn_value GEMM stamps
-  std::string dbg_gstamp_path_;
   template <typename T>
   int alloc(T** p, size_t count);
 };

@@ -156,8 +156,10 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
   use_graphs_ = desc.use_graphs != 0;
   // split-K so that every GEMM slice is 128/256/512 deep and the grids fill the 256 CUs
   auto pick = [](int K, int want) {  // K slices of 128 / 256 / 512 (the GEMM kernels' shapes)
-    int ks = std::max(128, std::min(std::min(want, 512), K));
-    while (ks > 128 && K % ks) ks >>= 1;
+    // (halving from a power of two: K = 384 with want = 512 took the whole K as one 384-deep slice,
+    // a depth no GEMM kernel has, and the head GEMM was silently not launched)
+    int ks = std::min(want, 512);
+    while (ks > 128 && (ks > K || K % ks)) ks >>= 1;
     return K / ks;
   };
   // (K-slice depths measured at B = 32 and B = 1: twice or half the slices of any projection are
@@ -186,9 +188,9 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
   value_32x64_ = (desc.forms & RWKVTTS_FORM_VALUE_TILE_32X64) != 0;
   if ((ffn_persist_ || att_persist_) && !claim_persistent(desc.device, this, &lock_fd_)) ffn_persist_ = att_persist_ = false;
   // debug instrumentation (tools/: stamps of one layer's launches, the launch timeline), off in
-  // production: RWKVTTS_DEBUG_STAMPS="kind=path[;kind=path...]", kind one of gemm (layer-5 rkv /
-  // value GEMM), ffn / att (layer-5 persistent-launch block stamps), timeline (per-launch start /
-  // end of every decode step), adv (k_advance phases), wkv (layer-5 WKV phases)
+  // production: RWKVTTS_DEBUG_STAMPS="kind=path[;kind=path...]", kind one of ffn / att (layer-5
+  // persistent-launch block stamps), timeline (per-launch start / end of every decode step), adv
+  // (k_advance phases), wkv (layer-5 WKV phases); any other item is reported on stderr and ignored
   if (const char* ds = getenv("RWKVTTS_DEBUG_STAMPS")) {
     std::string spec(ds);
     size_t pos = 0;
@@ -198,12 +200,12 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
       const std::string item = spec.substr(pos, end - pos);
       pos = end + 1;
       const size_t eq = item.find('=');
-      if (eq == std::string::npos) continue;
+      if (eq == std::string::npos) {
+        if (!item.empty()) fprintf(stderr, "rwkvtts: RWKVTTS_DEBUG_STAMPS: item without '=' ignored: %s\n", item.c_str());
+        continue;
+      }
       const std::string kind = item.substr(0, eq), path = item.substr(eq + 1);
-      if (kind == "gemm") {
-        dbg_gstamp_path_ = path;
-        RT_OK(alloc(&dbg_gstamps_, 2 * 4096 * 4));
-      } else if (kind == "ffn") {
+      if (kind == "ffn") {
         dbg_fstamp_path_ = path;
         RT_OK(alloc(&dbg_fstamps_, 1024 * 4));
       } else if (kind == "att") {
@@ -218,6 +220,8 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
       } else if (kind == "wkv") {
         dbg_stamp_path_ = path;
         RT_OK(alloc(&dbg_stamps_, 4096 * 8));
+      } else {
+        fprintf(stderr, "rwkvtts: RWKVTTS_DEBUG_STAMPS: unknown kind ignored: %s\n", kind.c_str());
       }
     }
   }
@@ -315,7 +319,7 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
         }
     }
   }
-  // GEMM matrices -> MFMA fragment blocks (k_gemm streams each wave's weights as contiguous 1 KB
+  // GEMM matrices -> MFMA fragment blocks (the GEMM kernels stream each wave's weights as contiguous 1 KB
   // blocks); the blob's row-major copies stay for the embedding gather and the oracle layout
   {
     auto packed_elems = [](int N, int K) { return (size_t)((N + 15) / 16) * 16 * K; };
@@ -585,8 +589,8 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
   for (const LayerW& lw : L_) any_quant = any_quant || lw.quant != 0;
   // (every row count: with the 1-us weight-stream hold the persistent halves win at B = 1, 8 and 32,
   // profiles/r04h7_small_batch_ab.txt)
-  bool use_att = att_persist_ && inplace && Lc >= 2 && !dbg_stamps_ && !dbg_gstamps_ && !any_quant && emb_fused;
-  bool use_ffn = ffn_persist_ && inplace && Lc >= 2 && !dbg_gstamps_ && !any_quant;
+  bool use_att = att_persist_ && inplace && Lc >= 2 && !dbg_stamps_ && !any_quant && emb_fused;
+  bool use_ffn = ffn_persist_ && inplace && Lc >= 2 && !any_quant;
   // one-row passes: the FFN key -> value hand-off as granules, live once the layer-0 attention
   // launch (which bumps the pass epoch) has been issued
   const bool gran_pass = gran_ && d_gran_ && fuse_ln1_ && R == 1 && use_att && use_ffn;
@@ -688,7 +692,6 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
     g.allow_xmap = xmap(kClsRkv);
     g.xalign = xalign(kClsRkv) ? 1 : 0;  // r / k / v tile h (head h) on the XCD of WKV head h
     g.wt = wt(kClsRkv);
-    g.stamps = (l == kStampLayer && dbg_gstamps_) ? dbg_gstamps_ : nullptr;
     // ---- WKV + LoRA-up + GroupNorm + bonus + gate
     WkvArgs k{};
     k.f16 = f16_;
@@ -781,11 +784,14 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
       gv.seg[0] = {w.ffn_v, xk_hi_, xk_lo_, F, C, 0, 0};
       gv.xmode = kXPlanes;
     }
+    // the fused staging holds its key slabs in registers and has forms for 1, 2 and 4 of them: any
+    // other key split is summed into slab 0 once (launch_sum_slabs) and staged as one slab
+    const bool presum = !planes && splitK_ != 1 && splitK_ != 2 && splitK_ != 4;
+    if (presum) gv.x_nsplit = 1;
     gv.out = partF_; gv.split_stride = RC; gv.ldo = C;
     gv.allow_xmap = xmap(kClsValue);
     if (w.quant) { gv.q_fmt = w.quant; gv.qw = w.q_fv; gv.qs = w.s_fv; gv.q_shift = w.qs_fv; }
     gv.wt = wt(kClsValue);
-    gv.stamps = (l == kStampLayer && dbg_gstamps_) ? dbg_gstamps_ + 4096 * 4 : nullptr;
     // decode steps: the whole FFN half as ONE persistent launch (k_ffn_persist, in-launch
     // hand-offs; bit-identical outputs) where the shapes allow it
     bool persisted = false;
@@ -801,7 +807,14 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
       timed("ln_ffn", "ln_mix_ffn", [&](unsigned long long* tl) { f.tl = tl; launch_ln_mix(f, R, stream_); });
       timed("gemm_key", "gemm_ffn_key", [&](unsigned long long* tl) { gk.tl = tl; launch_gemm(gk, stream_); });
       if (planes) launch_relu2_planes(partK_, splitK_, (int64_t)Rmax_ * F, F, F, R, xk_hi_, xk_lo_, stream_);
-      timed("gemm_value", "gemm_ffn_value", [&](unsigned long long* tl) { gv.tl = tl; launch_gemm(gv, stream_); });
+      if (presum) launch_sum_slabs(partK_, splitK_, (int64_t)Rmax_ * F, F, F, R, stream_);
+      {  // (timed() spelled out, as ln_att: a refused launch returns before prof_end)
+        hipEvent_t ev;
+        gv.tl = tl_next("gemm_value");
+        prof_begin(&ev);
+        RT_CHECK(launch_gemm(gv, stream_) >= 0, RWKVTTS_EUNSUPPORTED, "FFN value GEMM: no form for this key split");
+        prof_end("gemm_ffn_value", ev);
+      }
     }
   }
   if (n_lg > 0) {
@@ -1628,6 +1641,18 @@ int Engine::degrade_persistent() {
   return RWKVTTS_OK;
 }
 
+// n 8-byte words of a debug stamp buffer (null: none) -> path, as they are
+static int dump_words(const uint64_t* dev, size_t n, const std::string& path) {
+  if (!dev) return RWKVTTS_OK;
+  std::vector<uint64_t> h(n);
+  RT_HIP(hipMemcpy(h.data(), dev, n * 8, hipMemcpyDeviceToHost));
+  if (FILE* f = fopen(path.c_str(), "wb")) {
+    fwrite(h.data(), 8, n, f);
+    fclose(f);
+  }
+  return RWKVTTS_OK;
+}
+
 int Engine::dump_stamps() {
   if (d_tl_ && tl_steps_ > 0) {
     FILE* f = fopen(tl_path_.c_str(), "w");
@@ -1638,50 +1663,12 @@ int Engine::dump_stamps() {
       fclose(f);
     }
   }
-  if (dbg_astamps_) {
-    std::vector<uint64_t> ha(256 * 16);
-    RT_HIP(hipMemcpy(ha.data(), dbg_astamps_, ha.size() * 8, hipMemcpyDeviceToHost));
-    FILE* f = fopen(dbg_astamp_path_.c_str(), "wb");
-    if (f) {
-      fwrite(ha.data(), 8, ha.size(), f);
-      fclose(f);
-    }
-  }
-  if (dbg_astamps2_) {
-    std::vector<uint64_t> hf(2048 * 4);
-    RT_HIP(hipMemcpy(hf.data(), dbg_astamps2_, hf.size() * 8, hipMemcpyDeviceToHost));
-    FILE* f = fopen(dbg_astamp2_path_.c_str(), "wb");
-    if (f) {
-      fwrite(hf.data(), 8, hf.size(), f);
-      fclose(f);
-    }
-  }
-  if (dbg_fstamps_) {
-    std::vector<uint64_t> hf(1024 * 4);
-    RT_HIP(hipMemcpy(hf.data(), dbg_fstamps_, hf.size() * 8, hipMemcpyDeviceToHost));
-    FILE* f = fopen(dbg_fstamp_path_.c_str(), "wb");
-    if (f) {
-      fwrite(hf.data(), 8, hf.size(), f);
-      fclose(f);
-    }
-  }
-  if (dbg_gstamps_) {
-    std::vector<uint64_t> hg(2 * 4096 * 4);
-    RT_HIP(hipMemcpy(hg.data(), dbg_gstamps_, hg.size() * 8, hipMemcpyDeviceToHost));
-    FILE* f = fopen(dbg_gstamp_path_.c_str(), "wb");
-    if (f) {
-      fwrite(hg.data(), 8, hg.size(), f);
-      fclose(f);
-    }
-  }
-  if (!dbg_stamps_) return RWKVTTS_OK;
-  std::vector<uint64_t> hs(4096 * 8);  // debug: layer-5 WKV stamps of the last step -> file
-  RT_HIP(hipMemcpy(hs.data(), dbg_stamps_, hs.size() * 8, hipMemcpyDeviceToHost));
-  FILE* f = fopen(dbg_stamp_path_.c_str(), "wb");
-  if (f) {
-    fwrite(hs.data(), 8, hs.size(), f);
-    fclose(f);
-  }
+  // the binary stamp dumps: each buffer's words as they are (adv [256][16], att [2048][4], ffn [1024][4],
+  // wkv [4096][8]: layer kStampLayer's launches of the last step)
+  RT_OK(dump_words(dbg_astamps_, 256 * 16, dbg_astamp_path_));
+  RT_OK(dump_words(dbg_astamps2_, 2048 * 4, dbg_astamp2_path_));
+  RT_OK(dump_words(dbg_fstamps_, 1024 * 4, dbg_fstamp_path_));
+  RT_OK(dump_words(dbg_stamps_, 4096 * 8, dbg_stamp_path_));
   return RWKVTTS_OK;
 }
 

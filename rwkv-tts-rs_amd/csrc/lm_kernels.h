@@ -75,7 +75,8 @@ struct GemmArgs {
   float* out;          // [k_split][rows][ldo] f32
   int64_t split_stride;
   int ldo;
-  uint64_t* stamps;    // debug: 4 s_memtime stamps per workgroup (null in production)
+  uint64_t* stamps;    // unused, always null: kept for the layout (the struct is the kernel argument;
+                       // dropping the slot moves every later field's offset in every GEMM kernel)
   int f16;             // weights and activation planes in f16 (fp16 model)
   unsigned long long* tl;  // debug timeline slot (null in production)
   // Multi-segment launches whose segments are packed back to back in 64-column tiles (set by
@@ -149,7 +150,9 @@ struct WkvArgs {
 void launch_embed(const uint32_t* tokens, const int4* rows, const int* ctrl_tok, int ctrl_stride,
                   const bf16_t* emb, const float* w, const float* b, float* h, int R, int C, int f16, hipStream_t st,
                   unsigned long long* tl, int n_vocab);
-// Launchers return the workgroup count of the launch.
+// Launchers return the workgroup count of the launch; launch_gemm -1, with nothing launched, for a
+// kXRelu2 x_nsplit other than 1, 2 or 4 (the fused relu^2 staging has no form for it) or a kslice
+// other than 128, 256 or 512.
 int launch_ln_mix(const LnMixArgs& a, int n_out_rows, hipStream_t st);
 int launch_gemm(const GemmArgs& a, hipStream_t st);
 // a one-row step's head GEMM with ln_out folded in (k_gemm2_lnrow); false if not covered
@@ -264,7 +267,9 @@ int wkv_perm_layout(int Dw, int Da, int Dv, int Dg, int n_part);
 // relu(sum of nx f32 slabs [nx][R][ld])^2 -> bf16 hi/lo planes [R][F] (bf16 prefill steps)
 void launch_relu2_planes(const float* part, int nx, int64_t pstride, int ld, int F, int R, bf16_t* hi, bf16_t* lo,
                          hipStream_t st);
-// Repack a GEMM matrix W [N][K] (K % 32 == 0) into MFMA fragment blocks (k_gemm's layout):
+// slab 0 of [nx][R][ld] f32 slabs += slabs 1 .. nx - 1 (in that order), columns < F
+void launch_sum_slabs(float* part, int nx, int64_t pstride, int ld, int F, int R, hipStream_t st);
+// Repack a GEMM matrix W [N][K] (K % 32 == 0) into MFMA fragment blocks (gemm2_body's weight stream):
 // out holds ceil(N/16)*16*K elements.
 void launch_pack_frag(const bf16_t* W, int N, int K, bf16_t* out, hipStream_t st);
 

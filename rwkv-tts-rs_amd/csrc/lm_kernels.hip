@@ -439,191 +439,24 @@ __global__ __launch_bounds__(256) void k_ln1024(LnMixArgs a) {
 }
 
 // ------------------------------------------------------------------------------------
-// gemm: out[split][row][col_off + n] = sum_{k in split} X[row][k] * W[n][k]
-//   W bf16 [N][K] row-major; X as bf16 hi/lo planes (or, mode kXRelu2, relu(sum of f32
-//   partial slabs)^2 split on the fly). MFMA 16x16x32 bf16.
+// gemm (gemm2_body; k_gemm2 and the persistent launches' GEMM roles):
+//   out[split][row][col_off + n] = sum_{k in split} X[row][k] * W[n][k]
+//   W bf16 / f16 [N][K], pre-packed in MFMA fragment order (launch_pack_frag); X as 16-bit hi/lo
+//   planes (or, mode kXRelu2, relu(sum of NX f32 partial slabs)^2 split on the fly). MFMA 16x16x32.
 //   Workgroup = 4 waves = 64 output columns (16 per wave) x MT*16 rows x one K slice.
-//   * every wave issues ALL of its weight loads for the slice first (HBM stream, one 16-byte
-//     load per lane per 32-deep K step: lane l reads W[col0 + (l&15)][k0 + 8(l>>4) .. +8]);
-//   * meanwhile the workgroup stages its X slice into LDS once (shared by the 4 waves);
-//   * A fragments come from LDS (ds_read_b128), B fragments from the registers.
+//   * every wave streams the weights of its 16 columns for the whole slice into registers (HBM
+//     stream, one 16-byte load per lane per 32-deep K step: lane l holds
+//     W[col0 + (l&15)][k0 + 8(l>>4) .. +8]; in the packed layout each load instruction reads one
+//     contiguous 1 KB block and the wave's KSTEPS blocks are consecutive);
+//   * the X slice (L2-resident activations) is requested BEFORE the weight stream, so staging X
+//     into LDS (once, shared by the 4 waves) waits only for X (vmcnt counts in issue order) and
+//     overlaps the HBM weight latency; in kXRelu2 mode all NX key slabs are in flight at once;
+//   * A fragments come from LDS (ds_read_b128), B fragments from the registers; hi and lo products
+//     accumulate in separate MFMA chains (2*MT independent accumulators), added at the end;
+//   * segment lookup without dependent scalar loads: every segment's fields are read in one
+//     round and the tile's segment is picked by selects (or the per-tile descriptor table).
 //   Each wave owns complete output columns: no cross-wave reduction; split-K partial slabs
 //   are summed (fixed order) by the consumer.
-// ------------------------------------------------------------------------------------
-template <int MT, int KSTEPS, int XMODE, bool F16>
-__global__ __launch_bounds__(256) void k_gemm(GemmArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ uint32_t s_rexp[MT * 16];  // f16 relu^2 rows: bits of the row maximum if >= 2^15
-  constexpr int KS = KSTEPS * 32;      // K slice
-  constexpr int LD = KS + 8;           // LDS row stride (elements): +16 B breaks bank aliasing
-  constexpr int ROWS = MT * 16;
-  bf16_t* xh = (bf16_t*)smem;
-  bf16_t* xl = xh + ROWS * LD;
-  uint64_t* gst = (a.stamps && threadIdx.x == 0)
-                      ? a.stamps + ((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 4 : nullptr;
-  if (gst) gst[0] = __builtin_amdgcn_s_memtime();
-  const int tile = blockIdx.x;
-  int s = 0;
-  while (s + 1 < a.nseg && tile >= a.seg[s + 1].tile_start) ++s;
-  const GemmSeg& sg = a.seg[s];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int g = lane >> 4, li = lane & 15;
-  const int col0 = (tile - sg.tile_start) * 64 + wave * 16;
-  const int split = blockIdx.y;
-  const int kbeg = split * KS;
-  const int row0 = blockIdx.z * ROWS;
-  // 1) weight stream for this wave's 16 columns: W is pre-packed in MFMA fragment order
-  // (launch_pack_frag), so each load instruction reads one contiguous 1 KB block and the
-  // wave's KSTEPS blocks are consecutive
-  int nb = col0 >> 4;
-  const int nblk = (sg.N + 15) >> 4;
-  if (nb >= nblk) nb = nblk - 1;
-  const bf16_t* wp = sg.W + (((int64_t)nb * (a.K >> 5) + (kbeg >> 5)) * 64 + lane) * 8;
-  short8 b[KSTEPS];
-#pragma unroll
-  for (int t = 0; t < KSTEPS; ++t)
-    b[t] = __builtin_nontemporal_load((const short8*)(wp + t * 512));
-  // 2) stage X slice
-  constexpr int CH = KS / 8;  // 16-byte chunks per row
-  if constexpr (XMODE == kXPlanes) {
-    constexpr int PER = ROWS * CH / 256;  // 16-byte chunks per thread per plane
-    short8 vh[PER], vl[PER];
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-      const int c = threadIdx.x + u * 256;
-      const int r = c / CH, k8 = (c % CH) * 8;
-      const int src = row0 + r;
-      vh[u] = vl[u] = (short8){0, 0, 0, 0, 0, 0, 0, 0};
-      if (src < a.M) {
-        const int64_t o = (int64_t)src * sg.ldx + kbeg + k8;
-        vh[u] = *(const short8*)(sg.Xhi + o);
-        vl[u] = *(const short8*)(sg.Xlo + o);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-      const int c = threadIdx.x + u * 256;
-      const int r = c / CH, k8 = (c % CH) * 8;
-      *(short8*)(xh + r * LD + k8) = vh[u];
-      *(short8*)(xl + r * LD + k8) = vl[u];
-    }
-  } else {  // kXRelu2: x = relu(sum_p P[p][row][k])^2, partials summed in order 0..n-1
-    constexpr int PER = ROWS * KS / 4 / 256;  // float4 chunks per thread
-    float4_ x[PER];
-#pragma unroll
-    for (int u = 0; u < PER; ++u) x[u] = (float4_){0.f, 0.f, 0.f, 0.f};
-    for (int p0 = 0; p0 < a.x_nsplit; p0 += 2) {
-      float4_ t[2][PER];
-#pragma unroll
-      for (int pp = 0; pp < 2; ++pp)
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-          const int c = threadIdx.x + u * 256;
-          const int r = c / (KS / 4), k4 = (c % (KS / 4)) * 4;
-          const int src = row0 + r;
-          t[pp][u] = (src < a.M && p0 + pp < a.x_nsplit)
-                         ? *(const float4_*)(a.x_part + (p0 + pp) * a.x_part_stride + (int64_t)src * a.x_ld + kbeg + k4)
-                         : (float4_){0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-      for (int pp = 0; pp < 2; ++pp)
-#pragma unroll
-        for (int u = 0; u < PER; ++u) x[u] += t[pp][u];
-    }
-    // f16 model: per-row power-of-two range scaling of relu^2 (see k_gemm2)
-    if constexpr (F16) {
-      if (threadIdx.x < ROWS) s_rexp[threadIdx.x] = 0u;
-      __syncthreads();
-#pragma unroll
-      for (int u = 0; u < PER; ++u) {
-        const int r = (threadIdx.x + u * 256) / (KS / 4);
-        float m = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) m = fmaxf(m, x[u][e] > 0.f ? x[u][e] * x[u][e] : 0.f);
-        if (m >= 32768.f) atomicMax(&s_rexp[r], as_u32(m));
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-      const int c = threadIdx.x + u * 256;
-      const int r = c / (KS / 4), k4 = (c % (KS / 4)) * 4;
-      uint16_t h[4], l[4];
-      float sc = 1.f;
-      if constexpr (F16) {
-        const uint32_t mb = s_rexp[r];
-        if (mb) sc = as_f32((uint32_t)(127 - (int)((mb >> 23) & 0xFF) + 127 + 14) << 23);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float y = (x[u][e] > 0.f ? x[u][e] * x[u][e] : 0.f) * sc;
-        h[e] = f32_to_w16(y, F16);
-        l[e] = f32_to_w16(y - w16_to_f32(h[e], F16), F16);
-      }
-      *(uint2*)(xh + r * LD + k4) = make_uint2(h[0] | ((uint32_t)h[1] << 16), h[2] | ((uint32_t)h[3] << 16));
-      *(uint2*)(xl + r * LD + k4) = make_uint2(l[0] | ((uint32_t)l[1] << 16), l[2] | ((uint32_t)l[3] << 16));
-    }
-  }
-  __syncthreads();
-  if (gst) gst[1] = __builtin_amdgcn_s_memtime();
-  // 3) MFMA over the slice: the hi and the lo plane in chains of their own, added at the end --
-  // k_gemm2's and k_gemm_wide's order of summation, so that this fallback gives their bits. (An
-  // engine runs one GEMM through both: a bf16 value GEMM whose key split has no fused k_gemm2
-  // form stages relu^2 here up to kPlaneRows rows and takes the planes route above them, and the
-  // outputs are promised chunk-invariant.)
-  float4_ acc[MT], acc_l[MT];
-#pragma unroll
-  for (int m = 0; m < MT; ++m) acc[m] = acc_l[m] = (float4_){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int t = 0; t < KSTEPS; ++t) {
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      const int o = (m * 16 + li) * LD + t * 32 + g * 8;
-      const short8 ah = *(const short8*)(xh + o);
-      const short8 al = *(const short8*)(xl + o);
-      if constexpr (F16) {
-        acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ah),
-                                                        __builtin_bit_cast(f16x8, b[t]), acc[m], 0, 0, 0);
-        acc_l[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, al),
-                                                          __builtin_bit_cast(f16x8, b[t]), acc_l[m], 0, 0, 0);
-      } else {
-        acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ah),
-                                                         __builtin_bit_cast(bf16x8, b[t]), acc[m], 0, 0, 0);
-        acc_l[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, al),
-                                                           __builtin_bit_cast(bf16x8, b[t]), acc_l[m], 0, 0, 0);
-      }
-    }
-  }
-#pragma unroll
-  for (int m = 0; m < MT; ++m) acc[m] += acc_l[m];
-  if (gst) gst[2] = __builtin_amdgcn_s_memtime() + (uint64_t)(acc[0][0] != acc[0][0]);
-  // 4) store (D layout: col = lane&15, row = 4*(lane>>4) + j)
-  const int col = col0 + li;
-  if (col < sg.N) {
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int row = row0 + m * 16 + 4 * g + j;
-        float v = acc[m][j];
-        if constexpr (F16 && XMODE == kXRelu2) {
-          const uint32_t mb = s_rexp[m * 16 + 4 * g + j];
-          if (mb) v *= as_f32((uint32_t)((int)((mb >> 23) & 0xFF) - 127 - 14 + 127) << 23);
-        }
-        if (row < a.M) a.out[split * a.split_stride + (int64_t)row * a.ldo + sg.col_off + col] = v;
-      }
-  }
-  if (gst) gst[3] = __builtin_amdgcn_s_memtime();
-}
-
-// ------------------------------------------------------------------------------------
-// gemm2: k_gemm with a shorter critical path.
-//  * segment lookup without dependent scalar loads: every segment's fields are read in one
-//    round and the tile's segment is picked by selects;
-//  * the X slice (L2-resident activations) is requested BEFORE the weight stream, so staging X
-//    into LDS waits only for X (vmcnt counts in issue order) and overlaps the HBM weight
-//    latency; in kXRelu2 mode all NX key slabs are in flight at once;
-//  * hi and lo products accumulate in separate MFMA chains (2*MT independent accumulators).
 // ------------------------------------------------------------------------------------
 // Inter-workgroup hand-offs of the persistent FFN launch (k_ffn_persist): counters kSyncStride
 // ints (256 B) apart, [kSyncStride * r] (r < kLnReplicas) = LayerNorm rows published (one replica
@@ -1499,7 +1332,7 @@ __global__ __launch_bounds__(256) void k_gemm2_lnrow(GemmArgs a, LnMixArgs lo) {
 bool launch_gemm_lnrow(const GemmArgs& a, const LnMixArgs& lo, hipStream_t st) {
   // one row, the head's shape: one segment of 16-bit planes, 512-wide K-slices, no XCD remap;
   // ln_out's: C = 1024, 16 partial slabs, no row remap beyond row 0
-  if (a.M != 1 || a.nseg != 1 || a.kslice != 512 || a.xmode != kXPlanes || a.q_fmt || a.stamps ||
+  if (a.M != 1 || a.nseg != 1 || a.kslice != 512 || a.xmode != kXPlanes || a.q_fmt ||
       a.allow_xmap || a.xalign > 0 || lo.C != 1024 || lo.n_part != 16 || lo.n_mix != 1 || lo.h_out != nullptr ||
       a.f16 != lo.f16)
     return false;
@@ -1825,37 +1658,35 @@ int launch_ln_mix(const LnMixArgs& a, int n_out_rows, hipStream_t st) {
 }
 
 template <int MT, int KSTEPS>
-static void launch_gemm_t(const GemmArgs& a, dim3 grid, hipStream_t st) {
+static bool launch_gemm_t(const GemmArgs& a, dim3 grid, hipStream_t st) {
   const size_t lds = (size_t)MT * 16 * (KSTEPS * 32 + 8) * 2 * 2;
-  // k_gemm2 (fragment-packed weights, per-tile descriptors) covers the 0.4B shapes; k_gemm is the
-  // generic fallback (other slab counts) and the debug-stamp build
-  // (quantised weights exist only in k_gemm2: debug stamps / experiments are ignored for them)
-  const bool nx_ok = a.x_nsplit == 4 || a.x_nsplit == 2 || (a.x_nsplit == 1 && a.q_fmt);
-  if ((a.xmode == kXPlanes || nx_ok) && (a.stamps == nullptr || a.q_fmt)) {
-    const int ms = a.nseg > 1 ? (a.n_tinfo > 0 ? 2 : 1) : 0;
-    GemmArgs b = a;
-    b.xmap = 0;
-    if (grid.z == 1 && a.xalign > 0) {
-      b.xmap = 2;
-      b.ntiles = (int)grid.x;
-      const int groups = ((int)grid.x + a.xalign - 1) / a.xalign;
-      grid = dim3(8 * ((groups + 7) / 8) * a.xalign * a.k_split);
-    } else if (grid.z == 1 && a.allow_xmap && (a.k_split % 8 == 0 || 8 % a.k_split == 0)) {
-      b.xmap = 1;
-      b.ntiles = (int)grid.x;
-      if (a.k_split >= 8) {
-        grid = dim3(grid.x * a.k_split);
-      } else {
-        b.tiles_per_xcd = (int)((grid.x * a.k_split + 7) / 8);
-        grid = dim3(8 * b.tiles_per_xcd);
-      }
+  // the fused relu^2 staging (kXRelu2) holds all NX key slabs in registers: forms for 1, 2 and 4 slabs
+  // (the engine sums other counts into slab 0 first, launch_sum_slabs)
+  if (a.xmode != kXPlanes && a.x_nsplit != 1 && a.x_nsplit != 2 && a.x_nsplit != 4) return false;
+  const int ms = a.nseg > 1 ? (a.n_tinfo > 0 ? 2 : 1) : 0;
+  GemmArgs b = a;
+  b.xmap = 0;
+  if (grid.z == 1 && a.xalign > 0) {
+    b.xmap = 2;
+    b.ntiles = (int)grid.x;
+    const int groups = ((int)grid.x + a.xalign - 1) / a.xalign;
+    grid = dim3(8 * ((groups + 7) / 8) * a.xalign * a.k_split);
+  } else if (grid.z == 1 && a.allow_xmap && (a.k_split % 8 == 0 || 8 % a.k_split == 0)) {
+    b.xmap = 1;
+    b.ntiles = (int)grid.x;
+    if (a.k_split >= 8) {
+      grid = dim3(grid.x * a.k_split);
+    } else {
+      b.tiles_per_xcd = (int)((grid.x * a.k_split + 7) / 8);
+      grid = dim3(8 * b.tiles_per_xcd);
     }
-    // prefill steps of one segment with planes X (FFN key / value, Wo): k_gemm_wide, several
-    // 64-column tiles per workgroup (bit-identical slabs)
-    // (KSTEPS 8: the FFN key / value GEMMs, 47 -> 42 us per launch on a 1280-row step; the Wo GEMM's
-    // 4-step slices measured 18 -> 19 us at four tiles per workgroup and keep k_gemm2)
-    constexpr int kWideNB = 2;
-    if constexpr (MT == 2 && KSTEPS == 8) {
+  }
+  // prefill steps of one segment with planes X (FFN key / value, Wo): k_gemm_wide, several
+  // 64-column tiles per workgroup (bit-identical slabs)
+  // (KSTEPS 8: the FFN key / value GEMMs, 47 -> 42 us per launch on a 1280-row step; the Wo GEMM's
+  // 4-step slices measured 18 -> 19 us at four tiles per workgroup and keep k_gemm2)
+  constexpr int kWideNB = 2;
+  if constexpr (MT == 2 && KSTEPS == 8) {
     if (grid.z > 1 && !a.q_fmt && a.xmode == kXPlanes && a.nseg == 1 && a.seg[0].tile_start == 0 &&
         (int)grid.x % kWideNB == 0 && b.xmap == 0) {
       dim3 gw((int)grid.x / kWideNB, grid.y, grid.z);
@@ -1864,43 +1695,35 @@ static void launch_gemm_t(const GemmArgs& a, dim3 grid, hipStream_t st) {
       const size_t lw = std::max(lds, (size_t)MT * 16 * (kWideNB * 64 + 4) * 4);
       if (a.f16) RT_LAUNCH((k_gemm_wide<KSTEPS, true, kWideNB>), gw, dim3(256), lw, st, b);
       else RT_LAUNCH((k_gemm_wide<KSTEPS, false, kWideNB>), gw, dim3(256), lw, st, b);
-      return;
+      return true;
     }
-    }
-    // prefill steps: several row groups per workgroup (weights loaded once), as many as keep >= 4
-    // workgroups per CU (measured over 1 / 2 / 4 / 8 / 10 / 20 / 40 groups per workgroup on a
-    // 1280-row step: 9.3 / 8.5 / 8.3 / 8.1 / 8.1 / 8.0 / 10.0 ms)
-    if (grid.z > 1 && !a.q_fmt) {
-      const int per_group = (int)(grid.x * grid.y);
-      const int rpw = std::max(1, (int)grid.z * per_group / 1024);
-      grid.z = (grid.z + rpw - 1) / rpw;
-    }
+  }
+  // prefill steps: several row groups per workgroup (weights loaded once), as many as keep >= 4
+  // workgroups per CU (measured over 1 / 2 / 4 / 8 / 10 / 20 / 40 groups per workgroup on a
+  // 1280-row step: 9.3 / 8.5 / 8.3 / 8.1 / 8.1 / 8.0 / 10.0 ms)
+  if (grid.z > 1 && !a.q_fmt) {
+    const int per_group = (int)(grid.x * grid.y);
+    const int rpw = std::max(1, (int)grid.z * per_group / 1024);
+    grid.z = (grid.z + rpw - 1) / rpw;
+  }
 #define G2(F, XM, NX_, MS_)                                                               \
   do {                                                                                    \
     if (b.q_fmt) RT_LAUNCH((k_gemm2<MT, KSTEPS, XM, F, NX_, MS_, true>), grid, dim3(256), lds, st, b); \
     else RT_LAUNCH((k_gemm2<MT, KSTEPS, XM, F, NX_, MS_>), grid, dim3(256), lds, st, b);  \
   } while (0)
-    if (a.f16) {
-      if (a.xmode == kXPlanes) { if (ms == 2) G2(true, kXPlanes, 1, 2); else if (ms == 1) G2(true, kXPlanes, 1, 1); else G2(true, kXPlanes, 1, 0); }
-      else if (a.x_nsplit == 4) G2(true, kXRelu2, 4, 0);
-      else if (a.x_nsplit == 2) G2(true, kXRelu2, 2, 0);
-      else G2(true, kXRelu2, 1, 0);
-    } else {
-      if (a.xmode == kXPlanes) { if (ms == 2) G2(false, kXPlanes, 1, 2); else if (ms == 1) G2(false, kXPlanes, 1, 1); else G2(false, kXPlanes, 1, 0); }
-      else if (a.x_nsplit == 4) G2(false, kXRelu2, 4, 0);
-      else if (a.x_nsplit == 2) G2(false, kXRelu2, 2, 0);
-      else G2(false, kXRelu2, 1, 0);
-    }
-#undef G2
-    return;
-  }
   if (a.f16) {
-    if (a.xmode == kXPlanes) RT_LAUNCH((k_gemm<MT, KSTEPS, kXPlanes, true>), grid, dim3(256), lds, st, a);
-    else RT_LAUNCH((k_gemm<MT, KSTEPS, kXRelu2, true>), grid, dim3(256), lds, st, a);
+    if (a.xmode == kXPlanes) { if (ms == 2) G2(true, kXPlanes, 1, 2); else if (ms == 1) G2(true, kXPlanes, 1, 1); else G2(true, kXPlanes, 1, 0); }
+    else if (a.x_nsplit == 4) G2(true, kXRelu2, 4, 0);
+    else if (a.x_nsplit == 2) G2(true, kXRelu2, 2, 0);
+    else G2(true, kXRelu2, 1, 0);
   } else {
-    if (a.xmode == kXPlanes) RT_LAUNCH((k_gemm<MT, KSTEPS, kXPlanes, false>), grid, dim3(256), lds, st, a);
-    else RT_LAUNCH((k_gemm<MT, KSTEPS, kXRelu2, false>), grid, dim3(256), lds, st, a);
+    if (a.xmode == kXPlanes) { if (ms == 2) G2(false, kXPlanes, 1, 2); else if (ms == 1) G2(false, kXPlanes, 1, 1); else G2(false, kXPlanes, 1, 0); }
+    else if (a.x_nsplit == 4) G2(false, kXRelu2, 4, 0);
+    else if (a.x_nsplit == 2) G2(false, kXRelu2, 2, 0);
+    else G2(false, kXRelu2, 1, 0);
   }
+#undef G2
+  return true;
 }
 
 // Prefill steps (bf16 models): relu(sum of the key GEMM's NX partial slabs)^2 as bf16 hi/lo planes
@@ -1928,6 +1751,21 @@ void launch_relu2_planes(const float* part, int nx, int64_t pstride, int ld, int
   RT_LAUNCH(k_relu2_planes, dim3((F / 4 + 255) / 256, R), dim3(256), 0, st, part, nx, pstride, ld, F, hi, lo);
 }
 
+// Key splits the fused relu^2 staging has no form for (k_gemm2's NX: 1, 2 and 4): the key GEMM's nx
+// partial slabs summed once into slab 0, in place, so that the value GEMM stages one slab. The
+// staging's sum order (slab 0 + slab 1 + ...), hence its bits.
+__global__ __launch_bounds__(256) void k_sum_slabs(float* part, int nx, int64_t pstride, int ld, int F) {
+  const int row = blockIdx.y, c = 4 * (blockIdx.x * 256 + threadIdx.x);
+  if (c >= F) return;
+  const int64_t o = (int64_t)row * ld + c;
+  float4_ x = *(const float4_*)(part + o);
+  for (int p = 1; p < nx; ++p) x += *(const float4_*)(part + p * pstride + o);
+  *(float4_*)(part + o) = x;
+}
+void launch_sum_slabs(float* part, int nx, int64_t pstride, int ld, int F, int R, hipStream_t st) {
+  RT_LAUNCH(k_sum_slabs, dim3((F / 4 + 255) / 256, R), dim3(256), 0, st, part, nx, pstride, ld, F);
+}
+
 // The FFN half of a decode step as one launch (k_ffn_persist); false: a shape it does not cover
 // (the caller runs the three launches). ln / key / val: the three launches' arguments as built by
 // the engine; cnt / cnt_prev: this and the previous layer's counter blocks ((1 + kFfnSlices) x
@@ -1949,7 +1787,7 @@ bool launch_ffn_persist(const LnMixArgs& ln, const GemmArgs& key, const GemmArgs
   if (ln.C != 1024 || !ln.shift || ln.n_mix != 1 || ln.n_part != 8 || ln.emb || R < 1 || R > 32 ||
       key.xmode != kXPlanes || val.xmode != kXRelu2 || val.x_nsplit != 4 || key.kslice != 256 ||
       val.kslice != 256 || key.M != R || val.M != R || key.nseg != 1 || val.nseg != 1 || key.q_fmt || val.q_fmt ||
-      key.stamps || val.stamps || key.xalign <= 0 || key.f16 != val.f16 || key.f16 != ln.f16 ||
+      key.xalign <= 0 || key.f16 != val.f16 || key.f16 != ln.f16 ||
       cnt == cnt_prev)
     return false;
   const int kt = (key.seg[0].N + 63) / 64, vt = (val.seg[0].N + 63) / 64;
@@ -2042,10 +1880,10 @@ int launch_gemm(const GemmArgs& a, hipStream_t st) {
   const int mg = (a.M + mt * 16 - 1) / (mt * 16);
   dim3 grid(tiles, a.k_split, mg);
   const int ks = a.kslice / 32;
-#define GEMM_CASE(KS_)                                          \
-  case KS_:                                                     \
-    if (mt == 1) launch_gemm_t<1, KS_>(a, grid, st);            \
-    else launch_gemm_t<2, KS_>(a, grid, st);                    \
+  bool ok = false;
+#define GEMM_CASE(KS_)                                                                        \
+  case KS_:                                                                                   \
+    ok = mt == 1 ? launch_gemm_t<1, KS_>(a, grid, st) : launch_gemm_t<2, KS_>(a, grid, st);   \
     break;
   switch (ks) {
     GEMM_CASE(4)
@@ -2054,7 +1892,7 @@ int launch_gemm(const GemmArgs& a, hipStream_t st) {
     default: break;  // rejected at engine init (kslice in {128, 256, 512})
   }
 #undef GEMM_CASE
-  return (int)(grid.x * grid.y * grid.z);
+  return ok ? (int)(grid.x * grid.y * grid.z) : -1;
 }
 // W [N][K] -> MFMA B-fragment blocks: block (nb, kb) = 16 columns x 32 k = 1 KB, lane
 // l = 16 g + li holding W[16 nb + li][32 kb + 8 g .. + 8]; blocks ordered nb-major. Rows >= N are 0.
@@ -2992,11 +2830,11 @@ bool launch_att_persist(const LnMixArgs& ln, const GemmArgs& rkv, const WkvArgs&
   const int lora_tiles = rkv_tiles - 3 * ln.C / 64;
   if (ln.C != 1024 || H != 16 || !ln.shift || ln.n_mix != 6 || ln.n_part != (emb ? 0 : 16) || R < 1 || R > 32 ||
       rkv.xmode != kXPlanes || rkv.n_tinfo != rkv_tiles || rkv.kslice != 256 || rkv.k_split != 4 || rkv.M != R ||
-      rkv.q_fmt || rkv.stamps || rkv.xalign || lora_tiles < 1 || rkv.ldo != wkv.ldp ||
+      rkv.q_fmt || rkv.xalign || lora_tiles < 1 || rkv.ldo != wkv.ldp ||
       wkv.perm != 2 || wkv.n_part != 4 || wkv.multi_row || !wkv.allow_xmap || wkv.n_seg != R || wkv.stamps ||
       wkv.Dw != 64 || wkv.Da != 64 || wkv.Dv != 32 || wkv.Dg != 128 ||
       wo.xmode != kXPlanes || wo.kslice != 128 || wo.k_split != 8 || wo.nseg != 1 || wo.M != R || wo.q_fmt ||
-      wo.stamps || (wo.seg[0].N + 63) / 64 != 16 ||
+      (wo.seg[0].N + 63) / 64 != 16 ||
       rkv.f16 != ln.f16 || wo.f16 != ln.f16 || wkv.f16 != ln.f16 || cnt == cnt_prev)
     return false;
   LnMixArgs l = ln;

@@ -1,6 +1,6 @@
 """fp16 models whose FFN activations leave the f16 range (relu(k)^2 > 65504, as real RWKV
 checkpoints do -- the reason ChatRWKV rescales in fp16). The GPU stages relu^2 as per-row
-power-of-two-scaled f16 planes (lm_kernels.hip k_gemm2 / k_gemm); the oracle computes in f32.
+power-of-two-scaled f16 planes (lm_kernels.hip gemm2_body, the kXRelu2 staging); the oracle computes in f32.
 Without the scaling the logits are inf / NaN."""
 import numpy as np
 import pytest

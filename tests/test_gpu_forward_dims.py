@@ -18,14 +18,17 @@ Where they land (Engine::init's pick(); launch_wkv, launch_ln_mix, launch_gemm_t
                  k_ln_mix<1,-1> with 3 / 1 and 12 / 6 slabs (LN1 of layers > 0 and ln_out sum the
                  value split's slabs, LN2 the Wo split's). c2048: C > 1024 -> k_ln_mix<2,-1>
                  (16 / 16 slabs).
-  launch_gemm_t  the value GEMM's fused relu^2 staging has k_gemm2 forms for x_nsplit (= key split)
-                 2 and 4 only: c128x (1), c768 (3) and c2048 (8) take the generic k_gemm, at
-                 <= 64 rows on bf16 engines and at every row count on f16 engines (no relu^2 planes).
-                 The planes-mode GEMMs (rkv, Wo, key, head) stay k_gemm2 with kslice 128 / 256.
+  launch_gemm_t  the value GEMM's fused relu^2 staging has k_gemm2 forms for 1, 2 and 4 key slabs:
+                 c128x (key split 1) stages its one slab; c768 (3) and c2048 (8) sum their slabs into
+                 slab 0 first (k_sum_slabs) and stage that, at <= 64 rows on bf16 engines and at every
+                 row count on f16 engines (no relu^2 planes). The planes-mode GEMMs (rkv, Wo, key,
+                 head; the bf16 value GEMM above 64 rows) are k_gemm2 / k_gemm_wide with kslice
+                 128 / 256.
   grids          the XCD-mapped 1-D grids (kXmapMask: value GEMM and WKV) exist in k_gemm2 and
-                 k_wkv6 only, so every launch above keeps the plain (tiles, k_split, mg) and
-                 (n_seg, H) grids, c768 with H = 12 and splits 3 / 6 / 12 that are no divisor or
-                 multiple of 8. The key GEMM's XCD-aligned grid (kXalignMask, steps of <= 32 rows) pads
+                 k_wkv6 only and need a split that divides 8 or is a multiple of it: c2048's fused
+                 value GEMM (split 16) takes the 1-D grid in steps of one row group; c128x (3) and
+                 c768 (12; H = 12, splits 3 / 6 / 12) keep the plain (tiles, k_split, mg) grid, and
+                 every WKV launch the (n_seg, H) grid. The key GEMM's XCD-aligned grid (kXalignMask, steps of <= 32 rows) pads
                  its tile groups to a multiple of 8: c128x has 3 groups of 2 tiles (-> 8), c768 12
                  groups of 4 (-> 16); the 0.4B widths have 16 and never pad.
 
