@@ -1029,6 +1029,140 @@ int rwkvtts_pitch_kernel_ms(rwkvtts_pitch* p, double* ms);
 /* HIP-event time of the last call's marks kernel alone, the serial part, in ms; 0 before the first. */
 int rwkvtts_pitch_walk_ms(rwkvtts_pitch* p, double* ms);
 
+/* ---- wm: a provenance watermark on the GPU, the `watermark` of the pipeline -- a time-domain
+ * spread-spectrum mark that carries a payload under a key, and its detector (no reference counterpart:
+ * the reference marks nothing) -----------------------------------------------------------------
+ * Embedding runs on the 16 kHz PCM, last of the stages at that rate: after the leveller and before
+ * the resampler. n_out = n. One causal definition, so a stream's pieces are bitwise the one-shot
+ * result. The embedder's arithmetic contract (every output bit is defined by IEEE f32 operations:
+ * rounded add, subtract and multiply, never fused, and correctly rounded divide and square root;
+ * DESIGN.md §30):
+ *   B, L      block length and filter length; NB payload bits, TB samples per bit; the mark's period
+ *             is NP = NB * TB samples
+ *   s         the strength, an f32 per signal: (float)10^(strength_dB / 20), in double
+ *             (rwkvtts_wm_strength)
+ *   table     h[0, L) then r[0, B), f32, built in double and rounded once. With t = k - (L - 1) / 2,
+ *             w[k] = 0.42 - 0.5 cos(2 pi k / (L - 1)) + 0.08 cos(4 pi k / (L - 1)) (Blackman),
+ *             fh = 2 band_hi / 16000, fl = 2 band_lo / 16000 and sinc(x) = sin(pi x) / (pi x):
+ *             g[k] = w[k] * (fh sinc(fh t) - fl sinc(fl t)), h[k] = g[k] / sqrt(sum g^2) (unit energy).
+ *             r[i] = (float)((double)(i + 1) / (double)B).
+ *   chips     splitmix64(x): z = x + 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *             z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31), all mod 2^64.
+ *             c(key, m) = +1 if the top bit of splitmix64(splitmix64(key) + m) is set, else -1, for m
+ *             in [0, NP) (the inner hash keeps neighbouring keys from giving shifted copies of one
+ *             sequence). The chip at sample n is c(key, n mod NP) * (+1 if payload bit
+ *             (n mod NP) / TB is set, else -1); n mod NP is taken in [0, NP) for n < 0 too.
+ *   carrier   u[n] = sum_k h[k] * chip[n - k]: a sequential f32 sum in ascending k from +0, one rounded
+ *             multiply (exact: the chip is +-1) then one rounded add per tap. Chips below sample 0 are
+ *             the periodic sequence's, not zeros: a crop is indistinguishable from a start.
+ *   gain      block j covers samples [jB, (j+1)B); x at or past the signal's end is +0 (the last block
+ *             may be partial). E_j from 64 partials as the leveller's: p[l] = sum of x[i]*x[i] over the
+ *             block's i = l (mod 64), ascending from +0, then p[l] += p[l+s] for l < s, s = 32 .. 1;
+ *             E_j = p[0]. a_j = s * sqrt(E_j / (float)B). a_{-1} = a_0.
+ *   apply     sample i of block j, n = jB + i: y = x + (a_{j-1} + (a_j - a_{j-1}) * r[i]) * u[n].
+ * So +0 silence comes back bit for bit (a = +0, and +0 + (+-0) = +0); |y - x| <= max(a_{j-1}, a_j) *
+ * sum|h| (the ramp lies between its ends and |u| <= sum|h|; exact in real arithmetic, where a random
+ * +-1 sum leaves |u| far below sum|h| -- the f32 roundings of u, of the ramp and of the last add could
+ * pass it only by 2^-20 of it plus half an ulp of y, at a sample whose chips all align with h); there is no
+ * clamp (a mark on a full-scale signal can pass 1.0: the leveller's ceiling leaves 1 dB); a stream lags
+ * one block, 20 ms at the default; and the only carried state is a_{j-1}. A non-finite sample leaves its
+ * block and the next unspecified; nothing is read or written out of bounds.
+ *
+ * The detector takes 16 kHz PCM of any origin and a key. It is not bitwise: its contract is the
+ * float64 restatement (tests/wm_ref.py) and the forward-error bound of its f32 sums.
+ *   whiten    w[n] = x[n] / (sqrt(E_j / B) + 2^-17), blocks counted from the clip's first sample
+ *   filter    v[n] = sum_k h[k] * w[n + k], n in [0, N); w past the end is 0
+ *   fold      F[m] = sum v[n] over n = m (mod NP), ascending n, m in [0, NP)
+ *   search    for every offset tau in [0, NP) and bit slot b (phases m in [b TB, (b+1) TB)):
+ *             r_b = sum_m F[(m - tau) mod NP] * c(key, m), d_b = sum_m F[(m - tau) mod NP]^2, ascending
+ *             m; z_b = r_b / sqrt(d_b), 0 where d_b is 0 (a slot the clip never covers);
+ *             S(tau) = sum_b z_b^2
+ *   result    offset = argmax S (the lowest tau on a tie) -- the phase of the mark at the clip's first
+ *             sample; score = S(offset); payload = the slots with z_b > 0; seen = the slots with
+ *             d_b > 0; min_z = min |z_b| over them; detected = score >= T.
+ * Each r_b and d_b lies within TB * 2^-24 * sum|addend| of the float64 value. For an unmarked clip or a
+ * wrong key the chips are independent +-1, independent of the audio, so Var(r_b) = sum F^2 = d_b
+ * exactly, however coloured v is and whatever the clip's folds share (a host periodic in NP, another
+ * key's mark): z_b is a unit-variance sum of TB bounded terms, S is chi-square with NB degrees of
+ * freedom at every tau to the accuracy of the central limit, and T (rwkvtts_wm_threshold) is the
+ * smallest T with NP * Q(T; NB) <= 1e-6, Q the chi-square upper tail: e^{-T/2} sum_{i < NB/2}
+ * (T/2)^i / i! for even NB. (Dividing by the fold of v^2 instead is the same where the folds are
+ * independent and lets whatever folds coherently pass T: DESIGN.md §30.2.) Every default below is
+ * untuned and nobody has listened to the output: the repository has no real checkpoint. */
+typedef struct {
+  uint32_t struct_size;
+  int32_t block;     /* B: a multiple of 64, 64 .. 4800; 0 = 320 (one vocoder frame, 20 ms) */
+  int32_t taps;      /* L: odd, 3 .. 1023; 0 = 129 */
+  int32_t bits;      /* NB: 1 .. 32; 0 = 16 */
+  int32_t bit_len;   /* TB: a multiple of B, at most 6400; 0 = 1600 (100 ms) */
+  float band_lo;     /* Hz, > 0; 0 = 1000 */
+  float band_hi;     /* Hz, band_lo < band_hi < 8000; 0 = 3400 (below 0.95 * 4 kHz: survives 8 kHz output) */
+  float strength_db; /* -60 .. -6; 0 = -26: the strength of an embed call that gives none */
+} rwkvtts_wm_desc;
+/* The library's own table builder (host only): out[L + B]. Anything outside the ranges above (NaN
+ * included) is RWKVTTS_EINVAL, here and in every call that takes a desc. */
+int rwkvtts_wm_table(const rwkvtts_wm_desc* desc, float* out);
+/* s of a strength in dB (host only): (float)pow(10, strength_db / 20). A value outside -60 .. -6 (NaN
+ * included) returns NaN, which every embed call refuses. */
+float rwkvtts_wm_strength(double strength_db);
+/* The detection threshold T of the desc's NB and NP (host only; both parities of NB). */
+int rwkvtts_wm_threshold(const rwkvtts_wm_desc* desc, double* out);
+/* Streaming plan (host only, a pure function). With samples [0, n_known) of a signal known and blocks
+ * [0, block_first) done: *out_ready_end = B * floor(n_known / B) -- block j is exact once it is
+ * complete -- or n_known with final. *in_first_needed = block_first * B. Either pointer may be NULL. */
+int rwkvtts_wm_plan(const rwkvtts_wm_desc* desc, int64_t n_known, int final, int64_t block_first,
+                    int64_t* out_ready_end, int64_t* in_first_needed);
+typedef struct rwkvtts_wm rwkvtts_wm;
+/* table == NULL: the table of rwkvtts_wm_table; otherwise the caller's [L + B] table (copied). */
+int rwkvtts_wm_create(int device, const rwkvtts_wm_desc* desc, const float* table, rwkvtts_wm** out);
+int rwkvtts_wm_destroy(rwkvtts_wm* w);
+/* n signals (ragged), each with its own key, payload (bits at and above NB must be 0) and strength s
+ * (finite, 0 < s <= 1; strength == NULL: the desc's for every signal), in one launch. Host buffers; out[i] has capacity n_in[i]. n_in[i] == 0 writes
+ * nothing. Calls on one handle serialise on its lock. */
+int rwkvtts_wm_embed_batch(rwkvtts_wm* w, const float* const* in, const int64_t* n_in, const uint64_t* key,
+                           const uint32_t* payload, const float* strength, int n, float* const* out);
+typedef struct {
+  uint32_t struct_size;
+  const float* in;     /* points at sample in_first of the signal */
+  int64_t in_first;
+  int64_t n_in;
+  int32_t final;       /* 1: in_first + n_in is the signal's length */
+  float strength;
+  uint64_t key;
+  uint32_t payload;
+  float a_prev;        /* a of block block_first - 1, as the last call returned it (ignored for block_first 0) */
+  int64_t block_first; /* outputs [block_first * B, block_first * B + out_count) */
+  int64_t out_count;   /* whole blocks, or up to the signal's end with final */
+  float* out;          /* capacity out_count */
+  float a_last;        /* out: a of the last block written (a_prev if out_count is 0) */
+} rwkvtts_wm_window;
+/* n windows (of any signals, keys, payloads, strengths) in one launch: outputs [block_first * B,
+ * + out_count) of the whole-signal result, bitwise, whatever follows the known samples.
+ * RWKVTTS_EINVAL before anything is launched (and nothing written, a_last included) if a window asks
+ * for more than rwkvtts_wm_plan allows: block_first * B + out_count > out_ready_end(in_first + n_in,
+ * final), in_first > block_first * B, an out_count that ends inside a block before the signal's end,
+ * or an a_prev that is negative or not finite. */
+int rwkvtts_wm_embed_windows(rwkvtts_wm* w, rwkvtts_wm_window* win, int n);
+typedef struct {
+  uint32_t struct_size;
+  int32_t detected;  /* score >= T */
+  float score;       /* S(offset) */
+  int32_t offset;    /* tau*: the mark's phase at the clip's first sample */
+  uint32_t payload;  /* bit b set: z_b(offset) > 0 */
+  uint32_t seen;     /* bit b set: d_b(offset) > 0 */
+  float min_z;       /* min |z_b(offset)| over the seen slots; 0 if none */
+  float* dbg_r;      /* in: NULL, or capacity NB * NP: r_b(tau) at [b * NP + tau] (tests) */
+  float* dbg_d;      /* in: NULL, or capacity NB * NP: d_b(tau) likewise */
+} rwkvtts_wm_result;
+/* n clips (ragged, 16 kHz, each at most 2^30 samples), a key each, in one launch sequence (whiten,
+ * filter and fold, search, reduce). results: n structs whose stride is results[0].struct_size; dbg_r /
+ * dbg_d are read from each. An empty clip gives detected 0, score 0, seen 0. */
+int rwkvtts_wm_detect_batch(rwkvtts_wm* w, const float* const* in, const int64_t* n_in, const uint64_t* key, int n,
+                            rwkvtts_wm_result* results);
+/* HIP-event time of the last call's kernels (embed: one launch; detect: all four; no copies), in ms;
+ * 0 before the first. */
+int rwkvtts_wm_kernel_ms(rwkvtts_wm* w, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

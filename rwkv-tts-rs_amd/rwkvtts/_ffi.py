@@ -237,6 +237,26 @@ class PitchWindow(ctypes.Structure):
                 ("s_last", ctypes.c_int64)]
 
 
+class WmDesc(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("block", ctypes.c_int32), ("taps", ctypes.c_int32),
+                ("bits", ctypes.c_int32), ("bit_len", ctypes.c_int32), ("band_lo", ctypes.c_float),
+                ("band_hi", ctypes.c_float), ("strength_db", ctypes.c_float)]
+
+
+class WmWindow(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("in_", ctypes.c_void_p), ("in_first", ctypes.c_int64),
+                ("n_in", ctypes.c_int64), ("final", ctypes.c_int32), ("strength", ctypes.c_float),
+                ("key", ctypes.c_uint64), ("payload", ctypes.c_uint32), ("a_prev", ctypes.c_float),
+                ("block_first", ctypes.c_int64), ("out_count", ctypes.c_int64), ("out", ctypes.c_void_p),
+                ("a_last", ctypes.c_float)]
+
+
+class WmResult(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("detected", ctypes.c_int32), ("score", ctypes.c_float),
+                ("offset", ctypes.c_int32), ("payload", ctypes.c_uint32), ("seen", ctypes.c_uint32),
+                ("min_z", ctypes.c_float), ("dbg_r", ctypes.c_void_p), ("dbg_d", ctypes.c_void_p)]
+
+
 # Every symbol include/rwkvtts.h declares (checked by tests/test_abi.py against the header).
 EXPORTS = {
     "rwkvtts_synth_weights": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p]),
@@ -389,6 +409,21 @@ EXPORTS = {
     "rwkvtts_pitch_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PitchWindow), ctypes.c_int]),
     "rwkvtts_pitch_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
     "rwkvtts_pitch_walk_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    # watermark: table, strength, threshold and plan (host only), batched / exact stream embedding, the detector
+    "rwkvtts_wm_table": (ctypes.c_int, [ctypes.POINTER(WmDesc), ctypes.c_void_p]),
+    "rwkvtts_wm_strength": (ctypes.c_float, [ctypes.c_double]),
+    "rwkvtts_wm_threshold": (ctypes.c_int, [ctypes.POINTER(WmDesc), ctypes.POINTER(ctypes.c_double)]),
+    "rwkvtts_wm_plan": (ctypes.c_int, [ctypes.POINTER(WmDesc), ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                       ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "rwkvtts_wm_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(WmDesc), ctypes.c_void_p,
+                                         ctypes.POINTER(ctypes.c_void_p)]),
+    "rwkvtts_wm_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "rwkvtts_wm_embed_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "rwkvtts_wm_embed_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(WmWindow), ctypes.c_int]),
+    "rwkvtts_wm_detect_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_int, ctypes.POINTER(WmResult)]),
+    "rwkvtts_wm_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None

@@ -35,6 +35,11 @@ and the clip / silence helpers it uses), feeding the HIP mel kernel (features.py
   one-shot, batched with a target per signal, and exact over stream chunks. Its arithmetic contract
   (include/rwkvtts.h) is f32 add, subtract, multiply and correctly rounded divide and
   square root; pinned bitwise to its numpy restatement (tests/level_ref.py).
+* `Watermarker` (no reference counterpart: the reference marks nothing): a provenance watermark as HIP
+  kernels (csrc/wm.hip) -- a spread-spectrum mark under a key that carries a payload, embedded
+  one-shot, batched and exact over stream chunks (bitwise its numpy restatement, tests/wm_ref.py),
+  and a detector that searches every alignment of the mark's period (held to the float64
+  restatement within the error bound of its f32 sums). Contract: include/rwkvtts.h, DESIGN.md §30.
 """
 import ctypes
 import struct
@@ -845,6 +850,202 @@ class PitchStream(_ExactStream):
 
     def _first_needed(self, n_known):
         return self.p.plan(n_known, False, self._out_next, *self._state)[1]
+
+
+# ---- provenance watermark on the GPU ---------------------------------------------------------
+def _wm_table(taps: int, block: int, band_lo: float, band_hi: float, fs: float = 16000.0) -> np.ndarray:
+    """h[0, taps) -- a Blackman-windowed band-pass, the difference of two windowed sincs, at unit
+    energy -- then r[i] = (float)((i + 1) / block), in double: the table both sides read."""
+    import math
+    k = np.arange(taps, dtype=np.float64)
+    t = k - float((taps - 1) // 2)
+    w = (0.42 - 0.5 * np.cos(2.0 * np.pi * k / float(taps - 1))) + 0.08 * np.cos(4.0 * np.pi * k / float(taps - 1))
+    fh, fl = 2.0 * float(band_hi) / fs, 2.0 * float(band_lo) / fs
+    g = w * (fh * np.sinc(fh * t) - fl * np.sinc(fl * t))
+    h = g / math.sqrt(float(np.sum(g * g)))
+    r = np.arange(1, block + 1, dtype=np.float64) / float(block)
+    return np.concatenate([h, r]).astype(F32)
+
+
+def wm_strength(strength_db: float) -> np.float32:
+    """s, the f32 amplitude of a strength in dB: 10^(strength_db / 20), taken in double
+    (rwkvtts_wm_strength, host only); ValueError outside -60 .. -6."""
+    s = F32(_ffi.lib().rwkvtts_wm_strength(float(strength_db)))
+    if not np.isfinite(s):
+        raise ValueError("a watermark strength must be in [-60, -6] dB")
+    return s
+
+
+class Watermarker(_NativeStage):
+    """A provenance watermark as HIP kernels (csrc/wm.hip; the contract is in include/rwkvtts.h,
+    DESIGN.md §30): a time-domain spread-spectrum mark on 16 kHz PCM. A +-1 chip sequence hashed from
+    a 64-bit key, repeating every bits * bit_len samples and multiplied by the payload's bit of the
+    moment, is shaped by a `taps`-long band-pass (band_lo .. band_hi Hz) and added at `strength_db`
+    relative to the signal's own level, block by block, with a linear ramp over each block. n_out = n,
+    silence stays silence, one causal definition, so a stream's pieces are bitwise the one-shot
+    result (a lag of one block). The pipeline applies it last at 16 kHz: after the leveller, before
+    the resampler. The detector whitens, matched-filters and folds a clip of any origin onto the
+    period and tries every alignment; each bit's correlation is divided by the root of its own exact
+    variance under random chips, so the score is chi-square with `bits` degrees of freedom where there
+    is no mark under the key -- whatever the host, another key's mark included -- and `threshold` is
+    set on that law (one false alarm in 10^6 clips).
+
+    0 means the default as in the C desc: block 320 (one vocoder frame), taps 129, bits 16, bit_len
+    1600 (100 ms; period 1.6 s), band 1000 .. 3400 Hz, strength -26 dB. Every default is untuned and
+    nobody has listened to the output. The kernels read the table `_wm_table` builds.
+
+    evaluator: a callable (marker, items) -> [(ndarray, a_last)] standing in for the native window
+    call, items being [(samples from in_first on, in_first, final, s, key, payload, a_prev, block_first,
+    out_count)]; detector: a callable (marker, [clip], [key]) -> [dict] standing in for the native
+    detect call. No GPU object is created with an evaluator (the host-only entry points are still the
+    library's)."""
+    _NAME = "wm"
+
+    def __init__(self, device: int = 0, block: int = 320, taps: int = 129, bits: int = 16, bit_len: int = 1600,
+                 band_lo: float = 1000.0, band_hi: float = 3400.0, strength_db: float = -26.0, evaluator=None,
+                 detector=None):
+        self.device = int(device)
+        self._desc = _ffi.WmDesc(struct_size=ctypes.sizeof(_ffi.WmDesc), block=int(block), taps=int(taps), bits=int(bits),
+                                 bit_len=int(bit_len), band_lo=float(band_lo), band_hi=float(band_hi),
+                                 strength_db=float(strength_db))
+        super().__init__(evaluator)
+        self._detector = detector
+        self.plan(0, False)  # (refuses a bad description before anything is built)
+        self.block, self.taps, self.bits = int(block) or 320, int(taps) or 129, int(bits) or 16
+        self.bit_len = int(bit_len) or 1600
+        self.period = self.bits * self.bit_len
+        self.band_lo, self.band_hi = float(F32(band_lo)) or 1000.0, float(F32(band_hi)) or 3400.0
+        self.strength_db = float(F32(strength_db)) or -26.0
+        t = ctypes.c_double()
+        _native("wm_threshold", ctypes.byref(self._desc), ctypes.byref(t))
+        self.threshold = t.value
+        self.table = _wm_table(self.taps, self.block, self.band_lo, self.band_hi)
+        self._create(self.table)
+
+    # ---- host-only plan ----
+    def plan(self, n_known: int, final: bool, block_first: int = 0):
+        """(out_ready_end, in_first_needed) of rwkvtts_wm_plan."""
+        end, first = ctypes.c_int64(), ctypes.c_int64()
+        _native("wm_plan", ctypes.byref(self._desc), int(n_known), 1 if final else 0, int(block_first),
+                ctypes.byref(end), ctypes.byref(first))
+        return end.value, first.value
+
+    def _s(self, strength_db):
+        return wm_strength(self.strength_db if strength_db is None else strength_db)
+
+    def _payload(self, payload):
+        if isinstance(payload, bool) or not isinstance(payload, (int, np.integer)) or not 0 <= int(payload) < 1 << self.bits:
+            raise ValueError(f"a watermark payload must be an integer in [0, 2^{self.bits})")
+        return int(payload)
+
+    @staticmethod
+    def _key(key):
+        if isinstance(key, bool) or not isinstance(key, (int, np.integer)) or not 0 <= int(key) < 1 << 64:
+            raise ValueError("a watermark key must be an integer in [0, 2^64)")
+        return int(key)
+
+    # ---- the embed kernel ----
+    def embed_windows(self, items) -> list:
+        """[(samples from in_first on, in_first, final, s, key, payload, a_prev, block_first, out_count)]
+        -> [(outputs [block_first * block, + out_count) of the whole-signal result, a_last)], all windows
+        in one launch; s is the f32 strength (wm_strength). Raises RwkvTtsError(EINVAL), with nothing
+        computed, if a window asks for more than plan() allows."""
+        items = [(np.ascontiguousarray(x, dtype=F32).reshape(-1), int(a), bool(f), float(F32(s)), self._key(k),
+                  self._payload(p), float(F32(ap)), int(b), int(c)) for x, a, f, s, k, p, ap, b, c in items]
+        if self._evaluator is not None:
+            return [(np.ascontiguousarray(y, dtype=F32), F32(a)) for y, a in self._evaluator(self, items)]
+        ws, outs = self._windows("wm_embed_windows", _ffi.WmWindow, items, strength=3, key=4, payload=5, a_prev=6,
+                                 block_first=7)
+        return [(o, F32(w.a_last)) for o, w in zip(outs, ws)]
+
+    def embed_batch(self, signals, keys, payloads, strengths_db=None) -> list:
+        """[signal], [key], [payload] (, [strength in dB]) -> [marked signal], ragged, in one launch; an
+        empty signal gives an empty one."""
+        xs = [np.ascontiguousarray(x, dtype=F32).reshape(-1) for x in signals]
+        ks, ps = [self._key(k) for k in keys], [self._payload(p) for p in payloads]
+        ss = [self._s(None)] * len(xs) if strengths_db is None else [self._s(v) for v in strengths_db]
+        if not len(xs) == len(ks) == len(ps) == len(ss):
+            raise ValueError("embed_batch: one key, one payload and one strength per signal")
+        if self._evaluator is not None:
+            return [y for y, _ in self.embed_windows([(x, 0, True, s, k, p, 0.0, 0, x.size)
+                                                      for x, s, k, p in zip(xs, ss, ks, ps)])]
+        if not xs:
+            return []
+        outs, ins, lens, ous = self._ragged(xs, [x.size for x in xs])
+        self._call("wm_embed_batch", ins, lens, (ctypes.c_uint64 * len(ks))(*ks), (ctypes.c_uint32 * len(ps))(*ps),
+                   (ctypes.c_float * len(ss))(*[float(s) for s in ss]), len(xs), ous)
+        return outs
+
+    def embed(self, x, key: int, payload: int, strength_db=None) -> np.ndarray:
+        return self.embed_batch([x], [key], [payload], None if strength_db is None else [strength_db])[0]
+
+    def stream(self, key: int, payload: int, strength_db=None) -> "WatermarkStream":
+        return WatermarkStream(self, key, payload, strength_db)
+
+    # ---- the detector ----
+    def detect_batch(self, signals, keys, debug: bool = False) -> list:
+        """[clip at 16 kHz], [key] -> [{detected, score, threshold, payload, seen, offset, min_z}], ragged,
+        in one launch sequence. debug adds r and d, float32 [bits, period]: r_b(tau) and d_b(tau)."""
+        xs = [np.ascontiguousarray(x, dtype=F32).reshape(-1) for x in signals]
+        ks = [self._key(k) for k in keys]
+        if len(xs) != len(ks):
+            raise ValueError("detect_batch: one key per clip")
+        if self._detector is not None:
+            return [dict(d) for d in self._detector(self, xs, ks)]
+        if self._evaluator is not None:
+            raise RuntimeError("this Watermarker stands on an evaluator without a detector")
+        if not xs:
+            return []
+        res = (_ffi.WmResult * len(xs))()
+        dbg = []
+        for r in res:
+            r.struct_size = ctypes.sizeof(_ffi.WmResult)
+            if debug:
+                dbg.append((np.zeros((self.bits, self.period), dtype=F32), np.zeros((self.bits, self.period), dtype=F32)))
+                r.dbg_r, r.dbg_d = dbg[-1][0].ctypes.data, dbg[-1][1].ctypes.data
+        P = ctypes.c_void_p * len(xs)
+        self._call("wm_detect_batch", P(*[x.ctypes.data for x in xs]), (ctypes.c_int64 * len(xs))(*[x.size for x in xs]),
+                   (ctypes.c_uint64 * len(ks))(*ks), len(xs), res)
+        out = []
+        for i, r in enumerate(res):
+            d = dict(detected=bool(r.detected), score=float(r.score), threshold=self.threshold, payload=int(r.payload),
+                     seen=int(r.seen), offset=int(r.offset), min_z=float(r.min_z))
+            if debug:
+                d["r"], d["d"] = dbg[i]
+            out.append(d)
+        return out
+
+    def detect(self, x, key: int, debug: bool = False) -> dict:
+        return self.detect_batch([x], [key], debug)[0]
+
+
+class WatermarkStream(_ExactStream):
+    """Watermarker.stream(key, payload): feed(pcm_chunk, final=False) -> the blocks that became exact
+    with it. The concatenation of what feed returns is bitwise Watermarker.embed(the concatenated
+    input, key, payload), however the input was cut. A block goes out once it is complete, so the
+    output lags the input by less than one block (20 ms at the default); the kept tail is shorter than
+    a block, and the carried state is one float, the last block's amplitude."""
+
+    def __init__(self, marker: Watermarker, key: int, payload: int, strength_db=None):
+        super().__init__()
+        self.m = marker
+        self.key, self.payload, self.s = marker._key(key), marker._payload(payload), marker._s(strength_db)
+        self._block_next = 0      # blocks [0, _block_next) went out
+        self._a = F32(0.0)        # a of block _block_next - 1
+
+    def _emit(self, n_known, final):
+        B = self.m.block
+        end, _ = self.m.plan(n_known, final, self._block_next)
+        count = end - self._block_next * B
+        if count <= 0:
+            return np.zeros(0, dtype=F32)
+        out, self._a = self.m.embed_windows([(self._tail, self._tail_first, final, self.s, self.key, self.payload,
+                                              self._a, self._block_next, count)])[0]
+        self._block_next += -(-count // B)
+        return out
+
+    def _first_needed(self, n_known):
+        return self.m.plan(n_known, False, self._block_next)[1]
 
 
 # ---- normalisation / trimming ------------------------------------------------------------

@@ -23,6 +23,12 @@ All five also take `pitch_shift` (no reference counterpart: the reference's only
 in semitones, -12 .. 12, moves the fundamental of the 16 kHz PCM on the GPU and keeps its spectral
 envelope and its length (audio.PitchShifter), first of the stages -- before the
 stretch, and in long-form after the join -- exact over stream chunks.
+All five also take `watermark` (no reference counterpart: the reference marks nothing): None leaves the
+PCM unmarked; a payload, an integer 0 .. 65535, embeds it as a spread-spectrum mark under the
+pipeline's `watermark_key` (audio.Watermarker) on the 16 kHz PCM, after the
+leveller and before the resampler -- in long-form on the joined signal, one continuous sequence --
+exact over stream chunks. The key belongs to the pipeline, not to a request; without one, `watermark`
+raises ValueError before anything is generated. detect_watermark reads a clip back.
 LightweightTtsPipelineArgs.global_sampling / semantic_sampling (no reference counterpart: the
 reference carries temperature / top_p / top_k and samples with fixed values) set the token
 generator's temperature, top-p and top-k per phase (runtime.PhaseSampling); a value outside its
@@ -139,11 +145,12 @@ class LongSpeech(np.ndarray):
         return c
 
 
-def audio_stages(stretcher, tempo, resampler, leveller=None, loudness=None, shifter=None, pitch_shift=None) -> list:
+def audio_stages(stretcher, tempo, resampler, leveller=None, loudness=None, shifter=None, pitch_shift=None,
+                 marker=None, watermark=None, watermark_key=None) -> list:
     """The stages behind the vocoder in the order they apply -- the pitch shift at 16 kHz, then the
-    stretch, then the leveller, then the resampler; None is no stage -- each as (batch, stream):
-    batch([pcm]) -> [pcm] in one native call (one shift, one tempo, one loudness for the call),
-    stream() -> an object whose feed(pcm, final) is exact over chunks."""
+    stretch, then the leveller, then the watermark, then the resampler; None is no stage -- each as
+    (batch, stream): batch([pcm]) -> [pcm] in one native call (one shift, one tempo, one loudness, one
+    key and payload for the call), stream() -> an object whose feed(pcm, final) is exact over chunks."""
     stages = []
     if shifter is not None:
         stages.append((lambda pcm: shifter.shift_batch(pcm, [pitch_shift] * len(pcm)), lambda: shifter.stream(pitch_shift)))
@@ -151,6 +158,9 @@ def audio_stages(stretcher, tempo, resampler, leveller=None, loudness=None, shif
         stages.append((lambda pcm: stretcher.stretch_batch(pcm, [tempo] * len(pcm)), lambda: stretcher.stream(tempo)))
     if leveller is not None:
         stages.append((lambda pcm: leveller.level_batch(pcm, [loudness] * len(pcm)), lambda: leveller.stream(loudness)))
+    if marker is not None:
+        stages.append((lambda pcm: marker.embed_batch(pcm, [watermark_key] * len(pcm), [watermark] * len(pcm)),
+                       lambda: marker.stream(watermark_key, watermark)))
     if resampler is not None:
         stages.append((resampler.resample_batch, resampler.stream))
     return stages
@@ -166,7 +176,8 @@ def feed_stages(streams, pcm, final: bool):
 class LightweightTtsPipeline:
     """manager: rwkvtts.DynamicBatchManager (with a tokenizer); codec: BiCodecDetokenizer."""
 
-    def __init__(self, manager, codec, raf_dir: str = "./raf", reference_tokenizer=None):
+    def __init__(self, manager, codec, raf_dir: str = "./raf", reference_tokenizer=None,
+                 watermark_key: Optional[int] = None):
         self.manager = manager
         self.codec = codec
         self.raf_dir = raf_dir
@@ -179,7 +190,14 @@ class LightweightTtsPipeline:
         self._joiners = {}  # (trim, keep, fade) -> audio.Joiner (created on first use, kept)
         self._levellers = {}  # horizon -> audio.Leveller (created on the first loudness, kept)
         self._shifter = None  # audio.PitchShifter (created on the first pitch_shift other than 0, kept)
-        self._stage_cache_lock = threading.Lock()  # guards all five (the server's worker threads share the pipeline)
+        # no reference counterpart: the 64-bit key of this deployment's provenance mark (None: the
+        # pipeline marks nothing and `watermark` is refused); it is the pipeline's, never a request's
+        if watermark_key is not None and (isinstance(watermark_key, bool) or not isinstance(watermark_key, int)
+                                          or not 0 <= watermark_key < 1 << 64):
+            raise ValueError("watermark_key must be an integer in [0, 2^64)")
+        self.watermark_key = watermark_key
+        self._marker = None  # audio.Watermarker (created on the first watermark or detect_watermark, kept)
+        self._stage_cache_lock = threading.Lock()  # guards all six (the server's worker threads share the pipeline)
 
     # ---- output rates other than 16 kHz (no reference counterpart: the reference emits 16 kHz only)
     def resampler(self, sample_rate: Optional[int]):
@@ -260,13 +278,41 @@ class LightweightTtsPipeline:
                 self._shifter = PitchShifter(device=getattr(self.codec, "device", 0))
         return self._shifter
 
+    # ---- provenance (no reference counterpart: the reference marks nothing)
+    def marker(self, watermark: Optional[int] = 0):
+        """None for None (nothing is created: the PCM is unmarked); otherwise the pipeline's one
+        Watermarker (the untuned defaults of audio.Watermarker), on the codec's GPU. The payload is
+        per call, the key is the pipeline's. A payload that is not an integer in 0 .. 65535, or any
+        payload on a pipeline without a watermark_key, raises ValueError before anything is generated."""
+        if watermark is None:
+            return None
+        if isinstance(watermark, bool) or not isinstance(watermark, (int, np.integer)) or not 0 <= int(watermark) <= 65535:
+            raise ValueError("watermark must be an integer payload in [0, 65535]")
+        if self.watermark_key is None:
+            raise ValueError("watermark needs a pipeline with a watermark_key")
+        with self._stage_cache_lock:
+            if self._marker is None:
+                from .audio import Watermarker
+                self._marker = Watermarker(device=getattr(self.codec, "device", 0))
+        return self._marker
+
+    def detect_watermark(self, pcm) -> dict:
+        """16 kHz PCM of any origin -> audio.Watermarker.detect under the pipeline's key: {detected,
+        score, threshold, payload, seen, offset, min_z}. ValueError without a watermark_key. detected
+        is score >= threshold, set for one false alarm in 10^6 clips that carry no mark under this key
+        (another key's mark included); payload and offset mean something only where it is true, and a
+        payload bit is as sure as min_z is large (under 1: a guess). DESIGN.md section 30."""
+        return self.marker(0).detect(pcm, self.watermark_key)
+
     def _stages(self, sample_rate: Optional[int], tempo: Optional[float], loudness: Optional[float] = None,
-                pitch_shift: Optional[float] = None):  # -> (stages, output rate)
+                pitch_shift: Optional[float] = None, watermark: Optional[int] = None):  # -> (stages, output rate)
         rs = self.resampler(sample_rate)
         lv = self.leveller(loudness)
         sh = self.shifter(pitch_shift)
+        mk = self.marker(watermark)
         return (audio_stages(self.stretcher(tempo), tempo, rs, lv, None if lv is None else float(loudness),
-                             sh, None if sh is None else float(pitch_shift)),
+                             sh, None if sh is None else float(pitch_shift),
+                             mk, None if mk is None else int(watermark), self.watermark_key),
                 rs.sr_out if rs else SAMPLE_RATE)
 
     # ---- text / attribute handling (:148-193)
@@ -329,7 +375,7 @@ class LightweightTtsPipeline:
 
     def generate_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
                         tempo: Optional[float] = None, loudness: Optional[float] = None,
-                        pitch_shift: Optional[float] = None) -> np.ndarray:
+                        watermark: Optional[int] = None, pitch_shift: Optional[float] = None) -> np.ndarray:
         """sample_rate None / 16000: the vocoder's 16 kHz PCM. Any other rate: that PCM resampled on
         the GPU (resampler()); the failed-request second of silence is sample_rate zeros.
         tempo None / 1.0: nothing. Any other: the 16 kHz PCM time-stretched on the GPU (stretcher())
@@ -340,9 +386,12 @@ class LightweightTtsPipeline:
         pitch_shift None / 0: nothing. A shift in semitones, -12 .. 12: the 16 kHz PCM's fundamental
         moved on the GPU (shifter()) before the stretch, its envelope and length kept; independent of
         args.pitch, which stays the property token.
+        watermark None: nothing. A payload 0 .. 65535: the 16 kHz PCM marked on the GPU (marker())
+        under the pipeline's key, after the leveller and before the resampler; the failed-request
+        second of silence is not marked (silence carries no mark).
         args.global_sampling / semantic_sampling outside their ranges raise ValueError, like tempo."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark)
         try:
             req = self._request(args)
         except ValueError:  # untokenisable text: the request fails -> empty result
@@ -357,7 +406,8 @@ class LightweightTtsPipeline:
 
     def stream_speech(self, args: LightweightTtsPipelineArgs, chunk_frames: int = 16,
                       sample_rate: Optional[int] = None, tempo: Optional[float] = None,
-                      loudness: Optional[float] = None, pitch_shift: Optional[float] = None):
+                      loudness: Optional[float] = None, watermark: Optional[int] = None,
+                      pitch_shift: Optional[float] = None):
         """generate_speech as a generator of float32 PCM chunks (SpeechChunk: an ndarray that also
         carries t0, t1, n_known, done), each decoded while the request is still generating tokens.
 
@@ -387,7 +437,11 @@ class LightweightTtsPipeline:
 
         pitch_shift (semitones, -12 .. 12, not 0): PitchShifter.stream(pitch_shift) comes first, and
         the concatenation is bitwise generate_speech(args, pitch_shift=...). A shifted item lags its
-        frames by the shifter's look-ahead, 0.1 s at the defaults."""
+        frames by the shifter's look-ahead, 0.1 s at the defaults.
+
+        watermark (a payload 0 .. 65535): Watermarker.stream(key, payload) sits after the leveller, and
+        the concatenation is bitwise generate_speech(args, watermark=...). A marked item lags its
+        frames by less than one block, 20 ms."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         check_sampling(args)
@@ -396,22 +450,26 @@ class LightweightTtsPipeline:
         except ValueError:  # untokenisable text: the request fails -> one second of silence
             req = None
         self.leveller(loudness)  # (refuses a bad loudness here, not at the first next())
-        if pitch_shift is None:
-            return self.stream_request(req, chunk_frames, sample_rate=sample_rate, tempo=tempo, loudness=loudness)
-        self.shifter(pitch_shift)  # (the same for a bad shift)
-        return self.stream_request(req, chunk_frames, sample_rate=sample_rate, tempo=tempo, loudness=loudness,
-                                   pitch_shift=pitch_shift)
+        kw = {}
+        if pitch_shift is not None:
+            self.shifter(pitch_shift)  # (the same for a bad shift)
+            kw["pitch_shift"] = pitch_shift
+        if watermark is not None:
+            self.marker(watermark)  # (and for a bad payload or a missing key)
+            kw["watermark"] = watermark
+        return self.stream_request(req, chunk_frames, sample_rate=sample_rate, tempo=tempo, loudness=loudness, **kw)
 
     def stream_request(self, req: Optional[TtsBatchRequest], chunk_frames: int = 16,
                        sample_rate: Optional[int] = None, tempo: Optional[float] = None,
-                       loudness: Optional[float] = None, pitch_shift: Optional[float] = None):
+                       loudness: Optional[float] = None, watermark: Optional[int] = None,
+                       pitch_shift: Optional[float] = None):
         """stream_speech for a request that is already built (None: a request that failed before it
         was submitted)."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         if req is not None:
             check_sampling(req.args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark)
         streams = [stream() for _, stream in stages]
         H = self.codec.halo()
         g, sem, t0, yielded, status = None, [], 0, False, 0
@@ -446,17 +504,18 @@ class LightweightTtsPipeline:
 
     def generate_speech_batch(self, batch_args: Sequence[LightweightTtsPipelineArgs],
                               sample_rate: Optional[int] = None, tempo: Optional[float] = None,
-                              loudness: Optional[float] = None,
+                              loudness: Optional[float] = None, watermark: Optional[int] = None,
                               pitch_shift: Optional[float] = None) -> List[np.ndarray]:
         """sample_rate other than None / 16000: the whole batch is resampled in one resample_batch
         call (a failed item stays an empty array). tempo other than None / 1.0: the whole batch is
         first stretched in one stretch_batch call, one tempo for the call. loudness other than None:
         the whole batch is levelled in one level_batch call between the two, one target for the call.
         pitch_shift other than None / 0: the whole batch is shifted in one shift_batch call before
-        all of them, one shift for the call."""
+        all of them, one shift for the call. watermark other than None: the whole batch is marked in
+        one embed_batch call after the leveller, one payload for the call."""
         for a in batch_args:
             check_sampling(a)
-        stages, _ = self._stages(sample_rate, tempo, loudness, pitch_shift)
+        stages, _ = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark)
         reqs, idx = [], []
         for i, a in enumerate(batch_args):
             try:
@@ -531,7 +590,7 @@ class LightweightTtsPipeline:
     def generate_long_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
                              tempo: Optional[float] = None, segment_tokens: int = 64, pauses=None,
                              trim: bool = True, keep: int = 800, fade: int = 80,
-                             loudness: Optional[float] = None,
+                             loudness: Optional[float] = None, watermark: Optional[int] = None,
                              pitch_shift: Optional[float] = None) -> "LongSpeech":
         """generate_speech for a text of any length: the text is cut into segments of at most
         segment_tokens text tokens (segment.split_text), the segments decode side by side in the
@@ -546,9 +605,10 @@ class LightweightTtsPipeline:
         keep and fade are unmeasured defaults. loudness levels the joined
         signal as one (generate_speech), so the segments, decoded as independent requests, come out
         at one level; the second of silence is not levelled. pitch_shift shifts the joined signal as
-        one, after the join and before the stretch."""
+        one, after the join and before the stretch. watermark marks the joined signal as one, so a
+        job carries one continuous sequence across its segments and pauses."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)
         if plan is None:
@@ -570,7 +630,7 @@ class LightweightTtsPipeline:
     def stream_long_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
                            tempo: Optional[float] = None, segment_tokens: int = 64, pauses=None,
                            trim: bool = True, keep: int = 800, fade: int = 80, loudness: Optional[float] = None,
-                           pitch_shift: Optional[float] = None):
+                           watermark: Optional[int] = None, pitch_shift: Optional[float] = None):
         """generate_long_speech as a generator of LongSpeech items, one per segment, in order: segment
         i is emitted once it and every segment before it are done -- decoded, joined alone with its
         gap (a piece depends on its own segment only), and fed through the stages' exact streams,
@@ -581,9 +641,9 @@ class LightweightTtsPipeline:
         first good one are held back until it arrives, so a text whose every segment fails yields
         the one second of silence alone. Streaming inside a segment is out of scope. With loudness
         an item also waits for the leveller's look-ahead (up to 0.5 s of the next segment), with
-        pitch_shift for the shifter's (0.1 s)."""
+        pitch_shift for the shifter's (0.1 s), with watermark for the rest of its last block (20 ms)."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)
         if plan is None:

@@ -56,6 +56,15 @@
   of the finished 16 kHz PCM's fundamental on the GPU that keeps the spectral envelope and the
   length (audio.PitchShifter), before the stretch, and works for every voice. Without the field (or
   with 0) the routes are unchanged.
+* `watermark` in the body of both TTS routes (no reference counterpart: the reference marks nothing):
+  a JSON integer in [WATERMARK_MIN, WATERMARK_MAX] = [0, 65535], anything else a 400, and a 400 too on
+  a server whose pipeline has no `watermark_key`. The payload is embedded in the 16 kHz PCM under the
+  pipeline's key as a spread-spectrum mark (audio.Watermarker), after the leveller and before the
+  resampler. Without the field the routes are unchanged.
+* `handle_watermark_detect(path, pipeline)`, POST /api/watermark/detect (no reference counterpart): an
+  uploaded WAV at any supported rate, brought to 16 kHz by `load_audio(..., device=)` without volume
+  normalisation, read back under the pipeline's key -> {detected, score, threshold, payload,
+  seen_bits, offset, seconds}.
 * `handle_tts_stream(body, pipeline, voice_dir)` (no reference counterpart): the same request as a
   WAV stream, POST /api/tts/stream -- audio while the request is still decoding, at a fixed scale
   (no peak normalisation: that needs the whole utterance).
@@ -122,6 +131,9 @@ LOUDNESS_MIN, LOUDNESS_MAX = -40.0, -10.0
 # `pitch_shift` of the same bodies (no reference counterpart): semitones, an octave either way -- the
 # kernel's own range
 PITCH_SHIFT_MIN, PITCH_SHIFT_MAX = -12.0, 12.0
+# `watermark` of the same bodies (no reference counterpart): the payload of the provenance mark, 16
+# bits at the marker's defaults -- a tenant or deployment number, not a secret (the key is the secret)
+WATERMARK_MIN, WATERMARK_MAX = 0, 65535
 
 
 def map_speed(speed) -> str:
@@ -213,6 +225,11 @@ def _tts_args(body, voice_dir: str):
           or not PITCH_SHIFT_MIN <= shift <= PITCH_SHIFT_MAX):  # (NaN fails the comparison)
         return (400, {"success": False, "error": f"不支持的音高偏移: {shift} (支持: "
                                                  f"{PITCH_SHIFT_MIN} - {PITCH_SHIFT_MAX} 半音)"}), None, None
+    mark = body.get("watermark")
+    if mark is not None and (isinstance(mark, bool) or not isinstance(mark, int)
+                             or not WATERMARK_MIN <= mark <= WATERMARK_MAX):
+        return (400, {"success": False, "error": f"不支持的水印载荷: {mark} (支持: "
+                                                 f"{WATERMARK_MIN} - {WATERMARK_MAX} 的整数)"}), None, None
     sampling = {}
     for what in ("global_sampling", "semantic_sampling"):
         o = body.get(what)
@@ -276,12 +293,22 @@ def _tts_args(body, voice_dir: str):
         kw["loudness"] = float(loudness)
     if float(shift) != 0.0:
         kw["pitch_shift"] = float(shift)
+    if mark is not None:
+        kw["watermark"] = int(mark)
     return None, args, kw
+
+
+def _no_key(kw, pipeline):
+    """The 400 of a `watermark` sent to a server whose pipeline has no key, else None."""
+    if "watermark" in kw and getattr(pipeline, "watermark_key", None) is None:
+        return 400, {"success": False, "error": "服务器未配置水印密钥 (watermark_key)，无法使用 watermark"}
+    return None
 
 
 def handle_tts_json(body, pipeline, voice_dir: str = "assets/raf") -> Tuple[int, dict]:
     t0 = time.perf_counter()
     err, args, kw = _tts_args(body, voice_dir)
+    err = err or _no_key(kw, pipeline)
     if err:
         return err
     rate = kw.get("sample_rate", 16000)
@@ -337,6 +364,7 @@ def handle_tts_stream(body, pipeline, voice_dir: str = "assets/raf", chunk_frame
     A refused body gives /api/tts's status and JSON body (as one bytes item); so does a failure
     before the first chunk (500). A failure after the first chunk can only end the stream."""
     err, args, kw = _tts_args(body, voice_dir)
+    err = err or _no_key(kw, pipeline)
     if err:
         return err[0], iter([json.dumps(err[1], ensure_ascii=False).encode("utf-8")])
     rate = kw.get("sample_rate", 16000)
@@ -360,6 +388,36 @@ def handle_tts_stream(body, pipeline, voice_dir: str = "assets/raf", chunk_frame
             if len(c):
                 yield samples_to_pcm16(c)
     return 200, gen()
+
+
+def handle_watermark_detect(audio_path: Optional[str], pipeline) -> Tuple[int, dict]:
+    """POST /api/watermark/detect: an uploaded WAV saved to a temporary path (None: no file) ->
+    (HTTP status, JSON). The clip is brought to 16 kHz mono by load_audio without volume
+    normalisation (on the codec's GPU when it has to be resampled; its silent edges are trimmed, which
+    moves `offset` only), then read under the pipeline's key (pipeline.detect_watermark). 200:
+    {success, detected, score, threshold, payload, seen_bits, offset, seconds} -- payload and offset
+    mean something only where detected is true; seen_bits is the mask of payload bits the clip
+    covers (a clip shorter than the mark's period misses some). The threshold is set for one false
+    alarm in 10^6 clips without this key's mark; on noise-like audio a few seconds long the score can
+    pass it while single payload bits are still unsure. A server without a key, a missing or
+    unreadable file: 400 with {success: false, error}."""
+    if getattr(pipeline, "watermark_key", None) is None:
+        return 400, {"success": False, "error": "服务器未配置水印密钥 (watermark_key)，无法检测水印"}
+    if not audio_path:
+        return 400, {"success": False, "error": "未找到音频文件"}
+    try:
+        from .audio import load_audio
+        pcm = load_audio(audio_path, 16000, volume_normalize=False,
+                         device=getattr(getattr(pipeline, "codec", None), "device", None))
+    except Exception as e:  # noqa: BLE001 -- every way a file can be unreadable is the caller's error
+        return 400, {"success": False, "error": f"音频文件读取失败: {e}"}
+    try:
+        d = pipeline.detect_watermark(pcm)
+    except Exception as e:  # noqa: BLE001 -- rendered as the reference's 500 body
+        return 500, {"success": False, "error": f"水印检测失败: {e}"}
+    return 200, {"success": True, "detected": bool(d["detected"]), "score": float(d["score"]),
+                 "threshold": float(d["threshold"]), "payload": int(d["payload"]), "seen_bits": int(d["seen"]),
+                 "offset": int(d["offset"]), "seconds": len(pcm) / 16000.0}
 
 
 def handle_voice_list(voice_dir: str = "assets/raf") -> Tuple[int, dict]:
@@ -445,6 +503,38 @@ def create_app(pipeline, voice_dir: str = "assets/raf"):
         if code != 200:
             return Response(b"".join(it), status_code=code, media_type="application/json")
         return StreamingResponse(it, media_type="audio/wav")  # (a sync iterator: iterated in a worker thread)
+
+    @app.post("/api/watermark/detect")
+    async def api_watermark_detect(request: Request):
+        import anyio
+        import tempfile
+        data = None
+        limit = 100 * 1024 * 1024  # load_audio's own bound, checked before the upload is read or written
+        try:
+            declared = int(request.headers.get("content-length", "0"))
+        except ValueError:
+            declared = 0
+        if declared > limit:
+            return JSONResponse({"success": False, "error": "音频文件超过 100 MB"}, status_code=413)
+        if request.headers.get("content-type", "").startswith("multipart/"):
+            up = (await request.form()).get("audio_file")
+            if up is not None and not isinstance(up, str):
+                data = await up.read()
+        else:
+            data = await request.body()  # (the WAV itself as the body)
+        if data and len(data) > limit:  # (a body without a declared length)
+            return JSONResponse({"success": False, "error": "音频文件超过 100 MB"}, status_code=413)
+        path = None
+        if data:
+            fd, path = tempfile.mkstemp(suffix=".wav")
+            with os.fdopen(fd, "wb") as f:
+                f.write(data)
+        try:
+            code, payload = await anyio.to_thread.run_sync(handle_watermark_detect, path, pipeline)
+        finally:
+            if path and os.path.exists(path):
+                os.remove(path)
+        return JSONResponse(payload, status_code=code)
 
     @app.get("/api/voice-clone/list")
     async def api_voice_list():
