@@ -1163,6 +1163,86 @@ int rwkvtts_wm_detect_batch(rwkvtts_wm* w, const float* const* in, const int64_t
  * 0 before the first. */
 int rwkvtts_wm_kernel_ms(rwkvtts_wm* w, double* ms);
 
+/* ---- flac: lossless compressed output on the GPU, the `format: "flac"` of the TTS routes -- f32 PCM
+ * in, the frames of a FLAC stream out (no reference counterpart: the reference sends WAV only) ------
+ * Standard FLAC (RFC 9639) in the streamable subset: mono, 16 bits, a fixed block size B of 256, 512,
+ * 1024, 2048 or 4096 (the header codes for 256 * 2^n); a signal's last block may hold 1 .. B - 1
+ * samples, its size then an explicit 8-bit (up to 256 samples) or 16-bit value; the seven output
+ * rates have direct header codes. A frame depends on its own samples, its frame number, the rate and
+ * B, nothing else, so a stream's pieces are byte for byte the one-shot frames. Every output bit is
+ * defined (the numpy restatement is tests/flac_ref.py):
+ *   quantise  q = trunc(clamp(x * scale, -1, 1) * 32767): f32, each operation rounded on its own --
+ *             samples_to_pcm16 of the server after convert_samples_to_wav's scale. A non-finite
+ *             sample gives an unspecified q in range.
+ *   subframe  candidates in this order: CONSTANT when all samples are equal (then nothing else is
+ *             tried); FIXED orders 0 .. 4; LPC orders 1 .. 12 (unless the window turns LPC off);
+ *             VERBATIM. An order that is not below the block's length n is not tried. The candidate
+ *             of the fewest bits wins, the earlier on a tie; VERBATIM wins unless another is smaller
+ *             than its 8 + 16 n bits. Wasted bits are always 0.
+ *   window    Q15 Welch, integer: w[i] = 32768 - floor(32768 d^2 / D^2), d = 2 i - n + 1, D = n + 1
+ *             (the table holds it for n = B; a short block uses the formula at its own n).
+ *   autocorr  v[i] = (q[i] * w[i]) >> 10 (arithmetic); R[l] = sum_{i >= l} v[i] v[i - l], l = 0 ..
+ *             min(12, n - 1), in int64: |R| <= 2^52, so the sum is exact in any order and so is its f64.
+ *   levinson  f64, every operation rounded on its own: E = R[0]; for i = 0 .. : stop unless E > 0;
+ *             acc = R[i + 1]; acc = acc - a[j] * R[i - j] for j = 0 .. i - 1 in turn; k = acc / E;
+ *             a'[j] = a[j] - k * a[i - 1 - j] for j < i, a'[i] = k; E = E * (1 - k * k). a' is the
+ *             predictor of order i + 1: a[j] multiplies q[t - 1 - j].
+ *   quantise  12-bit coefficients: with 2^(e-1) <= max|a| < 2^e, shift = min(11 - e, 15); the order is
+ *             dropped if shift < 0 or max|a| is 0 or not finite; c[j] = clamp(rint(a[j] * 2^shift),
+ *             -2048, 2047), rint to even.
+ *   predict   r[t] = q[t] - ((sum_j c[j] * q[t - 1 - j]) >> shift), int64 sum, arithmetic shift (the
+ *             sum stays below 2^31 and r fits int32 for 16-bit samples, so no candidate is ever
+ *             dropped for its residual); FIXED: the order-th difference.
+ *   rice      partitioned Rice, 4-bit parameters k in 0 .. 14, no escape code. Partition order o in 0 ..
+ *             the largest o <= 8 with 2^o | n and (n >> o) > order. For every o the exact bit count with
+ *             the best k of each partition (the lowest k on a tie: sum (zz >> k) + (k + 1) * count,
+ *             zz = (r << 1) ^ (r >> 31)), 4 bits per partition; the lowest o on a tie.
+ *   frame     sync 0xFFF8, block-size and rate codes, 0x08 (mono, 16 bits), the frame number in the
+ *             UTF-8-like coding (up to 6 bytes), the explicit block size if any, CRC-8 (0x07) of the
+ *             header; the subframe; zero bits to a byte; CRC-16 (0x8005, initial 0) of all before it.
+ * The largest frame is 2 n + 16 bytes. */
+#define RWKVTTS_FLAC_LAST 1u   /* the window ends its signal: a short last block is allowed */
+#define RWKVTTS_FLAC_NO_LPC 2u /* CONSTANT, FIXED and VERBATIM only */
+/* The window of block size B (host only): out[B], int32. */
+int rwkvtts_flac_table(int32_t block_size, int32_t* out);
+/* The largest byte count n samples can give at block size B: 2 n + 16 ceil(n / B); -1 for a bad B or n
+ * outside 0 .. 2^40 (host only). */
+int64_t rwkvtts_flac_bound(int64_t n, int32_t block_size);
+/* "fLaC" and one STREAMINFO block (the last metadata block), 42 bytes, into out (host only): both block
+ * sizes B, the frame sizes, the rate, mono, 16 bits, the sample count and the MD5 of the int16
+ * little-endian samples (md5 NULL: zeros). Zeros in min_frame / max_frame / total_samples / md5 mean
+ * "unknown", which the format allows: the header of a stream whose length is not known yet. */
+int rwkvtts_flac_streaminfo(int32_t sample_rate, int32_t block_size, int32_t min_frame, int32_t max_frame,
+                            int64_t total_samples, const uint8_t* md5, uint8_t* out);
+typedef struct rwkvtts_flac rwkvtts_flac;
+/* table == NULL: the windows of rwkvtts_flac_table for 256, 512, 1024, 2048 and 4096 back to back (7936
+ * int32); otherwise the caller's (copied). */
+int rwkvtts_flac_create(int device, const int32_t* table, rwkvtts_flac** out);
+int rwkvtts_flac_destroy(rwkvtts_flac* f);
+typedef struct {
+  uint32_t struct_size;
+  const float* in;     /* n_in samples, host */
+  int64_t n_in;        /* a multiple of block_size unless flags has RWKVTTS_FLAC_LAST */
+  float scale;         /* finite, >= 0 */
+  int32_t sample_rate; /* 8000, 16000, 22050, 24000, 32000, 44100 or 48000 */
+  int32_t block_size;  /* 256, 512, 1024, 2048 or 4096 */
+  uint32_t flags;      /* RWKVTTS_FLAC_* */
+  int64_t first_frame; /* the frame number of the window's first block */
+  uint8_t* out;        /* the frames back to back, host */
+  int64_t out_cap;     /* >= rwkvtts_flac_bound(n_in, block_size) */
+  int64_t out_len;     /* out: bytes written */
+  int32_t min_frame;   /* out: the smallest and the largest frame of the window, bytes (0 without frames) */
+  int32_t max_frame;
+} rwkvtts_flac_window;
+/* n windows (of any signals, rates, block sizes and scales) in one launch pair: the frames
+ * [first_frame, first_frame + ceil(n_in / block_size)) of each signal. RWKVTTS_EINVAL before anything is
+ * launched (and nothing written) if a window has an unknown rate or block size, n_in that is not a
+ * multiple of block_size without RWKVTTS_FLAC_LAST, out_cap below the bound, or first_frame + blocks
+ * above 2^31. Calls on one handle serialise on its lock. */
+int rwkvtts_flac_encode(rwkvtts_flac* f, rwkvtts_flac_window* win, int n);
+/* HIP-event time of the last call's two kernels (no copies), in ms; 0 before the first. */
+int rwkvtts_flac_kernel_ms(rwkvtts_flac* f, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

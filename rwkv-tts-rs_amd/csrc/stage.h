@@ -33,12 +33,15 @@ struct DevBuf {
 };
 
 // What every stage object holds; the stage's own struct derives from it. Desc is the per-workgroup
-// descriptor its kernels read (one array per call, built on the host under mu).
-template <typename Desc>
+// descriptor its kernels read (one array per call, built on the host under mu). Out and Tab: the
+// element types of the outputs and of the table, f32 for every stage but the FLAC encoder (flac.hip),
+// whose outputs are bytes and whose table is int32.
+template <typename Desc, typename Out = float, typename Tab = float>
 struct Stage {
   int device = 0;
-  float* d_table = nullptr;
-  DevBuf<float> d_in, d_out;  // the windows' inputs / outputs, back to back
+  Tab* d_table = nullptr;
+  DevBuf<float> d_in;   // the windows' inputs, back to back
+  DevBuf<Out> d_out;    // the windows' outputs, back to back
   DevBuf<Desc> d_desc;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;  // bracket the kernels of a call, not its copies
@@ -73,12 +76,12 @@ static int guard_alloc(const char* who, F&& f) {
   }
 }
 
-// A new S on `device` with its stream, its events and its table of n floats on the device: the
-// caller's table, or make(float*) when that is null.
-template <typename S, typename Make>
-static int stage_create(const char* who, int device, const float* table, size_t n, Make&& make, S** out) {
+// A new S on `device` with its stream, its events and its table of n elements on the device: the
+// caller's table, or make(T*) when that is null.
+template <typename S, typename T, typename Make>
+static int stage_create(const char* who, int device, const T* table, size_t n, Make&& make, S** out) {
   S* s = nullptr;
-  std::vector<float> own;
+  std::vector<T> own;
   int rc = guard_alloc(who, [&] {
     s = new S();
     if (!table) {
@@ -103,8 +106,8 @@ static int stage_create(const char* who, int device, const float* table, size_t 
   if ((e = hipStreamCreate(&s->stream)) != hipSuccess) return fail(e, "hipStreamCreate");
   if ((e = hipEventCreate(&s->ev0)) != hipSuccess) return fail(e, "hipEventCreate");
   if ((e = hipEventCreate(&s->ev1)) != hipSuccess) return fail(e, "hipEventCreate");
-  if ((e = hipMalloc(&s->d_table, n * sizeof(float))) != hipSuccess) return fail(e, "hipMalloc");
-  if ((e = hipMemcpy(s->d_table, table, n * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)
+  if ((e = hipMalloc(&s->d_table, n * sizeof(T))) != hipSuccess) return fail(e, "hipMalloc");
+  if ((e = hipMemcpy(s->d_table, table, n * sizeof(T), hipMemcpyHostToDevice)) != hipSuccess)
     return fail(e, "hipMemcpy");
   *out = s;
   return RWKVTTS_OK;

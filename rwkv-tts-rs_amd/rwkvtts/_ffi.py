@@ -257,6 +257,17 @@ class WmResult(ctypes.Structure):
                 ("min_z", ctypes.c_float), ("dbg_r", ctypes.c_void_p), ("dbg_d", ctypes.c_void_p)]
 
 
+FLAC_LAST, FLAC_NO_LPC = 1, 2
+
+
+class FlacWindow(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("in_", ctypes.c_void_p), ("n_in", ctypes.c_int64),
+                ("scale", ctypes.c_float), ("sample_rate", ctypes.c_int32), ("block_size", ctypes.c_int32),
+                ("flags", ctypes.c_uint32), ("first_frame", ctypes.c_int64), ("out", ctypes.c_void_p),
+                ("out_cap", ctypes.c_int64), ("out_len", ctypes.c_int64), ("min_frame", ctypes.c_int32),
+                ("max_frame", ctypes.c_int32)]
+
+
 # Every symbol include/rwkvtts.h declares (checked by tests/test_abi.py against the header).
 EXPORTS = {
     "rwkvtts_synth_weights": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p]),
@@ -424,6 +435,15 @@ EXPORTS = {
     "rwkvtts_wm_detect_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_int, ctypes.POINTER(WmResult)]),
     "rwkvtts_wm_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    # flac: window table, bound and stream header (host only), ragged windows in one launch pair
+    "rwkvtts_flac_table": (ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p]),
+    "rwkvtts_flac_bound": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
+    "rwkvtts_flac_streaminfo": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "rwkvtts_flac_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "rwkvtts_flac_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "rwkvtts_flac_encode": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(FlacWindow), ctypes.c_int]),
+    "rwkvtts_flac_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None

@@ -40,6 +40,11 @@ and the clip / silence helpers it uses), feeding the HIP mel kernel (features.py
   one-shot, batched and exact over stream chunks (bitwise its numpy restatement, tests/wm_ref.py),
   and a detector that searches every alignment of the mark's period (held to the float64
   restatement within the error bound of its f32 sums). Contract: include/rwkvtts.h, DESIGN.md §30.
+* `FlacEncoder` (no reference counterpart: the reference sends WAV only): a FLAC encoder as HIP kernels
+  (csrc/flac.hip) -- the int16 samples of the WAV routes, losslessly compressed, one-shot, batched and
+  exact over stream chunks (`FlacStream`); the subframe of each block chosen by exact bit count. Bitwise
+  its numpy restatement (tests/flac_ref.py); read back by the independent decoder rwkvtts/flac.py.
+  Contract: include/rwkvtts.h, DESIGN.md §31.
 """
 import ctypes
 import struct
@@ -1048,6 +1053,171 @@ class WatermarkStream(_ExactStream):
         return self.m.plan(n_known, False, self._block_next)[1]
 
 
+# ---- lossless compressed output on the GPU ---------------------------------------------------
+FLAC_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
+FLAC_BLOCKS = (256, 512, 1024, 2048, 4096)
+
+
+def _flac_table() -> np.ndarray:
+    """The Q15 Welch windows of the five block sizes back to back, int32: w[i] = 32768 -
+    floor(32768 d^2 / D^2), d = 2 i - B + 1, D = B + 1, in integers: the table both sides read."""
+    rows = []
+    for B in FLAC_BLOCKS:
+        d = 2 * np.arange(B, dtype=np.int64) - B + 1
+        rows.append(32768 - (32768 * d * d) // ((B + 1) * (B + 1)))
+    return np.concatenate(rows).astype(np.int32)
+
+
+def flac_default_block(rate: int) -> int:
+    """1024 samples up to 24 kHz, 2048 above: at most 64 ms of lag in a stream."""
+    return 1024 if int(rate) <= 24000 else 2048
+
+
+class FlacEncoder(_NativeStage):
+    """A FLAC encoder as HIP kernels (csrc/flac.hip; the contract is in include/rwkvtts.h, DESIGN.md
+    §31): f32 PCM -> a standard mono 16-bit FLAC stream (RFC 9639, streamable subset, fixed block size)
+    whose decoded samples are the int16 samples the WAV routes send, byte for byte. Per block the
+    subframe is chosen by exact bit count among CONSTANT, FIXED orders 0 .. 4, LPC orders 1 .. 12 (12-bit
+    coefficients from an integer-windowed autocorrelation) and VERBATIM, each with the best Rice
+    partitioning. A frame depends on its own samples, its number, the rate and the block size only, so
+    a stream's frames are byte for byte the one-shot frames (FlacStream). One call encodes a ragged
+    batch -- a rate, a block size and a scale per signal -- in one launch pair; only the compressed
+    bytes cross to the host. Pinned bitwise to its numpy restatement (tests/flac_ref.py) and read back
+    by an independent decoder (rwkvtts.flac); unverified against libFLAC.
+
+    evaluator: a callable (encoder, items) -> [(bytes, min_frame, max_frame)] standing in for the native
+    call, items being [(samples, scale, rate, block, first_frame, final, lpc)]; no GPU object is created
+    then (the host-only entry points are still the library's)."""
+    _NAME = "flac"
+
+    def __init__(self, device: int = 0, evaluator=None):
+        self.device = int(device)
+        super().__init__(evaluator)
+        self.table = _flac_table()
+        if self._evaluator is None:
+            h = ctypes.c_void_p()
+            _native("flac_create", self.device, self.table.ctypes.data_as(ctypes.c_void_p), ctypes.byref(h))
+            self._h = h
+
+    # ---- host only ----
+    @staticmethod
+    def bound(n: int, block: int) -> int:
+        """The largest byte count n samples can give (rwkvtts_flac_bound)."""
+        b = int(_ffi.lib().rwkvtts_flac_bound(int(n), int(block)))
+        if b < 0:
+            raise _ffi.RwkvTtsError(_ffi.EINVAL, "flac_bound")
+        return b
+
+    @staticmethod
+    def header(rate: int, block: int, min_frame: int = 0, max_frame: int = 0, total: int = 0, md5=None) -> bytes:
+        """"fLaC" and the STREAMINFO block, 42 bytes (rwkvtts_flac_streaminfo); the zeros of the
+        defaults mean "unknown": the header of a stream."""
+        out = (ctypes.c_uint8 * 42)()
+        m = None if md5 is None else (ctypes.c_uint8 * 16)(*bytes(md5))
+        _native("flac_streaminfo", int(rate), int(block), int(min_frame), int(max_frame), int(total), m, out)
+        return bytes(out)
+
+    @staticmethod
+    def _check(rate, block):
+        if rate not in FLAC_RATES:
+            raise ValueError(f"FLAC output rate must be one of {FLAC_RATES}")
+        if block not in FLAC_BLOCKS:
+            raise ValueError(f"FLAC block size must be one of {FLAC_BLOCKS}")
+
+    # ---- the kernels ----
+    def encode_windows(self, items) -> list:
+        """[(samples, scale, rate, block, first_frame, final, lpc)] -> [(the frames first_frame .. of
+        that signal back to back, the smallest frame, the largest frame)], all windows in one launch
+        pair. Without final the samples must be whole blocks. Raises RwkvTtsError(EINVAL), with nothing
+        computed, on a window that breaks the rules."""
+        items = [(np.ascontiguousarray(x, dtype=F32).reshape(-1), float(F32(s)), int(r), int(b), int(f), bool(fin),
+                  bool(lpc)) for x, s, r, b, f, fin, lpc in items]
+        if self._evaluator is not None:
+            for x, s, r, b, f, fin, lpc in items:  # the native call's own refusals
+                if (r not in FLAC_RATES or b not in FLAC_BLOCKS or (not fin and x.size % b) or f < 0
+                        or f + -(-x.size // b) > 1 << 31 or not 0.0 <= s < float("inf")):
+                    raise _ffi.RwkvTtsError(_ffi.EINVAL, "flac_encode")
+            return [(bytes(y), int(a), int(b)) for y, a, b in self._evaluator(self, items)]
+        if not items:
+            return []
+        ws = (_ffi.FlacWindow * len(items))()
+        outs = []
+        for w, (x, s, r, b, f, fin, lpc) in zip(ws, items):
+            cap = 2 * x.size + 16 * -(-x.size // max(b, 1))
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            outs.append(out)
+            w.struct_size = ctypes.sizeof(_ffi.FlacWindow)
+            w.in_, w.n_in, w.scale, w.sample_rate, w.block_size = x.ctypes.data, x.size, s, r, b
+            w.flags = (_ffi.FLAC_LAST if fin else 0) | (0 if lpc else _ffi.FLAC_NO_LPC)
+            w.first_frame, w.out, w.out_cap = f, out.ctypes.data, cap
+        self._call("flac_encode", ws, len(items))
+        return [(out[:int(w.out_len)].tobytes(), int(w.min_frame), int(w.max_frame)) for w, out in zip(ws, outs)]
+
+    def encode_batch(self, signals, rates, scales=None, blocks=None, lpc: bool = True) -> list:
+        """[signal], [rate] (, [scale], [block]) -> [FLAC file], ragged, in one launch pair. Each file's
+        STREAMINFO carries the true frame sizes, the sample count and the MD5 of the int16 samples."""
+        import hashlib
+        xs = [np.ascontiguousarray(x, dtype=F32).reshape(-1) for x in signals]
+        rs = [int(r) for r in rates]
+        ss = [1.0] * len(xs) if scales is None else [float(s) for s in scales]
+        bs = [None] * len(xs) if blocks is None else list(blocks)
+        if not len(xs) == len(rs) == len(ss) == len(bs):
+            raise ValueError("encode_batch: one rate, one scale and one block size per signal")
+        bs = [flac_default_block(r) if b is None else int(b) for r, b in zip(rs, bs)]
+        for r, b in zip(rs, bs):
+            self._check(r, b)
+        res = self.encode_windows([(x, s, r, b, 0, True, lpc) for x, s, r, b in zip(xs, ss, rs, bs)])
+        out = []
+        for x, s, r, b, (frames, mn, mx) in zip(xs, ss, rs, bs, res):
+            y = np.clip(x * F32(s), F32(-1.0), F32(1.0)) * F32(32767.0)
+            md5 = hashlib.md5(np.trunc(y).astype("<i2").tobytes()).digest()
+            out.append(self.header(r, b, mn, mx, x.size, md5) + frames)
+        return out
+
+    def encode(self, pcm, rate: int, scale: float = 1.0, block=None) -> bytes:
+        return self.encode_batch([pcm], [rate], [scale], [block])[0]
+
+    def stream(self, rate: int, block=None, scale: float = 1.0) -> "FlacStream":
+        return FlacStream(self, rate, block, scale)
+
+
+class FlacStream:
+    """FlacStream(encoder, rate, block): feed(pcm_chunk, final=False) -> bytes. The first call's bytes
+    begin with the stream header (STREAMINFO with unknown totals: the length is not known when it goes
+    out); then frames as blocks complete, and with final the short last block. Fed in any chunking, the
+    bytes are those of FlacEncoder.encode apart from STREAMINFO's totals. The carried state is the
+    samples short of a block and the next frame number; the lag is under one block."""
+
+    def __init__(self, encoder: FlacEncoder, rate: int, block=None, scale: float = 1.0):
+        self.e, self.rate, self.scale = encoder, int(rate), float(scale)
+        self.block = flac_default_block(self.rate) if block is None else int(block)
+        encoder._check(self.rate, self.block)
+        self._tail = np.zeros(0, dtype=F32)
+        self._frame = 0
+        self._header_sent = False
+        self._closed = False
+
+    def feed(self, pcm_chunk, final: bool = False) -> bytes:
+        if self._closed:
+            raise ValueError("the stream has ended (a chunk was fed with final=True)")
+        x = np.asarray(pcm_chunk, dtype=F32).reshape(-1)
+        if x.size:
+            self._tail = np.concatenate([self._tail, x])
+        out = b""
+        if not self._header_sent:
+            out, self._header_sent = self.e.header(self.rate, self.block), True
+        take = self._tail.size if final else self._tail.size // self.block * self.block
+        if take:
+            frames, _, _ = self.e.encode_windows([(self._tail[:take], self.scale, self.rate, self.block, self._frame,
+                                                   final, True)])[0]
+            out += frames
+            self._frame += -(-take // self.block)
+            self._tail = self._tail[take:].copy()
+        if final:
+            self._closed = True
+        return out
+
+
 # ---- normalisation / trimming ------------------------------------------------------------
 def audio_volume_normalize(audio, coeff: float = 0.2) -> np.ndarray:
     x = np.asarray(audio, dtype=F32).copy()
@@ -1125,8 +1295,18 @@ def get_ref_clip(wav, sample_rate: int = 16000, ref_segment_duration: float = 6.
     return x[:seg].copy()
 
 
+def read_flac(path: str) -> Tuple[np.ndarray, int, int]:
+    """A mono 16-bit FLAC file -> (f32 samples as s / 2^15, sample_rate, 1), through rwkvtts.flac.decode
+    (no reference counterpart: the reference reads WAV and MP3)."""
+    from . import flac
+    with open(path, "rb") as f:
+        pcm, sr = flac.decode(f.read())
+    return pcm.astype(F32) / F32(32768.0), sr, 1
+
+
 def load_audio(path: str, target_sr: int = 16000, volume_normalize: bool = True, device=None) -> np.ndarray:
-    """device: None resamples with the numpy restatement, an integer on that GPU (Resampler)."""
+    """device: None resamples with the numpy restatement, an integer on that GPU (Resampler). A file
+    that begins with "fLaC" is read as FLAC (read_flac), whatever its name."""
     import os
     if not os.path.exists(path):
         raise FileNotFoundError(path)
@@ -1135,7 +1315,9 @@ def load_audio(path: str, target_sr: int = 16000, volume_normalize: bool = True,
         raise ValueError("audio file empty or larger than 100 MB")
     if path.lower().endswith(".mp3"):
         raise NotImplementedError("MP3 decoding (symphonia) is not available")
-    x, sr, ch = read_wav(path)
+    with open(path, "rb") as f:
+        is_flac = f.read(4) == b"fLaC"
+    x, sr, ch = read_flac(path) if is_flac else read_wav(path)
     if x.size == 0 or x.size < ch:
         raise ValueError("no audio samples")
     if x.size < int(F32(sr) * F32(0.1)):

@@ -197,7 +197,8 @@ class LightweightTtsPipeline:
             raise ValueError("watermark_key must be an integer in [0, 2^64)")
         self.watermark_key = watermark_key
         self._marker = None  # audio.Watermarker (created on the first watermark or detect_watermark, kept)
-        self._stage_cache_lock = threading.Lock()  # guards all six (the server's worker threads share the pipeline)
+        self._encoder = None  # audio.FlacEncoder (created on the first `format: "flac"`, kept)
+        self._stage_cache_lock = threading.Lock()  # guards all seven (the server's worker threads share the pipeline)
 
     # ---- output rates other than 16 kHz (no reference counterpart: the reference emits 16 kHz only)
     def resampler(self, sample_rate: Optional[int]):
@@ -303,6 +304,16 @@ class LightweightTtsPipeline:
         (another key's mark included); payload and offset mean something only where it is true, and a
         payload bit is as sure as min_z is large (under 1: a guess). DESIGN.md section 30."""
         return self.marker(0).detect(pcm, self.watermark_key)
+
+    # ---- compressed output (no reference counterpart: the reference sends WAV only)
+    def encoder(self):
+        """The pipeline's one FlacEncoder, on the codec's GPU, created on first use. It is no stage of
+        the PCM chain: the server's handlers run finished PCM through it for `format: "flac"`."""
+        with self._stage_cache_lock:
+            if self._encoder is None:
+                from .audio import FlacEncoder
+                self._encoder = FlacEncoder(device=getattr(self.codec, "device", 0))
+        return self._encoder
 
     def _stages(self, sample_rate: Optional[int], tempo: Optional[float], loudness: Optional[float] = None,
                 pitch_shift: Optional[float] = None, watermark: Optional[int] = None):  # -> (stages, output rate)

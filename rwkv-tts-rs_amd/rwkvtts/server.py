@@ -68,6 +68,15 @@
 * `handle_tts_stream(body, pipeline, voice_dir)` (no reference counterpart): the same request as a
   WAV stream, POST /api/tts/stream -- audio while the request is still decoding, at a fixed scale
   (no peak normalisation: that needs the whole utterance).
+* `format` in the body of both TTS routes (no reference counterpart: the reference sends WAV only):
+  "wav" (the default; the field absent is the same) or "flac", anything else a 400. With "flac" the
+  same int16 samples go out losslessly compressed by the GPU's FLAC encoder (audio.FlacEncoder):
+  /api/tts puts the FLAC file into `audio_base64` and adds `"format": "flac"` to the response, at the
+  peak rule's scale (1.0 with `loudness`), so rwkvtts.flac.decode of it gives the WAV's data bytes;
+  /api/tts/stream answers audio/flac -- the stream header (STREAMINFO with unknown totals), then frames
+  as blocks complete (1024 samples up to 24 kHz, 2048 above), the short last block at the end.
+  /api/watermark/detect takes a FLAC upload too (load_audio reads it through rwkvtts.flac.decode).
+  Without the field the routes are unchanged.
 The embedded web UI and model download are out of scope.
 """
 import base64
@@ -82,14 +91,21 @@ from .pipeline import LightweightTtsPipelineArgs
 from .runtime import PhaseSampling
 
 
-def convert_samples_to_wav(samples, sample_rate: int = 16000) -> bytes:
+def peak_scale(samples) -> np.float32:
+    """The peak rule of convert_samples_to_wav (:98-148): max|x| > 1 -> 1 / max, else min(0.8 / max, 10);
+    silence -> 1. f32."""
     x = np.asarray(samples, dtype=np.float32)
     max_abs = np.float32(np.max(np.abs(x))) if x.size else np.float32(0.0)
     if max_abs > 0.0:
         scale = np.float32(1.0) / max_abs if max_abs > 1.0 else min(np.float32(0.8) / max_abs, np.float32(10.0))
     else:
         scale = np.float32(1.0)
-    scale = np.float32(scale)
+    return np.float32(scale)
+
+
+def convert_samples_to_wav(samples, sample_rate: int = 16000) -> bytes:
+    x = np.asarray(samples, dtype=np.float32)
+    scale = peak_scale(x)
     y = np.clip(x * scale, np.float32(-1.0), np.float32(1.0)) * np.float32(32767.0)
     pcm = np.trunc(y).astype("<i2")  # Rust `as i16`: truncation toward zero
     return _wav_header(x.size, sample_rate) + pcm.tobytes()
@@ -131,6 +147,8 @@ LOUDNESS_MIN, LOUDNESS_MAX = -40.0, -10.0
 # `pitch_shift` of the same bodies (no reference counterpart): semitones, an octave either way -- the
 # kernel's own range
 PITCH_SHIFT_MIN, PITCH_SHIFT_MAX = -12.0, 12.0
+# `format` of the same bodies (no reference counterpart): the container of the audio that goes out
+FORMATS = ("wav", "flac")
 # `watermark` of the same bodies (no reference counterpart): the payload of the provenance mark, 16
 # bits at the marker's defaults -- a tenant or deployment number, not a secret (the key is the secret)
 WATERMARK_MIN, WATERMARK_MAX = 0, 65535
@@ -230,6 +248,11 @@ def _tts_args(body, voice_dir: str):
                              or not WATERMARK_MIN <= mark <= WATERMARK_MAX):
         return (400, {"success": False, "error": f"不支持的水印载荷: {mark} (支持: "
                                                  f"{WATERMARK_MIN} - {WATERMARK_MAX} 的整数)"}), None, None
+    fmt = body.get("format")
+    if fmt is None:
+        fmt = "wav"
+    elif not isinstance(fmt, str) or fmt not in FORMATS:
+        return (400, {"success": False, "error": f"不支持的输出格式: {fmt} (支持: {', '.join(FORMATS)})"}), None, None
     sampling = {}
     for what in ("global_sampling", "semantic_sampling"):
         o = body.get(what)
@@ -295,6 +318,8 @@ def _tts_args(body, voice_dir: str):
         kw["pitch_shift"] = float(shift)
     if mark is not None:
         kw["watermark"] = int(mark)
+    if fmt != "wav":
+        kw["format"] = fmt  # (the handler's, not the pipeline's: taken out before the call, as long_form is)
     return None, args, kw
 
 
@@ -313,16 +338,25 @@ def handle_tts_json(body, pipeline, voice_dir: str = "assets/raf") -> Tuple[int,
         return err
     rate = kw.get("sample_rate", 16000)
     long_form = kw.pop("long_form", False)
+    flac = kw.pop("format", "wav") == "flac"
     try:
         audio = pipeline.generate_long_speech(args, **kw) if long_form else pipeline.generate_speech(args, **kw)
     except Exception as e:  # noqa: BLE001 -- rendered as the reference's 500 body
         return 500, {"success": False, "error": f"生成TTS音频失败: {e}"}
     # (levelled PCM goes out at scale 1.0, as the stream route sends it: the peak rule would undo the target)
-    wav = levelled_samples_to_wav(audio, rate) if "loudness" in kw else convert_samples_to_wav(audio, rate)
+    if flac:  # the same samples as the WAV below: the peak rule's scale, or 1.0 for levelled PCM
+        try:
+            wav = pipeline.encoder().encode(audio, rate, scale=1.0 if "loudness" in kw else float(peak_scale(audio)))
+        except Exception as e:  # noqa: BLE001 -- rendered as the reference's 500 body
+            return 500, {"success": False, "error": f"生成TTS音频失败: {e}"}
+    else:
+        wav = levelled_samples_to_wav(audio, rate) if "loudness" in kw else convert_samples_to_wav(audio, rate)
     b64 =base64.standard_b64encode(wav).decode("ascii")
     total = time.perf_counter() - t0
     out = {"success": True, "message": "TTS生成成功", "audio_base64": b64,
            "duration_ms": int(total * 1000), "rtf": calculate_rtf(audio, total, rate)}
+    if flac:
+        out["format"] = "flac"
     if long_form:
         out["voice_tokens"] = audio.global_tokens
         out["segments"] = list(audio.segments)
@@ -368,7 +402,10 @@ def handle_tts_stream(body, pipeline, voice_dir: str = "assets/raf", chunk_frame
     if err:
         return err[0], iter([json.dumps(err[1], ensure_ascii=False).encode("utf-8")])
     rate = kw.get("sample_rate", 16000)
+    flac = kw.pop("format", "wav") == "flac"
     try:
+        # (created before the status line goes out: a failure is still a 500)
+        fs = pipeline.encoder().stream(rate) if flac else None
         if kw.pop("long_form", False):  # one item per segment: the first audio when segment 0 is done
             chunks = pipeline.stream_long_speech(args, **kw)
         else:
@@ -377,6 +414,22 @@ def handle_tts_stream(body, pipeline, voice_dir: str = "assets/raf", chunk_frame
     except Exception as e:  # noqa: BLE001 -- rendered as the reference's 500 body
         payload = {"success": False, "error": f"生成TTS音频失败: {e}"}
         return 500, iter([json.dumps(payload, ensure_ascii=False).encode("utf-8")])
+
+    def gen_flac():
+        # the stream header (STREAMINFO with unknown totals), then frames as blocks complete, then the
+        # short last block; an item without a complete block is empty and is not sent
+        yield fs.feed(np.zeros(0, dtype=np.float32))
+        if first is not None:
+            b = fs.feed(first)
+            if b:
+                yield b
+        for c in chunks:
+            b = fs.feed(c)
+            if b:
+                yield b
+        b = fs.feed(np.zeros(0, dtype=np.float32), final=True)
+        if b:
+            yield b
 
     def gen():
         yield streaming_wav_header(rate)
@@ -387,11 +440,22 @@ def handle_tts_stream(body, pipeline, voice_dir: str = "assets/raf", chunk_frame
         for c in chunks:
             if len(c):
                 yield samples_to_pcm16(c)
-    return 200, gen()
+    return 200, gen_flac() if flac else gen()
+
+
+def tts_stream_media_type(body) -> str:
+    """The media type of a 200 from handle_tts_stream for this body: audio/flac with `format: "flac"`,
+    else audio/wav."""
+    try:
+        if isinstance(body, (bytes, str)):
+            body = json.loads(body)
+        return "audio/flac" if isinstance(body, dict) and body.get("format") == "flac" else "audio/wav"
+    except ValueError:
+        return "audio/wav"
 
 
 def handle_watermark_detect(audio_path: Optional[str], pipeline) -> Tuple[int, dict]:
-    """POST /api/watermark/detect: an uploaded WAV saved to a temporary path (None: no file) ->
+    """POST /api/watermark/detect: an uploaded WAV (or mono 16-bit FLAC) saved to a temporary path (None: no file) ->
     (HTTP status, JSON). The clip is brought to 16 kHz mono by load_audio without volume
     normalisation (on the codec's GPU when it has to be resampled; its silent edges are trimmed, which
     moves `offset` only), then read under the pipeline's key (pipeline.detect_watermark). 200:
@@ -502,7 +566,7 @@ def create_app(pipeline, voice_dir: str = "assets/raf"):
         code, it = await anyio.to_thread.run_sync(handle_tts_stream, body, pipeline, voice_dir)
         if code != 200:
             return Response(b"".join(it), status_code=code, media_type="application/json")
-        return StreamingResponse(it, media_type="audio/wav")  # (a sync iterator: iterated in a worker thread)
+        return StreamingResponse(it, media_type=tts_stream_media_type(body))  # (a sync iterator: iterated in a worker thread)
 
     @app.post("/api/watermark/detect")
     async def api_watermark_detect(request: Request):
