@@ -251,6 +251,10 @@ typedef struct {
   int32_t top_k;
 } rwkvtts_phase_sampling;
 typedef struct {
+  float repetition, frequency, presence; /* neutral: 1, 0, 0 */
+  int32_t window;                        /* last `window` semantic tokens; 0: all of them */
+} rwkvtts_penalties;
+typedef struct {
   const int32_t* text_tokens;
   int32_t n_text;
   const int32_t* property_tokens;
@@ -297,9 +301,36 @@ typedef struct {
    * request sampled returns that request's (G, S), bit for bit. max_tokens == 0 (without
    * fixed_semantic) gives status 0, the 32 globals and no semantic tokens. 0: as before. */
   int32_t pinned_voice;
+  /* Repetition, frequency and presence penalties (src/sampler_manager.rs:229-292; the reference's
+   * TTS path never calls them). penalty_set bit 0: `penalties` holds; any other bit fails the
+   * request alone; 0: the request is sampled as before, by the kernel that served it before.
+   * They apply to the SEMANTIC phase only: the global phase draws its 32 tokens once, from logits
+   * over another id range, and has nothing to loop over. For one semantic step of a request that
+   * has emitted h[0, n_sem): H = h[max(0, n_sem - window), n_sem) (window 0: all of h), cnt[t] =
+   * occurrences of t in H, x = the f32 logit of t as the sampler receives it, before EOS masking.
+   * Every t with cnt[t] > 0 is adjusted, in this order, each operation one f32 operation rounded
+   * to nearest:
+   *   1. repetition != 1: cnt[t] times x = x > 0 ? x / repetition : x * repetition. PER
+   *      OCCURRENCE, as apply_repetition_penalty loops over the token list: it compounds. It is
+   *      not the once-per-distinct-token rule of other libraries.
+   *   2. frequency != 0: x = x - (frequency * (float)cnt[t]), a multiply, then a subtract (no FMA).
+   *   3. presence != 0:  x = x - presence.
+   * -inf stays -inf. The sampler then runs as before on the adjusted row (EOS mask, top-k, top-p,
+   * temperature, draw); the zero-shot re-draw with EOS masked uses the same adjusted row. EOS is
+   * never part of the history -- a step that draws it ends the request or re-draws with it masked
+   * -- so EOS is never penalised.
+   * repetition in [0.25, 4], frequency and presence in [-8, 8], window in [0, 2048], all finite;
+   * anything else fails the request alone (RWKVTTS_EINVAL). Unlike sampling_set, penalties may be
+   * combined with `greedy` (top-k 1 at (1.0, 0.95)): deterministic decoding is where loops are
+   * worst. They combine with sampling_set, pinned_voice, fixed_semantic and zero-shot mode. The
+   * neutral values (1, 0, 0) are valid and change nothing, the kernel included; any other value
+   * puts the request's steps on the parameter-reading controller. */
+  int32_t penalty_set;
+  rwkvtts_penalties penalties;
 } rwkvtts_request;
 #define RWKVTTS_SAMPLING_GLOBAL 1
 #define RWKVTTS_SAMPLING_SEMANTIC 2
+#define RWKVTTS_PENALTY_SET 1
 
 typedef struct {
   int32_t status;         /* 0 ok; <0 this request failed -> (vec![], vec![]) as dbm.rs:466-469
@@ -454,6 +485,14 @@ int rwkvtts_debug_advance(rwkvtts_engine* e, const float* logits, int n_rows, co
  * (1.0, 0.95) gives what rwkvtts_debug_advance gives for its first 72 bytes. */
 int rwkvtts_debug_advance_ex(rwkvtts_engine* e, const float* logits, int n_rows, const void* rows, int exact,
                              int n_steps, int32_t* out_tok, int32_t* out_used, int32_t* out_phase);
+/* The same with per-row penalties: `rows` points to n_rows records of 104 bytes, the 88 above
+ * (struct_size = 104) followed by float repetition, frequency, presence and int32 window, in the
+ * ranges of rwkvtts_request::penalties. n_steps may be up to 256 here: the fixed logits are sampled
+ * step after step while the row's semantic history grows. A row with penalties other than (1, 0, 0)
+ * must start at n_sem 0. A row with (1, 0, 0) gives what rwkvtts_debug_advance_ex gives for its
+ * first 88 bytes. */
+int rwkvtts_debug_advance_pen(rwkvtts_engine* e, const float* logits, int n_rows, const void* rows, int exact,
+                              int n_steps, int32_t* out_tok, int32_t* out_used, int32_t* out_phase);
 
 /* Test hook, not part of the drop-in surface: rows [0, n_rows) x head_rows of the logits that the
  * engine's last forward step left on the device (n_rows <= the engine's row capacity; a decode step

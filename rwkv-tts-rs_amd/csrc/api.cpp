@@ -136,6 +136,17 @@ int rwkvtts_debug_advance_ex(rwkvtts_engine* e, const float* logits, int n_rows,
   })
 }
 
+// The same with per-row penalties (engine.h DebugAdvanceRowPen); up to 256 steps.
+int rwkvtts_debug_advance_pen(rwkvtts_engine* e, const float* logits, int n_rows, const void* rows, int exact,
+                              int n_steps, int32_t* out_tok, int32_t* out_used, int32_t* out_phase) {
+  RT_CHECK(e && logits && rows && out_tok && out_used && out_phase, RWKVTTS_EINVAL, "debug_advance_pen: bad arguments");
+  LOCK(e);
+  GUARD({
+    return e->eng.debug_advance_pen(logits, n_rows, (const DebugAdvanceRowPen*)rows, exact, n_steps, out_tok, out_used,
+                                    out_phase);
+  })
+}
+
 // Test hook (not part of the drop-in surface): rows [0, n_rows) x head_rows of the logits the engine's
 // last forward step left on the device (the head GEMM's split-K slabs summed in order)
 int rwkvtts_debug_last_logits(rwkvtts_engine* e, int n_rows, int head_rows, float* out) {

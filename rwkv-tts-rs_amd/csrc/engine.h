@@ -33,7 +33,14 @@ struct DebugAdvanceRowEx {
   float top_p;
   uint32_t pad;
 };
-static_assert(sizeof(DebugAdvanceRow) == 72 && sizeof(DebugAdvanceRowEx) == 88, "test-hook row layouts");
+// rwkvtts_debug_advance_pen: the row above (struct_size = 104) plus its penalties
+struct DebugAdvanceRowPen {
+  DebugAdvanceRowEx ex;
+  float repetition, frequency, presence;
+  int32_t window;
+};
+static_assert(sizeof(DebugAdvanceRow) == 72 && sizeof(DebugAdvanceRowEx) == 88 && sizeof(DebugAdvanceRowPen) == 104,
+              "test-hook row layouts");
 
 struct LayerW {
   const float *ln1_w, *ln1_b, *ln2_w, *ln2_b;
@@ -104,6 +111,9 @@ class Engine {
   // rwkvtts_debug_advance_ex: rows carry their own temperature / top-p, top_k may be 0
   int debug_advance_ex(const float* logits, int n_rows, const struct DebugAdvanceRowEx* rows, int exact, int n_steps,
                        int32_t* out_tok, int32_t* out_used, int32_t* out_phase);
+  // rwkvtts_debug_advance_pen: rows carry penalties too; up to max_steps launches
+  int debug_advance_pen(const float* logits, int n_rows, const struct DebugAdvanceRowPen* rows, int exact, int n_steps,
+                        int32_t* out_tok, int32_t* out_used, int32_t* out_phase, int max_steps = 256);
   // Test hook (rwkvtts_debug_last_logits): rows [0, n_rows) of the logits the last forward step left on
   // the device (its head GEMM's split-K slabs summed in order, as infer returns them)
   int debug_last_logits(int n_rows, int head_rows, float* out);
@@ -292,6 +302,7 @@ class Engine {
   int* slot_par_ = nullptr;  // [S]
   std::vector<int> par_host_;
   std::vector<SlotCtrl> ctrl_stage_;  // [S] host copy of each admitted slot's initial control block
+  std::vector<SlotPenalty> pen_stage_;  // [S] and of its penalties
   // per-step tables
   uint32_t* d_tok_ = nullptr;
   int4* d_rows_ = nullptr;
@@ -308,6 +319,8 @@ class Engine {
   // controller
   SlotCtrl* d_ctrl_ = nullptr;
   int32_t* d_sem_ = nullptr;
+  SlotPenalty* d_pen_ = nullptr;      // [S] AdvanceArgs::pen
+  uint16_t* d_pen_counts_ = nullptr;  // [S][kPenCounts] AdvanceArgs::pen_counts
   SlotCtrl* h_ctrl_ = nullptr;  // pinned mirror
   // token progress: pinned [2 unit buffers][S][RWKVTTS_SEMANTIC_LIMIT], token i of a slot at index i;
   // allocated when the first request with a sink is admitted (engines that never see one: no change)

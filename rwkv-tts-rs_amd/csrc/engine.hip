@@ -356,6 +356,7 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
   RT_OK(alloc(&slot_par_, (size_t)S_));
   par_host_.assign(S_, 0);
   ctrl_stage_.assign(S_, SlotCtrl{});
+  pen_stage_.assign(S_, SlotPenalty{1.0f, 0.0f, 0.0f, 0});
   // tables
   RT_OK(alloc(&d_tok_, (size_t)Rmax_));
   RT_OK(alloc(&d_rows_, (size_t)Rmax_));
@@ -402,6 +403,8 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
   RT_OK(alloc(&d_ctrl_, (size_t)S_ + 1));
   RT_HIP(hipMemset(d_ctrl_ + S_, 0, sizeof(SlotCtrl)));
   RT_OK(alloc(&d_sem_, (size_t)S_ * RWKVTTS_SEMANTIC_LIMIT));
+  RT_OK(alloc(&d_pen_, (size_t)S_));  // written at every admission, before the slot's first step
+  RT_OK(alloc(&d_pen_counts_, (size_t)S_ * kPenCounts));  // a slot's row is zeroed by its first penalised step
   RT_HIP(hipHostMalloc((void**)&h_ctrl_, sizeof(SlotCtrl) * 2 * (S_ + 1), hipHostMallocDefault));  // 2 snapshots
   // granule hand-off of the one-row FFN form (FfnSync::gran): four key splits x F granules, and the
   // pass counter that tags them (starts at 1: a zeroed granule never carries a live tag)
@@ -856,6 +859,8 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
       a.row_slot = d_lg_slot_;
       a.ctrl = d_ctrl_;
       a.sem_out = d_sem_;
+      a.pen = d_pen_;
+      a.pen_counts = d_pen_counts_;
       a.n_rows = n_lg;
       a.stamps = dbg_astamps_;
       a.params = sampling_params ? 1 : 0;
@@ -1024,17 +1029,41 @@ int Engine::debug_advance(const float* logits, int n_rows, const DebugAdvanceRow
 
 int Engine::debug_advance_ex(const float* logits, int n_rows, const DebugAdvanceRowEx* rows, int exact, int n_steps,
                              int32_t* out_tok, int32_t* out_used, int32_t* out_phase) {
+  RT_CHECK(n_rows > 0 && n_rows <= 4096, RWKVTTS_EINVAL, "debug_advance: bad sizes");
+  std::vector<DebugAdvanceRowPen> pen(n_rows);
+  for (int i = 0; i < n_rows; ++i) {
+    RT_CHECK(rows[i].struct_size == sizeof(DebugAdvanceRowEx), RWKVTTS_EINVAL, "debug_advance: bad row");
+    pen[i] = DebugAdvanceRowPen{rows[i], 1.0f, 0.0f, 0.0f, 0};
+    pen[i].ex.struct_size = (uint32_t)sizeof(DebugAdvanceRowPen);
+  }
+  return debug_advance_pen(logits, n_rows, pen.data(), exact, n_steps, out_tok, out_used, out_phase, 64);
+}
+
+int Engine::debug_advance_pen(const float* logits, int n_rows, const DebugAdvanceRowPen* prows, int exact, int n_steps,
+                              int32_t* out_tok, int32_t* out_used, int32_t* out_phase, int max_steps) {
   RT_HIP(hipSetDevice(device_));
-  RT_CHECK(n_rows > 0 && n_rows <= 4096 && n_steps > 0 && n_steps <= 64, RWKVTTS_EINVAL, "debug_advance: bad sizes");
+  RT_CHECK(n_rows > 0 && n_rows <= 4096 && n_steps > 0 && n_steps <= max_steps, RWKVTTS_EINVAL, "debug_advance: bad sizes");
   constexpr int LD = RWKVTTS_EOS_TOKEN + 1;
   std::vector<SlotCtrl> c(n_rows);
+  std::vector<SlotPenalty> pens(n_rows);
+  bool any_pen = false;
   for (int i = 0; i < n_rows; ++i) {
-    const DebugAdvanceRow& r = rows[i].row;
+    const DebugAdvanceRowPen& pr = prows[i];
+    const DebugAdvanceRowEx& e = pr.ex;
+    const DebugAdvanceRow& r = e.row;
     RT_CHECK((r.phase == kPhGlobal || r.phase == kPhSemantic) && r.top_k >= 0 && r.n_sem >= 0 &&
                  r.n_sem + n_steps <= RWKVTTS_SEMANTIC_LIMIT && (r.mode == 0 || r.mode == 1) &&
-                 rows[i].struct_size == sizeof(DebugAdvanceRowEx) && rows[i].temperature >= 0.1f &&
-                 rows[i].temperature <= 4.0f && rows[i].top_p >= 0.0f && rows[i].top_p <= 1.0f,
+                 e.struct_size == sizeof(DebugAdvanceRowPen) && e.temperature >= 0.1f && e.temperature <= 4.0f &&
+                 e.top_p >= 0.0f && e.top_p <= 1.0f,
              RWKVTTS_EINVAL, "debug_advance: bad row");
+    const bool neutral = pr.repetition == 1.0f && pr.frequency == 0.0f && pr.presence == 0.0f;
+    // a penalised row starts with an empty history: its counts are the kernel's own from step 0 on
+    RT_CHECK(pr.repetition >= 0.25f && pr.repetition <= 4.0f && pr.frequency >= -8.0f && pr.frequency <= 8.0f &&
+                 pr.presence >= -8.0f && pr.presence <= 8.0f && pr.window >= 0 && pr.window <= RWKVTTS_SEMANTIC_LIMIT &&
+                 (neutral || r.n_sem == 0),
+             RWKVTTS_EINVAL, "debug_advance: bad penalties");
+    any_pen |= !neutral;
+    pens[i] = SlotPenalty{pr.repetition, pr.frequency, pr.presence, pr.window};
     SlotCtrl& x = c[i];
     memset(&x, 0, sizeof(x));
     x.mode = r.mode;
@@ -1044,8 +1073,8 @@ int Engine::debug_advance_ex(const float* logits, int n_rows, const DebugAdvance
     x.hard_min = r.hard_min;
     x.fixed = r.fixed;
     x.top_k_g = x.top_k_s = r.top_k;
-    x.temp_g = x.temp_s = rows[i].temperature;
-    x.top_p_g = x.top_p_s = rows[i].top_p;
+    x.temp_g = x.temp_s = e.temperature;
+    x.top_p_g = x.top_p_s = e.top_p;
     x.win_bits = r.win_bits;
     x.win_len = r.win_len;
     memcpy(x.gkey, r.key, 32);
@@ -1055,15 +1084,19 @@ int Engine::debug_advance_ex(const float* logits, int n_rows, const DebugAdvance
   float* d_lg = nullptr;
   SlotCtrl* d_c = nullptr;
   int32_t *d_slot = nullptr, *d_sem = nullptr;
+  uint16_t* d_cnt = nullptr;  // [n_rows][kPenCounts], only when some row is penalised
+  SlotPenalty* d_pen = nullptr;
   auto cleanup = [&] {
-    for (void* p : {(void*)d_lg, (void*)d_c, (void*)d_slot, (void*)d_sem})
+    for (void* p : {(void*)d_lg, (void*)d_c, (void*)d_slot, (void*)d_sem, (void*)d_cnt, (void*)d_pen})
       if (p) hipFree(p);
   };
   int rc = RWKVTTS_OK;
   do {
     if (hipMalloc(&d_lg, (size_t)n_rows * LD * 4) != hipSuccess || hipMalloc(&d_c, sizeof(SlotCtrl) * n_rows) != hipSuccess ||
         hipMalloc(&d_slot, 4 * (size_t)n_rows) != hipSuccess ||
-        hipMalloc(&d_sem, 4 * (size_t)n_rows * RWKVTTS_SEMANTIC_LIMIT) != hipSuccess) {
+        hipMalloc(&d_sem, 4 * (size_t)n_rows * RWKVTTS_SEMANTIC_LIMIT) != hipSuccess ||
+        hipMalloc(&d_pen, sizeof(SlotPenalty) * n_rows) != hipSuccess ||
+        (any_pen && hipMalloc(&d_cnt, sizeof(uint16_t) * (size_t)n_rows * kPenCounts) != hipSuccess)) {
       set_error("debug_advance: allocation");
       rc = RWKVTTS_ENOMEM;
       break;
@@ -1073,6 +1106,7 @@ int Engine::debug_advance_ex(const float* logits, int n_rows, const DebugAdvance
     if (hipMemcpy(d_lg, logits, (size_t)n_rows * LD * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_c, c.data(), sizeof(SlotCtrl) * n_rows, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_slot, slot.data(), 4 * (size_t)n_rows, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_pen, pens.data(), sizeof(SlotPenalty) * n_rows, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(d_sem, 0xFF, 4 * (size_t)n_rows * RWKVTTS_SEMANTIC_LIMIT) != hipSuccess) {
       set_error("debug_advance: upload");
       rc = RWKVTTS_EHIP;
@@ -1086,9 +1120,14 @@ int Engine::debug_advance_ex(const float* logits, int n_rows, const DebugAdvance
     a.row_slot = d_slot;
     a.ctrl = d_c;
     a.sem_out = d_sem;
+    a.pen = d_pen;
+    a.pen_counts = d_cnt;
     a.n_rows = n_rows;
-    for (int i = 0; i < n_rows; ++i)
-      a.params |= rows[i].temperature != 1.0f || rows[i].top_p != 0.95f || rows[i].row.top_k < 1 || rows[i].row.top_k > kFastTopK;
+    a.params = any_pen ? 1 : 0;
+    for (int i = 0; i < n_rows; ++i) {
+      const DebugAdvanceRowEx& e = prows[i].ex;
+      a.params |= e.temperature != 1.0f || e.top_p != 0.95f || e.row.top_k < 1 || e.row.top_k > kFastTopK;
+    }
     std::vector<SlotCtrl> prev = c, now(n_rows);
     for (int s = 0; s < n_steps && rc == RWKVTTS_OK; ++s) {
       launch_advance(a, stream_, exact ? 0 : 1);
@@ -1362,6 +1401,8 @@ int Engine::admit(ServeState& st, Job* j) {
   // stream-ordered copy (the slot's entry is rewritten only after the slot retires)
   ctrl_stage_[slot] = ad.ctrl;
   RT_HIP(hipMemcpyAsync(d_ctrl_ + slot, &ctrl_stage_[slot], sizeof(SlotCtrl), hipMemcpyHostToDevice, stream_));
+  pen_stage_[slot] = ad.pen;
+  RT_HIP(hipMemcpyAsync(d_pen_ + slot, &pen_stage_[slot], sizeof(SlotPenalty), hipMemcpyHostToDevice, stream_));
   Active a;
   a.job = j;
   a.slot = slot;

@@ -44,7 +44,15 @@ struct AdvanceArgs {
   // (SlotCtrl::temp_* / top_p_*) or another top-k -- k_advance_params reads them per row and
   // carries every path. Both give a row of the first kind the same token.
   int params;
+  const SlotPenalty* pen;  // [S] penalties of each slot (read by k_advance_params only)
+  // [S][kPenCounts] occurrences of each semantic id in a penalised slot's history window
+  // (pen). Derived state that k_advance_params keeps by itself: a slot's row is zeroed
+  // at its first semantic step instead of being read, the emitted id is counted after every step
+  // and the id that leaves the window is uncounted. Rows of slots without penalties are never
+  // touched. May be null when no row's slot is penalised.
+  uint16_t* pen_counts;
 };
+constexpr int kPenCounts = RWKVTTS_EOS_TOKEN;  // ids [0, 8192): EOS never enters the history
 
 size_t wide_scratch_bytes(int n);
 void launch_sample_rows(const SampleRowArgs& a, int rows, hipStream_t st);

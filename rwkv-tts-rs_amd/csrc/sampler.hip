@@ -1990,6 +1990,52 @@ __device__ __attribute__((always_inline)) void advance_prep(const float* raw, co
   STAMP(10);
 }
 
+// Penalties of a semantic row (rwkvtts.h rwkvtts_request::penalties), on the row in registers
+// before advance_prep sees it: element i = tid + k NT with cnt[i] > 0 occurrences in the slot's
+// history window gets, in this order and one rounded f32 operation each, cnt times x = x > 0 ?
+// x / rep : x * rep, then x - (freq * cnt) as a multiply and a subtract, then x - pres. The counts
+// are the slot's row of AdvanceArgs::pen_counts, one coalesced 2-byte read per element with every
+// load issued before the first use. At the slot's first semantic step the row is zeroed instead of
+// read (whatever an earlier request left there is gone; the history is empty, so nothing is
+// adjusted). The repetition loop stops early only where a pass returns its input bit for bit (0,
+// -0, +-inf, a denormal that x / rep rounds back to itself): every later pass would return it
+// again, so the result is that of cnt passes. -inf stays -inf through all three steps (rep > 0,
+// and -inf - finite == -inf).
+template <int NT, int PT>
+__device__ __attribute__((always_inline)) void advance_penalise(float* raw, uint16_t* cnt, int n_sem, float rep, float freq,
+                                                                float pres) {
+  const int tid = threadIdx.x;
+  if (n_sem == 0) {
+#pragma unroll
+    for (int k = 0; k < PT; ++k) {
+      const int i = tid + k * NT;
+      if (i < kPenCounts) cnt[i] = 0;
+    }
+    return;
+  }
+  uint32_t cn[PT];
+#pragma unroll
+  for (int k = 0; k < PT; ++k) {
+    const int i = tid + k * NT;
+    cn[k] = i < kPenCounts ? cnt[i] : 0u;
+  }
+#pragma unroll
+  for (int k = 0; k < PT; ++k) {
+    if (cn[k] == 0u) continue;
+    float x = raw[k];
+    if (rep != 1.0f) {
+      for (uint32_t r = 0; r < cn[k]; ++r) {
+        const float y = x > 0.0f ? __fdiv_rn(x, rep) : __fmul_rn(x, rep);
+        if (__builtin_bit_cast(uint32_t, y) == __builtin_bit_cast(uint32_t, x)) break;
+        x = y;
+      }
+    }
+    if (freq != 0.0f) x = __fsub_rn(x, __fmul_rn(freq, (float)cn[k]));
+    if (pres != 0.0f) x = __fsub_rn(x, pres);
+    raw[k] = x;
+  }
+}
+
 template <bool kParams>
 __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a, char* smem) {
   constexpr int NT = kSampleThreads;
@@ -2027,6 +2073,18 @@ __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a
   const float top_p = !kParams ? 0.95f : (glob ? c->top_p_g : c->top_p_s);
   const uint32_t* key = glob ? c->gkey : c->skey;
   const uint64_t draw = glob ? c->gdraw : c->sdraw;
+  // penalties (k_advance_params, semantic rows of a slot whose values are not neutral): the row is
+  // adjusted once, so the zero-shot re-draw below samples the same adjusted row
+  bool pen = false;
+  uint16_t* pen_cnt = nullptr;
+  if constexpr (kParams) {
+    const float rep = a.pen[slot].repetition, freq = a.pen[slot].frequency, pres = a.pen[slot].presence;
+    pen = !glob && (rep != 1.0f || freq != 0.0f || pres != 0.0f);
+    if (pen) {
+      pen_cnt = a.pen_counts + (int64_t)slot * kPenCounts;
+      advance_penalise<NT, PT>(raw, pen_cnt, c->n_sem, rep, freq, pres);
+    }
+  }
   // attempt 1 (zero-shot only): EOS drawn while the window rule does not stop the request ->
   // re-draw with EOS masked from the same logits and the next draw (zero_shot_inference.rs:287-297)
   int id = 0, status;
@@ -2073,6 +2131,19 @@ __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a
         if (c->win_len < 12) c->win_len++;
       }
       a.sem_out[(int64_t)slot * RWKVTTS_SEMANTIC_LIMIT + c->n_sem] = id;
+      if constexpr (kParams) {
+        // the counts follow the history: the new id enters, and once the window is full the id
+        // that leaves it goes (ids outside [0, 8192) cannot occur: EOS ends the request or is
+        // re-drawn masked above, and is never stored; the range checks cost nothing beside that)
+        if (pen) {
+          const int W = a.pen[slot].window, ns = c->n_sem;
+          if ((uint32_t)id < (uint32_t)kPenCounts) pen_cnt[id] += 1;
+          if (W > 0 && ns >= W) {
+            const int old = a.sem_out[(int64_t)slot * RWKVTTS_SEMANTIC_LIMIT + ns - W];
+            if ((uint32_t)old < (uint32_t)kPenCounts) pen_cnt[old] -= 1;
+          }
+        }
+      }
       c->n_sem++;
       c->next_token = id;
       if (c->n_sem >= c->sem_limit) c->phase = kPhDone;

@@ -119,6 +119,18 @@ inline bool validate(const rwkvtts_request& q, int n_vocab, std::string& why) {
   };
   if ((q.sampling_set & RWKVTTS_SAMPLING_GLOBAL) && !phase_ok(q.global_sampling, "global_sampling")) return false;
   if ((q.sampling_set & RWKVTTS_SAMPLING_SEMANTIC) && !phase_ok(q.semantic_sampling, "semantic_sampling")) return false;
+  if (q.penalty_set & ~RWKVTTS_PENALTY_SET) {
+    why = "penalty_set: unknown bits";
+    return false;
+  }
+  if (q.penalty_set) {  // (allowed together with greedy; NaN fails every comparison)
+    const rwkvtts_penalties& p = q.penalties;
+    if (!(p.repetition >= 0.25f && p.repetition <= 4.0f)) why = "penalties: repetition must be in [0.25, 4.0]";
+    else if (!(p.frequency >= -8.0f && p.frequency <= 8.0f)) why = "penalties: frequency must be in [-8.0, 8.0]";
+    else if (!(p.presence >= -8.0f && p.presence <= 8.0f)) why = "penalties: presence must be in [-8.0, 8.0]";
+    else if (p.window < 0 || p.window > RWKVTTS_SEMANTIC_LIMIT) why = "penalties: window must be in [0, 2048]";
+    if (!why.empty()) return false;
+  }
   return true;
 }
 
@@ -137,15 +149,22 @@ inline bool pinned_without_tokens(const rwkvtts_request& q) { return is_pinned(q
 struct Admission {
   std::vector<uint32_t> prompt;
   SlotCtrl ctrl;         // the slot's initial control block, gkey / skey still zero
+  SlotPenalty pen;       // the slot's penalties ((1, 0, 0, 0) without penalty_set)
   uint64_t gseed, sseed;  // the engine derives gkey / skey from them (StdRng::seed_from_u64)
   bool zero_shot;
   bool pinned;           // is_pinned: decodes as normal mode from its first logits row on
   int total;             // Active::total
   // a phase's temperature or top-p differs from the reference's (1.0, 0.95), or its top-k is
   // outside the fast path's [1, kFastTopK]: steps with this request run the controller that reads
-  // the parameters from the control block and carries the general path for every top-k
+  // the parameters from the control block and carries the general path for every top-k. Also set
+  // by a penalty that is not neutral (pen): that controller alone applies penalties.
   bool own_sampling;
 };
+
+// (1, 0, 0): the semantic rows are sampled as they arrive
+inline bool penalties_neutral(const SlotPenalty& p) {
+  return p.repetition == 1.0f && p.frequency == 0.0f && p.presence == 0.0f;
+}
 
 inline bool any_own_sampling(const std::vector<Active>& act) {
   bool any = false;
@@ -188,6 +207,10 @@ inline Admission admission_of(const rwkvtts_request& q, uint64_t entropy) {
   }
   a.own_sampling = c.temp_g != 1.0f || c.temp_s != 1.0f || c.top_p_g != 0.95f || c.top_p_s != 0.95f ||
                    c.top_k_g < 1 || c.top_k_g > kFastTopK || c.top_k_s < 1 || c.top_k_s > kFastTopK;
+  a.pen = SlotPenalty{1.0f, 0.0f, 0.0f, 0};
+  if (q.penalty_set & RWKVTTS_PENALTY_SET)
+    a.pen = SlotPenalty{q.penalties.repetition, q.penalties.frequency, q.penalties.presence, q.penalties.window};
+  a.own_sampling |= !penalties_neutral(a.pen);
   c.fixed = q.fixed_semantic > 0;
   c.sem_limit = sem_limit_of(q);
   if (a.zero_shot) {

@@ -50,4 +50,16 @@ struct SlotCtrl {
 };
 static_assert(sizeof(SlotCtrl) % 8 == 0, "control blocks are copied as an array; next_token is read at a 4-byte stride");
 
+// Penalties of a slot's semantic phase (rwkvtts.h rwkvtts_penalties), in an array beside the
+// control blocks (AdvanceArgs::pen) that only the host writes, at admission: the control block
+// keeps the size and layout its snapshots and tests/native/sched_sampling_main.cpp know.
+// k_advance_params applies them to the logits of every token that occurs in the last `window`
+// semantic tokens (0: in all of them). Neutral (1, 0, 0): the row is sampled as it arrived and the
+// slot's count row (AdvanceArgs::pen_counts) is neither read nor written.
+struct SlotPenalty {
+  float repetition, frequency, presence;
+  int32_t window;
+};
+static_assert(sizeof(SlotPenalty) == 16, "penalty blocks are copied as an array");
+
 }  // namespace rwkvtts

@@ -90,7 +90,13 @@ class PhaseSampling(ctypes.Structure):
     _fields_ = [("temperature", ctypes.c_float), ("top_p", ctypes.c_float), ("top_k", ctypes.c_int32)]
 
 
+class Penalties(ctypes.Structure):
+    _fields_ = [("repetition", ctypes.c_float), ("frequency", ctypes.c_float), ("presence", ctypes.c_float),
+                ("window", ctypes.c_int32)]
+
+
 SAMPLING_GLOBAL, SAMPLING_SEMANTIC = 1, 2
+PENALTY_SET = 1
 
 
 class Request(ctypes.Structure):
@@ -104,7 +110,8 @@ class Request(ctypes.Structure):
                 ("use_independent_seeds", ctypes.c_int32), ("global_seed_offset", ctypes.c_uint64),
                 ("semantic_seed_offset", ctypes.c_uint64),
                 ("sampling_set", ctypes.c_int32), ("global_sampling", PhaseSampling),
-                ("semantic_sampling", PhaseSampling), ("pinned_voice", ctypes.c_int32)]
+                ("semantic_sampling", PhaseSampling), ("pinned_voice", ctypes.c_int32),
+                ("penalty_set", ctypes.c_int32), ("penalties", Penalties)]
 
 
 class Result(ctypes.Structure):
@@ -314,6 +321,9 @@ EXPORTS = {
     "rwkvtts_debug_advance_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                                 ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_void_p]),
+    "rwkvtts_debug_advance_pen": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p]),
     # test hook (tests/test_gpu_value_tile.py): the logits the last forward step left on the device
     "rwkvtts_debug_last_logits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "rwkvtts_profile_entry": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,

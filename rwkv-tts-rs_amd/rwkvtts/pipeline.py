@@ -33,6 +33,10 @@ LightweightTtsPipelineArgs.global_sampling / semantic_sampling (no reference cou
 reference carries temperature / top_p / top_k and samples with fixed values) set the token
 generator's temperature, top-p and top-k per phase (runtime.PhaseSampling); a value outside its
 range raises ValueError in the same four entry points before anything is generated.
+LightweightTtsPipelineArgs.penalties (runtime.Penalties; no reference counterpart in the TTS path)
+sets repetition, frequency and presence penalties over the request's own semantic tokens, in all
+five entry points; in the long-form ones every segment gets the same penalties over its own history.
+A value outside its range raises ValueError before anything is generated.
 
 generate_long_speech / stream_long_speech (no reference counterpart: a request of the reference ends
 at 2048 semantic tokens, 41 s, without an error) take a text of any length: segment.split_text cuts
@@ -52,7 +56,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from .properties import convert_standard_properties_to_tokens
-from .runtime import LayeredRandomnessConfig, PhaseSampling, SamplerArgs, TtsBatchRequest
+from .runtime import LayeredRandomnessConfig, Penalties, PhaseSampling, SamplerArgs, TtsBatchRequest
 
 SAMPLE_RATE = 16000
 
@@ -82,6 +86,8 @@ class LightweightTtsPipelineArgs:  # :18-65 (Default)
     # ignored, as in the reference.
     global_sampling: Optional[PhaseSampling] = None
     semantic_sampling: Optional[PhaseSampling] = None
+    # repetition / frequency / presence penalties of the semantic phase (runtime.Penalties; None: none)
+    penalties: Optional[Penalties] = None
     # no reference counterpart: with voice_global_tokens set and voice_semantic_tokens None, a
     # normal-mode request whose 32 global tokens are those (rwkvtts_request.pinned_voice): the same
     # voice again, still with its property tokens. Without it that combination ignores the tokens.
@@ -111,6 +117,11 @@ def check_sampling(args) -> None:
         if not isinstance(ph, PhaseSampling):
             raise ValueError(f"{what} must be a PhaseSampling")
         ph.check(what)
+    pen = getattr(args, "penalties", None)
+    if pen is not None:
+        if not isinstance(pen, Penalties):
+            raise ValueError("penalties must be a Penalties")
+        pen.check()
     check_voice_pin(args)
 
 
@@ -380,7 +391,8 @@ class LightweightTtsPipeline:
         sargs = SamplerArgs(temperature=args.temperature, top_p=args.top_p, top_k=args.top_k,
                             max_tokens=args.max_tokens, seed=args.seed, voice_fidelity=0.8,
                             layered_randomness=LayeredRandomnessConfig(), token_chunk_size=512,
-                            global_sampling=args.global_sampling, semantic_sampling=args.semantic_sampling)
+                            global_sampling=args.global_sampling, semantic_sampling=args.semantic_sampling,
+                            penalties=args.penalties)
         return TtsBatchRequest(self.manager._tokens(text), props, rg, rs, sargs, args.voice_id,
                                pinned_voice=rg is not None and rs is None)
 

@@ -116,6 +116,14 @@ def request_struct(r: "TtsBatchRequest"):
         dst.top_p = float(ph.top_p)
         dst.top_k = k_default if ph.top_k is None else int(ph.top_k)
     q.pinned_voice = 1 if r.pinned_voice else 0
+    pen = r.args.penalties
+    q.penalty_set = 0
+    if pen is not None:
+        q.penalty_set = _ffi.PENALTY_SET
+        q.penalties.repetition = float(pen.repetition)
+        q.penalties.frequency = float(pen.frequency)
+        q.penalties.presence = float(pen.presence)
+        q.penalties.window = int(pen.window)
     return q, keep
 
 
@@ -416,10 +424,38 @@ class PhaseSampling:
 
 
 @dataclasses.dataclass
+class Penalties:
+    """Repetition, frequency and presence penalties of a request's semantic phase
+    (rwkvtts.h rwkvtts_request.penalties; src/sampler_manager.rs:229-292, which the reference's TTS
+    path never calls). Over the last `window` semantic tokens (0: all of them), every token that
+    occurs cnt > 0 times has its logit x adjusted before sampling: cnt times x = x / repetition if
+    x > 0 else x * repetition (per occurrence: it compounds), then x -= frequency * cnt, then
+    x -= presence. repetition in [0.25, 4], frequency and presence in [-8, 8], window in
+    [0, 2048]; (1, 0, 0) changes nothing."""
+    repetition: float = 1.0
+    frequency: float = 0.0
+    presence: float = 0.0
+    window: int = 0
+
+    def check(self, what: str = "penalties") -> "Penalties":
+        """Raises ValueError for a value the engine would refuse (sched.h validate)."""
+        for name, lo, hi in (("repetition", 0.25, 4.0), ("frequency", -8.0, 8.0), ("presence", -8.0, 8.0)):
+            v = getattr(self, name)
+            # (a NaN fails the comparison)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo <= v <= hi:
+                raise ValueError(f"{what}: {name} must be a number in [{lo}, {hi}]")
+        w = self.window
+        if isinstance(w, bool) or not isinstance(w, int) or not 0 <= w <= 2048:
+            raise ValueError(f"{what}: window must be an integer in [0, 2048]")
+        return self
+
+
+@dataclasses.dataclass
 class SamplerArgs:  # src/rwkv_sampler.rs:234-290
     """temperature, top_p and top_k are carried and ignored, as in the reference
     (normal_mode_inference.rs:114-127 fixes the parameters per phase). global_sampling /
-    semantic_sampling (None: the reference's values) are what the decode step honours."""
+    semantic_sampling (None: the reference's values) are what the decode step honours, and so
+    are penalties (None: none)."""
     temperature: float = 1.0
     top_p: float = 0.85
     top_k: int = 0
@@ -430,6 +466,7 @@ class SamplerArgs:  # src/rwkv_sampler.rs:234-290
     token_chunk_size: int = 512
     global_sampling: Optional[PhaseSampling] = None
     semantic_sampling: Optional[PhaseSampling] = None
+    penalties: Optional[Penalties] = None
 
 
 @dataclasses.dataclass

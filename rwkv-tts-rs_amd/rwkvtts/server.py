@@ -31,6 +31,12 @@
   key left out keeps the phase's own 1.0 / 0.95 / 20 global, 80 semantic); anything else a 400. The
   top-level `temperature` and `top_p` keep doing nothing, as in the reference, which parses them
   and then samples with fixed values (normal_mode_inference.rs:114-127).
+* `penalties` in the body of both TTS routes (the reference's sampler_manager.rs has the three
+  penalties, its TTS path never calls them): an object with any of `repetition` (0.25 .. 4.0),
+  `frequency` (-8 .. 8), `presence` (-8 .. 8) and `window` (an integer 0 .. 2048, 0: the whole
+  history) over the request's own semantic tokens (runtime.Penalties; a key left out keeps its
+  neutral 1 / 0 / 0 / 0); anything else a 400. With `long_form` every segment gets the same
+  penalties over its own history. Without the key the routes are unchanged.
 * `long_form`, `segment_tokens` and `voice_tokens` in the body of both TTS routes (no reference
   counterpart: a request of the reference ends at 2048 semantic tokens, 41 s of audio, without an
   error). `long_form`: a JSON bool; true routes the request to pipeline.generate_long_speech /
@@ -88,7 +94,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from .pipeline import LightweightTtsPipelineArgs
-from .runtime import PhaseSampling
+from .runtime import Penalties, PhaseSampling
 
 
 def peak_scale(samples) -> np.float32:
@@ -264,6 +270,14 @@ def _tts_args(body, voice_dir: str):
             sampling[what] = PhaseSampling(**{k: v for k, v in o.items() if v is not None}).check(what)
         except ValueError as e:
             return (400, {"success": False, "error": f"不支持的采样参数: {e}"}), None, None
+    pen = body.get("penalties")
+    if pen is not None:
+        try:
+            if not isinstance(pen, dict) or set(pen) - {"repetition", "frequency", "presence", "window"}:
+                raise ValueError("penalties: an object with any of repetition, frequency, presence, window")
+            sampling["penalties"] = Penalties(**{k: v for k, v in pen.items() if v is not None}).check()
+        except ValueError as e:
+            return (400, {"success": False, "error": f"不支持的惩罚参数: {e}"}), None, None
     long_form = body.get("long_form")
     if long_form is not None and not isinstance(long_form, bool):
         return (400, {"success": False, "error": f"不支持的长文本开关: {long_form} (支持: true, false)"}), None, None

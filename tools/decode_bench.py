@@ -4,6 +4,9 @@ change that keeps the arithmetic must keep the checksum). Usage: decode_bench.py
 [--temperature T] [--top-p P] [--top-k K] [--sampling-slots N]: the semantic phase's sampling
 parameters (runtime.PhaseSampling; an option left out keeps the phase's own value) for the first N
 requests (default: all of them); without any of the three, no request carries parameters.
+[--repetition R] [--frequency F] [--presence P] [--window W] [--penalty-slots N]: the penalties
+(runtime.Penalties) of the first N requests (default: all of them); without any of the first three, no
+request carries penalties. The report adds the most often repeated token's count over all requests.
 Env: DB_B requests (default 32), DB_F16=1 fp16 weights, DB_ZS=1 zero-shot prompts (32 reference
 global tokens + 128 reference semantic tokens per request), DB_QUANT=int8|nf4 (every layer quantised,
 the server's --quant-layers 24 --quant-type ...), DB_FORMS=n (rwkvtts_engine_desc.forms: RWKVTTS_FORM_* bits)."""
@@ -25,12 +28,22 @@ ap.add_argument("--temperature", type=float, default=None)
 ap.add_argument("--top-p", type=float, default=None)
 ap.add_argument("--top-k", type=int, default=None)
 ap.add_argument("--sampling-slots", type=int, default=None)
+ap.add_argument("--repetition", type=float, default=None)
+ap.add_argument("--frequency", type=float, default=None)
+ap.add_argument("--presence", type=float, default=None)
+ap.add_argument("--window", type=int, default=0)
+ap.add_argument("--penalty-slots", type=int, default=None)
 opt = ap.parse_args()
 S, reps = opt.S, opt.reps
 sampling = None
 if opt.temperature is not None or opt.top_p is not None or opt.top_k is not None:
     sampling = rwkvtts.PhaseSampling(**{k: v for k, v in (("temperature", opt.temperature), ("top_p", opt.top_p),
                                                            ("top_k", opt.top_k)) if v is not None}).check("semantic")
+penalties = None
+if opt.repetition is not None or opt.frequency is not None or opt.presence is not None:
+    penalties = rwkvtts.Penalties(**{k: v for k, v in (("repetition", opt.repetition), ("frequency", opt.frequency),
+                                                       ("presence", opt.presence)) if v is not None},
+                                  window=opt.window).check()
 f16 = os.environ.get("DB_F16", "0") == "1"
 B = int(os.environ.get("DB_B", "32"))
 zs = os.environ.get("DB_ZS", "0") == "1"
@@ -53,6 +66,8 @@ for i in range(B):
                                         args=rwkvtts.SamplerArgs(seed=i), fixed_semantic=S, **ref))
     if sampling is not None and i < (B if opt.sampling_slots is None else opt.sampling_slots):
         reqs[-1].args.semantic_sampling = sampling
+    if penalties is not None and i < (B if opt.penalty_slots is None else opt.penalty_slots):
+        reqs[-1].args.penalties = penalties
 for r in range(reps):
     t0 = time.perf_counter()
     out = rt.generate_batch(reqs)
@@ -60,7 +75,9 @@ for r in range(reps):
     st = rt.stats()
     h = hashlib.sha1(repr(out).encode()).hexdigest()[:12]
     us = st['decode_ms'] / max(st['steps'], 1) * 1000
-    print(f"rep {r}: B={B} f16={int(f16)} zs={int(zs)} quant={qt} sampling={sampling} decode {us:.1f} us/step over {st['steps']} steps "
+    top = max((max(np.bincount(np.asarray(s, dtype=np.int64), minlength=1)) for _, s in out if len(s)), default=0)
+    print(f"rep {r}: B={B} f16={int(f16)} zs={int(zs)} quant={qt} sampling={sampling} penalties={penalties} "
+          f"max_repeat={top} decode {us:.1f} us/step over {st['steps']} steps "
           f"({B * 320 / us * 1e6:.0f} samples/s decode-only), "
           f"prefill {st['prefill_ms']:.2f} ms, wall {wall * 1000:.1f} ms, tokens {h}", flush=True)
 rt.close()
