@@ -332,6 +332,50 @@ typedef struct {
 #define RWKVTTS_SAMPLING_SEMANTIC 2
 #define RWKVTTS_PENALTY_SET 1
 
+/* ---- request extension block ----------------------------------------------------------------
+ * rwkvtts_request keeps its size and layout; what a request may ask for beyond it travels in a
+ * block beside it (rwkvtts_generate_batch_ex, rwkvtts_manager_submit_ex). struct_size is
+ * sizeof(rwkvtts_request_ext) as the caller was built with it: a library reads no field that lies
+ * past it, and a request whose struct_size is smaller than the fields it asks the library to read
+ * fails alone with RWKVTTS_EINVAL. No block, or mirostat_set == 0: the request is the plain one.
+ *
+ * Mirostat (mirostat_set bit 0: `mirostat` holds; any other bit fails the request alone), the
+ * reference's one sampler with state from step to step (参考/ai00_server/crates/ai00-core/src/
+ * sampler/mirostat.rs; its TTS path never calls it). SEMANTIC phase only -- the global phase has 32
+ * draws and nothing to adapt over -- where it REPLACES the phase's top-k, top-p and temperature:
+ * each step's distribution is cut at a surprise threshold mu, and mu moves so that the running
+ * surprise of the emitted tokens stays near tau. For one semantic attempt of a slot with threshold
+ * mu, on the row as the sampler receives it, after any penalty adjustment, every operation one f32
+ * operation rounded to nearest:
+ *   1. p[i] exactly as the sampler's softmax: the forbid / EOS mask to -inf, the max, glibc
+ *      expf(x - max), the sequential f32 sum in index order, the divide.
+ *   2. c = #{i : p[i] > 0 and -lg(p[i]) <= mu}, n_pos = #{i : p[i] > 0}, K = min(c + 1, n_pos).
+ *   3. The kept set is the first K ranks in the order (p descending, index ascending). (ai00's
+ *      "first rank whose surprise exceeds the threshold, inclusive", written as a count: it can
+ *      be taken in parallel and stays well defined where lg is not monotone in its last bit.)
+ *   4. cum[r] = the sequential f32 sum over ranks 0..r; S = cum[K-1].
+ *   5. u = r32 * S, one rounded multiply; r32 is the semantic stream's next draw (the same
+ *      draw + attempt indexing as without Mirostat).
+ *   6. The token is the first rank with u <= cum[r] (rank K-1 always satisfies it).
+ *   7. After the attempt whose token is emitted, and only then: s = lg(S) - lg(p_tok);
+ *      e = s - tau; mu = mu - rate * e, a multiply and then a subtract, never an FMA;
+ *      mu = fminf(mu, 4 * tau).
+ * A zero-shot attempt that draws EOS and is re-drawn leaves mu unchanged, and the re-draw uses the
+ * same mu; an EOS that ends the request needs no update. Initial mu = 2 * tau, set at admission.
+ * lg(x) = (float) of the double log2_inline of glibc 2.35's powf (the 16-entry table and the
+ * degree-5 polynomial with its written fmas; csrc/exact_math.h lg2f, one source for host and
+ * kernel; rwkvtts_debug_lg2 exports it).
+ * tau in [0.5, 10], rate in [0.001, 1], both finite; anything else fails the request alone, and so
+ * does Mirostat together with `greedy` or with RWKVTTS_SAMPLING_SEMANTIC (ai00's sampler kinds
+ * exclude each other). It combines with RWKVTTS_SAMPLING_GLOBAL, penalty_set, pinned_voice,
+ * fixed_semantic and zero-shot mode. The threshold is not returned. */
+typedef struct {
+  uint32_t struct_size;  /* sizeof(rwkvtts_request_ext) the caller was built with */
+  int32_t mirostat_set;  /* bit 0: `mirostat` holds; other bits fail the request alone */
+  struct { float tau, rate; } mirostat; /* ai00's defaults: 3.0, 0.1 */
+} rwkvtts_request_ext;
+#define RWKVTTS_MIROSTAT_SET 1
+
 typedef struct {
   int32_t status;         /* 0 ok; <0 this request failed -> (vec![], vec![]) as dbm.rs:466-469
                              (the others of its batch still complete) */
@@ -370,6 +414,11 @@ typedef struct {
  * without sinks enqueues exactly the GPU work rwkvtts_generate_batch enqueues. */
 int rwkvtts_generate_batch_stream(rwkvtts_engine* e, const rwkvtts_request* reqs, int n,
                                   rwkvtts_result* results, const rwkvtts_token_sink* sinks);
+/* rwkvtts_generate_batch_stream with one extension block per request: exts == NULL, a NULL element
+ * or mirostat_set == 0 is that call exactly (it and rwkvtts_generate_batch are wrappers over this
+ * one). The blocks are copied when the call starts. */
+int rwkvtts_generate_batch_ex(rwkvtts_engine* e, const rwkvtts_request* reqs, const rwkvtts_request_ext* const* exts,
+                              int n, rwkvtts_result* results, const rwkvtts_token_sink* sinks);
 
 /* ---- request manager: DynamicBatchManager (dynamic_batch_manager.rs:22-164,185-405) ------ */
 /* The reference collects requests (enqueue_worker: first request, then try_recv up to
@@ -422,6 +471,10 @@ int rwkvtts_manager_wait(rwkvtts_manager* m, uint64_t ticket, int timeout_ms, rw
  * submit can be polled too (its tokens then appear at completion). One thread at a time may be in
  * wait / wait_tokens on a ticket. */
 int rwkvtts_manager_submit_stream(rwkvtts_manager* m, const rwkvtts_request* req, uint64_t* ticket);
+/* submit (stream == 0) or submit_stream (stream != 0) with an extension block, which is copied;
+ * ext == NULL is the plain call (both are wrappers over this one). */
+int rwkvtts_manager_submit_ex(rwkvtts_manager* m, const rwkvtts_request* req, const rwkvtts_request_ext* ext,
+                              int stream, uint64_t* ticket);
 int rwkvtts_manager_wait_tokens(rwkvtts_manager* m, uint64_t ticket, int32_t have_semantic, int timeout_ms,
                                 int32_t* global32, int32_t* n_global, int32_t* semantic_out,
                                 int32_t* n_semantic, int32_t* done, int32_t* status);
@@ -493,6 +546,16 @@ int rwkvtts_debug_advance_ex(rwkvtts_engine* e, const float* logits, int n_rows,
  * first 88 bytes. */
 int rwkvtts_debug_advance_pen(rwkvtts_engine* e, const float* logits, int n_rows, const void* rows, int exact,
                               int n_steps, int32_t* out_tok, int32_t* out_used, int32_t* out_phase);
+/* The same with per-row Mirostat: `rows` points to n_rows records of 120 bytes, the 104 above
+ * (struct_size = 120) followed by float tau, rate, the initial mu and int32 on (0: the row is
+ * sampled as rwkvtts_debug_advance_pen samples its first 104 bytes; 1: tau and rate in the ranges
+ * of rwkvtts_request_ext::mirostat, mu finite). Up to 256 launches on the same logits; out_mu
+ * [n_steps][n_rows] receives every row's mu after each launch (the initial mu where on == 0). */
+int rwkvtts_debug_advance_miro(rwkvtts_engine* e, const float* logits, int n_rows, const void* rows, int exact,
+                               int n_steps, int32_t* out_tok, int32_t* out_used, int32_t* out_phase, float* out_mu);
+/* Host self-test entry point: out[i] = lg(x[i]) of the Mirostat contract above, for positive
+ * finite x (subnormals included). Needs no engine and no GPU. */
+void rwkvtts_debug_lg2(const float* x, int n, float* out);
 
 /* Test hook, not part of the drop-in surface: rows [0, n_rows) x head_rows of the logits that the
  * engine's last forward step left on the device (n_rows <= the engine's row capacity; a decode step

@@ -147,6 +147,18 @@ int rwkvtts_debug_advance_pen(rwkvtts_engine* e, const float* logits, int n_rows
   })
 }
 
+// The same with per-row Mirostat blocks (engine.h DebugAdvanceRowMiro); also returns every mu.
+int rwkvtts_debug_advance_miro(rwkvtts_engine* e, const float* logits, int n_rows, const void* rows, int exact,
+                               int n_steps, int32_t* out_tok, int32_t* out_used, int32_t* out_phase, float* out_mu) {
+  RT_CHECK(e && logits && rows && out_tok && out_used && out_phase && out_mu, RWKVTTS_EINVAL,
+           "debug_advance_miro: bad arguments");
+  LOCK(e);
+  GUARD({
+    return e->eng.debug_advance_miro(logits, n_rows, (const DebugAdvanceRowMiro*)rows, exact, n_steps, out_tok, out_used,
+                                     out_phase, out_mu);
+  })
+}
+
 // Test hook (not part of the drop-in surface): rows [0, n_rows) x head_rows of the logits the engine's
 // last forward step left on the device (the head GEMM's split-K slabs summed in order)
 int rwkvtts_debug_last_logits(rwkvtts_engine* e, int n_rows, int head_rows, float* out) {
@@ -155,34 +167,31 @@ int rwkvtts_debug_last_logits(rwkvtts_engine* e, int n_rows, int head_rows, floa
   GUARD({ return e->eng.debug_last_logits(n_rows, head_rows, out); })
 }
 
-int rwkvtts_generate_batch(rwkvtts_engine* e, const rwkvtts_request* reqs, int n,
-                           rwkvtts_result* results) {
+// The one generate entry: exts == NULL, a NULL element or mirostat_set == 0 is the plain request;
+// sinks == NULL: no token progress.
+int rwkvtts_generate_batch_ex(rwkvtts_engine* e, const rwkvtts_request* reqs, const rwkvtts_request_ext* const* exts,
+                              int n, rwkvtts_result* results, const rwkvtts_token_sink* sinks) {
   RT_CHECK(e && reqs && results && n >= 0, RWKVTTS_EINVAL, "generate_batch: bad arguments");
   LOCK(e);
   GUARD({
-    const int rc = e->eng.generate(reqs, n, results);
+    const int rc = e->eng.generate(reqs, n, results, sinks, exts);
     if (rc != RWKVTTS_OK)
       for (int i = 0; i < n; ++i) {  // dynamic_batch_manager.rs:387-392: errors -> empty results
-        results[i].status = rc;
+        results[i].status = rc;      // (every sink has had its done call with this status: Engine::generate)
         results[i].n_global = results[i].n_semantic = 0;
       }
     return rc;
   })
 }
 
+int rwkvtts_generate_batch(rwkvtts_engine* e, const rwkvtts_request* reqs, int n,
+                           rwkvtts_result* results) {
+  return rwkvtts_generate_batch_ex(e, reqs, nullptr, n, results, nullptr);
+}
+
 int rwkvtts_generate_batch_stream(rwkvtts_engine* e, const rwkvtts_request* reqs, int n, rwkvtts_result* results,
                                   const rwkvtts_token_sink* sinks) {
-  RT_CHECK(e && reqs && results && n >= 0, RWKVTTS_EINVAL, "generate_batch_stream: bad arguments");
-  LOCK(e);
-  GUARD({
-    const int rc = e->eng.generate(reqs, n, results, sinks);
-    if (rc != RWKVTTS_OK)
-      for (int i = 0; i < n; ++i) {  // (every sink has had its done call with this status: Engine::generate)
-        results[i].status = rc;
-        results[i].n_global = results[i].n_semantic = 0;
-      }
-    return rc;
-  })
+  return rwkvtts_generate_batch_ex(e, reqs, nullptr, n, results, sinks);
 }
 
 int rwkvtts_get_stats(rwkvtts_engine* e, rwkvtts_stats* out) {

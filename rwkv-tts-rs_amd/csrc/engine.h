@@ -39,7 +39,14 @@ struct DebugAdvanceRowPen {
   float repetition, frequency, presence;
   int32_t window;
 };
-static_assert(sizeof(DebugAdvanceRow) == 72 && sizeof(DebugAdvanceRowEx) == 88 && sizeof(DebugAdvanceRowPen) == 104,
+// rwkvtts_debug_advance_miro: the row above (struct_size = 120) plus its Mirostat block
+struct DebugAdvanceRowMiro {
+  DebugAdvanceRowPen pen;
+  float tau, rate, mu;
+  int32_t on;
+};
+static_assert(sizeof(DebugAdvanceRow) == 72 && sizeof(DebugAdvanceRowEx) == 88 && sizeof(DebugAdvanceRowPen) == 104 &&
+                  sizeof(DebugAdvanceRowMiro) == 120,
               "test-hook row layouts");
 
 struct LayerW {
@@ -61,6 +68,7 @@ constexpr int kLookahead = 8;  // decode steps queued per host poll of the contr
 // One request in flight through Engine::serve. The request's arrays stay valid until finish().
 struct Job {
   rwkvtts_request req{};
+  HeldExt ext;  // the request's extension block by value (sched.h), or none
   rwkvtts_result* res = nullptr;
   void* user = nullptr;  // const rwkvtts_token_sink*: the request's token progress (null: none)
 };
@@ -102,7 +110,9 @@ class Engine {
   int sample(const float* logits, int n_rows, int row_len, const rwkvtts_sample_args* args,
              rwkvtts_rng* const* rngs, int32_t* out, float* dbg_host = nullptr);
   // sinks: one per request (null: none), called on this thread between units of work
-  int generate(const rwkvtts_request* reqs, int n, rwkvtts_result* res, const rwkvtts_token_sink* sinks = nullptr);
+  // exts: one extension block per request (null, or a null element: none)
+  int generate(const rwkvtts_request* reqs, int n, rwkvtts_result* res, const rwkvtts_token_sink* sinks = nullptr,
+               const rwkvtts_request_ext* const* exts = nullptr);
   // Test hook (rwkvtts_debug_advance): k_advance itself -- advance_prep + the prepped
   // sample_block, the certified fast path or the exact walk -- on caller-given logit rows and
   // per-row controller states, for n_steps consecutive launches on the same rows.
@@ -114,13 +124,19 @@ class Engine {
   // rwkvtts_debug_advance_pen: rows carry penalties too; up to max_steps launches
   int debug_advance_pen(const float* logits, int n_rows, const struct DebugAdvanceRowPen* rows, int exact, int n_steps,
                         int32_t* out_tok, int32_t* out_used, int32_t* out_phase, int max_steps = 256);
+  // rwkvtts_debug_advance_miro: rows carry a Mirostat block too; out_mu (may be null): every row's mu
+  // after each launch
+  int debug_advance_miro(const float* logits, int n_rows, const struct DebugAdvanceRowMiro* rows, int exact, int n_steps,
+                         int32_t* out_tok, int32_t* out_used, int32_t* out_phase, float* out_mu, int max_steps = 256);
   // Test hook (rwkvtts_debug_last_logits): rows [0, n_rows) of the logits the last forward step left on
   // the device (its head GEMM's split-K slabs summed in order, as infer returns them)
   int debug_last_logits(int n_rows, int head_rows, float* out);
   // Continuous batching until `src` is closed and every admitted job has finished.
   int serve(JobSource& src);
   // Checks a request before admission; fills `why` and returns false for a bad one.
-  bool validate(const rwkvtts_request& q, std::string& why) const { return rwkvtts::validate(q, dims.n_vocab, why); }
+  bool validate(const rwkvtts_request& q, std::string& why, const rwkvtts_request_ext* ext = nullptr) const {
+    return rwkvtts::validate(q, dims.n_vocab, why, ext);
+  }
   int max_slots() const { return S_; }
   // whether this engine holds its device's persistent-launch slot (claim_persistent)
   bool persistent() const { return att_persist_ || ffn_persist_; }
@@ -162,7 +178,7 @@ class Engine {
   int finish_unit(const Unit& u, ServeState& st);
   int accumulate_stamps(const Unit& u);
   int launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_from_ctrl, bool advance,
-                     bool sampling_params = false);
+                     int ctrl_kind = 0);  // AdvanceArgs::params
   int upload_plan(const StepPlan& p);
   void prof_begin(hipEvent_t* ev);
   void prof_end(const char* name, hipEvent_t ev);
@@ -303,6 +319,7 @@ class Engine {
   std::vector<int> par_host_;
   std::vector<SlotCtrl> ctrl_stage_;  // [S] host copy of each admitted slot's initial control block
   std::vector<SlotPenalty> pen_stage_;  // [S] and of its penalties
+  std::vector<SlotMiro> miro_stage_;    // [S] and of its Mirostat block
   // per-step tables
   uint32_t* d_tok_ = nullptr;
   int4* d_rows_ = nullptr;
@@ -321,6 +338,7 @@ class Engine {
   int32_t* d_sem_ = nullptr;
   SlotPenalty* d_pen_ = nullptr;      // [S] AdvanceArgs::pen
   uint16_t* d_pen_counts_ = nullptr;  // [S][kPenCounts] AdvanceArgs::pen_counts
+  SlotMiro* d_miro_ = nullptr;        // [S] AdvanceArgs::miro
   SlotCtrl* h_ctrl_ = nullptr;  // pinned mirror
   // token progress: pinned [2 unit buffers][S][RWKVTTS_SEMANTIC_LIMIT], token i of a slot at index i;
   // allocated when the first request with a sink is admitted (engines that never see one: no change)

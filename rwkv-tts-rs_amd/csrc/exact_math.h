@@ -71,16 +71,12 @@ __host__ __device__ inline double powf_log2_tab(int i) {  // 2 i: invc, 2 i + 1:
     0x1.886e6037841edp-1, 0x1.88e9c2c1b9ff8p-2,  0x1.767dcf5534862p-1, 0x1.ce0a44eb17bccp-2};
   return kTab[i];
 }
-template <typename Tab>
-__host__ __device__ inline float glibc_powf_t(float x, float y, const Tab& tab) {  // tab: as glibc_expf_t's
+// log2_inline of that powf: log2 of the positive normal number whose bits are ix (a subnormal is
+// normalised by the caller first, as powf does), in double: the table entry (1/c, log2 c) of the
+// interval that holds the mantissa and the degree-5 polynomial in r = z / c - 1 with the fused
+// operations glibc's build has. glibc_powf_t and lg2f share this one copy, on host and device.
+__host__ __device__ inline __attribute__((always_inline)) double powf_log2_inline(uint32_t ix) {
 #pragma clang fp contract(off)  // only the fused operations glibc's build has, written as fma
-  uint32_t ix = __builtin_bit_cast(uint32_t, x);
-  if (ix < 0x00800000u) {  // subnormal x: normalise so that the exponent becomes negative
-    ix = __builtin_bit_cast(uint32_t, x * 0x1p23f);
-    ix &= 0x7fffffffu;
-    ix -= 23u << 23;
-  }
-  // log2_inline
   const uint32_t tmp = ix - 0x3f330000u;
   const int i = (int)((tmp >> (23 - 4)) % 16u);
   const uint32_t top = tmp & 0xff800000u;
@@ -99,6 +95,27 @@ __host__ __device__ inline float glibc_powf_t(float x, float y, const Tab& tab) 
   double q = __builtin_fma(A4, r, y0);
   q = __builtin_fma(p, r2, q);
   yl = __builtin_fma(yl, r4, q);
+  return yl;
+}
+// powf's normalisation of a subnormal x, so that the exponent becomes negative
+__host__ __device__ inline __attribute__((always_inline)) uint32_t powf_norm_bits(float x) {
+  uint32_t ix = __builtin_bit_cast(uint32_t, x);
+  if (ix < 0x00800000u) {
+    ix = __builtin_bit_cast(uint32_t, x * 0x1p23f);
+    ix &= 0x7fffffffu;
+    ix -= 23u << 23;
+  }
+  return ix;
+}
+// lg(x) of the Mirostat contract (rwkvtts.h): log2 of a positive finite x, subnormals included, as
+// the double above rounded once to f32. The same source on the host (rwkvtts_debug_lg2) and in
+// the decode-step controller, so the two agree bit for bit by construction.
+__host__ __device__ inline float lg2f(float x) { return (float)powf_log2_inline(powf_norm_bits(x)); }
+
+template <typename Tab>
+__host__ __device__ inline float glibc_powf_t(float x, float y, const Tab& tab) {  // tab: as glibc_expf_t's
+#pragma clang fp contract(off)  // only the fused operations glibc's build has, written as fma
+  const double yl = powf_log2_inline(powf_norm_bits(x));
   const double ylogx = (double)y * yl;
   if (((__builtin_bit_cast(uint64_t, ylogx) >> 47) & 0xffff) >= (__builtin_bit_cast(uint64_t, 126.0) >> 47)) {
     if (ylogx > 0x1.fffffffd1d571p+6) return __builtin_inff();  // overflow (outside the domain)

@@ -83,6 +83,16 @@ const Rccl& rccl() {
 
 class Manager;
 
+// Job::ext takes the request's extension block by value (sched.h HeldExt). Written against the
+// member, not the type: a host-only stand-in for engine.h whose Job has no such member (the
+// sanitizer build of this file) compiles the second overload, and its requests carry no block.
+template <typename J>
+auto hold_ext(J* j, const rwkvtts_request_ext* e, int) -> decltype(j->ext.hold(e), void()) {
+  j->ext.hold(e);
+}
+template <typename J>
+void hold_ext(J*, const rwkvtts_request_ext*, long) {}
+
 struct MJob : Job {
   uint64_t ticket = 0;
   std::vector<int32_t> text, props, ref_g, ref_s;  // owned copies of the request arrays
@@ -363,7 +373,7 @@ class Manager {
     j->prog_sem = first + count;
   }
 
-  int submit(const rwkvtts_request& q, uint64_t* ticket, bool stream = false) {
+  int submit(const rwkvtts_request& q, const rwkvtts_request_ext* ext, uint64_t* ticket, bool stream = false) {
     MJob* j = new MJob();
     j->mgr = this;
     if (stream) {
@@ -379,6 +389,7 @@ class Manager {
     copy(q.ref_global, q.n_ref_global, j->ref_g);
     copy(q.ref_semantic, q.n_ref_semantic, j->ref_s);
     j->req = q;
+    hold_ext(static_cast<Job*>(j), ext, 0);
     j->req.text_tokens = j->text.empty() ? nullptr : j->text.data();
     j->req.property_tokens = j->props.empty() ? nullptr : j->props.data();
     // presence (Some / None) of the reference token sets is part of the request's meaning
@@ -705,14 +716,19 @@ int rwkvtts_manager_destroy(rwkvtts_manager* m) {
   return RWKVTTS_OK;
 }
 
-int rwkvtts_manager_submit(rwkvtts_manager* m, const rwkvtts_request* req, uint64_t* ticket) {
+int rwkvtts_manager_submit_ex(rwkvtts_manager* m, const rwkvtts_request* req, const rwkvtts_request_ext* ext, int stream,
+                              uint64_t* ticket) {
   RT_CHECK(m && req && ticket, RWKVTTS_EINVAL, "manager_submit: null argument");
   try {
-    return m->m.submit(*req, ticket);
+    return m->m.submit(*req, ext, ticket, stream != 0);
   } catch (const std::exception& ex) {
     set_error(ex.what());
     return RWKVTTS_ENOMEM;
   }
+}
+
+int rwkvtts_manager_submit(rwkvtts_manager* m, const rwkvtts_request* req, uint64_t* ticket) {
+  return rwkvtts_manager_submit_ex(m, req, nullptr, 0, ticket);
 }
 
 int rwkvtts_manager_wait(rwkvtts_manager* m, uint64_t ticket, int timeout_ms, rwkvtts_result* out) {
@@ -721,13 +737,7 @@ int rwkvtts_manager_wait(rwkvtts_manager* m, uint64_t ticket, int timeout_ms, rw
 }
 
 int rwkvtts_manager_submit_stream(rwkvtts_manager* m, const rwkvtts_request* req, uint64_t* ticket) {
-  RT_CHECK(m && req && ticket, RWKVTTS_EINVAL, "manager_submit_stream: null argument");
-  try {
-    return m->m.submit(*req, ticket, true);
-  } catch (const std::exception& ex) {
-    set_error(ex.what());
-    return RWKVTTS_ENOMEM;
-  }
+  return rwkvtts_manager_submit_ex(m, req, nullptr, 1, ticket);
 }
 
 int rwkvtts_manager_wait_tokens(rwkvtts_manager* m, uint64_t ticket, int32_t have_semantic, int timeout_ms,

@@ -42,7 +42,9 @@ struct AdvanceArgs {
   // 0: every row's slot samples with the reference's (temperature 1.0, top_p 0.95) and a top-k in
   // [1, kFastTopK] -- k_advance, the two values compiled in; 1: some slot carries its own
   // (SlotCtrl::temp_* / top_p_*) or another top-k -- k_advance_params reads them per row and
-  // carries every path. Both give a row of the first kind the same token.
+  // carries every path. Both give a row of the first kind the same token. 2: some slot runs
+  // Mirostat (miro[slot].on) -- k_advance_miro, k_advance_params with the Mirostat path for the
+  // semantic rows of such slots; every other row gets what k_advance_params gives it.
   int params;
   const SlotPenalty* pen;  // [S] penalties of each slot (read by k_advance_params only)
   // [S][kPenCounts] occurrences of each semantic id in a penalised slot's history window
@@ -51,6 +53,9 @@ struct AdvanceArgs {
   // and the id that leaves the window is uncounted. Rows of slots without penalties are never
   // touched. May be null when no row's slot is penalised.
   uint16_t* pen_counts;
+  // [S] Mirostat block of each slot (read, and its mu updated, by k_advance_miro only; may be null
+  // when params < 2)
+  SlotMiro* miro;
 };
 constexpr int kPenCounts = RWKVTTS_EOS_TOKEN;  // ids [0, 8192): EOS never enters the history
 

@@ -2036,7 +2036,172 @@ __device__ __attribute__((always_inline)) void advance_penalise(float* raw, uint
   }
 }
 
-template <bool kParams>
+// Mirostat on a prepared semantic row (rwkvtts.h rwkvtts_request_ext::mirostat, steps 1-6; the
+// caller makes step 7's update). On entry p holds e = glibc expf(l - max) and fred[21] the draw r,
+// as advance_prep leaves them. (1) p = e / sum with the exact sequential f32 sum, as the general
+// path of sample_block divides. (2) c = #{p > 0 and -lg(p) <= mu} and n_pos, counted in parallel
+// from contiguous chunks, K = min(c + 1, n_pos). (3) the K largest in the order (p descending,
+// index ascending): for K <= kFastK the bound-and-rank selection of sample_block's top-k step,
+// which leaves sorted (p, index) keys; for a larger K, or where that bound is 0, the bisection on
+// the bits of the K-th largest p, then the K surviving VALUES sorted without indices (up to 8193
+// of them fit the keys / dscan / list regions, as in the top-p step's value sort). (4)-(6) wave 0
+// walks the ranks twice, 64 values in lanes per round: S = cum[K-1], then u = r * S as one rounded
+// multiply and the first rank with u <= cum[rank]. On the value path the token is then found from
+// (value v at that rank, j = rank - #{p > v}): the j-th index in ascending order with p == v,
+// which is where (p descending, index ascending) puts it. Leaves fred[22] = S and fred[23] = the
+// token's p for the update. Returns the token, an index < n.
+template <int NT>
+__device__ __attribute__((always_inline)) int sample_miro(const SampleSmem& sm, int n, float mu, uint64_t* stamps) {
+  constexpr int NW = NT / 64;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float sum = exact_seq_sum<NT>(sm, n, stamps);
+  if (sum > 0.0f)
+    for (int i = tid; i < n; i += NT) sm.p[i] = sm.p[i] / sum;
+  __syncthreads();
+  const int chunk = (n + NT - 1) / NT;
+  const int b = min(n, tid * chunk), e = min(n, b + chunk);
+  int pk = 0;  // n_pos << 16 | c (both <= n <= kSampleMaxN < 2^16)
+  for (int i = b; i < e; ++i) {
+    const float v = sm.p[i];
+    if (v > 0.0f) pk += 0x10000 + (-lg2f(v) <= mu ? 1 : 0);
+  }
+  pk = wave_sum_i(pk);
+  if (lane == 0) sm.ired[8 + wave] = pk;
+  __syncthreads();
+  int tot = 0;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) tot += sm.ired[8 + w];
+  const int npos = tot >> 16, K = min((tot & 0xFFFF) + 1, npos);
+  __syncthreads();  // ired[8 ..) is written again below
+  if (K <= 0 || n > kSampleMaxVals) {  // no positive entry (a row of -inf or NaN): nothing to rank
+    if (tid == 0) sm.fred[22] = sm.fred[23] = 1.0f;
+    __syncthreads();
+    return 0;
+  }
+  bool byval = true;
+  if (K <= kFastK) {
+    // lower bound L of the K-th largest p: min over waves of the ceil(K / NW)-th largest
+    // thread-local maximum, as in sample_block's top-k step
+    float lm = -1.0f;  // every p >= 0
+    for (int i = b; i < e; ++i) lm = fmaxf(lm, sm.p[i]);
+    const int kw = (K + NW - 1) / NW;
+    int gt = 0, ge = 0;
+#pragma unroll 16
+    for (int j = 0; j < 64; ++j) {
+      const float o = readlane_f(lm, j);
+      gt += o > lm ? 1 : 0;
+      ge += o >= lm ? 1 : 0;
+    }
+    const uint64_t selm = __ballot(gt < kw && kw <= ge);
+    const float vw = readlane_f(lm, __builtin_ctzll(selm));
+    if (lane == 0) sm.fred[wave] = vw;
+    __syncthreads();
+    float Lm = sm.fred[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) Lm = fminf(Lm, sm.fred[w]);
+    const float L = fmaxf(Lm, 0.0f);
+    int cnt = 0;
+    for (int i = b; i < e; ++i) cnt += sm.p[i] >= L;
+    int tc;
+    int off = block_excl_scan<NT>(cnt, sm.scan, &tc);
+    if (tc <= sm.cap) {
+      for (int i = b; i < e; ++i)
+        if (sm.p[i] >= L) sm.keys[off++] = pkey(sm.p[i], i);
+      __syncthreads();
+      if (tc <= NT) {  // rank sort (keys are unique)
+        const uint64_t kq = tid < tc ? sm.keys[tid] : 0ull;
+        int rank = 0;
+        if (tid < tc)
+          for (int j = 0; j < tc; ++j) rank += sm.keys[j] > kq ? 1 : 0;
+        __syncthreads();
+        if (tid < tc) sm.keys[rank] = kq;
+        __syncthreads();
+      } else {
+        int M = 1;
+        while (M < tc) M <<= 1;
+        for (int q = tc + tid; q < M; q += NT) sm.keys[q] = 0ull;
+        __syncthreads();
+        bitonic_desc<NT>(sm.keys, M);
+      }
+      byval = false;
+    }
+  }
+  uint32_t* vals = (uint32_t*)sm.keys;
+  if (byval) {
+    // bisection on the bits of the K-th largest p (p >= 0: bits order as values): #{p >= lo} >= K
+    // and #{p >= hi} < K throughout, so at hi = lo + 1 the K-th largest is t = lo
+    uint32_t lo = 0, hi = 0x7F800000u;
+    int it = 0;
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + ((hi - lo) >> 1);
+      int c = 0;
+      for (int i = tid; i < n; i += NT) c += __builtin_bit_cast(uint32_t, sm.p[i]) >= mid;
+      c = wave_sum_i(c);
+      if (lane == 0) sm.ired[8 + (it & 1) * NW + wave] = c;
+      __syncthreads();
+      const int* r4 = sm.ired + 8 + (it & 1) * NW;
+      int t4 = 0;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) t4 += r4[w];
+      if (t4 >= K) lo = mid;
+      else hi = mid;
+      ++it;
+    }
+    // the survivors' values: every p > t (tc of them), and K - tc copies of t (which of the entries equal
+    // to t survive, the lowest indices, matters only to the token search below)
+    const float t = __builtin_bit_cast(float, lo);
+    int cnt = 0;
+    for (int i = b; i < e; ++i) cnt += sm.p[i] > t;
+    int tc;
+    int off = block_excl_scan<NT>(cnt, sm.scan, &tc);
+    for (int i = b; i < e; ++i)
+      if (sm.p[i] > t) vals[off++] = __builtin_bit_cast(uint32_t, sm.p[i]);
+    for (int q = tc + tid; q < K; q += NT) vals[q] = lo;
+    __syncthreads();
+    sort_desc_u32<NT>(vals, K);
+  }
+  if (tid < 64) {
+    auto val = [&](int q) {
+      return __builtin_bit_cast(float, byval ? vals[q] : (uint32_t)(sm.keys[q] >> 32));
+    };
+    float S = 0.0f;  // (+0 pads the last round: s + 0 == s exactly)
+    for (int q0 = 0; q0 < K; q0 += 64) S = add64(S, q0 + lane < K ? val(q0 + lane) : 0.0f);
+    const float u = __fmul_rn(sm.fred[21], S);
+    int rank = -1;
+    float cum = 0.0f;
+    for (int q0 = 0; q0 < K && rank < 0; q0 += 64) {
+      const bool in = q0 + lane < K;
+      float tot2;
+      const float pre = prefix64(cum, in ? val(q0 + lane) : 0.0f, &tot2);
+      const uint64_t hit = __ballot(in && u <= pre);
+      if (hit) rank = q0 + __builtin_ctzll(hit);
+      cum = tot2;
+    }
+    if (rank < 0) rank = K - 1;  // (u <= S = cum[K-1]: not reached)
+    if (tid == 0) {
+      sm.fred[22] = S;
+      sm.fred[23] = val(rank);
+      sm.ired[24] = rank;
+      sm.ired[5] = byval ? 0 : (int)min(0xFFFFFFFFu - (uint32_t)sm.keys[rank], (uint32_t)(n - 1));
+    }
+  }
+  __syncthreads();
+  if (byval) {
+    const float v = sm.fred[23];
+    int pk2 = 0;  // #{p == v} << 16 | #{p > v}
+    for (int i = b; i < e; ++i) pk2 += (sm.p[i] > v ? 1 : 0) + (sm.p[i] == v ? 0x10000 : 0);
+    int tot2;
+    const int ex = block_excl_scan<NT>(pk2, sm.scan, &tot2);
+    int j = sm.ired[24] - (tot2 & 0xFFFF) - (ex >> 16);  // among this thread's entries equal to v
+    if (j >= 0 && j < (pk2 >> 16))
+      for (int i = b; i < e; ++i)
+        if (sm.p[i] == v && j-- == 0) sm.ired[5] = i;
+    __syncthreads();
+  }
+  return sm.ired[5];
+}
+
+template <bool kParams, bool kMiro = false>
 __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a, char* smem) {
   constexpr int NT = kSampleThreads;
   const int row = blockIdx.x;
@@ -2085,16 +2250,32 @@ __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a
       advance_penalise<NT, PT>(raw, pen_cnt, c->n_sem, rep, freq, pres);
     }
   }
+  // Mirostat (k_advance_miro, semantic rows of a slot whose block is on): it replaces the phase's
+  // top-k, top-p and temperature; mu is read here by every thread, before the barriers of the
+  // first attempt, and written once below by the lane that writes sem_out. advance_prep collects
+  // no top-k candidates for such a row (top_k 0).
+  bool miro = false;
+  float mu = 0.0f;
+  if constexpr (kMiro) {
+    miro = !glob && a.miro[slot].on != 0;
+    mu = a.miro[slot].mu;
+  }
+  const int prep_k = (kMiro && miro) ? 0 : top_k;
   // attempt 1 (zero-shot only): EOS drawn while the window rule does not stop the request ->
   // re-draw with EOS masked from the same logits and the next draw (zero_shot_inference.rs:287-297)
   int id = 0, status;
   uint64_t used = 1;
   bool stop = false, masked = eos_masked;
   for (int attempt = 0; attempt < 2; ++attempt) {
-    if (glob) advance_prep<NT, 4096, PT>(raw, sm, false, top_k, key, draw + attempt, c->gblk, &c->gblk_id, stamps);
-    else advance_prep<NT, NS, PT>(raw, sm, masked, top_k, key, draw + attempt, c->sblk, &c->sblk_id, stamps);
-    id = sample_block<NT, kParams>(sm, n, temp, top_p, top_k, key, draw + attempt, false, nullptr, &status, stamps,
-                          a.cert != 0, true);
+    if (glob) advance_prep<NT, 4096, PT>(raw, sm, false, prep_k, key, draw + attempt, c->gblk, &c->gblk_id, stamps);
+    else advance_prep<NT, NS, PT>(raw, sm, masked, prep_k, key, draw + attempt, c->sblk, &c->sblk_id, stamps);
+    if (kMiro && miro) {
+      status = 0;
+      id = sample_miro<NT>(sm, n, mu, stamps);
+    } else {
+      id = sample_block<NT, kParams>(sm, n, temp, top_p, top_k, key, draw + attempt, false, nullptr, &status, stamps,
+                                     a.cert != 0, true);
+    }
     used = attempt + 1;
     if (glob || id != RWKVTTS_EOS_TOKEN) break;
     if (c->mode == 0) {
@@ -2144,6 +2325,17 @@ __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a
           }
         }
       }
+      if constexpr (kMiro) {
+        // the threshold follows the surprise of the token just emitted (contract step 7), never
+        // that of an EOS that was re-drawn or that ends the request: s = lg(S) - lg(p_tok),
+        // mu -= rate * (s - tau) as a multiply and a subtract, capped at 4 tau
+        if (miro) {
+          SlotMiro* m = a.miro + slot;
+          const float tau = m->tau;
+          const float err = __fsub_rn(__fsub_rn(lg2f(sm.fred[22]), lg2f(sm.fred[23])), tau);
+          m->mu = fminf(__fsub_rn(mu, __fmul_rn(m->rate, err)), __fmul_rn(4.0f, tau));
+        }
+      }
       c->n_sem++;
       c->next_token = id;
       if (c->n_sem >= c->sem_limit) c->phase = kPhDone;
@@ -2165,11 +2357,21 @@ __global__ __launch_bounds__(kSampleThreads, 2) void k_advance_params(AdvanceArg
   tl_end(a.tl);
 }
 
+// and for launches in which some slot runs Mirostat: a third instantiation, so that k_advance_params
+// keeps its registers and instruction count
+__global__ __launch_bounds__(kSampleThreads, 2) void k_advance_miro(AdvanceArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  tl_begin(a.tl);
+  advance_body<true, true>(a, smem);
+  tl_end(a.tl);
+}
+
 int launch_advance(const AdvanceArgs& a0, hipStream_t st, int cert) {
   AdvanceArgs a = a0;
   a.cert = cert;  // 0: always walk the exact sequential sum (RWKVTTS_FORM_EXACT_SAMPLER)
   const size_t lds = smem_bytes<kSampleThreads>(RWKVTTS_EOS_TOKEN + 1);
-  if (a.params) RT_LAUNCH(k_advance_params, dim3(a.n_rows), dim3(kSampleThreads), lds, st, a);
+  if (a.params >= 2) RT_LAUNCH(k_advance_miro, dim3(a.n_rows), dim3(kSampleThreads), lds, st, a);
+  else if (a.params) RT_LAUNCH(k_advance_params, dim3(a.n_rows), dim3(kSampleThreads), lds, st, a);
   else RT_LAUNCH(k_advance, dim3(a.n_rows), dim3(kSampleThreads), lds, st, a);
   return a.n_rows;
 }

@@ -5,6 +5,7 @@
 // header), so tests/native/sched_main.cpp checks them on a CPU.
 #pragma once
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -37,6 +38,9 @@ struct StepPlan {
   // some active request samples with parameters of its own (Active::own_sampling): the step's
   // controller reads every row's from its control block (AdvanceArgs::params)
   bool sampling_params = false;
+  // some active request runs Mirostat (Active::mirostat): the step's controller is the one that
+  // reads the slots' Mirostat blocks (AdvanceArgs::params == 2); implies sampling_params
+  bool mirostat = false;
 };
 
 // A request decoding in a state slot.
@@ -50,6 +54,7 @@ struct Active {
   bool zero_shot = false;
   bool pinned = false;        // Admission::pinned: normal mode, the 32 global tokens given
   bool own_sampling = false;  // Admission::own_sampling
+  bool mirostat = false;      // Admission::mirostat
   // token progress (Job::user): semantic tokens handed to the sink so far, and per unit buffer the
   // end of the range of this slot's d_sem_ that the unit copied to h_prog_
   const rwkvtts_token_sink* sink = nullptr;
@@ -62,8 +67,33 @@ inline bool is_zero_shot(const rwkvtts_request& q) { return q.ref_global != null
 // pinned voice: a normal-mode request whose global phase is replaced by the 32 ids of ref_global
 inline bool is_pinned(const rwkvtts_request& q) { return q.pinned_voice != 0; }
 
-// Checks a request before admission; fills `why` and returns false for a bad one.
-inline bool validate(const rwkvtts_request& q, int n_vocab, std::string& why) {
+// The extension block as a job carries it, by value: the first min(struct_size, sizeof) bytes of
+// the caller's block, the rest zero, struct_size still the caller's (validate judges it), and
+// whether there was a block at all.
+struct HeldExt {
+  rwkvtts_request_ext ext{};
+  bool present = false;
+  void hold(const rwkvtts_request_ext* e) {
+    memset(&ext, 0, sizeof(ext));
+    present = e != nullptr;
+    if (e) {
+      uint32_t sz = 0;
+      memcpy(&sz, e, sizeof(sz));
+      memcpy(&ext, e, std::min<size_t>(std::max<size_t>(sz, sizeof(sz)), sizeof(ext)));
+    }
+  }
+  const rwkvtts_request_ext* ptr() const { return present ? &ext : nullptr; }
+};
+inline HeldExt ext_copy(const rwkvtts_request_ext* e) {
+  HeldExt h;
+  h.hold(e);
+  return h;
+}
+inline bool has_mirostat(const rwkvtts_request_ext* ext) { return ext && (ext->mirostat_set & RWKVTTS_MIROSTAT_SET); }
+
+// Checks a request (and its extension block, if any) before admission; fills `why` and returns
+// false for a bad one.
+inline bool validate(const rwkvtts_request& q, int n_vocab, std::string& why, const rwkvtts_request_ext* ext = nullptr) {
   auto ids_ok = [&](const int32_t* p, int n, int lo, int hi, const char* what) {
     if (n < 0 || (n > 0 && !p)) {
       why = std::string(what) + ": bad array";
@@ -131,6 +161,26 @@ inline bool validate(const rwkvtts_request& q, int n_vocab, std::string& why) {
     else if (p.window < 0 || p.window > RWKVTTS_SEMANTIC_LIMIT) why = "penalties: window must be in [0, 2048]";
     if (!why.empty()) return false;
   }
+  if (ext) {  // a field is read only where the caller's struct_size covers it
+    const size_t have = ext->struct_size;
+    if (have < offsetof(rwkvtts_request_ext, mirostat_set) + sizeof(ext->mirostat_set)) {
+      why = "ext: struct_size does not cover mirostat_set";
+      return false;
+    }
+    if (ext->mirostat_set & ~RWKVTTS_MIROSTAT_SET) {
+      why = "mirostat_set: unknown bits";
+      return false;
+    }
+    if (ext->mirostat_set) {  // (NaN fails every comparison)
+      if (have < offsetof(rwkvtts_request_ext, mirostat) + sizeof(ext->mirostat)) why = "ext: struct_size does not cover mirostat";
+      else if (!(ext->mirostat.tau >= 0.5f && ext->mirostat.tau <= 10.0f)) why = "mirostat: tau must be in [0.5, 10]";
+      else if (!(ext->mirostat.rate >= 0.001f && ext->mirostat.rate <= 1.0f)) why = "mirostat: rate must be in [0.001, 1]";
+      else if (q.greedy) why = "mirostat and greedy exclude each other";
+      else if (q.sampling_set & RWKVTTS_SAMPLING_SEMANTIC)
+        why = "mirostat replaces the semantic phase's top-k, top-p and temperature: semantic_sampling excludes it";
+      if (!why.empty()) return false;
+    }
+  }
   return true;
 }
 
@@ -159,11 +209,22 @@ struct Admission {
   // the parameters from the control block and carries the general path for every top-k. Also set
   // by a penalty that is not neutral (pen): that controller alone applies penalties.
   bool own_sampling;
+  // the slot's Mirostat block: {tau, rate, mu = 2 tau, on = 1} with rwkvtts_request_ext::mirostat,
+  // all zero without. mirostat (== miro.on) routes the slot's steps to the controller that reads
+  // the block (StepPlan::mirostat) and sets own_sampling with it.
+  SlotMiro miro;
+  bool mirostat;
 };
 
 // (1, 0, 0): the semantic rows are sampled as they arrive
 inline bool penalties_neutral(const SlotPenalty& p) {
   return p.repetition == 1.0f && p.frequency == 0.0f && p.presence == 0.0f;
+}
+
+inline bool any_mirostat(const std::vector<Active>& act) {
+  bool any = false;
+  for (const Active& a : act) any |= a.mirostat;
+  return any;
 }
 
 inline bool any_own_sampling(const std::vector<Active>& act) {
@@ -173,7 +234,7 @@ inline bool any_own_sampling(const std::vector<Active>& act) {
 }
 
 // entropy: the seed of a request without one (dynamic_batch_manager.rs:491-499, from_entropy)
-inline Admission admission_of(const rwkvtts_request& q, uint64_t entropy) {
+inline Admission admission_of(const rwkvtts_request& q, uint64_t entropy, const rwkvtts_request_ext* ext = nullptr) {
   Admission a;
   a.zero_shot = is_zero_shot(q);
   a.pinned = is_pinned(q);
@@ -211,6 +272,10 @@ inline Admission admission_of(const rwkvtts_request& q, uint64_t entropy) {
   if (q.penalty_set & RWKVTTS_PENALTY_SET)
     a.pen = SlotPenalty{q.penalties.repetition, q.penalties.frequency, q.penalties.presence, q.penalties.window};
   a.own_sampling |= !penalties_neutral(a.pen);
+  a.miro = SlotMiro{0.0f, 0.0f, 0.0f, 0};
+  a.mirostat = has_mirostat(ext);
+  if (a.mirostat) a.miro = SlotMiro{ext->mirostat.tau, ext->mirostat.rate, 2.0f * ext->mirostat.tau, 1};
+  a.own_sampling |= a.mirostat;
   c.fixed = q.fixed_semantic > 0;
   c.sem_limit = sem_limit_of(q);
   if (a.zero_shot) {
@@ -310,6 +375,7 @@ inline StepPlan mixed_plan(std::vector<Active>& act, int chunk, int n_vocab) {
   }
   p.head_rows = head_rows_of(act, n_vocab);
   p.sampling_params = any_own_sampling(act);
+  p.mirostat = any_mirostat(act);
   for (Active& a : act) a.advances += !a.in_prompt();  // one advance per logits row
   return p;
 }
@@ -320,6 +386,7 @@ inline StepPlan decode_plan(const std::vector<Active>& act) {
   p.tok_from_ctrl = true;
   p.advance = true;
   p.sampling_params = any_own_sampling(act);
+  p.mirostat = any_mirostat(act);
   for (const Active& a : act) append_decode_row(p, a.slot);
   return p;
 }

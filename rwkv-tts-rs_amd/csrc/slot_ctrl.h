@@ -62,4 +62,16 @@ struct SlotPenalty {
 };
 static_assert(sizeof(SlotPenalty) == 16, "penalty blocks are copied as an array");
 
+// Mirostat state of a slot's semantic phase (rwkvtts.h rwkvtts_request_ext::mirostat), in a third
+// array beside the control blocks (AdvanceArgs::miro) for the same reason. The host writes the
+// block at every admission, in stream order before the slot's first step -- on = 0 for a request
+// without Mirostat, so nothing survives from the slot's previous owner, mu = 2 tau for one with
+// it; after that k_advance_miro alone moves mu, once per emitted semantic token. The address is
+// fixed, so the step stays capturable in the decode graph.
+struct SlotMiro {
+  float tau, rate, mu;
+  int32_t on;
+};
+static_assert(sizeof(SlotMiro) == 16, "Mirostat blocks are copied as an array");
+
 }  // namespace rwkvtts

@@ -150,3 +150,11 @@ extern "C" float rwkvtts_debug_expf(float x) { return rwkvtts::glibc_expf(x); }
 extern "C" void rwkvtts_debug_powf(const float* x, const float* y, int n, float* out) {
   for (int i = 0; i < n; ++i) out[i] = rwkvtts::glibc_powf(x[i], y[i]);
 }
+// Host self-test hooks of the Mirostat contract (tests/miro_ref.py): lg of rwkvtts.h, the same
+// source the decode-step controller runs (exact_math.h lg2f), and the sampler's expf for arrays.
+extern "C" void rwkvtts_debug_lg2(const float* x, int n, float* out) {
+  for (int i = 0; i < n; ++i) out[i] = rwkvtts::lg2f(x[i]);
+}
+extern "C" void rwkvtts_debug_expf_n(const float* x, int n, float* out) {
+  for (int i = 0; i < n; ++i) out[i] = rwkvtts::glibc_expf(x[i]);
+}

@@ -5,7 +5,7 @@ from ._ffi import (EOS_TOKEN, GLOBAL_TOKEN_OFFSET, HOP, N_GLOBAL, SAMPLE_RATE, S
                    SPECIAL_TOKEN_OFFSET, TAG_0, TAG_1, TAG_2, RwkvTtsError)
 from .properties import convert_standard_properties_to_tokens  # noqa: F401
 from .runtime import (DynamicBatchConfig, DynamicBatchManager, LayeredRandomnessConfig, RnnInput,  # noqa: F401
-                      Penalties, PhaseSampling, RnnInputBatch, RnnOption, SamplerArgs, SharedRwkvRuntime, StdRng, TtsBatchRequest,
+                      Mirostat, Penalties, PhaseSampling, RnnInputBatch, RnnOption, SamplerArgs, SharedRwkvRuntime, StdRng, TtsBatchRequest,
                       sample_logits_with_top_p_k)
 from . import weights  # noqa: F401
 # streaming (audio during decode): BiCodecDetokenizer.halo / decode_windows, SharedRwkvRuntime.generate_batch(on_tokens=),

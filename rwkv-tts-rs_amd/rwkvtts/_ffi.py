@@ -97,6 +97,16 @@ class Penalties(ctypes.Structure):
 
 SAMPLING_GLOBAL, SAMPLING_SEMANTIC = 1, 2
 PENALTY_SET = 1
+MIROSTAT_SET = 1
+
+
+class MirostatParams(ctypes.Structure):
+    _fields_ = [("tau", ctypes.c_float), ("rate", ctypes.c_float)]
+
+
+class RequestExt(ctypes.Structure):
+    """rwkvtts_request_ext: what a request asks for beyond rwkvtts_request, whose layout stays."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("mirostat_set", ctypes.c_int32), ("mirostat", MirostatParams)]
 
 
 class Request(ctypes.Structure):
@@ -297,6 +307,11 @@ EXPORTS = {
     # streaming: token progress
     "rwkvtts_generate_batch_stream": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Request), ctypes.c_int,
                                                      ctypes.POINTER(Result), ctypes.POINTER(TokenSink)]),
+    "rwkvtts_generate_batch_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Request),
+                                                 ctypes.POINTER(ctypes.POINTER(RequestExt)), ctypes.c_int,
+                                                 ctypes.POINTER(Result), ctypes.POINTER(TokenSink)]),
+    "rwkvtts_manager_submit_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Request), ctypes.POINTER(RequestExt),
+                                                 ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
     "rwkvtts_manager_submit_stream": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Request),
                                                      ctypes.POINTER(ctypes.c_uint64)]),
     "rwkvtts_manager_wait_tokens": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int,
@@ -324,6 +339,11 @@ EXPORTS = {
     "rwkvtts_debug_advance_pen": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                                  ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p]),
+    "rwkvtts_debug_advance_miro": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                  ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p]),
+    # host self-test hook of the Mirostat contract (tests/miro_ref.py): lg for arrays
+    "rwkvtts_debug_lg2": (None, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     # test hook (tests/test_gpu_value_tile.py): the logits the last forward step left on the device
     "rwkvtts_debug_last_logits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "rwkvtts_profile_entry": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,

@@ -37,6 +37,11 @@ LightweightTtsPipelineArgs.penalties (runtime.Penalties; no reference counterpar
 sets repetition, frequency and presence penalties over the request's own semantic tokens, in all
 five entry points; in the long-form ones every segment gets the same penalties over its own history.
 A value outside its range raises ValueError before anything is generated.
+LightweightTtsPipelineArgs.mirostat (runtime.Mirostat; the reference has the sampler in its ai00
+server and never calls it from its TTS path) samples the semantic phase with Mirostat in all five
+entry points; in the long-form ones every segment gets the same tau and rate and a threshold of its
+own. A bad value, or Mirostat together with semantic_sampling, raises ValueError before anything
+is generated.
 
 generate_long_speech / stream_long_speech (no reference counterpart: a request of the reference ends
 at 2048 semantic tokens, 41 s, without an error) take a text of any length: segment.split_text cuts
@@ -56,7 +61,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from .properties import convert_standard_properties_to_tokens
-from .runtime import LayeredRandomnessConfig, Penalties, PhaseSampling, SamplerArgs, TtsBatchRequest
+from .runtime import LayeredRandomnessConfig, Mirostat, Penalties, PhaseSampling, SamplerArgs, TtsBatchRequest
 
 SAMPLE_RATE = 16000
 
@@ -88,6 +93,8 @@ class LightweightTtsPipelineArgs:  # :18-65 (Default)
     semantic_sampling: Optional[PhaseSampling] = None
     # repetition / frequency / presence penalties of the semantic phase (runtime.Penalties; None: none)
     penalties: Optional[Penalties] = None
+    # Mirostat in the semantic phase (runtime.Mirostat; None: top-k / top-p / temperature as before)
+    mirostat: Optional[Mirostat] = None
     # no reference counterpart: with voice_global_tokens set and voice_semantic_tokens None, a
     # normal-mode request whose 32 global tokens are those (rwkvtts_request.pinned_voice): the same
     # voice again, still with its property tokens. Without it that combination ignores the tokens.
@@ -122,6 +129,14 @@ def check_sampling(args) -> None:
         if not isinstance(pen, Penalties):
             raise ValueError("penalties must be a Penalties")
         pen.check()
+    miro = getattr(args, "mirostat", None)
+    if miro is not None:
+        if not isinstance(miro, Mirostat):
+            raise ValueError("mirostat must be a Mirostat")
+        miro.check()
+        if getattr(args, "semantic_sampling", None) is not None:
+            raise ValueError("mirostat replaces the semantic phase's top-k, top-p and temperature: "
+                             "semantic_sampling excludes it")
     check_voice_pin(args)
 
 
@@ -392,7 +407,7 @@ class LightweightTtsPipeline:
                             max_tokens=args.max_tokens, seed=args.seed, voice_fidelity=0.8,
                             layered_randomness=LayeredRandomnessConfig(), token_chunk_size=512,
                             global_sampling=args.global_sampling, semantic_sampling=args.semantic_sampling,
-                            penalties=args.penalties)
+                            penalties=args.penalties, mirostat=args.mirostat)
         return TtsBatchRequest(self.manager._tokens(text), props, rg, rs, sargs, args.voice_id,
                                pinned_voice=rg is not None and rs is None)
 

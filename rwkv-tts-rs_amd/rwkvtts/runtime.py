@@ -127,6 +127,32 @@ def request_struct(r: "TtsBatchRequest"):
     return q, keep
 
 
+def request_ext(r: "TtsBatchRequest"):
+    """-> the request's _ffi.RequestExt (rwkvtts_request_ext), or None when it asks for nothing
+    beyond _ffi.Request: such a request goes through the entry points without a block."""
+    miro = getattr(r.args, "mirostat", None)
+    if miro is None:
+        return None
+    x = _ffi.RequestExt()
+    x.struct_size = ctypes.sizeof(_ffi.RequestExt)
+    x.mirostat_set = _ffi.MIROSTAT_SET
+    x.mirostat.tau = float(miro.tau)
+    x.mirostat.rate = float(miro.rate)
+    return x
+
+
+def _ext_array(requests):
+    """(the rwkvtts_request_ext* array of a batch or None when no request has a block, keep-alive)"""
+    exts = [request_ext(r) for r in requests]
+    if all(x is None for x in exts):
+        return None, exts
+    arr = (ctypes.POINTER(_ffi.RequestExt) * len(exts))()
+    for i, x in enumerate(exts):
+        if x is not None:
+            arr[i] = ctypes.pointer(x)
+    return arr, exts
+
+
 _EMPTY = ctypes.c_int32(0)
 
 
@@ -318,7 +344,11 @@ class SharedRwkvRuntime:
             sb = np.zeros(_ffi.SEMANTIC_LIMIT, dtype=np.int32)
             sem_bufs.append(sb)
             res[i].semantic_tokens = sb.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-        check(lib().rwkvtts_generate_batch(self._h, reqs, n, res), "generate_batch")
+        exts, _keep_exts = _ext_array(requests)
+        if exts is None:
+            check(lib().rwkvtts_generate_batch(self._h, reqs, n, res), "generate_batch")
+        else:
+            check(lib().rwkvtts_generate_batch_ex(self._h, reqs, exts, n, res, None), "generate_batch_ex")
         out, self.last_status = _unpack_results(res, sem_bufs)
         return out
 
@@ -353,7 +383,11 @@ class SharedRwkvRuntime:
             if cbs[i] is not None:
                 fns.append(make(i, cbs[i]))
                 sinks[i].fn = fns[-1]
-        rc = lib().rwkvtts_generate_batch_stream(self._h, reqs, n, res, sinks)
+        exts, _keep_exts = _ext_array(requests)
+        if exts is None:
+            rc = lib().rwkvtts_generate_batch_stream(self._h, reqs, n, res, sinks)
+        else:
+            rc = lib().rwkvtts_generate_batch_ex(self._h, reqs, exts, n, res, sinks)
         if raised:
             raise raised[0]
         check(rc, "generate_batch_stream")
@@ -451,6 +485,28 @@ class Penalties:
 
 
 @dataclasses.dataclass
+class Mirostat:
+    """Mirostat sampling of a request's semantic phase (rwkvtts.h rwkvtts_request_ext.mirostat;
+    参考/ai00_server/crates/ai00-core/src/sampler/mirostat.rs, which the reference's TTS path never
+    calls; the defaults are its MirostatParams'). Each step's distribution is cut at a surprise
+    threshold that the decode step moves so that the running surprise (-log2 p of the emitted
+    tokens) stays near `tau`; `rate` is the step of that correction. It replaces the semantic
+    phase's top-k, top-p and temperature (semantic_sampling and greedy exclude it) and leaves the
+    global phase alone. tau in [0.5, 10], rate in [0.001, 1]."""
+    tau: float = 3.0
+    rate: float = 0.1
+
+    def check(self, what: str = "mirostat") -> "Mirostat":
+        """Raises ValueError for a value the engine would refuse (sched.h validate)."""
+        for name, lo, hi in (("tau", 0.5, 10.0), ("rate", 0.001, 1.0)):
+            v = getattr(self, name)
+            # (a NaN fails the comparison)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo <= v <= hi:
+                raise ValueError(f"{what}: {name} must be a number in [{lo}, {hi}]")
+        return self
+
+
+@dataclasses.dataclass
 class SamplerArgs:  # src/rwkv_sampler.rs:234-290
     """temperature, top_p and top_k are carried and ignored, as in the reference
     (normal_mode_inference.rs:114-127 fixes the parameters per phase). global_sampling /
@@ -467,6 +523,8 @@ class SamplerArgs:  # src/rwkv_sampler.rs:234-290
     global_sampling: Optional[PhaseSampling] = None
     semantic_sampling: Optional[PhaseSampling] = None
     penalties: Optional[Penalties] = None
+    # Mirostat in the semantic phase (None: the phase samples with top-k / top-p / temperature)
+    mirostat: Optional[Mirostat] = None
 
 
 @dataclasses.dataclass
@@ -599,8 +657,13 @@ class DynamicBatchManager:
         t = ctypes.c_uint64()
         self._enter()
         try:
-            fn = lib().rwkvtts_manager_submit_stream if stream else lib().rwkvtts_manager_submit
-            check(fn(self._h, ctypes.byref(q), ctypes.byref(t)), "manager_submit")
+            ext = request_ext(request)
+            if ext is None:
+                fn = lib().rwkvtts_manager_submit_stream if stream else lib().rwkvtts_manager_submit
+                check(fn(self._h, ctypes.byref(q), ctypes.byref(t)), "manager_submit")
+            else:  # (the manager copies the block)
+                check(lib().rwkvtts_manager_submit_ex(self._h, ctypes.byref(q), ctypes.byref(ext), 1 if stream else 0,
+                                                      ctypes.byref(t)), "manager_submit_ex")
         finally:
             self._leave()
         return int(t.value)

@@ -37,6 +37,12 @@
   history) over the request's own semantic tokens (runtime.Penalties; a key left out keeps its
   neutral 1 / 0 / 0 / 0); anything else a 400. With `long_form` every segment gets the same
   penalties over its own history. Without the key the routes are unchanged.
+* `mirostat` in the body of both TTS routes (the reference's ai00 server has the sampler, its TTS
+  path never calls it): an object with any of `tau` (0.5 .. 10, default 3.0) and `rate`
+  (0.001 .. 1, default 0.1) (runtime.Mirostat); it replaces the semantic phase's top-k, top-p and
+  temperature, so together with `semantic_sampling` it is a 400, as is anything else. With
+  `long_form` every segment gets the same values and a threshold of its own. Without the key the
+  routes are unchanged.
 * `long_form`, `segment_tokens` and `voice_tokens` in the body of both TTS routes (no reference
   counterpart: a request of the reference ends at 2048 semantic tokens, 41 s of audio, without an
   error). `long_form`: a JSON bool; true routes the request to pipeline.generate_long_speech /
@@ -94,7 +100,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from .pipeline import LightweightTtsPipelineArgs
-from .runtime import Penalties, PhaseSampling
+from .runtime import Mirostat, Penalties, PhaseSampling
 
 
 def peak_scale(samples) -> np.float32:
@@ -278,6 +284,17 @@ def _tts_args(body, voice_dir: str):
             sampling["penalties"] = Penalties(**{k: v for k, v in pen.items() if v is not None}).check()
         except ValueError as e:
             return (400, {"success": False, "error": f"不支持的惩罚参数: {e}"}), None, None
+    miro = body.get("mirostat")
+    if miro is not None:
+        try:
+            if not isinstance(miro, dict) or set(miro) - {"tau", "rate"}:
+                raise ValueError("mirostat: an object with any of tau, rate")
+            if "semantic_sampling" in sampling:
+                raise ValueError("mirostat replaces the semantic phase's top-k, top-p and temperature: "
+                                 "semantic_sampling excludes it")
+            sampling["mirostat"] = Mirostat(**{k: v for k, v in miro.items() if v is not None}).check()
+        except ValueError as e:
+            return (400, {"success": False, "error": f"不支持的 Mirostat 参数: {e}"}), None, None
     long_form = body.get("long_form")
     if long_form is not None and not isinstance(long_form, bool):
         return (400, {"success": False, "error": f"不支持的长文本开关: {long_form} (支持: true, false)"}), None, None

@@ -1,5 +1,6 @@
-"""Compile each HIP source for gfx950 with the resource-usage remarks and list every kernel's VGPRs and
-scratch bytes per lane; exit 1 if any kernel spills to scratch. Usage: check_spills.py [files...]"""
+"""Compile each HIP source for gfx950 with the resource-usage remarks and list every kernel's VGPRs,
+scratch bytes per lane and SGPR / VGPR spill counts; exit 1 if any kernel spills to scratch or spills
+VGPRs. Usage: check_spills.py [files...]"""
 import os
 import re
 import subprocess
@@ -18,17 +19,19 @@ def usage(src):
     for name, body in re.findall(r"Function Name: (\S+)(.*?)(?=Function Name:|\Z)", out, re.S):
         v = re.search(r"VGPRs: (\d+)", body)
         sc = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", body)
-        res[name] = (int(v.group(1)) if v else -1, int(sc.group(1)) if sc else -1)
+        ss, vs = re.search(r"SGPRs Spill: (\d+)", body), re.search(r"VGPRs Spill: (\d+)", body)
+        res[name] = (int(v.group(1)) if v else -1, int(sc.group(1)) if sc else -1, int(ss.group(1)) if ss else -1,
+                     int(vs.group(1)) if vs else -1)
     return res
 
 
 def main(files):
     bad = []
     for f in files:
-        for k, (v, sc) in usage(f).items():
-            if sc > 0:
-                bad.append((f, k, v, sc))
-            print(f"{f:16s} {v:4d} VGPRs {sc:5d} B scratch  {k[:90]}")
+        for k, (v, sc, ss, vs) in usage(f).items():
+            if sc > 0 or vs > 0:
+                bad.append((f, k, v, sc, vs))
+            print(f"{f:16s} {v:4d} VGPRs {sc:5d} B scratch {ss:4d} SGPR spills {vs:3d} VGPR spills  {k[:90]}")
     if bad:
         print("SPILLS:", bad)
     return 1 if bad else 0

@@ -7,6 +7,9 @@ requests (default: all of them); without any of the three, no request carries pa
 [--repetition R] [--frequency F] [--presence P] [--window W] [--penalty-slots N]: the penalties
 (runtime.Penalties) of the first N requests (default: all of them); without any of the first three, no
 request carries penalties. The report adds the most often repeated token's count over all requests.
+[--mirostat-tau T] [--mirostat-rate R] [--mirostat-slots N]: Mirostat (runtime.Mirostat; either option
+selects it, the other keeps its default 3.0 / 0.1) in the semantic phase of the first N requests
+(default: all of them); it excludes the three sampling options.
 Env: DB_B requests (default 32), DB_F16=1 fp16 weights, DB_ZS=1 zero-shot prompts (32 reference
 global tokens + 128 reference semantic tokens per request), DB_QUANT=int8|nf4 (every layer quantised,
 the server's --quant-layers 24 --quant-type ...), DB_FORMS=n (rwkvtts_engine_desc.forms: RWKVTTS_FORM_* bits)."""
@@ -33,6 +36,9 @@ ap.add_argument("--frequency", type=float, default=None)
 ap.add_argument("--presence", type=float, default=None)
 ap.add_argument("--window", type=int, default=0)
 ap.add_argument("--penalty-slots", type=int, default=None)
+ap.add_argument("--mirostat-tau", type=float, default=None)
+ap.add_argument("--mirostat-rate", type=float, default=None)
+ap.add_argument("--mirostat-slots", type=int, default=None)
 opt = ap.parse_args()
 S, reps = opt.S, opt.reps
 sampling = None
@@ -44,6 +50,12 @@ if opt.repetition is not None or opt.frequency is not None or opt.presence is no
     penalties = rwkvtts.Penalties(**{k: v for k, v in (("repetition", opt.repetition), ("frequency", opt.frequency),
                                                        ("presence", opt.presence)) if v is not None},
                                   window=opt.window).check()
+mirostat = None
+if opt.mirostat_tau is not None or opt.mirostat_rate is not None:
+    if sampling is not None:
+        ap.error("--mirostat-* replaces the semantic phase's top-k, top-p and temperature")
+    mirostat = rwkvtts.Mirostat(**{k: v for k, v in (("tau", opt.mirostat_tau), ("rate", opt.mirostat_rate))
+                                   if v is not None}).check()
 f16 = os.environ.get("DB_F16", "0") == "1"
 B = int(os.environ.get("DB_B", "32"))
 zs = os.environ.get("DB_ZS", "0") == "1"
@@ -68,6 +80,8 @@ for i in range(B):
         reqs[-1].args.semantic_sampling = sampling
     if penalties is not None and i < (B if opt.penalty_slots is None else opt.penalty_slots):
         reqs[-1].args.penalties = penalties
+    if mirostat is not None and i < (B if opt.mirostat_slots is None else opt.mirostat_slots):
+        reqs[-1].args.mirostat = mirostat
 for r in range(reps):
     t0 = time.perf_counter()
     out = rt.generate_batch(reqs)
@@ -76,7 +90,7 @@ for r in range(reps):
     h = hashlib.sha1(repr(out).encode()).hexdigest()[:12]
     us = st['decode_ms'] / max(st['steps'], 1) * 1000
     top = max((max(np.bincount(np.asarray(s, dtype=np.int64), minlength=1)) for _, s in out if len(s)), default=0)
-    print(f"rep {r}: B={B} f16={int(f16)} zs={int(zs)} quant={qt} sampling={sampling} penalties={penalties} "
+    print(f"rep {r}: B={B} f16={int(f16)} zs={int(zs)} quant={qt} sampling={sampling} penalties={penalties} mirostat={mirostat} "
           f"max_repeat={top} decode {us:.1f} us/step over {st['steps']} steps "
           f"({B * 320 / us * 1e6:.0f} samples/s decode-only), "
           f"prefill {st['prefill_ms']:.2f} ms, wall {wall * 1000:.1f} ms, tokens {h}", flush=True)
