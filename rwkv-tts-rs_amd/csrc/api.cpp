@@ -34,6 +34,30 @@ struct rwkvtts_engine {
     return RWKVTTS_EINVAL;                               \
   }
 
+// The k_advance test hooks that take rows narrower than Engine::debug_advance's: `size` = 72 / 88 /
+// 104 bytes per row (engine.h DebugAdvanceRow / Ex / Pen). Each row is widened to a full row -- the
+// caller's bytes over the neutral defaults: temperature 1.0, top-p 0.95, penalties (1, 0, 0, 0),
+// Mirostat all zero. The 72-byte row has no struct_size and must carry a top-k; the others state
+// their own size.
+static int debug_advance_narrow(rwkvtts_engine* e, const float* logits, int n_rows, const void* rows, size_t size,
+                                int exact, int n_steps, int32_t* out_tok, int32_t* out_used, int32_t* out_phase,
+                                int max_steps) {
+  RT_CHECK(n_rows > 0 && n_rows <= 4096, RWKVTTS_EINVAL, "debug_advance: bad sizes");
+  DebugAdvanceRowMiro neutral{};
+  neutral.pen.ex.temperature = 1.0f;
+  neutral.pen.ex.top_p = 0.95f;
+  neutral.pen.repetition = 1.0f;
+  std::vector<DebugAdvanceRowMiro> full(n_rows, neutral);
+  for (int i = 0; i < n_rows; ++i) {
+    DebugAdvanceRowEx& x = full[i].pen.ex;
+    memcpy(&full[i], (const char*)rows + i * size, size);
+    RT_CHECK(size == sizeof(DebugAdvanceRow) ? x.row.top_k > 0 : x.struct_size == size, RWKVTTS_EINVAL,
+             "debug_advance: bad row");
+    x.struct_size = (uint32_t)sizeof(DebugAdvanceRowMiro);
+  }
+  return e->eng.debug_advance(logits, n_rows, full.data(), exact, n_steps, out_tok, out_used, out_phase, nullptr, max_steps);
+}
+
 extern "C" {
 
 const char* rwkvtts_last_error(void) { return g_last_error.c_str(); }
@@ -120,8 +144,8 @@ int rwkvtts_debug_advance(rwkvtts_engine* e, const float* logits, int n_rows, co
   RT_CHECK(e && logits && rows && out_tok && out_used && out_phase, RWKVTTS_EINVAL, "debug_advance: bad arguments");
   LOCK(e);
   GUARD({
-    return e->eng.debug_advance(logits, n_rows, (const DebugAdvanceRow*)rows, exact, n_steps, out_tok, out_used,
-                                out_phase);
+    return debug_advance_narrow(e, logits, n_rows, rows, sizeof(DebugAdvanceRow), exact, n_steps, out_tok, out_used,
+                                out_phase, 64);
   })
 }
 
@@ -131,8 +155,8 @@ int rwkvtts_debug_advance_ex(rwkvtts_engine* e, const float* logits, int n_rows,
   RT_CHECK(e && logits && rows && out_tok && out_used && out_phase, RWKVTTS_EINVAL, "debug_advance_ex: bad arguments");
   LOCK(e);
   GUARD({
-    return e->eng.debug_advance_ex(logits, n_rows, (const DebugAdvanceRowEx*)rows, exact, n_steps, out_tok, out_used,
-                                   out_phase);
+    return debug_advance_narrow(e, logits, n_rows, rows, sizeof(DebugAdvanceRowEx), exact, n_steps, out_tok, out_used,
+                                out_phase, 64);
   })
 }
 
@@ -142,8 +166,8 @@ int rwkvtts_debug_advance_pen(rwkvtts_engine* e, const float* logits, int n_rows
   RT_CHECK(e && logits && rows && out_tok && out_used && out_phase, RWKVTTS_EINVAL, "debug_advance_pen: bad arguments");
   LOCK(e);
   GUARD({
-    return e->eng.debug_advance_pen(logits, n_rows, (const DebugAdvanceRowPen*)rows, exact, n_steps, out_tok, out_used,
-                                    out_phase);
+    return debug_advance_narrow(e, logits, n_rows, rows, sizeof(DebugAdvanceRowPen), exact, n_steps, out_tok, out_used,
+                                out_phase, 256);
   })
 }
 
@@ -154,8 +178,8 @@ int rwkvtts_debug_advance_miro(rwkvtts_engine* e, const float* logits, int n_row
            "debug_advance_miro: bad arguments");
   LOCK(e);
   GUARD({
-    return e->eng.debug_advance_miro(logits, n_rows, (const DebugAdvanceRowMiro*)rows, exact, n_steps, out_tok, out_used,
-                                     out_phase, out_mu);
+    return e->eng.debug_advance(logits, n_rows, (const DebugAdvanceRowMiro*)rows, exact, n_steps, out_tok, out_used,
+                                out_phase, out_mu, 256);
   })
 }
 

@@ -115,19 +115,10 @@ class Engine {
                const rwkvtts_request_ext* const* exts = nullptr);
   // Test hook (rwkvtts_debug_advance): k_advance itself -- advance_prep + the prepped
   // sample_block, the certified fast path or the exact walk -- on caller-given logit rows and
-  // per-row controller states, for n_steps consecutive launches on the same rows.
-  int debug_advance(const float* logits, int n_rows, const struct DebugAdvanceRow* rows, int exact, int n_steps,
-                    int32_t* out_tok, int32_t* out_used, int32_t* out_phase);
-  // rwkvtts_debug_advance_ex: rows carry their own temperature / top-p, top_k may be 0
-  int debug_advance_ex(const float* logits, int n_rows, const struct DebugAdvanceRowEx* rows, int exact, int n_steps,
-                       int32_t* out_tok, int32_t* out_used, int32_t* out_phase);
-  // rwkvtts_debug_advance_pen: rows carry penalties too; up to max_steps launches
-  int debug_advance_pen(const float* logits, int n_rows, const struct DebugAdvanceRowPen* rows, int exact, int n_steps,
-                        int32_t* out_tok, int32_t* out_used, int32_t* out_phase, int max_steps = 256);
-  // rwkvtts_debug_advance_miro: rows carry a Mirostat block too; out_mu (may be null): every row's mu
-  // after each launch
-  int debug_advance_miro(const float* logits, int n_rows, const struct DebugAdvanceRowMiro* rows, int exact, int n_steps,
-                         int32_t* out_tok, int32_t* out_used, int32_t* out_phase, float* out_mu, int max_steps = 256);
+  // per-row controller states, for n_steps <= max_steps consecutive launches on the same rows. Full
+  // rows (api.cpp widens the narrower ones); out_mu (may be null): every row's mu after each launch.
+  int debug_advance(const float* logits, int n_rows, const struct DebugAdvanceRowMiro* rows, int exact, int n_steps,
+                    int32_t* out_tok, int32_t* out_used, int32_t* out_phase, float* out_mu, int max_steps);
   // Test hook (rwkvtts_debug_last_logits): rows [0, n_rows) of the logits the last forward step left on
   // the device (its head GEMM's split-K slabs summed in order, as infer returns them)
   int debug_last_logits(int n_rows, int head_rows, float* out);
@@ -178,7 +169,7 @@ class Engine {
   int finish_unit(const Unit& u, ServeState& st);
   int accumulate_stamps(const Unit& u);
   int launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_from_ctrl, bool advance,
-                     int ctrl_kind = 0);  // AdvanceArgs::params
+                     AdvanceKind kind = kAdvFixed);  // AdvanceArgs::kind
   int upload_plan(const StepPlan& p);
   void prof_begin(hipEvent_t* ev);
   void prof_end(const char* name, hipEvent_t ev);
@@ -318,8 +309,7 @@ class Engine {
   int* slot_par_ = nullptr;  // [S]
   std::vector<int> par_host_;
   std::vector<SlotCtrl> ctrl_stage_;  // [S] host copy of each admitted slot's initial control block
-  std::vector<SlotPenalty> pen_stage_;  // [S] and of its penalties
-  std::vector<SlotMiro> miro_stage_;    // [S] and of its Mirostat block
+  std::vector<SlotSampling> samp_stage_;  // [S] and of its sampling block
   // per-step tables
   uint32_t* d_tok_ = nullptr;
   int4* d_rows_ = nullptr;
@@ -336,9 +326,8 @@ class Engine {
   // controller
   SlotCtrl* d_ctrl_ = nullptr;
   int32_t* d_sem_ = nullptr;
-  SlotPenalty* d_pen_ = nullptr;      // [S] AdvanceArgs::pen
+  SlotSampling* d_samp_ = nullptr;    // [S] AdvanceArgs::samp
   uint16_t* d_pen_counts_ = nullptr;  // [S][kPenCounts] AdvanceArgs::pen_counts
-  SlotMiro* d_miro_ = nullptr;        // [S] AdvanceArgs::miro
   SlotCtrl* h_ctrl_ = nullptr;  // pinned mirror
   // token progress: pinned [2 unit buffers][S][RWKVTTS_SEMANTIC_LIMIT], token i of a slot at index i;
   // allocated when the first request with a sink is admitted (engines that never see one: no change)
@@ -352,7 +341,7 @@ class Engine {
   uint32_t* d_keys_ = nullptr;
   uint64_t* d_draws_ = nullptr;
   int32_t* d_out_ = nullptr;
-  // graphs keyed by (R, head_rows)
+  // graphs keyed by (R, head_rows / kind / advance packed: run_step)
   std::map<std::pair<int, int>, hipGraphExec_t> graphs_;
   std::vector<std::pair<std::string, hipEvent_t>> pending_prof_;
   std::vector<void*> allocs_;

@@ -356,8 +356,7 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
   RT_OK(alloc(&slot_par_, (size_t)S_));
   par_host_.assign(S_, 0);
   ctrl_stage_.assign(S_, SlotCtrl{});
-  pen_stage_.assign(S_, SlotPenalty{1.0f, 0.0f, 0.0f, 0});
-  miro_stage_.assign(S_, SlotMiro{0.0f, 0.0f, 0.0f, 0});
+  samp_stage_.assign(S_, SlotSampling{{1.0f, 0.0f, 0.0f, 0}, {0.0f, 0.0f, 0.0f, 0}});
   // tables
   RT_OK(alloc(&d_tok_, (size_t)Rmax_));
   RT_OK(alloc(&d_rows_, (size_t)Rmax_));
@@ -404,10 +403,10 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
   RT_OK(alloc(&d_ctrl_, (size_t)S_ + 1));
   RT_HIP(hipMemset(d_ctrl_ + S_, 0, sizeof(SlotCtrl)));
   RT_OK(alloc(&d_sem_, (size_t)S_ * RWKVTTS_SEMANTIC_LIMIT));
-  RT_OK(alloc(&d_pen_, (size_t)S_));  // written at every admission, before the slot's first step
+  // neutral until a slot's first admission, which writes its block before its first step (slot_ctrl.h)
+  RT_OK(alloc(&d_samp_, (size_t)S_));
+  RT_HIP(hipMemcpy(d_samp_, samp_stage_.data(), sizeof(SlotSampling) * (size_t)S_, hipMemcpyHostToDevice));
   RT_OK(alloc(&d_pen_counts_, (size_t)S_ * kPenCounts));  // a slot's row is zeroed by its first penalised step
-  RT_OK(alloc(&d_miro_, (size_t)S_));  // written at every admission too; mu moves on the device after that
-  RT_HIP(hipMemset(d_miro_, 0, sizeof(SlotMiro) * (size_t)S_));
   RT_HIP(hipHostMalloc((void**)&h_ctrl_, sizeof(SlotCtrl) * 2 * (S_ + 1), hipHostMallocDefault));  // 2 snapshots
   // granule hand-off of the one-row FFN form (FfnSync::gran): four key splits x F granules, and the
   // pass counter that tags them (starts at 1: a zeroed granule never carries a live tag)
@@ -572,7 +571,7 @@ int Engine::flush_prof() {
 static constexpr int kPlaneRows = 64;
 
 int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_from_ctrl, bool advance,
-                           int ctrl_kind) {
+                           AdvanceKind kind) {
   const int C = dims.n_embd, F = dims.n_ffn, Lc = dims.n_layer;
   const int nb = (R + 255) / 256;
   // decode steps (tokens from the control blocks, one row per slot) keep each slot's shift
@@ -862,12 +861,11 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
       a.row_slot = d_lg_slot_;
       a.ctrl = d_ctrl_;
       a.sem_out = d_sem_;
-      a.pen = d_pen_;
+      a.samp = d_samp_;
       a.pen_counts = d_pen_counts_;
-      a.miro = d_miro_;
       a.n_rows = n_lg;
       a.stamps = dbg_astamps_;
-      a.params = ctrl_kind;
+      a.kind = kind;
       timed("advance", "sample_advance", [&](unsigned long long* tl) {
         a.tl = tl;
         launch_advance(a, stream_, exact_sampler_ ? 0 : 1);
@@ -913,9 +911,6 @@ int Engine::set_graph_timing(bool on) {
   return RWKVTTS_OK;
 }
 
-// AdvanceArgs::params of a step: 0 k_advance, 1 k_advance_params, 2 k_advance_miro
-static int ctrl_kind_of(const StepPlan& p) { return p.mirostat ? 2 : (p.sampling_params ? 1 : 0); }
-
 int Engine::run_step(const StepPlan& p, bool upload) {
   const int R = (int)p.rows.size();
   RT_CHECK(R > 0 && R <= Rmax_, RWKVTTS_EINVAL, "step rows out of range");
@@ -923,7 +918,8 @@ int Engine::run_step(const StepPlan& p, bool upload) {
   if (upload) RT_OK(upload_plan(p));
   const int n_seg = (int)p.segs.size(), n_lg = (int)p.lg_rows.size();
   if (p.tok_from_ctrl && use_graphs_ && !profiling) {
-    auto key = std::make_pair(R, (p.mirostat ? 1 << 24 : 0) + p.head_rows * 4 + (p.sampling_params ? 2 : 0) + (p.advance ? 1 : 0));
+    // one graph per (R, head_rows, kind, advance): kind < 4 and advance < 2 are the low three bits
+    auto key = std::make_pair(R, p.head_rows * 8 + p.kind * 2 + (p.advance ? 1 : 0));
     auto it = graphs_.find(key);
     if (it == graphs_.end()) {
       // the one-launch step's argument table is uploaded before the capture (no synchronous copy
@@ -934,7 +930,7 @@ int Engine::run_step(const StepPlan& p, bool upload) {
       std::unique_lock<std::mutex> cap_lock(capture_mu);
       hipGraph_t graph;
       RT_HIP(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-      int rc = launch_forward(R, n_seg, n_lg, p.head_rows, true, p.advance, ctrl_kind_of(p));
+      int rc = launch_forward(R, n_seg, n_lg, p.head_rows, true, p.advance, p.kind);
       hipError_t ce = hipStreamEndCapture(stream_, &graph);
       RT_OK(rc);
       RT_HIP(ce);
@@ -949,7 +945,7 @@ int Engine::run_step(const StepPlan& p, bool upload) {
     return RWKVTTS_OK;
   }
   last_graph_ = {-1, -1};
-  RT_OK(launch_forward(R, n_seg, n_lg, p.head_rows, p.tok_from_ctrl, p.advance, ctrl_kind_of(p)));
+  RT_OK(launch_forward(R, n_seg, n_lg, p.head_rows, p.tok_from_ctrl, p.advance, p.kind));
   return RWKVTTS_OK;
 }
 
@@ -1023,73 +1019,37 @@ int Engine::debug_last_logits(int n_rows, int head_rows, float* out) {
 // block; logits are [n_rows][8193] host floats (one partial). Per step and row: out_tok = the
 // token the step emitted (global or semantic; -1 if it emitted none: finished or stopped),
 // out_used = draws the step consumed, out_phase = the phase after the step.
-int Engine::debug_advance(const float* logits, int n_rows, const DebugAdvanceRow* rows, int exact, int n_steps,
-                          int32_t* out_tok, int32_t* out_used, int32_t* out_phase) {
-  RT_CHECK(n_rows > 0 && n_rows <= 4096, RWKVTTS_EINVAL, "debug_advance: bad sizes");
-  std::vector<DebugAdvanceRowEx> ex(n_rows);
-  for (int i = 0; i < n_rows; ++i) {
-    RT_CHECK(rows[i].top_k > 0, RWKVTTS_EINVAL, "debug_advance: bad row");
-    ex[i] = DebugAdvanceRowEx{rows[i], (uint32_t)sizeof(DebugAdvanceRowEx), 1.0f, 0.95f, 0u};
-  }
-  return debug_advance_ex(logits, n_rows, ex.data(), exact, n_steps, out_tok, out_used, out_phase);
-}
-
-int Engine::debug_advance_ex(const float* logits, int n_rows, const DebugAdvanceRowEx* rows, int exact, int n_steps,
-                             int32_t* out_tok, int32_t* out_used, int32_t* out_phase) {
-  RT_CHECK(n_rows > 0 && n_rows <= 4096, RWKVTTS_EINVAL, "debug_advance: bad sizes");
-  std::vector<DebugAdvanceRowPen> pen(n_rows);
-  for (int i = 0; i < n_rows; ++i) {
-    RT_CHECK(rows[i].struct_size == sizeof(DebugAdvanceRowEx), RWKVTTS_EINVAL, "debug_advance: bad row");
-    pen[i] = DebugAdvanceRowPen{rows[i], 1.0f, 0.0f, 0.0f, 0};
-    pen[i].ex.struct_size = (uint32_t)sizeof(DebugAdvanceRowPen);
-  }
-  return debug_advance_pen(logits, n_rows, pen.data(), exact, n_steps, out_tok, out_used, out_phase, 64);
-}
-
-int Engine::debug_advance_pen(const float* logits, int n_rows, const DebugAdvanceRowPen* prows, int exact, int n_steps,
-                              int32_t* out_tok, int32_t* out_used, int32_t* out_phase, int max_steps) {
-  RT_CHECK(n_rows > 0 && n_rows <= 4096, RWKVTTS_EINVAL, "debug_advance: bad sizes");
-  std::vector<DebugAdvanceRowMiro> m(n_rows);
-  for (int i = 0; i < n_rows; ++i) {
-    RT_CHECK(prows[i].ex.struct_size == sizeof(DebugAdvanceRowPen), RWKVTTS_EINVAL, "debug_advance: bad row");
-    m[i] = DebugAdvanceRowMiro{prows[i], 0.0f, 0.0f, 0.0f, 0};
-    m[i].pen.ex.struct_size = (uint32_t)sizeof(DebugAdvanceRowMiro);
-  }
-  return debug_advance_miro(logits, n_rows, m.data(), exact, n_steps, out_tok, out_used, out_phase, nullptr, max_steps);
-}
-
-int Engine::debug_advance_miro(const float* logits, int n_rows, const DebugAdvanceRowMiro* mrows, int exact, int n_steps,
-                               int32_t* out_tok, int32_t* out_used, int32_t* out_phase, float* out_mu, int max_steps) {
+int Engine::debug_advance(const float* logits, int n_rows, const DebugAdvanceRowMiro* mrows, int exact, int n_steps,
+                          int32_t* out_tok, int32_t* out_used, int32_t* out_phase, float* out_mu, int max_steps) {
   RT_HIP(hipSetDevice(device_));
   RT_CHECK(n_rows > 0 && n_rows <= 4096 && n_steps > 0 && n_steps <= max_steps, RWKVTTS_EINVAL, "debug_advance: bad sizes");
   constexpr int LD = RWKVTTS_EOS_TOKEN + 1;
   std::vector<SlotCtrl> c(n_rows);
-  std::vector<SlotPenalty> pens(n_rows);
-  std::vector<SlotMiro> miros(n_rows);
-  bool any_pen = false, any_miro = false;
+  std::vector<SlotSampling> samp(n_rows);
+  bool any_pen = false;
+  AdvanceKind kind = kAdvFixed;  // as admission_of derives a slot's, the step's the highest (step_kind)
+  std::string why;               // the range checks are validate's (sched.h); the hook reports its own messages
   for (int i = 0; i < n_rows; ++i) {
     const DebugAdvanceRowMiro& mr = mrows[i];
     const DebugAdvanceRowPen& pr = mr.pen;
     const DebugAdvanceRowEx& e = pr.ex;
     const DebugAdvanceRow& r = e.row;
-    RT_CHECK((r.phase == kPhGlobal || r.phase == kPhSemantic) && r.top_k >= 0 && r.n_sem >= 0 &&
+    RT_CHECK((r.phase == kPhGlobal || r.phase == kPhSemantic) && r.n_sem >= 0 &&
                  r.n_sem + n_steps <= RWKVTTS_SEMANTIC_LIMIT && (r.mode == 0 || r.mode == 1) &&
-                 e.struct_size == sizeof(DebugAdvanceRowMiro) && e.temperature >= 0.1f && e.temperature <= 4.0f &&
-                 e.top_p >= 0.0f && e.top_p <= 1.0f,
+                 e.struct_size == sizeof(DebugAdvanceRowMiro) &&
+                 phase_sampling_ok(rwkvtts_phase_sampling{e.temperature, e.top_p, r.top_k}, "row", why),
              RWKVTTS_EINVAL, "debug_advance: bad row");
-    const bool neutral = pr.repetition == 1.0f && pr.frequency == 0.0f && pr.presence == 0.0f;
+    samp[i] = SlotSampling{{pr.repetition, pr.frequency, pr.presence, pr.window}, {mr.tau, mr.rate, mr.mu, mr.on}};
+    const bool neutral = penalties_neutral(samp[i].pen);
     // a penalised row starts with an empty history: its counts are the kernel's own from step 0 on
-    RT_CHECK(pr.repetition >= 0.25f && pr.repetition <= 4.0f && pr.frequency >= -8.0f && pr.frequency <= 8.0f &&
-                 pr.presence >= -8.0f && pr.presence <= 8.0f && pr.window >= 0 && pr.window <= RWKVTTS_SEMANTIC_LIMIT &&
+    RT_CHECK(penalties_ok(rwkvtts_penalties{pr.repetition, pr.frequency, pr.presence, pr.window}, why) &&
                  (neutral || r.n_sem == 0),
              RWKVTTS_EINVAL, "debug_advance: bad penalties");
     any_pen |= !neutral;
-    pens[i] = SlotPenalty{pr.repetition, pr.frequency, pr.presence, pr.window};
-    RT_CHECK(mr.on == 0 || (mr.on == 1 && mr.tau >= 0.5f && mr.tau <= 10.0f && mr.rate >= 0.001f && mr.rate <= 1.0f &&
-                            isfinite(mr.mu)),
-             RWKVTTS_EINVAL, "debug_advance: bad mirostat");
-    any_miro |= mr.on != 0;
-    miros[i] = SlotMiro{mr.tau, mr.rate, mr.mu, mr.on};
+    RT_CHECK(mr.on == 0 || (mr.on == 1 && mirostat_ok(mr.tau, mr.rate, why) && isfinite(mr.mu)), RWKVTTS_EINVAL,
+             "debug_advance: bad mirostat");
+    const bool own = !neutral || e.temperature != 1.0f || e.top_p != 0.95f || r.top_k < 1 || r.top_k > kFastTopK;
+    kind = std::max(kind, mr.on ? kAdvMiro : (own ? kAdvParams : kAdvFixed));
     SlotCtrl& x = c[i];
     memset(&x, 0, sizeof(x));
     x.mode = r.mode;
@@ -1111,10 +1071,9 @@ int Engine::debug_advance_miro(const float* logits, int n_rows, const DebugAdvan
   SlotCtrl* d_c = nullptr;
   int32_t *d_slot = nullptr, *d_sem = nullptr;
   uint16_t* d_cnt = nullptr;  // [n_rows][kPenCounts], only when some row is penalised
-  SlotPenalty* d_pen = nullptr;
-  SlotMiro* d_miro = nullptr;
+  SlotSampling* d_samp = nullptr;
   auto cleanup = [&] {
-    for (void* p : {(void*)d_lg, (void*)d_c, (void*)d_slot, (void*)d_sem, (void*)d_cnt, (void*)d_pen, (void*)d_miro})
+    for (void* p : {(void*)d_lg, (void*)d_c, (void*)d_slot, (void*)d_sem, (void*)d_cnt, (void*)d_samp})
       if (p) hipFree(p);
   };
   int rc = RWKVTTS_OK;
@@ -1122,8 +1081,7 @@ int Engine::debug_advance_miro(const float* logits, int n_rows, const DebugAdvan
     if (hipMalloc(&d_lg, (size_t)n_rows * LD * 4) != hipSuccess || hipMalloc(&d_c, sizeof(SlotCtrl) * n_rows) != hipSuccess ||
         hipMalloc(&d_slot, 4 * (size_t)n_rows) != hipSuccess ||
         hipMalloc(&d_sem, 4 * (size_t)n_rows * RWKVTTS_SEMANTIC_LIMIT) != hipSuccess ||
-        hipMalloc(&d_pen, sizeof(SlotPenalty) * n_rows) != hipSuccess ||
-        hipMalloc(&d_miro, sizeof(SlotMiro) * n_rows) != hipSuccess ||
+        hipMalloc(&d_samp, sizeof(SlotSampling) * n_rows) != hipSuccess ||
         (any_pen && hipMalloc(&d_cnt, sizeof(uint16_t) * (size_t)n_rows * kPenCounts) != hipSuccess)) {
       set_error("debug_advance: allocation");
       rc = RWKVTTS_ENOMEM;
@@ -1134,8 +1092,7 @@ int Engine::debug_advance_miro(const float* logits, int n_rows, const DebugAdvan
     if (hipMemcpy(d_lg, logits, (size_t)n_rows * LD * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_c, c.data(), sizeof(SlotCtrl) * n_rows, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_slot, slot.data(), 4 * (size_t)n_rows, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_pen, pens.data(), sizeof(SlotPenalty) * n_rows, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_miro, miros.data(), sizeof(SlotMiro) * n_rows, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_samp, samp.data(), sizeof(SlotSampling) * n_rows, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(d_sem, 0xFF, 4 * (size_t)n_rows * RWKVTTS_SEMANTIC_LIMIT) != hipSuccess) {
       set_error("debug_advance: upload");
       rc = RWKVTTS_EHIP;
@@ -1149,22 +1106,16 @@ int Engine::debug_advance_miro(const float* logits, int n_rows, const DebugAdvan
     a.row_slot = d_slot;
     a.ctrl = d_c;
     a.sem_out = d_sem;
-    a.pen = d_pen;
+    a.samp = d_samp;
     a.pen_counts = d_cnt;
-    a.miro = d_miro;
     a.n_rows = n_rows;
-    a.params = any_pen ? 1 : 0;
-    for (int i = 0; i < n_rows; ++i) {
-      const DebugAdvanceRowEx& e = mrows[i].pen.ex;
-      a.params |= e.temperature != 1.0f || e.top_p != 0.95f || e.row.top_k < 1 || e.row.top_k > kFastTopK;
-    }
-    if (any_miro) a.params = 2;  // as a step with a Mirostat slot launches k_advance_miro
+    a.kind = kind;
     std::vector<SlotCtrl> prev = c, now(n_rows);
     for (int s = 0; s < n_steps && rc == RWKVTTS_OK; ++s) {
       launch_advance(a, stream_, exact ? 0 : 1);
       if (hipStreamSynchronize(stream_) != hipSuccess ||
           hipMemcpy(now.data(), d_c, sizeof(SlotCtrl) * n_rows, hipMemcpyDeviceToHost) != hipSuccess ||
-          (out_mu && hipMemcpy(miros.data(), d_miro, sizeof(SlotMiro) * n_rows, hipMemcpyDeviceToHost) != hipSuccess)) {
+          (out_mu && hipMemcpy(samp.data(), d_samp, sizeof(SlotSampling) * n_rows, hipMemcpyDeviceToHost) != hipSuccess)) {
         set_error("debug_advance: launch");
         rc = RWKVTTS_EHIP;
         break;
@@ -1173,7 +1124,7 @@ int Engine::debug_advance_miro(const float* logits, int n_rows, const DebugAdvan
         const SlotCtrl &p = prev[i], &q = now[i];
         const int64_t o = (int64_t)s * n_rows + i;
         out_phase[o] = q.phase;
-        if (out_mu) out_mu[o] = miros[i].mu;
+        if (out_mu) out_mu[o] = samp[i].miro.mu;
         if (p.phase == kPhGlobal) {
           out_tok[o] = q.n_global > p.n_global ? q.global_out[p.n_global] : -1;
           out_used[o] = (int32_t)(q.gdraw - p.gdraw);
@@ -1438,19 +1389,16 @@ int Engine::admit(ServeState& st, Job* j) {
   // stream-ordered copy (the slot's entry is rewritten only after the slot retires)
   ctrl_stage_[slot] = ad.ctrl;
   RT_HIP(hipMemcpyAsync(d_ctrl_ + slot, &ctrl_stage_[slot], sizeof(SlotCtrl), hipMemcpyHostToDevice, stream_));
-  pen_stage_[slot] = ad.pen;
-  RT_HIP(hipMemcpyAsync(d_pen_ + slot, &pen_stage_[slot], sizeof(SlotPenalty), hipMemcpyHostToDevice, stream_));
-  // every admission, on = 0 included: the previous owner's threshold does not survive
-  miro_stage_[slot] = ad.miro;
-  RT_HIP(hipMemcpyAsync(d_miro_ + slot, &miro_stage_[slot], sizeof(SlotMiro), hipMemcpyHostToDevice, stream_));
+  // every admission, neutral blocks included: nothing of the previous owner's survives
+  samp_stage_[slot] = ad.samp;
+  RT_HIP(hipMemcpyAsync(d_samp_ + slot, &samp_stage_[slot], sizeof(SlotSampling), hipMemcpyHostToDevice, stream_));
   Active a;
   a.job = j;
   a.slot = slot;
   a.sink = sink_of(j);
   a.zero_shot = ad.zero_shot;
   a.pinned = ad.pinned;
-  a.own_sampling = ad.own_sampling;
-  a.mirostat = ad.mirostat;
+  a.kind = ad.kind;
   a.prompt = std::move(ad.prompt);
   a.total = ad.total;
   st.act.push_back(std::move(a));

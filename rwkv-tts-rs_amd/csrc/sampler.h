@@ -39,23 +39,16 @@ struct AdvanceArgs {
   unsigned long long* tl;  // debug timeline slot (null in production)
   int cert;              // set by launch_advance: 1 certified fast path allowed (sample_cert)
   uint64_t* stamps;      // debug: [rows][16] s_memtime phase stamps (RWKVTTS_DEBUG_STAMPS adv=; null in production)
-  // 0: every row's slot samples with the reference's (temperature 1.0, top_p 0.95) and a top-k in
-  // [1, kFastTopK] -- k_advance, the two values compiled in; 1: some slot carries its own
-  // (SlotCtrl::temp_* / top_p_*) or another top-k -- k_advance_params reads them per row and
-  // carries every path. Both give a row of the first kind the same token. 2: some slot runs
-  // Mirostat (miro[slot].on) -- k_advance_miro, k_advance_params with the Mirostat path for the
-  // semantic rows of such slots; every other row gets what k_advance_params gives it.
-  int params;
-  const SlotPenalty* pen;  // [S] penalties of each slot (read by k_advance_params only)
+  AdvanceKind kind;      // the kernel launch_advance picks (slot_ctrl.h): the highest kind among the rows' slots
+  // [S] sampling block of each slot: k_advance_params and k_advance_miro read pen, k_advance_miro
+  // alone reads miro and moves miro.mu. May be null when kind == kAdvFixed.
+  SlotSampling* samp;
   // [S][kPenCounts] occurrences of each semantic id in a penalised slot's history window
-  // (pen). Derived state that k_advance_params keeps by itself: a slot's row is zeroed
+  // (samp[slot].pen). Derived state that k_advance_params keeps by itself: a slot's row is zeroed
   // at its first semantic step instead of being read, the emitted id is counted after every step
   // and the id that leaves the window is uncounted. Rows of slots without penalties are never
   // touched. May be null when no row's slot is penalised.
   uint16_t* pen_counts;
-  // [S] Mirostat block of each slot (read, and its mu updated, by k_advance_miro only; may be null
-  // when params < 2)
-  SlotMiro* miro;
 };
 constexpr int kPenCounts = RWKVTTS_EOS_TOKEN;  // ids [0, 8192): EOS never enters the history
 

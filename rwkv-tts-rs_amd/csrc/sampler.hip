@@ -117,88 +117,9 @@ __device__ inline float readlane_f(float v, int l) {
 }
 __device__ inline int readlane_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
 
-// wave-uniform sequential f32 sum of p[b..e) (all 64 lanes of the calling wave participate):
-// 64 elements are staged into lanes per round and added in order from registers.
 __device__ inline float add64(float s, float v) {  // s + v[lane 0] + ... + v[lane 63], in order
 #pragma unroll
   for (int i = 0; i < 64; ++i) s += readlane_f(v, i);
-  return s;
-}
-// Sequential adds of non-negative values: padding lanes hold +0.0, and s + 0 == s exactly.
-__device__ inline float wave_serial_add(float s, const float* p, int b, int e) {
-  const int lane = threadIdx.x & 63;
-  for (int q = b; q < e; q += 64) s = add64(s, (q + lane < e) ? p[q + lane] : 0.0f);
-  return s;
-}
-// Quantised increment of adding e (bits b) to an f32 s in binade E (ulp u = 2^(E-23); the
-// denormal range counts as E = -126): RN(s + e) = s + u * (a + [frac(e/u) > 1/2]) while the
-// result stays in the binade. Flags a tie (frac == 1/2: the result then depends on the parity of
-// s) and an increment too large for the binade.
-__device__ inline uint32_t qinc(uint32_t b, int E, bool& flag) {
-  const uint32_t ef = (b >> 23) & 0xFFu;
-  uint32_t M = b & 0x7FFFFFu;
-  int ex;
-  if (ef == 0) ex = -149;
-  else { M |= 0x800000u; ex = (int)ef - 150; }
-  if (M == 0) return 0u;
-  const int sh = (E - 23) - ex;  // e / u = M * 2^-sh
-  if (sh <= 0) {
-    if (sh < -7) { flag = true; return 0u; }
-    const uint32_t a = M << (-sh);
-    if (a >= 0x1000000u) flag = true;
-    return a;
-  }
-  if (sh > 25) return 0u;  // e < u / 4
-  const uint32_t a = M >> sh, r = M & ((1u << sh) - 1u), half = 1u << (sh - 1);
-  if (r == half) flag = true;
-  return a + (r > half ? 1u : 0u);
-}
-// u * mm for mm < 2^24 in binade E (E = -126: denormal or the lowest normal binade, bits = mm)
-__device__ inline float binade_value(uint32_t mm, int E) {
-  return __builtin_bit_cast(float, E == -126 ? mm : (((uint32_t)(E + 127) << 23) | (mm & 0x7FFFFFu)));
-}
-// Exact sequential f32 sum s + p[b] + ... + p[e-1] (p >= 0) by one wave, 128 elements per
-// round: every element's increment is quantised for s's binade and prefix-summed across the
-// wave; the first element that would leave the binade, tie or overflow the binade is added
-// with a real f32 add, and the round restarts after it. Bit-identical to the serial loop.
-__device__ float wave_exact_add(float s, const float* p, int b, int e) {
-  const int lane = threadIdx.x & 63;
-  int pos = b;
-  while (pos < e) {
-    const uint32_t sb = __builtin_bit_cast(uint32_t, s);
-    const int ef = (int)((sb >> 23) & 0xFFu);
-    const int E = ef ? ef - 127 : -126;
-    const uint32_t m = ef ? ((sb & 0x7FFFFFu) | 0x800000u) : (sb & 0x7FFFFFu);
-    const int i0 = pos + 2 * lane, i1 = i0 + 1;
-    bool f0 = false, f1 = false;
-    const uint32_t q0 = i0 < e ? qinc(__builtin_bit_cast(uint32_t, p[i0]), E, f0) : 0u;
-    const uint32_t q1 = i1 < e ? qinc(__builtin_bit_cast(uint32_t, p[i1]), E, f1) : 0u;
-    const uint32_t lt = q0 + q1;
-    uint32_t incl = lt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t v = __shfl_up(incl, o);
-      if (lane >= o) incl = min(incl + v, 0x4000000u);
-    }
-    uint32_t excl = __shfl_up(incl, 1);
-    if (lane == 0) excl = 0u;
-    const bool c0 = f0 || (i0 < e && m + excl + q0 >= 0x1000000u);
-    const bool c1 = f1 || (i1 < e && m + excl + q0 + q1 >= 0x1000000u);
-    const uint64_t bal = __ballot(c0 || c1);
-    if (bal == 0) {
-      s = binade_value(m + (uint32_t)readlane_i((int)incl, 63), E);
-      pos += 128;
-      continue;
-    }
-    const int fl = __ffsll((long long)bal) - 1;
-    const bool c0l = readlane_i(c0 ? 1 : 0, fl) != 0;
-    const uint32_t exl = (uint32_t)readlane_i((int)excl, fl);
-    const uint32_t pre = c0l ? exl : exl + (uint32_t)readlane_i((int)q0, fl);
-    const int f = pos + 2 * fl + (c0l ? 0 : 1);
-    s = binade_value(m + pre, E);
-    s = s + p[f];
-    pos = f + 1;
-  }
   return s;
 }
 // Sequential f32 sum s + p[b] + ... + p[e-1] by ONE lane from its own registers: each 128-
@@ -1764,39 +1685,10 @@ void launch_sample_rows(const SampleRowArgs& a, int rows, hipStream_t st) {
 // ---------------------------------------------------------------------------------------
 // Phase controller: one workgroup per step row that carries logits.
 // ---------------------------------------------------------------------------------------
-__device__ inline float load_logit(const AdvanceArgs& a, const float* lg, int i) {
-  float v = lg[i];
-  for (int p = 1; p < a.n_part; ++p) v += lg[p * a.part_stride + i];
-  return v;
-}
-
-// The row's logits into LDS: four elements per round with all their partial-slab loads issued
-// before any add (each element still sums its slabs in order p = 0, 1, ...: same values)
-template <int NT>
-__device__ inline void load_logits_row(const AdvanceArgs& a, const float* lg, float* p, int n) {
-  int i = threadIdx.x;
-  for (; i + 3 * NT < n; i += 4 * NT) {
-    float v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = lg[i + u * NT];
-    for (int q = 1; q < a.n_part; ++q) {
-      float w[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) w[u] = lg[q * a.part_stride + i + u * NT];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] += w[u];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) p[i + u * NT] = v[u];
-  }
-  for (; i < n; i += NT) p[i] = load_logit(a, lg, i);
-}
-
 // k_advance's preparation of a row for sample_block(prepped = true), with the row in registers
 // instead of LDS round trips: element i = tid + k NT of thread tid (k < PT); every partial-slab
-// load of the row is issued before the first add (each element sums its slabs in order p = 0, 1,
-// ..., as load_logit does) and the last wave makes the draw (a ChaCha12 block) while they are in
-// flight; block max; e = glibc expf(l - max) into p (the exact paths read it there); the real sum
+// load of the row is issued before the first add (advance_load_row) and the last wave makes the
+// draw (a ChaCha12 block) while they are in flight; block max; e = glibc expf(l - max) into p (the exact paths read it there); the real sum
 // E of the row in f64 from per-thread partial sums (any order: its error, <= n 2^-53 E, is inside
 // sample_cert's 2^-36 term); and, for top-k <= kFastK, the bound L and the candidates
 // e >= L (1 - 2^-19) appended straight from the registers (the collect() of sample_block with all
@@ -1806,9 +1698,10 @@ __device__ inline void load_logits_row(const AdvanceArgs& a, const float* lg, fl
 // The row length N is a template parameter: every i < N test but the last element's folds away
 // (with a runtime n the compiler hoisted seventeen lane masks per test into the kernel's preamble
 // and spilled them, +5 us per launch). mask_eos: the last element (EOS, semantic rows) is -inf.
-// The row's logits into registers, every partial-slab load issued before the first add (element i
-// = tid + k NT sums its slabs in order p = 0, 1, ..., as load_logit does). Issued by k_advance
-// before it reads the slot's control block. Indices past the row are clamped (never used).
+// The row's logits into registers, every partial-slab load issued before the first add. Element i
+// = tid + k NT is one f32 chain over the head GEMM's split-K slabs in slab order: slab 0's value,
+// plus slab 1's, plus slab 2's, ... (the order Engine::infer and debug_last_logits return). Issued
+// by k_advance before it reads the slot's control block. Indices past the row are clamped (never used).
 template <int NT, int PT>
 __device__ __attribute__((always_inline)) void advance_load_row(const AdvanceArgs& a, const float* lg, float* v) {
   const int last = a.ld - 1, tid = threadIdx.x;
@@ -2243,7 +2136,8 @@ __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a
   bool pen = false;
   uint16_t* pen_cnt = nullptr;
   if constexpr (kParams) {
-    const float rep = a.pen[slot].repetition, freq = a.pen[slot].frequency, pres = a.pen[slot].presence;
+    const SlotPenalty& sp = a.samp[slot].pen;
+    const float rep = sp.repetition, freq = sp.frequency, pres = sp.presence;
     pen = !glob && (rep != 1.0f || freq != 0.0f || pres != 0.0f);
     if (pen) {
       pen_cnt = a.pen_counts + (int64_t)slot * kPenCounts;
@@ -2257,8 +2151,8 @@ __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a
   bool miro = false;
   float mu = 0.0f;
   if constexpr (kMiro) {
-    miro = !glob && a.miro[slot].on != 0;
-    mu = a.miro[slot].mu;
+    miro = !glob && a.samp[slot].miro.on != 0;
+    mu = a.samp[slot].miro.mu;
   }
   const int prep_k = (kMiro && miro) ? 0 : top_k;
   // attempt 1 (zero-shot only): EOS drawn while the window rule does not stop the request ->
@@ -2317,7 +2211,7 @@ __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a
         // that leaves it goes (ids outside [0, 8192) cannot occur: EOS ends the request or is
         // re-drawn masked above, and is never stored; the range checks cost nothing beside that)
         if (pen) {
-          const int W = a.pen[slot].window, ns = c->n_sem;
+          const int W = a.samp[slot].pen.window, ns = c->n_sem;
           if ((uint32_t)id < (uint32_t)kPenCounts) pen_cnt[id] += 1;
           if (W > 0 && ns >= W) {
             const int old = a.sem_out[(int64_t)slot * RWKVTTS_SEMANTIC_LIMIT + ns - W];
@@ -2330,7 +2224,7 @@ __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a
         // that of an EOS that was re-drawn or that ends the request: s = lg(S) - lg(p_tok),
         // mu -= rate * (s - tau) as a multiply and a subtract, capped at 4 tau
         if (miro) {
-          SlotMiro* m = a.miro + slot;
+          SlotMiro* m = &a.samp[slot].miro;
           const float tau = m->tau;
           const float err = __fsub_rn(__fsub_rn(lg2f(sm.fred[22]), lg2f(sm.fred[23])), tau);
           m->mu = fminf(__fsub_rn(mu, __fmul_rn(m->rate, err)), __fmul_rn(4.0f, tau));
@@ -2370,9 +2264,11 @@ int launch_advance(const AdvanceArgs& a0, hipStream_t st, int cert) {
   AdvanceArgs a = a0;
   a.cert = cert;  // 0: always walk the exact sequential sum (RWKVTTS_FORM_EXACT_SAMPLER)
   const size_t lds = smem_bytes<kSampleThreads>(RWKVTTS_EOS_TOKEN + 1);
-  if (a.params >= 2) RT_LAUNCH(k_advance_miro, dim3(a.n_rows), dim3(kSampleThreads), lds, st, a);
-  else if (a.params) RT_LAUNCH(k_advance_params, dim3(a.n_rows), dim3(kSampleThreads), lds, st, a);
-  else RT_LAUNCH(k_advance, dim3(a.n_rows), dim3(kSampleThreads), lds, st, a);
+  switch (a.kind) {
+    case kAdvMiro: RT_LAUNCH(k_advance_miro, dim3(a.n_rows), dim3(kSampleThreads), lds, st, a); break;
+    case kAdvParams: RT_LAUNCH(k_advance_params, dim3(a.n_rows), dim3(kSampleThreads), lds, st, a); break;
+    case kAdvFixed: RT_LAUNCH(k_advance, dim3(a.n_rows), dim3(kSampleThreads), lds, st, a); break;
+  }
   return a.n_rows;
 }
 

@@ -35,12 +35,7 @@ struct StepPlan {
   int head_rows = 0;
   bool tok_from_ctrl = false;  // decode: token = ctrl[slot].next_token
   bool advance = false;        // run the phase controller on the logits rows
-  // some active request samples with parameters of its own (Active::own_sampling): the step's
-  // controller reads every row's from its control block (AdvanceArgs::params)
-  bool sampling_params = false;
-  // some active request runs Mirostat (Active::mirostat): the step's controller is the one that
-  // reads the slots' Mirostat blocks (AdvanceArgs::params == 2); implies sampling_params
-  bool mirostat = false;
+  AdvanceKind kind = kAdvFixed;  // the step's controller: step_kind of the active requests
 };
 
 // A request decoding in a state slot.
@@ -53,8 +48,7 @@ struct Active {
   int total = 0;     // advances after which the request is certainly done (its step limit)
   bool zero_shot = false;
   bool pinned = false;        // Admission::pinned: normal mode, the 32 global tokens given
-  bool own_sampling = false;  // Admission::own_sampling
-  bool mirostat = false;      // Admission::mirostat
+  AdvanceKind kind = kAdvFixed;  // Admission::kind
   // token progress (Job::user): semantic tokens handed to the sink so far, and per unit buffer the
   // end of the range of this slot's d_sem_ that the unit copied to h_prog_
   const rwkvtts_token_sink* sink = nullptr;
@@ -90,6 +84,31 @@ inline HeldExt ext_copy(const rwkvtts_request_ext* e) {
   return h;
 }
 inline bool has_mirostat(const rwkvtts_request_ext* ext) { return ext && (ext->mirostat_set & RWKVTTS_MIROSTAT_SET); }
+
+// The ranges of the three sampling options, for validate and the k_advance test hook
+// (Engine::debug_advance): each fills `why` and returns false for a bad value. Comparisons are
+// false for NaN, so a non-finite value fails its range.
+inline bool phase_sampling_ok(const rwkvtts_phase_sampling& s, const char* what, std::string& why) {
+  if (!(s.temperature >= 0.1f && s.temperature <= 4.0f)) why = std::string(what) + ": temperature must be in [0.1, 4.0]";
+  else if (!(s.top_p >= 0.0f && s.top_p <= 1.0f)) why = std::string(what) + ": top_p must be in [0, 1]";
+  else if (s.top_k < 0) why = std::string(what) + ": top_k must be >= 0";
+  else return true;
+  return false;
+}
+inline bool penalties_ok(const rwkvtts_penalties& p, std::string& why) {
+  if (!(p.repetition >= 0.25f && p.repetition <= 4.0f)) why = "penalties: repetition must be in [0.25, 4.0]";
+  else if (!(p.frequency >= -8.0f && p.frequency <= 8.0f)) why = "penalties: frequency must be in [-8.0, 8.0]";
+  else if (!(p.presence >= -8.0f && p.presence <= 8.0f)) why = "penalties: presence must be in [-8.0, 8.0]";
+  else if (p.window < 0 || p.window > RWKVTTS_SEMANTIC_LIMIT) why = "penalties: window must be in [0, 2048]";
+  else return true;
+  return false;
+}
+inline bool mirostat_ok(float tau, float rate, std::string& why) {
+  if (!(tau >= 0.5f && tau <= 10.0f)) why = "mirostat: tau must be in [0.5, 10]";
+  else if (!(rate >= 0.001f && rate <= 1.0f)) why = "mirostat: rate must be in [0.001, 1]";
+  else return true;
+  return false;
+}
 
 // Checks a request (and its extension block, if any) before admission; fills `why` and returns
 // false for a bad one.
@@ -139,28 +158,14 @@ inline bool validate(const rwkvtts_request& q, int n_vocab, std::string& why, co
     why = "greedy and sampling_set exclude each other";
     return false;
   }
-  auto phase_ok = [&](const rwkvtts_phase_sampling& s, const char* what) {
-    // (comparisons are false for NaN: a non-finite value fails its range)
-    if (!(s.temperature >= 0.1f && s.temperature <= 4.0f)) why = std::string(what) + ": temperature must be in [0.1, 4.0]";
-    else if (!(s.top_p >= 0.0f && s.top_p <= 1.0f)) why = std::string(what) + ": top_p must be in [0, 1]";
-    else if (s.top_k < 0) why = std::string(what) + ": top_k must be >= 0";
-    else return true;
+  if ((q.sampling_set & RWKVTTS_SAMPLING_GLOBAL) && !phase_sampling_ok(q.global_sampling, "global_sampling", why)) return false;
+  if ((q.sampling_set & RWKVTTS_SAMPLING_SEMANTIC) && !phase_sampling_ok(q.semantic_sampling, "semantic_sampling", why))
     return false;
-  };
-  if ((q.sampling_set & RWKVTTS_SAMPLING_GLOBAL) && !phase_ok(q.global_sampling, "global_sampling")) return false;
-  if ((q.sampling_set & RWKVTTS_SAMPLING_SEMANTIC) && !phase_ok(q.semantic_sampling, "semantic_sampling")) return false;
   if (q.penalty_set & ~RWKVTTS_PENALTY_SET) {
     why = "penalty_set: unknown bits";
     return false;
   }
-  if (q.penalty_set) {  // (allowed together with greedy; NaN fails every comparison)
-    const rwkvtts_penalties& p = q.penalties;
-    if (!(p.repetition >= 0.25f && p.repetition <= 4.0f)) why = "penalties: repetition must be in [0.25, 4.0]";
-    else if (!(p.frequency >= -8.0f && p.frequency <= 8.0f)) why = "penalties: frequency must be in [-8.0, 8.0]";
-    else if (!(p.presence >= -8.0f && p.presence <= 8.0f)) why = "penalties: presence must be in [-8.0, 8.0]";
-    else if (p.window < 0 || p.window > RWKVTTS_SEMANTIC_LIMIT) why = "penalties: window must be in [0, 2048]";
-    if (!why.empty()) return false;
-  }
+  if (q.penalty_set && !penalties_ok(q.penalties, why)) return false;  // (allowed together with greedy)
   if (ext) {  // a field is read only where the caller's struct_size covers it
     const size_t have = ext->struct_size;
     if (have < offsetof(rwkvtts_request_ext, mirostat_set) + sizeof(ext->mirostat_set)) {
@@ -171,10 +176,9 @@ inline bool validate(const rwkvtts_request& q, int n_vocab, std::string& why, co
       why = "mirostat_set: unknown bits";
       return false;
     }
-    if (ext->mirostat_set) {  // (NaN fails every comparison)
+    if (ext->mirostat_set) {
       if (have < offsetof(rwkvtts_request_ext, mirostat) + sizeof(ext->mirostat)) why = "ext: struct_size does not cover mirostat";
-      else if (!(ext->mirostat.tau >= 0.5f && ext->mirostat.tau <= 10.0f)) why = "mirostat: tau must be in [0.5, 10]";
-      else if (!(ext->mirostat.rate >= 0.001f && ext->mirostat.rate <= 1.0f)) why = "mirostat: rate must be in [0.001, 1]";
+      else if (!mirostat_ok(ext->mirostat.tau, ext->mirostat.rate, why)) return false;
       else if (q.greedy) why = "mirostat and greedy exclude each other";
       else if (q.sampling_set & RWKVTTS_SAMPLING_SEMANTIC)
         why = "mirostat replaces the semantic phase's top-k, top-p and temperature: semantic_sampling excludes it";
@@ -199,21 +203,17 @@ inline bool pinned_without_tokens(const rwkvtts_request& q) { return is_pinned(q
 struct Admission {
   std::vector<uint32_t> prompt;
   SlotCtrl ctrl;         // the slot's initial control block, gkey / skey still zero
-  SlotPenalty pen;       // the slot's penalties ((1, 0, 0, 0) without penalty_set)
+  // the slot's sampling block: penalties (1, 0, 0, 0) without penalty_set; Mirostat {tau, rate,
+  // mu = 2 tau, on = 1} with rwkvtts_request_ext::mirostat, all zero without
+  SlotSampling samp;
   uint64_t gseed, sseed;  // the engine derives gkey / skey from them (StdRng::seed_from_u64)
   bool zero_shot;
   bool pinned;           // is_pinned: decodes as normal mode from its first logits row on
   int total;             // Active::total
-  // a phase's temperature or top-p differs from the reference's (1.0, 0.95), or its top-k is
-  // outside the fast path's [1, kFastTopK]: steps with this request run the controller that reads
-  // the parameters from the control block and carries the general path for every top-k. Also set
-  // by a penalty that is not neutral (pen): that controller alone applies penalties.
-  bool own_sampling;
-  // the slot's Mirostat block: {tau, rate, mu = 2 tau, on = 1} with rwkvtts_request_ext::mirostat,
-  // all zero without. mirostat (== miro.on) routes the slot's steps to the controller that reads
-  // the block (StepPlan::mirostat) and sets own_sampling with it.
-  SlotMiro miro;
-  bool mirostat;
+  // the controller the slot's steps need: kAdvMiro with a Mirostat block; else kAdvParams where a
+  // phase's temperature or top-p differs from the reference's (1.0, 0.95), its top-k is outside
+  // the fast path's [1, kFastTopK] or the penalties are not neutral; else kAdvFixed
+  AdvanceKind kind;
 };
 
 // (1, 0, 0): the semantic rows are sampled as they arrive
@@ -221,16 +221,11 @@ inline bool penalties_neutral(const SlotPenalty& p) {
   return p.repetition == 1.0f && p.frequency == 0.0f && p.presence == 0.0f;
 }
 
-inline bool any_mirostat(const std::vector<Active>& act) {
-  bool any = false;
-  for (const Active& a : act) any |= a.mirostat;
-  return any;
-}
-
-inline bool any_own_sampling(const std::vector<Active>& act) {
-  bool any = false;
-  for (const Active& a : act) any |= a.own_sampling;
-  return any;
+// the controller of a step: the highest kind among the active requests
+inline AdvanceKind step_kind(const std::vector<Active>& act) {
+  AdvanceKind k = kAdvFixed;
+  for (const Active& a : act) k = std::max(k, a.kind);
+  return k;
 }
 
 // entropy: the seed of a request without one (dynamic_batch_manager.rs:491-499, from_entropy)
@@ -266,16 +261,13 @@ inline Admission admission_of(const rwkvtts_request& q, uint64_t entropy, const 
     c.top_p_s = q.semantic_sampling.top_p;
     c.top_k_s = q.semantic_sampling.top_k;
   }
-  a.own_sampling = c.temp_g != 1.0f || c.temp_s != 1.0f || c.top_p_g != 0.95f || c.top_p_s != 0.95f ||
-                   c.top_k_g < 1 || c.top_k_g > kFastTopK || c.top_k_s < 1 || c.top_k_s > kFastTopK;
-  a.pen = SlotPenalty{1.0f, 0.0f, 0.0f, 0};
+  a.samp = SlotSampling{{1.0f, 0.0f, 0.0f, 0}, {0.0f, 0.0f, 0.0f, 0}};
   if (q.penalty_set & RWKVTTS_PENALTY_SET)
-    a.pen = SlotPenalty{q.penalties.repetition, q.penalties.frequency, q.penalties.presence, q.penalties.window};
-  a.own_sampling |= !penalties_neutral(a.pen);
-  a.miro = SlotMiro{0.0f, 0.0f, 0.0f, 0};
-  a.mirostat = has_mirostat(ext);
-  if (a.mirostat) a.miro = SlotMiro{ext->mirostat.tau, ext->mirostat.rate, 2.0f * ext->mirostat.tau, 1};
-  a.own_sampling |= a.mirostat;
+    a.samp.pen = SlotPenalty{q.penalties.repetition, q.penalties.frequency, q.penalties.presence, q.penalties.window};
+  if (has_mirostat(ext)) a.samp.miro = SlotMiro{ext->mirostat.tau, ext->mirostat.rate, 2.0f * ext->mirostat.tau, 1};
+  const bool own = c.temp_g != 1.0f || c.temp_s != 1.0f || c.top_p_g != 0.95f || c.top_p_s != 0.95f || c.top_k_g < 1 ||
+                   c.top_k_g > kFastTopK || c.top_k_s < 1 || c.top_k_s > kFastTopK || !penalties_neutral(a.samp.pen);
+  a.kind = a.samp.miro.on ? kAdvMiro : (own ? kAdvParams : kAdvFixed);
   c.fixed = q.fixed_semantic > 0;
   c.sem_limit = sem_limit_of(q);
   if (a.zero_shot) {
@@ -374,8 +366,7 @@ inline StepPlan mixed_plan(std::vector<Active>& act, int chunk, int n_vocab) {
     budget -= take;
   }
   p.head_rows = head_rows_of(act, n_vocab);
-  p.sampling_params = any_own_sampling(act);
-  p.mirostat = any_mirostat(act);
+  p.kind = step_kind(act);
   for (Active& a : act) a.advances += !a.in_prompt();  // one advance per logits row
   return p;
 }
@@ -385,8 +376,7 @@ inline StepPlan decode_plan(const std::vector<Active>& act) {
   StepPlan p;
   p.tok_from_ctrl = true;
   p.advance = true;
-  p.sampling_params = any_own_sampling(act);
-  p.mirostat = any_mirostat(act);
+  p.kind = step_kind(act);
   for (const Active& a : act) append_decode_row(p, a.slot);
   return p;
 }

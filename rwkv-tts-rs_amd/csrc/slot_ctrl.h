@@ -9,10 +9,16 @@ constexpr int kRowFirst = 1;  // row flags
 constexpr int kRowLast = 2;
 constexpr int kRowCtrl = 4;   // the row's token is its slot's SlotCtrl::next_token (decode)
 
-// largest top-k of the sampler's fast path (sampler.hip kFastK): a slot whose phases keep the
-// reference's (temperature 1.0, top_p 0.95) and a top-k in [1, kFastTopK] is served by k_advance
-// with the two values compiled in, any other by k_advance_params (sched.h Admission::own_sampling)
-constexpr int kFastTopK = 256;
+constexpr int kFastTopK = 256;  // largest top-k of the sampler's fast path (sampler.hip kFastK)
+
+// Which phase controller a slot needs (sched.h admission_of) and a step launches (sampler.hip
+// launch_advance). kAdvFixed: k_advance, the reference's (temperature 1.0, top_p 0.95) compiled
+// in, for a top-k in [1, kFastTopK]. kAdvParams: k_advance_params reads the three per row from the
+// control block, carries every top-k path and applies the slot's penalties. kAdvMiro:
+// k_advance_miro is k_advance_params plus the Mirostat path for the semantic rows of slots whose
+// block is on. The kernels form a chain -- each kind's kernel gives a row of a lower kind the same
+// token -- so the values are ordered and the kind of a step is the maximum over its slots.
+enum AdvanceKind : int32_t { kAdvFixed = 0, kAdvParams = 1, kAdvMiro = 2 };
 
 enum SlotPhase : int32_t { kPhGlobal = 0, kPhGFeed = 1, kPhSemantic = 2, kPhDone = 3 };
 
@@ -50,28 +56,36 @@ struct SlotCtrl {
 };
 static_assert(sizeof(SlotCtrl) % 8 == 0, "control blocks are copied as an array; next_token is read at a 4-byte stride");
 
-// Penalties of a slot's semantic phase (rwkvtts.h rwkvtts_penalties), in an array beside the
-// control blocks (AdvanceArgs::pen) that only the host writes, at admission: the control block
-// keeps the size and layout its snapshots and tests/native/sched_sampling_main.cpp know.
-// k_advance_params applies them to the logits of every token that occurs in the last `window`
-// semantic tokens (0: in all of them). Neutral (1, 0, 0): the row is sampled as it arrived and the
-// slot's count row (AdvanceArgs::pen_counts) is neither read nor written.
+// The sampling options of a slot's semantic phase that do not fit the control block, which keeps
+// the size and layout its snapshots and tests/native/sched_sampling_main.cpp know: one array of
+// SlotSampling beside the control blocks (AdvanceArgs::samp). The host writes a slot's whole block
+// at every admission, in stream order before the slot's first step -- neutral penalties and
+// on = 0 for a request without them, so nothing survives from the slot's previous owner; after
+// that the kernel alone moves miro.mu. The address is fixed, so the step stays capturable in the
+// decode graph.
+
+// Penalties (rwkvtts.h rwkvtts_penalties): k_advance_params applies them to the logits of every
+// token that occurs in the last `window` semantic tokens (0: in all of them). Neutral (1, 0, 0):
+// the row is sampled as it arrived and the slot's count row (AdvanceArgs::pen_counts) is neither
+// read nor written.
 struct SlotPenalty {
   float repetition, frequency, presence;
   int32_t window;
 };
 static_assert(sizeof(SlotPenalty) == 16, "penalty blocks are copied as an array");
 
-// Mirostat state of a slot's semantic phase (rwkvtts.h rwkvtts_request_ext::mirostat), in a third
-// array beside the control blocks (AdvanceArgs::miro) for the same reason. The host writes the
-// block at every admission, in stream order before the slot's first step -- on = 0 for a request
-// without Mirostat, so nothing survives from the slot's previous owner, mu = 2 tau for one with
-// it; after that k_advance_miro alone moves mu, once per emitted semantic token. The address is
-// fixed, so the step stays capturable in the decode graph.
+// Mirostat state (rwkvtts.h rwkvtts_request_ext::mirostat): mu = 2 tau at admission, then moved
+// by k_advance_miro once per emitted semantic token.
 struct SlotMiro {
   float tau, rate, mu;
   int32_t on;
 };
 static_assert(sizeof(SlotMiro) == 16, "Mirostat blocks are copied as an array");
+
+struct SlotSampling {
+  SlotPenalty pen;
+  SlotMiro miro;
+};
+static_assert(sizeof(SlotSampling) == 32, "sampling blocks are copied as an array");
 
 }  // namespace rwkvtts

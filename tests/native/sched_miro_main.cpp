@@ -76,16 +76,17 @@ static bool ok(const rwkvtts_request& q, const rwkvtts_request_ext* caller) {
 static bool ok(const rwkvtts_request& q, const rwkvtts_request_ext& x) { return ok(q, &x); }
 
 static bool same_admission(const Admission& a, const Admission& b) {
-  return memcmp(&a.ctrl, &b.ctrl, sizeof(SlotCtrl)) == 0 && memcmp(&a.pen, &b.pen, sizeof(SlotPenalty)) == 0 &&
-         memcmp(&a.miro, &b.miro, sizeof(SlotMiro)) == 0 && a.prompt == b.prompt && a.gseed == b.gseed &&
-         a.sseed == b.sseed && a.zero_shot == b.zero_shot && a.pinned == b.pinned && a.total == b.total &&
-         a.own_sampling == b.own_sampling && a.mirostat == b.mirostat;
+  return memcmp(&a.ctrl, &b.ctrl, sizeof(SlotCtrl)) == 0 && memcmp(&a.samp, &b.samp, sizeof(SlotSampling)) == 0 &&
+         a.prompt == b.prompt && a.gseed == b.gseed && a.sseed == b.sseed && a.zero_shot == b.zero_shot &&
+         a.pinned == b.pinned && a.total == b.total && a.kind == b.kind;
 }
 
 static void case_layout() {
   CHECK(sizeof(rwkvtts_request_ext) == 16);
   CHECK(offsetof(rwkvtts_request_ext, struct_size) == 0 && offsetof(rwkvtts_request_ext, mirostat_set) == 4);
   CHECK(offsetof(rwkvtts_request_ext, mirostat) == 8 && sizeof(SlotMiro) == 16);
+  // the slot's one block beside its control block: penalties, then the Mirostat state
+  CHECK(sizeof(SlotSampling) == 32 && offsetof(SlotSampling, pen) == 0 && offsetof(SlotSampling, miro) == 16);
   // the request struct ends where it ended: at its penalties (rounded up to its 8-byte alignment)
   CHECK(sizeof(rwkvtts_request) == (offsetof(rwkvtts_request, penalties) + sizeof(rwkvtts_penalties) + 7) / 8 * 8);
 }
@@ -183,8 +184,8 @@ static void case_admission() {
   for (Kind kind : {kNormal, kZeroShot, kPinned}) {
     rwkvtts_request q = request(kind);
     const Admission a0 = admission_of(q, 999);  // the parent's call
-    CHECK(!a0.mirostat && !a0.own_sampling && a0.miro.on == 0 && a0.miro.tau == 0.0f && a0.miro.rate == 0.0f &&
-          a0.miro.mu == 0.0f);
+    CHECK(a0.kind == kAdvFixed && a0.samp.miro.on == 0 && a0.samp.miro.tau == 0.0f && a0.samp.miro.rate == 0.0f &&
+          a0.samp.miro.mu == 0.0f);
     // a null block and a block that sets nothing give that admission, byte for byte
     CHECK(same_admission(a0, admission_of(q, 999, nullptr)));
     const rwkvtts_request_ext unset = miro(7.0f, 0.9f, 0);  // values present but not set: unused
@@ -192,16 +193,16 @@ static void case_admission() {
 
     const rwkvtts_request_ext x = miro(3.0f, 0.1f);
     const Admission a1 = admission_of(q, 999, &x);  // normal, zero-shot and pinned admissions carry the block
-    CHECK(a1.mirostat && a1.own_sampling && a1.miro.on == 1 && a1.miro.tau == 3.0f && a1.miro.rate == 0.1f &&
-          a1.miro.mu == 6.0f);
+    CHECK(a1.kind == kAdvMiro && a1.samp.miro.on == 1 && a1.samp.miro.tau == 3.0f && a1.samp.miro.rate == 0.1f &&
+          a1.samp.miro.mu == 6.0f);
     // everything else is the request's without Mirostat: the control block byte for byte
-    CHECK(memcmp(&a0.ctrl, &a1.ctrl, sizeof(SlotCtrl)) == 0 && memcmp(&a0.pen, &a1.pen, sizeof(SlotPenalty)) == 0);
+    CHECK(memcmp(&a0.ctrl, &a1.ctrl, sizeof(SlotCtrl)) == 0 && memcmp(&a0.samp.pen, &a1.samp.pen, sizeof(SlotPenalty)) == 0);
     CHECK(a1.prompt == a0.prompt && a1.total == a0.total && a1.gseed == a0.gseed && a1.sseed == a0.sseed);
     CHECK(a1.zero_shot == (kind == kZeroShot) && a1.pinned == (kind == kPinned));
     CHECK(a1.ctrl.phase == (kind == kNormal ? kPhGlobal : kPhSemantic));
     for (float tau : {0.5f, 2.5f, 10.0f}) {  // mu = 2 tau
       const rwkvtts_request_ext y = miro(tau, 1.0f);
-      CHECK(admission_of(q, 999, &y).miro.mu == 2.0f * tau);
+      CHECK(admission_of(q, 999, &y).samp.miro.mu == 2.0f * tau);
     }
     // with penalties and the global phase's own values: all three sets arrive
     q.penalty_set = RWKVTTS_PENALTY_SET;
@@ -209,7 +210,7 @@ static void case_admission() {
     q.sampling_set = RWKVTTS_SAMPLING_GLOBAL;
     q.global_sampling = {0.8f, 0.9f, 10};
     const Admission a2 = admission_of(q, 999, &x);
-    CHECK(a2.mirostat && a2.miro.mu == 6.0f && a2.pen.repetition == 1.3f && a2.pen.window == 16 &&
+    CHECK(a2.kind == kAdvMiro && a2.samp.miro.mu == 6.0f && a2.samp.pen.repetition == 1.3f && a2.samp.pen.window == 16 &&
           a2.ctrl.temp_g == 0.8f && a2.ctrl.top_k_g == 10 && a2.ctrl.temp_s == 1.0f && a2.ctrl.top_k_s == 80);
   }
 }
@@ -222,34 +223,74 @@ static void case_plans() {
     Admission ad = admission_of(plain, 999, ext);
     Active a;
     a.slot = slot;
-    a.own_sampling = ad.own_sampling;  // as Engine::admit copies them
-    a.mirostat = ad.mirostat;
+    a.kind = ad.kind;  // as Engine::admit copies it
     a.prompt = ad.prompt;
     a.prefilled = prompt_in ? (int)a.prompt.size() : 0;
     a.total = ad.total;
     return a;
   };
   std::vector<Active> act = {active(nullptr, 0, true), active(&unset, 1, true)};
-  CHECK(!decode_plan(act).mirostat && !decode_plan(act).sampling_params);  // the default controller
+  CHECK(decode_plan(act).kind == kAdvFixed);  // the default controller
   std::vector<Active> m = act;
   const StepPlan mp = mixed_plan(m, 8, 65536);
-  CHECK(!mp.mirostat && !mp.sampling_params);
+  CHECK(mp.kind == kAdvFixed);
   act.push_back(active(&x, 2, true));
-  CHECK(decode_plan(act).mirostat && decode_plan(act).sampling_params);
+  CHECK(decode_plan(act).kind == kAdvMiro);
   m = act;
-  CHECK(mixed_plan(m, 8, 65536).mirostat);
+  CHECK(mixed_plan(m, 8, 65536).kind == kAdvMiro);
   // a Mirostat request still in its prompt already selects the controller of the mixed step
   m = {active(nullptr, 0, true), active(&x, 1, false)};
-  CHECK(mixed_plan(m, 8, 65536).mirostat);
+  CHECK(mixed_plan(m, 8, 65536).kind == kAdvMiro);
   // own sampling values without Mirostat keep the flag clear
   rwkvtts_request sp = plain;
   sp.sampling_set = RWKVTTS_SAMPLING_SEMANTIC;
   sp.semantic_sampling = {0.8f, 0.95f, 80};
   Active a;
-  a.own_sampling = admission_of(sp, 999).own_sampling;
+  a.kind = admission_of(sp, 999).kind;
   a.prefilled = 0;
   std::vector<Active> only = {a};
-  CHECK(decode_plan(only).sampling_params && !decode_plan(only).mirostat);
+  CHECK(decode_plan(only).kind == kAdvParams);
+}
+
+// The kind of a step is the highest kind among its actives, in whatever order they stand, and it
+// falls back when the highest leaves.
+static void case_step_kind() {
+  const rwkvtts_request plain = request(kNormal);
+  rwkvtts_request sp = plain;
+  sp.sampling_set = RWKVTTS_SAMPLING_SEMANTIC;
+  sp.semantic_sampling = {0.8f, 0.95f, 80};
+  const rwkvtts_request_ext x = miro(3.0f, 0.1f);
+  const AdvanceKind kinds[3] = {admission_of(plain, 999).kind, admission_of(sp, 999).kind, admission_of(plain, 999, &x).kind};
+  CHECK(kinds[0] == kAdvFixed && kinds[1] == kAdvParams && kinds[2] == kAdvMiro);
+  CHECK(kAdvFixed < kAdvParams && kAdvParams < kAdvMiro);
+  auto plans_are = [](const std::vector<Active>& act, AdvanceKind want) {
+    std::vector<Active> m = act;
+    CHECK(step_kind(act) == want && decode_plan(act).kind == want && mixed_plan(m, 8, 65536).kind == want);
+  };
+  int order[3] = {0, 1, 2};
+  do {
+    std::vector<Active> act;
+    for (int i = 0; i < 3; ++i) {
+      Active a;
+      a.slot = i;
+      a.kind = kinds[order[i]];
+      a.prompt = {1u};
+      a.prefilled = 1;
+      a.total = 8;
+      act.push_back(a);
+    }
+    plans_are(act, kAdvMiro);
+    for (int drop = 0; drop < 2; ++drop) {  // the highest active leaves: Miro, then Params
+      const AdvanceKind top = drop == 0 ? kAdvMiro : kAdvParams;
+      for (size_t i = 0; i < act.size(); ++i)
+        if (act[i].kind == top) {
+          act.erase(act.begin() + i);
+          break;
+        }
+      plans_are(act, drop == 0 ? kAdvParams : kAdvFixed);
+    }
+  } while (std::next_permutation(order, order + 3));
+  plans_are({}, kAdvFixed);
 }
 
 int main() {
@@ -258,6 +299,7 @@ int main() {
   case_struct_size();
   case_admission();
   case_plans();
+  case_step_kind();
   if (g_fail) {
     fprintf(stderr, "sched miro: %d check(s) failed\n", g_fail);
     return 1;

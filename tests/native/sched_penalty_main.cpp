@@ -126,15 +126,15 @@ static void case_admission() {
   for (Kind kind : {kNormal, kZeroShot, kPinned}) {
     rwkvtts_request q = request(kind);
     const Admission a0 = admission_of(q, 999);
-    CHECK(same_pen(a0.pen, 1.0f, 0.0f, 0.0f, 0) && !a0.own_sampling);
+    CHECK(same_pen(a0.samp.pen, 1.0f, 0.0f, 0.0f, 0) && a0.kind == kAdvFixed);
     q.penalties = {1.3f, 0.7f, 1.5f, 64};  // present but not set: unused
     const Admission a0b = admission_of(q, 999);
-    CHECK(same_pen(a0b.pen, 1.0f, 0.0f, 0.0f, 0) && !a0b.own_sampling);
+    CHECK(same_pen(a0b.samp.pen, 1.0f, 0.0f, 0.0f, 0) && a0b.kind == kAdvFixed);
     CHECK(memcmp(&a0.ctrl, &a0b.ctrl, sizeof(SlotCtrl)) == 0);
 
     q.penalty_set = RWKVTTS_PENALTY_SET;
     const Admission a1 = admission_of(q, 999);  // normal, zero-shot and pinned admissions carry the values
-    CHECK(same_pen(a1.pen, 1.3f, 0.7f, 1.5f, 64) && a1.own_sampling);
+    CHECK(same_pen(a1.samp.pen, 1.3f, 0.7f, 1.5f, 64) && a1.kind == kAdvParams);
     // everything else is the request's without penalties: the control block byte for byte
     CHECK(memcmp(&a0.ctrl, &a1.ctrl, sizeof(SlotCtrl)) == 0);
     CHECK(a1.zero_shot == (kind == kZeroShot) && a1.pinned == (kind == kPinned));
@@ -145,28 +145,28 @@ static void case_admission() {
     // neutral values leave the request on the default controller, whatever the window
     q.penalties = {1.0f, 0.0f, 0.0f, 32};
     const Admission a2 = admission_of(q, 999);
-    CHECK(same_pen(a2.pen, 1.0f, 0.0f, 0.0f, 32) && !a2.own_sampling);
+    CHECK(same_pen(a2.samp.pen, 1.0f, 0.0f, 0.0f, 32) && a2.kind == kAdvFixed);
     // each value alone moves it
     for (rwkvtts_penalties p : {rwkvtts_penalties{0.8f, 0.0f, 0.0f, 0}, rwkvtts_penalties{1.0f, -0.5f, 0.0f, 0},
                                 rwkvtts_penalties{1.0f, 0.0f, 1.5f, 0}}) {
       q.penalties = p;
-      CHECK(admission_of(q, 999).own_sampling);
+      CHECK(admission_of(q, 999).kind == kAdvParams);
     }
     // greedy with penalties: top-k 1 at (1.0, 0.95) through the parameter-reading controller
     q.penalties = {1.3f, 0.0f, 0.0f, 0};
     q.greedy = 1;
     const Admission a3 = admission_of(q, 999);
-    CHECK(a3.own_sampling && a3.ctrl.top_k_g == 1 && a3.ctrl.top_k_s == 1);
+    CHECK(a3.kind == kAdvParams && a3.ctrl.top_k_g == 1 && a3.ctrl.top_k_s == 1);
     CHECK(a3.ctrl.temp_s == 1.0f && a3.ctrl.top_p_s == 0.95f && a3.ctrl.temp_g == 1.0f && a3.ctrl.top_p_g == 0.95f);
     q.penalty_set = 0;
-    CHECK(!admission_of(q, 999).own_sampling);  // greedy alone stays on the default controller
+    CHECK(admission_of(q, 999).kind == kAdvFixed);  // greedy alone stays on the default controller
     // together with sampling_set: both sets of values arrive
     q.greedy = 0;
     q.penalty_set = RWKVTTS_PENALTY_SET;
     q.sampling_set = RWKVTTS_SAMPLING_SEMANTIC;
     q.semantic_sampling = {0.8f, 0.9f, 40};
     const Admission a4 = admission_of(q, 999);
-    CHECK(a4.own_sampling && a4.ctrl.temp_s == 0.8f && a4.ctrl.top_k_s == 40 && same_pen(a4.pen, 1.3f, 0.0f, 0.0f, 0));
+    CHECK(a4.kind == kAdvParams && a4.ctrl.temp_s == 0.8f && a4.ctrl.top_k_s == 40 && same_pen(a4.samp.pen, 1.3f, 0.0f, 0.0f, 0));
   }
 }
 
@@ -186,7 +186,7 @@ static void case_zeroed_block() {
   want.top_p_g = want.top_p_s = 0.95f;
   CHECK(sizeof(SlotCtrl) == offsetof(SlotCtrl, temp_g) + 16 && sizeof(SlotCtrl) % 8 == 0);
   CHECK(memcmp(&a.ctrl, &want, sizeof(SlotCtrl)) == 0);
-  CHECK(sizeof(SlotPenalty) == 16 && same_pen(a.pen, 1.0f, 0.0f, 0.0f, 0));
+  CHECK(sizeof(SlotPenalty) == 16 && same_pen(a.samp.pen, 1.0f, 0.0f, 0.0f, 0));
   // the request struct: the new fields are appended after pinned_voice
   CHECK(offsetof(rwkvtts_request, penalty_set) == offsetof(rwkvtts_request, pinned_voice) + 4);
   CHECK(offsetof(rwkvtts_request, penalties) == offsetof(rwkvtts_request, penalty_set) + 4);
@@ -203,23 +203,23 @@ static void case_plans() {
     Admission ad = admission_of(q, 999);
     Active a;
     a.slot = slot;
-    a.own_sampling = ad.own_sampling;  // as Engine::admit copies it
+    a.kind = ad.kind;  // as Engine::admit copies it
     a.prompt = ad.prompt;
     a.prefilled = prompt_in ? (int)a.prompt.size() : 0;
     a.total = ad.total;
     return a;
   };
   std::vector<Active> act = {active(plain, 0, true), active(neutral, 1, true)};
-  CHECK(!decode_plan(act).sampling_params);
+  CHECK(decode_plan(act).kind == kAdvFixed);
   std::vector<Active> m = act;
-  CHECK(!mixed_plan(m, 8, 65536).sampling_params);
+  CHECK(mixed_plan(m, 8, 65536).kind == kAdvFixed);
   act.push_back(active(pen, 2, true));
-  CHECK(decode_plan(act).sampling_params);
+  CHECK(decode_plan(act).kind == kAdvParams);
   m = act;
-  CHECK(mixed_plan(m, 8, 65536).sampling_params);
+  CHECK(mixed_plan(m, 8, 65536).kind == kAdvParams);
   // a penalised request still in its prompt already selects the controller of the mixed step
   m = {active(plain, 0, true), active(pen, 1, false)};
-  CHECK(mixed_plan(m, 8, 65536).sampling_params);
+  CHECK(mixed_plan(m, 8, 65536).kind == kAdvParams);
 }
 
 int main() {

@@ -126,7 +126,7 @@ static void case_admission() {
   CHECK(ap.ctrl.sdraw == 0 && ap.ctrl.n_sem == 0);
   // seeds as for a normal request: the semantic stream is seed + 2000 by default
   CHECK(ap.sseed == an.sseed && ap.sseed == 7 + 2000 && ap.gseed == an.gseed);
-  CHECK(ap.own_sampling == an.own_sampling && !ap.own_sampling);
+  CHECK(ap.kind == an.kind && ap.kind == kAdvFixed);
   // total: the semantic limit (a normal request: 32 globals, the g31 feed, then the limit)
   CHECK(an.total == 32 + 1 + 20 && ap.total == 20);
   {  // layered randomness, fixed_semantic and per-request sampling as for a normal request
@@ -141,7 +141,7 @@ static void case_admission() {
     const Admission aq = admission_of(q, 999), am = admission_of(m, 999);
     CHECK(aq.sseed == 7 + 200 && aq.sseed == am.sseed);
     CHECK(aq.ctrl.fixed == 1 && aq.ctrl.sem_limit == 40 && aq.total == 40 && am.total == 73);
-    CHECK(aq.ctrl.temp_s == 0.8f && aq.ctrl.top_p_s == 0.9f && aq.ctrl.top_k_s == 50 && aq.own_sampling && am.own_sampling);
+    CHECK(aq.ctrl.temp_s == 0.8f && aq.ctrl.top_p_s == 0.9f && aq.ctrl.top_k_s == 50 && aq.kind == kAdvParams && am.kind == kAdvParams);
   }
   {  // no seed: the entropy stands in, as for a normal request
     rwkvtts_request q = p;
@@ -175,7 +175,7 @@ static Active active_of(const Admission& a, int slot) {
   x.total = a.total;
   x.zero_shot = a.zero_shot;
   x.pinned = a.pinned;
-  x.own_sampling = a.own_sampling;
+  x.kind = a.kind;
   return x;
 }
 

@@ -126,20 +126,20 @@ static void case_admission() {
     rwkvtts_request q = request(zs != 0);
     const Admission a0 = admission_of(q, 999);
     expect(a0.ctrl, 1.0f, 0.95f, 20, 1.0f, 0.95f, 80);
-    CHECK(!a0.own_sampling);
+    CHECK(a0.kind == kAdvFixed);
     q.global_sampling = G;  // present but not set: unused
     q.semantic_sampling = S;
     const Admission a0b = admission_of(q, 999);
-    CHECK(memcmp(&a0.ctrl, &a0b.ctrl, sizeof(SlotCtrl)) == 0 && !a0b.own_sampling);
+    CHECK(memcmp(&a0.ctrl, &a0b.ctrl, sizeof(SlotCtrl)) == 0 && a0b.kind == kAdvFixed);
 
     q.sampling_set = RWKVTTS_SAMPLING_GLOBAL;
     const Admission a1 = admission_of(q, 999);
     expect(a1.ctrl, 0.7f, 0.5f, 0, 1.0f, 0.95f, 80);
-    CHECK(a1.own_sampling);
+    CHECK(a1.kind == kAdvParams);
     q.sampling_set = RWKVTTS_SAMPLING_SEMANTIC;
     const Admission a2 = admission_of(q, 999);
     expect(a2.ctrl, 1.0f, 0.95f, 20, 1.3f, 1.0f, 300);
-    CHECK(a2.own_sampling);
+    CHECK(a2.kind == kAdvParams);
     q.sampling_set = RWKVTTS_SAMPLING_GLOBAL | RWKVTTS_SAMPLING_SEMANTIC;
     const Admission a3 = admission_of(q, 999);
     expect(a3.ctrl, 0.7f, 0.5f, 0, 1.3f, 1.0f, 300);
@@ -154,14 +154,14 @@ static void case_admission() {
     q.semantic_sampling = {1.0f, 0.95f, 50};
     const Admission a4 = admission_of(q, 999);
     expect(a4.ctrl, 1.0f, 0.95f, 20, 1.0f, 0.95f, 50);
-    CHECK(!a4.own_sampling);
+    CHECK(a4.kind == kAdvFixed);
     // ... while a top-k outside the fast path's [1, 256] needs the controller with the general path
     for (int k : {0, 257, 8193}) {
       q.semantic_sampling.top_k = k;
-      CHECK(admission_of(q, 999).own_sampling);
+      CHECK(admission_of(q, 999).kind == kAdvParams);
     }
     q.semantic_sampling.top_k = 256;
-    CHECK(!admission_of(q, 999).own_sampling);
+    CHECK(admission_of(q, 999).kind == kAdvFixed);
   }
 }
 
@@ -191,14 +191,14 @@ static void case_zeroed_block() {
   act[0].total = 50;
   act[1] = act[0];
   act[1].slot = 1;
-  CHECK(!decode_plan(act).sampling_params);
-  act[1].own_sampling = true;
-  CHECK(decode_plan(act).sampling_params);
+  CHECK(decode_plan(act).kind == kAdvFixed);
+  act[1].kind = kAdvParams;
+  CHECK(decode_plan(act).kind == kAdvParams);
   std::vector<Active> m = act;
-  CHECK(mixed_plan(m, 8, 65536).sampling_params);
+  CHECK(mixed_plan(m, 8, 65536).kind == kAdvParams);
   m = act;
-  m[1].own_sampling = false;
-  CHECK(!mixed_plan(m, 8, 65536).sampling_params);
+  m[1].kind = kAdvFixed;
+  CHECK(mixed_plan(m, 8, 65536).kind == kAdvFixed);
 }
 
 int main() {
