@@ -1345,6 +1345,95 @@ int rwkvtts_flac_encode(rwkvtts_flac* f, rwkvtts_flac_window* win, int n);
 /* HIP-event time of the last call's two kernels (no copies), in ms; 0 before the first. */
 int rwkvtts_flac_kernel_ms(rwkvtts_flac* f, double* ms);
 
+/* ---- pause: silences capped on the GPU, the `max_pause` of the pipeline (no reference counterpart:
+ * the reference sends whatever silence the semantic model decided on) -- no silence inside the result
+ * longer than M samples, none at either end longer than half of it ---------------------------------
+ * Rate-agnostic; the pipeline applies it to the vocoder's 16 kHz PCM, first of the stages. The first
+ * stage whose output length depends on the data: n_out <= n. The arithmetic contract (comparisons and
+ * integers; one rounded f32 multiply per faded sample, every other sample a copy):
+ *   desc      block B (samples, a multiple of 4, 4 .. 4096; 0 = 160), hang H (blocks, 1 .. 32; 0 = 5),
+ *             fade F (samples, 1 .. 4096; 0 = 80), threshold (f32, finite, >= 0; 0 = 0.01, the join's)
+ *   signal    x[0, n), n <= 2^30, and M, the cap in samples, 2F <= M <= 2^30; hd = M - M / 2 (integer
+ *             division), tl = M / 2
+ *   blocks    block k covers [kB, min((k + 1)B, n)), k in [0, nb), nb = ceil(n / B). loud_k iff
+ *             fabsf(x) > threshold (an f32 compare, false for NaN) for a sample of the block. active_k
+ *             iff loud_j for an existing j with |j - k| <= H. No sums: nothing depends on an order.
+ *   runs      a quiet run is a maximal run of non-active blocks, samples [s, e), R = e - s (its last
+ *             block may be partial). Activity before it: its head is its first hd samples; activity
+ *             after it: its tail is its last tl samples.
+ *   rule      interior run (activity on both sides): cut iff R > M, head and tail kept (M samples);
+ *             leading run (nothing before it): cut iff R > tl, the tail kept; trailing run (nothing
+ *             after it): cut iff R > hd, the head kept; a run that is not cut is copied whole. No
+ *             active block at all: n_out = 0 (one cut if n > 0).
+ *   ramp      r[k] = (float)((k + 0.5) / F), in double, k in [0, F): the join's
+ *   fades     on a cut only: head sample i in [hd - F, hd) becomes x * r[hd - 1 - i], tail sample j in
+ *             [0, F) becomes x * r[j]: one rounded f32 multiply each, never fused. Everything else --
+ *             active blocks, uncut runs, unfaded kept samples -- is copied bit for bit.
+ * So the output is a subsequence of the input but for at most 2F faded samples per cut, and every faded
+ * sample lies in a block that is not loud.
+ * Streams: the rule is decidable with bounded memory. The state after blocks [0, c) is three integers:
+ * c, seen (an active block lies before c) and q (the samples of the quiet run that ends at cB; 0 if
+ * block c - 1 is active). active_k is decided once blocks up to k + H are complete (or the signal has
+ * ended). Of an open run after activity, the first hd - F samples go out at once, the next F once the
+ * run has ended or passed M (then it is cut whatever follows), its tail when it ends; a leading run is
+ * withheld until activity is decided. Samples still needed: from
+ *   p = cB if q == 0; cB - tl if the cut is certain (seen and q > M, or not seen and q > tl);
+ *       else cB - q + (seen ? min(q, hd - F) : 0)
+ * and the H blocks before c (their loudness reaches blocks from c on): in_first_needed =
+ * max(0, min(p, (c - H)B)), so a stream keeps fewer than M + (2H + 2)B samples however long a silence. */
+typedef struct {
+  uint32_t struct_size;
+  int32_t block;
+  int32_t hang;
+  int32_t fade;
+  float threshold;
+} rwkvtts_pause_desc;
+/* The ramp table (host only): out[F]. Anything outside the ranges above (a NaN or infinite threshold
+ * included) is RWKVTTS_EINVAL, here and in every call that takes a desc. */
+int rwkvtts_pause_ramp(const rwkvtts_pause_desc* desc, float* out);
+typedef struct rwkvtts_pause rwkvtts_pause;
+/* table == NULL: the ramp of rwkvtts_pause_ramp; otherwise the caller's [F] table (copied). */
+int rwkvtts_pause_create(int device, const rwkvtts_pause_desc* desc, const float* table, rwkvtts_pause** out);
+int rwkvtts_pause_destroy(rwkvtts_pause* p);
+/* n signals (ragged, an M per signal) in one launch triple -- flags (a wave per 64 blocks: vector loads,
+ * a compare per sample, a ballot; one bit per block), plan (a workgroup per signal: dilation by H, the
+ * runs, the rule, the prefix of what is removed; a table of cuts), gather (a workgroup per output tile:
+ * copy, or multiply by the ramp). Host buffers; out[i] has capacity n_in[i]; n_out[i] and n_cuts[i]
+ * (NULL: not wanted) are read back first, with a synchronisation of their own, then n_out[i] samples
+ * of each output. RWKVTTS_EINVAL before anything is launched, nothing written, for an M below 2F or
+ * above 2^30, a negative or too long signal or a null buffer. Calls on one handle serialise on its lock. */
+int rwkvtts_pause_batch(rwkvtts_pause* p, const float* const* in, const int64_t* n_in,
+                        const int64_t* max_pause_samples, int n, float* const* out, int64_t* n_out,
+                        int64_t* n_cuts);
+typedef struct {
+  uint32_t struct_size;
+  int32_t final;               /* the known samples end the signal */
+  const float* in;             /* signal samples [in_first, in_first + n_in), host */
+  int64_t in_first;            /* <= in_first_needed of the state below */
+  int64_t n_in;
+  int64_t max_pause_samples;   /* M, the same for every window of a signal */
+  int64_t block_next;          /* c: blocks [0, c) are decided (0 at the start) */
+  int64_t quiet;               /* q (0 at the start) */
+  int32_t seen;                /* 0 or 1 (0 at the start) */
+  int32_t seen_last;           /* out: the state after this window */
+  int64_t block_last;          /* out */
+  int64_t quiet_last;          /* out (0 after a final window: no run is open) */
+  float* out;                  /* host, capacity out_cap */
+  int64_t out_cap;             /* >= (the end of what this window decides) - p: n_in is always enough */
+  int64_t out_count;           /* out: samples written */
+  int64_t n_cuts;              /* out: cuts decided in this window (a cut counts where its run ends) */
+  int64_t in_first_needed;     /* out: the first sample the next window must still carry */
+} rwkvtts_pause_window;
+/* n windows (of any signals) in one launch triple: each gives the outputs that its known samples decide
+ * beyond its state, bitwise the whole-signal result whatever follows them. The caller cannot plan the
+ * count, so the capacity is part of the struct. RWKVTTS_EINVAL before anything is launched, nothing
+ * written, for an M outside its range, too little capacity, samples that start after in_first_needed
+ * or end before block c, or a state no scan can have left (c < 0, seen not 0 or 1, q negative, no
+ * multiple of B or above cB, seen with q above (c - 1)B, not seen with q below cB). */
+int rwkvtts_pause_windows(rwkvtts_pause* p, rwkvtts_pause_window* w, int n);
+/* HIP-event time of the last call's three kernels (no copies), in ms; 0 before the first. */
+int rwkvtts_pause_kernel_ms(rwkvtts_pause* p, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

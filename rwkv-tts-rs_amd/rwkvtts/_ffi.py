@@ -277,6 +277,20 @@ class WmResult(ctypes.Structure):
 FLAC_LAST, FLAC_NO_LPC = 1, 2
 
 
+class PauseDesc(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("block", ctypes.c_int32), ("hang", ctypes.c_int32),
+                ("fade", ctypes.c_int32), ("threshold", ctypes.c_float)]
+
+
+class PauseWindow(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("final", ctypes.c_int32), ("in_", ctypes.c_void_p),
+                ("in_first", ctypes.c_int64), ("n_in", ctypes.c_int64), ("max_pause_samples", ctypes.c_int64),
+                ("block_next", ctypes.c_int64), ("quiet", ctypes.c_int64), ("seen", ctypes.c_int32),
+                ("seen_last", ctypes.c_int32), ("block_last", ctypes.c_int64), ("quiet_last", ctypes.c_int64),
+                ("out", ctypes.c_void_p), ("out_cap", ctypes.c_int64), ("out_count", ctypes.c_int64),
+                ("n_cuts", ctypes.c_int64), ("in_first_needed", ctypes.c_int64)]
+
+
 class FlacWindow(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("in_", ctypes.c_void_p), ("n_in", ctypes.c_int64),
                 ("scale", ctypes.c_float), ("sample_rate", ctypes.c_int32), ("block_size", ctypes.c_int32),
@@ -474,6 +488,15 @@ EXPORTS = {
     "rwkvtts_flac_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "rwkvtts_flac_encode": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(FlacWindow), ctypes.c_int]),
     "rwkvtts_flac_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    # pause: ramp (host only), batched / exact stream windows; the output length depends on the data
+    "rwkvtts_pause_ramp": (ctypes.c_int, [ctypes.POINTER(PauseDesc), ctypes.c_void_p]),
+    "rwkvtts_pause_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(PauseDesc), ctypes.c_void_p,
+                                            ctypes.POINTER(ctypes.c_void_p)]),
+    "rwkvtts_pause_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "rwkvtts_pause_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "rwkvtts_pause_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PauseWindow), ctypes.c_int]),
+    "rwkvtts_pause_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None

@@ -45,6 +45,11 @@ and the clip / silence helpers it uses), feeding the HIP mel kernel (features.py
   exact over stream chunks (`FlacStream`); the subframe of each block chosen by exact bit count. Bitwise
   its numpy restatement (tests/flac_ref.py); read back by the independent decoder rwkvtts/flac.py.
   Contract: include/rwkvtts.h, DESIGN.md §31.
+* `PauseShaper` (no reference counterpart: the reference sends whatever silence the semantic model
+  chose): silences capped as HIP kernels (csrc/pause.hip) -- loud and active blocks by comparison, runs
+  of non-active blocks longer than the cap cut to a faded head and tail -- one-shot, batched with a cap
+  per signal and exact over stream chunks (`PauseStream`), the output shorter than the input by what
+  was cut. Bitwise its numpy restatement (tests/pause_ref.py). Contract: include/rwkvtts.h, DESIGN.md §35.
 """
 import ctypes
 import struct
@@ -1215,6 +1220,154 @@ class FlacStream:
             self._tail = self._tail[take:].copy()
         if final:
             self._closed = True
+        return out
+
+
+# ---- pause control on the GPU ----------------------------------------------------------------
+class PauseShaper(_NativeStage):
+    """Silences capped as HIP kernels (csrc/pause.hip; the arithmetic contract is in include/rwkvtts.h,
+    DESIGN.md §35): a block of `block` samples is loud if a sample of it passes `threshold`, active if
+    a block within `hang` of it is loud; a run of non-active blocks is cut when it is longer than M
+    inside the signal (head M - M // 2 and tail M // 2 kept), longer than M // 2 at the start (tail
+    kept) or longer than M - M // 2 at the end (head kept), and each kept edge of a cut is faded over
+    `fade` samples. Everything else is copied bit for bit, so the output is a subsequence of the input
+    but for the faded samples, and n_out <= n: the first stage whose output length depends on the data.
+    One-shot, batched with a cap per signal, and exact over stream chunks. The pipeline applies it at
+    16 kHz, first of the stages. A cap is in milliseconds at `rate` (shape_batch) or in samples.
+
+    0 means the default as in the C desc: block 160 (10 ms), hang 5, fade 80, threshold 0.01 (the
+    join's). Every default, and the half-and-half split of M, is untuned and nobody has listened to the
+    output: the repository has no real checkpoint. The kernels read the table `_join_ramp` builds.
+
+    evaluator: a callable (shaper, items) -> [(ndarray, block_next, seen, quiet, in_first_needed,
+    n_cuts)] standing in for the native window call, items being [(samples from in_first on, in_first,
+    final, M, block_next, seen, quiet)]; no GPU object is created then (the host-only ramp entry point
+    is still the library's)."""
+    _NAME = "pause"
+
+    def __init__(self, device: int = 0, block: int = 160, hang: int = 5, fade: int = 80, threshold: float = 0.01,
+                 evaluator=None, rate: int = 16000):
+        self.device, self.rate = int(device), int(rate)
+        self._desc = _ffi.PauseDesc(struct_size=ctypes.sizeof(_ffi.PauseDesc), block=int(block), hang=int(hang),
+                                    fade=int(fade), threshold=float(threshold))
+        super().__init__(evaluator)
+        self.block, self.hang, self.fade = int(block) or 160, int(hang) or 5, int(fade) or 80
+        self.threshold = float(F32(threshold)) or float(F32(0.01))
+        probe = np.zeros(self.fade if 1 <= self.fade <= 4096 else 1, dtype=F32)
+        _native("pause_ramp", ctypes.byref(self._desc), probe.ctypes.data_as(ctypes.c_void_p))  # (refuses a bad description)
+        self.table = _join_ramp(self.fade)
+        self.cuts = []  # the cuts of each signal of the last shape_* call
+        self._create(self.table)
+
+    def samples(self, max_pause_ms) -> int:
+        """M, the cap in samples at the shaper's rate; ValueError below 2 * fade."""
+        if isinstance(max_pause_ms, bool) or not isinstance(max_pause_ms, (int, np.integer)):
+            raise ValueError("max_pause must be an integer number of milliseconds")
+        m = int(max_pause_ms) * self.rate // 1000
+        if not 2 * self.fade <= m <= 1 << 30:
+            raise ValueError(f"max_pause gives {m} samples, outside [2 * fade, 2^30]")
+        return m
+
+    def kept_bound(self, m: int) -> int:
+        """What a stream keeps at most: M + (2 * hang + 2) * block samples."""
+        return int(m) + (2 * self.hang + 2) * self.block
+
+    # ---- the kernels ----
+    def shape_windows(self, items) -> list:
+        """[(samples from in_first on, in_first, final, M, block_next, seen, quiet)] -> [(what the
+        window decides beyond its state -- bitwise the whole-signal result, whatever follows --
+        block_next, seen, quiet, in_first_needed, n_cuts)], all windows in one launch triple. Raises
+        RwkvTtsError(EINVAL), with nothing computed, for an M outside [2 * fade, 2^30], samples that
+        start after the state's in_first_needed, or a state no scan can have left."""
+        items = [(np.ascontiguousarray(x, dtype=F32).reshape(-1), int(a), bool(f), int(m), int(c), int(s), int(q))
+                 for x, a, f, m, c, s, q in items]
+        if self._evaluator is not None:
+            for x, a, f, m, c, s, q in items:  # the native call's own refusals
+                B = self.block
+                ok = (2 * self.fade <= m <= 1 << 30 and a >= 0 and c >= 0 and s in (0, 1) and q >= 0 and q % B == 0
+                      and ((c >= 1 and q <= (c - 1) * B) if s else q == c * B) and c * B <= a + x.size)
+                if not ok:
+                    raise _ffi.RwkvTtsError(_ffi.EINVAL, "pause_windows")
+            res = [(np.ascontiguousarray(y, dtype=F32), int(c), int(s), int(q), int(need), int(cuts))
+                   for y, c, s, q, need, cuts in self._evaluator(self, items)]
+        else:
+            ws = (_ffi.PauseWindow * len(items))()
+            outs = [np.empty(x.size, dtype=F32) for x, *_ in items]
+            for w, (x, a, f, m, c, s, q), out in zip(ws, items, outs):
+                w.struct_size = ctypes.sizeof(_ffi.PauseWindow)
+                w.in_, w.in_first, w.n_in, w.final = x.ctypes.data, a, x.size, 1 if f else 0
+                w.max_pause_samples, w.block_next, w.seen, w.quiet = m, c, s, q
+                w.out, w.out_cap = out.ctypes.data, out.size
+            if items:
+                self._call("pause_windows", ws, len(items))
+            res = [(out[:int(w.out_count)].copy(), int(w.block_last), int(w.seen_last), int(w.quiet_last),
+                    int(w.in_first_needed), int(w.n_cuts)) for w, out in zip(ws, outs)]
+        self.cuts = [r[5] for r in res]
+        return res
+
+    def shape_samples_batch(self, signals, caps) -> list:
+        """[signal], [M in samples] -> [shaped signal], ragged, a cap per signal, in one launch triple;
+        an empty signal gives an empty one. self.cuts: the cuts made in each."""
+        xs = [np.ascontiguousarray(x, dtype=F32).reshape(-1) for x in signals]
+        ms = [int(m) for m in caps]
+        if len(xs) != len(ms):
+            raise ValueError("shape_batch: one cap per signal")
+        if self._evaluator is not None:
+            return [r[0] for r in self.shape_windows([(x, 0, True, m, 0, 0, 0) for x, m in zip(xs, ms)])]
+        if not xs:
+            self.cuts = []
+            return []
+        outs, ins, lens, ous = self._ragged(xs, [x.size for x in xs])
+        n_out, n_cuts = (ctypes.c_int64 * len(xs))(), (ctypes.c_int64 * len(xs))()
+        self._call("pause_batch", ins, lens, (ctypes.c_int64 * len(ms))(*ms), len(xs), ous, n_out, n_cuts)
+        self.cuts = [int(c) for c in n_cuts]
+        return [o[:int(n)].copy() for o, n in zip(outs, n_out)]
+
+    def shape_batch(self, pcm, max_pause_ms) -> list:
+        """[signal], a cap in ms for all (or one per signal) -> [shaped signal] (shape_samples_batch)."""
+        pcm = list(pcm)
+        caps = list(max_pause_ms) if isinstance(max_pause_ms, (list, tuple)) else [max_pause_ms] * len(pcm)
+        return self.shape_samples_batch(pcm, [self.samples(m) for m in caps])
+
+    def shape(self, x, max_pause_ms) -> np.ndarray:
+        return self.shape_batch([x], max_pause_ms)[0]
+
+    def stream(self, max_pause_ms) -> "PauseStream":
+        return PauseStream(self, self.samples(max_pause_ms))
+
+
+class PauseStream(_ExactStream):
+    """PauseShaper.stream(max_pause_ms): feed(pcm_chunk, final=False) -> the samples that became exact
+    with it (often none: leading silence is withheld, and the last `fade` samples of a kept head wait
+    until the run has ended or passed M). The concatenation of what feed returns is bitwise
+    PauseShaper.shape(the concatenated input), however the input was cut. The state is three integers
+    and no samples; the kept tail is what the window call asks for, never more than
+    M + (2 * hang + 2) * block samples however long a silence (checked on every feed). cuts: the cuts
+    made so far."""
+
+    def __init__(self, shaper: PauseShaper, m: int):
+        super().__init__()
+        self.p, self.m = shaper, int(m)
+        if not 2 * shaper.fade <= self.m <= 1 << 30:
+            raise ValueError("the cap must be in [2 * fade, 2^30] samples")
+        self._state = (0, 0, 0)  # (block_next, seen, quiet)
+        self._need = 0
+        self.cuts = 0
+
+    def _emit(self, n_known, final):
+        out, c, s, q, self._need, cuts = self.p.shape_windows([(self._tail, self._tail_first, final, self.m,
+                                                                *self._state)])[0]
+        self._state = (c, s, q)
+        self.cuts += cuts
+        return out
+
+    def _first_needed(self, n_known):
+        return self._need
+
+    def feed(self, pcm_chunk, final: bool = False) -> np.ndarray:
+        out = super().feed(pcm_chunk, final)
+        if self.kept > self.p.kept_bound(self.m):
+            raise RuntimeError(f"pause stream keeps {self.kept} samples, above its bound {self.p.kept_bound(self.m)}")
         return out
 
 

@@ -29,6 +29,12 @@ pipeline's `watermark_key` (audio.Watermarker) on the 16 k
 leveller and before the resampler -- in long-form on the joined signal, one continuous sequence --
 exact over stream chunks. The key belongs to the pipeline, not to a request; without one, `watermark`
 raises ValueError before anything is generated. detect_watermark reads a clip back.
+All five also take `max_pause` (no reference counterpart: the reference sends whatever silence the
+semantic model chose): None leaves the PCM as it is; a cap in milliseconds, an integer 20 .. 5000,
+cuts every silence of the 16 kHz PCM on the GPU to at most that inside the result and half of it at
+either end (audio.PauseShaper), first of the stages -- in long-form per segment,
+before the join, whose own pauses stay -- exact over stream chunks. It is the one stage whose output
+length depends on the data.
 LightweightTtsPipelineArgs.global_sampling / semantic_sampling (no reference counterpart: the
 reference carries temperature / top_p / top_k and samples with fixed values) set the token
 generator's temperature, top-p and top-k per phase (runtime.PhaseSampling); a value outside its
@@ -143,7 +149,9 @@ def check_sampling(args) -> None:
 class SpeechChunk(np.ndarray):
     """One item of stream_speech: float32 PCM of frames [t0, t1) (an ndarray, so b"".join(chunks) and
     np.concatenate work on it), decoded when n_known semantic tokens were known; done: the request had
-    finished by then."""
+    finished by then. t0 and t1 are always the vocoder's frames; behind a stage that changes the
+    length (tempo, sample_rate, and max_pause, which removes a data-dependent number of samples) the
+    chunk's length does not follow from them."""
     t0 = t1 = n_known = 0
     done = False
 
@@ -159,7 +167,9 @@ class LongSpeech(np.ndarray):
     ndarray) that also carries global_tokens (the voice every segment spoke with; None if none is
     known) and segments, one record per segment it holds: text, status, n_semantic, truncated (the
     segment emitted as many semantic tokens as its limit allows: it was probably cut off), pause_ms,
-    and a, b (the samples [a, b) of the segment's 16 kHz PCM that the join kept)."""
+    and a, b (the samples [a, b) of the segment's 16 kHz PCM that the join kept). With max_pause a
+    record also has cut (the samples the pause cap removed from the segment before the join), and a, b
+    refer to the shaped segment."""
     global_tokens = None
     segments = ()
 
@@ -172,12 +182,15 @@ class LongSpeech(np.ndarray):
 
 
 def audio_stages(stretcher, tempo, resampler, leveller=None, loudness=None, shifter=None, pitch_shift=None,
-                 marker=None, watermark=None, watermark_key=None) -> list:
-    """The stages behind the vocoder in the order they apply -- the pitch shift at 16 kHz, then the
-    stretch, then the leveller, then the watermark, then the resampler; None is no stage -- each as
-    (batch, stream): batch([pcm]) -> [pcm] in one native call (one shift, one tempo, one loudness, one
-    key and payload for the call), stream() -> an object whose feed(pcm, final) is exact over chunks."""
+                 marker=None, watermark=None, watermark_key=None, shaper=None, max_pause=None) -> list:
+    """The stages behind the vocoder in the order they apply -- the pause cap at 16 kHz, then the pitch
+    shift, then the stretch, then the leveller, then the watermark, then the resampler; None is no
+    stage -- each as (batch, stream): batch([pcm]) -> [pcm] in one native call (one cap, one shift, one
+    tempo, one loudness, one key and payload for the call), stream() -> an object whose feed(pcm, final)
+    is exact over chunks. The pause cap removes samples, so every stage behind it does less work."""
     stages = []
+    if shaper is not None:
+        stages.append((lambda pcm: shaper.shape_batch(pcm, max_pause), lambda: shaper.stream(max_pause)))
     if shifter is not None:
         stages.append((lambda pcm: shifter.shift_batch(pcm, [pitch_shift] * len(pcm)), lambda: shifter.stream(pitch_shift)))
     if stretcher is not None:
@@ -224,7 +237,9 @@ class LightweightTtsPipeline:
         self.watermark_key = watermark_key
         self._marker = None  # audio.Watermarker (created on the first watermark or detect_watermark, kept)
         self._encoder = None  # audio.FlacEncoder (created on the first `format: "flac"`, kept)
-        self._stage_cache_lock = threading.Lock()  # guards all seven (the server's worker threads share the pipeline)
+        self._shapers = {}  # threshold -> audio.PauseShaper (created on the first max_pause, kept)
+        self._pause_threshold = None  # the loudness threshold of `max_pause` (None: audio.PauseShaper's default)
+        self._stage_cache_lock = threading.Lock()  # guards all eight (the server's worker threads share the pipeline)
 
     # ---- output rates other than 16 kHz (no reference counterpart: the reference emits 16 kHz only)
     def resampler(self, sample_rate: Optional[int]):
@@ -331,6 +346,33 @@ class LightweightTtsPipeline:
         payload bit is as sure as min_z is large (under 1: a guess). DESIGN.md section 30."""
         return self.marker(0).detect(pcm, self.watermark_key)
 
+    # ---- pauses (no reference counterpart: the reference sends the silence the semantic model chose)
+    def pause_shaper(self, max_pause: Optional[int], threshold: Optional[float] = None):
+        """None for None (nothing is created: the PCM is the vocoder's); otherwise the pipeline's
+        PauseShaper (the untuned defaults of audio.PauseShaper), on the codec's GPU. The cap is an
+        integer number of milliseconds per call, not a part of the object: no silence inside the
+        result is longer than it, none at either end longer than half of it. A cap outside 20 .. 5000,
+        a bool, a NaN or a fraction raises ValueError before anything is generated. threshold: the
+        loudness threshold of the pipeline's pause stage from this call on (it belongs to the
+        deployment, like the watermark key; None keeps the current one, at first the join's 0.01)."""
+        if threshold is not None:
+            if isinstance(threshold, bool) or not 0.0 < float(threshold) <= 3.0e38:  # (NaN fails)
+                raise ValueError("the pause threshold must be finite and positive")
+            self._pause_threshold = float(np.float32(threshold))
+        if max_pause is None:
+            return None
+        if (isinstance(max_pause, bool) or not isinstance(max_pause, (int, float, np.integer, np.floating))
+                or not 20 <= max_pause <= 5000 or int(max_pause) != max_pause):  # (NaN fails the comparison)
+            raise ValueError("max_pause must be an integer number of milliseconds in [20, 5000]")
+        key = self._pause_threshold
+        with self._stage_cache_lock:
+            ps = self._shapers.get(key)
+            if ps is None:
+                from .audio import PauseShaper
+                ps = self._shapers[key] = PauseShaper(device=getattr(self.codec, "device", 0),
+                                                      **({} if key is None else {"threshold": key}))
+        return ps
+
     # ---- compressed output (no reference counterpart: the reference sends WAV only)
     def encoder(self):
         """The pipeline's one FlacEncoder, on the codec's GPU, created on first use. It is no stage of
@@ -342,14 +384,18 @@ class LightweightTtsPipeline:
         return self._encoder
 
     def _stages(self, sample_rate: Optional[int], tempo: Optional[float], loudness: Optional[float] = None,
-                pitch_shift: Optional[float] = None, watermark: Optional[int] = None):  # -> (stages, output rate)
+                pitch_shift: Optional[float] = None, watermark: Optional[int] = None,
+                max_pause: Optional[int] = None):  # -> (stages, output rate)
         rs = self.resampler(sample_rate)
         lv = self.leveller(loudness)
         sh = self.shifter(pitch_shift)
         mk = self.marker(watermark)
+        ps = self.pause_shaper(max_pause)
+        # (without max_pause the call is the one it always was: stand-ins of audio_stages see no new keyword)
+        kw = {} if ps is None else {"shaper": ps, "max_pause": int(max_pause)}
         return (audio_stages(self.stretcher(tempo), tempo, rs, lv, None if lv is None else float(loudness),
                              sh, None if sh is None else float(pitch_shift),
-                             mk, None if mk is None else int(watermark), self.watermark_key),
+                             mk, None if mk is None else int(watermark), self.watermark_key, **kw),
                 rs.sr_out if rs else SAMPLE_RATE)
 
     # ---- text / attribute handling (:148-193)
@@ -413,7 +459,8 @@ class LightweightTtsPipeline:
 
     def generate_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
                         tempo: Optional[float] = None, loudness: Optional[float] = None,
-                        watermark: Optional[int] = None, pitch_shift: Optional[float] = None) -> np.ndarray:
+                        watermark: Optional[int] = None, max_pause: Optional[int] = None,
+                        pitch_shift: Optional[float] = None) -> np.ndarray:
         """sample_rate None / 16000: the vocoder's 16 kHz PCM. Any other rate: that PCM resampled on
         the GPU (resampler()); the failed-request second of silence is sample_rate zeros.
         tempo None / 1.0: nothing. Any other: the 16 kHz PCM time-stretched on the GPU (stretcher())
@@ -427,9 +474,12 @@ class LightweightTtsPipeline:
         watermark None: nothing. A payload 0 .. 65535: the 16 kHz PCM marked on the GPU (marker())
         under the pipeline's key, after the leveller and before the resampler; the failed-request
         second of silence is not marked (silence carries no mark).
+        max_pause None: nothing. A cap in milliseconds, an integer 20 .. 5000: the silences of the
+        16 kHz PCM capped on the GPU (pause_shaper()), first of the stages, so the result is shorter
+        than the vocoder's PCM by what was cut; the failed-request second of silence is not shaped.
         args.global_sampling / semantic_sampling outside their ranges raise ValueError, like tempo."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause)
         try:
             req = self._request(args)
         except ValueError:  # untokenisable text: the request fails -> empty result
@@ -445,7 +495,7 @@ class LightweightTtsPipeline:
     def stream_speech(self, args: LightweightTtsPipelineArgs, chunk_frames: int = 16,
                       sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                       loudness: Optional[float] = None, watermark: Optional[int] = None,
-                      pitch_shift: Optional[float] = None):
+                      max_pause: Optional[int] = None, pitch_shift: Optional[float] = None):
         """generate_speech as a generator of float32 PCM chunks (SpeechChunk: an ndarray that also
         carries t0, t1, n_known, done), each decoded while the request is still generating tokens.
 
@@ -479,7 +529,13 @@ class LightweightTtsPipeline:
 
         watermark (a payload 0 .. 65535): Watermarker.stream(key, payload) sits after the leveller, and
         the concatenation is bitwise generate_speech(args, watermark=...). A marked item lags its
-        frames by less than one block, 20 ms."""
+        frames by less than one block, 20 ms.
+
+        max_pause (milliseconds, 20 .. 5000): PauseShaper.stream(max_pause) comes first of all, and the
+        concatenation is bitwise generate_speech(args, max_pause=...). t0 and t1 stay the vocoder's
+        frames, and a chunk's length no longer follows from them: an item holds what became exact
+        with its frames -- nothing while the request is still in its leading silence (which is latency
+        no more), less than its frames where a silence was cut."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         check_sampling(args)
@@ -495,19 +551,22 @@ class LightweightTtsPipeline:
         if watermark is not None:
             self.marker(watermark)  # (and for a bad payload or a missing key)
             kw["watermark"] = watermark
+        if max_pause is not None:
+            self.pause_shaper(max_pause)  # (and for a bad cap)
+            kw["max_pause"] = max_pause
         return self.stream_request(req, chunk_frames, sample_rate=sample_rate, tempo=tempo, loudness=loudness, **kw)
 
     def stream_request(self, req: Optional[TtsBatchRequest], chunk_frames: int = 16,
                        sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                        loudness: Optional[float] = None, watermark: Optional[int] = None,
-                       pitch_shift: Optional[float] = None):
+                       max_pause: Optional[int] = None, pitch_shift: Optional[float] = None):
         """stream_speech for a request that is already built (None: a request that failed before it
         was submitted)."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         if req is not None:
             check_sampling(req.args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause)
         streams = [stream() for _, stream in stages]
         H = self.codec.halo()
         g, sem, t0, yielded, status = None, [], 0, False, 0
@@ -543,17 +602,19 @@ class LightweightTtsPipeline:
     def generate_speech_batch(self, batch_args: Sequence[LightweightTtsPipelineArgs],
                               sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                               loudness: Optional[float] = None, watermark: Optional[int] = None,
-                              pitch_shift: Optional[float] = None) -> List[np.ndarray]:
+                              max_pause: Optional[int] = None, pitch_shift: Optional[float] = None) -> List[np.ndarray]:
         """sample_rate other than None / 16000: the whole batch is resampled in one resample_batch
         call (a failed item stays an empty array). tempo other than None / 1.0: the whole batch is
         first stretched in one stretch_batch call, one tempo for the call. loudness other than None:
         the whole batch is levelled in one level_batch call between the two, one target for the call.
         pitch_shift other than None / 0: the whole batch is shifted in one shift_batch call before
         all of them, one shift for the call. watermark other than None: the whole batch is marked in
-        one embed_batch call after the leveller, one payload for the call."""
+        one embed_batch call after the leveller, one payload for the call. max_pause other than None:
+        the silences of the whole batch are capped in one shape_batch call before all of them, one
+        cap for the call."""
         for a in batch_args:
             check_sampling(a)
-        stages, _ = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark)
+        stages, _ = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause)
         reqs, idx = [], []
         for i, a in enumerate(batch_args):
             try:
@@ -625,11 +686,19 @@ class LightweightTtsPipeline:
         return {"text": seg.text, "status": int(status), "n_semantic": len(s), "truncated": bool(s) and len(s) >= limit,
                 "pause_ms": int(seg.pause_ms), "a": 0, "b": 0}
 
+    @staticmethod
+    def _long_shape(shaper, max_pause, pcm, recs):
+        """The segments' PCM with their silences capped, in one call; each record gains `cut`."""
+        shaped = shaper.shape_batch(pcm, int(max_pause))
+        for rec, x, y in zip(recs, pcm, shaped):
+            rec["cut"] = int(np.asarray(x).size - y.size)
+        return shaped
+
     def generate_long_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
                              tempo: Optional[float] = None, segment_tokens: int = 64, pauses=None,
                              trim: bool = True, keep: int = 800, fade: int = 80,
                              loudness: Optional[float] = None, watermark: Optional[int] = None,
-                             pitch_shift: Optional[float] = None) -> "LongSpeech":
+                             max_pause: Optional[int] = None, pitch_shift: Optional[float] = None) -> "LongSpeech":
         """generate_speech for a text of any length: the text is cut into segments of at most
         segment_tokens text tokens (segment.split_text), the segments decode side by side in the
         manager's slots and engines with one voice (_long_submit), and their PCM is joined on the
@@ -644,9 +713,14 @@ class LightweightTtsPipeline:
         signal as one (generate_speech), so the segments, decoded as independent requests, come out
         at one level; the second of silence is not levelled. pitch_shift shifts the joined signal as
         one, after the join and before the stretch. watermark marks the joined signal as one, so a
-        job carries one continuous sequence across its segments and pauses."""
+        job carries one continuous sequence across its segments and pauses. max_pause caps the
+        silences of every segment's PCM before the join, all segments in one shape_batch call; the
+        pauses the join puts between segments are deliberate and stay. A record's `cut` is what the
+        cap removed from its segment, and its a, b then refer to the shaped segment. The second of
+        silence is not shaped."""
         check_sampling(args)
         stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark)
+        shaper = self.pause_shaper(max_pause)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)
         if plan is None:
@@ -658,6 +732,8 @@ class LightweightTtsPipeline:
         if not any(st == 0 and (r[0] or r[1]) for r, st in results):
             return LongSpeech.make(np.zeros(rate, dtype=np.float32), voice, recs)
         pcm = self.codec.decode_audio_batch([r if st == 0 else ([], []) for r, st in results])
+        if shaper is not None:
+            pcm = self._long_shape(shaper, max_pause, pcm, recs)
         out, ab = joiner.join(pcm, [sg.pause_ms * (SAMPLE_RATE // 1000) for sg in segs])
         for rec, (a, b) in zip(recs, ab):
             rec["a"], rec["b"] = a, b
@@ -668,7 +744,8 @@ class LightweightTtsPipeline:
     def stream_long_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
                            tempo: Optional[float] = None, segment_tokens: int = 64, pauses=None,
                            trim: bool = True, keep: int = 800, fade: int = 80, loudness: Optional[float] = None,
-                           watermark: Optional[int] = None, pitch_shift: Optional[float] = None):
+                           watermark: Optional[int] = None, max_pause: Optional[int] = None,
+                           pitch_shift: Optional[float] = None):
         """generate_long_speech as a generator of LongSpeech items, one per segment, in order: segment
         i is emitted once it and every segment before it are done -- decoded, joined alone with its
         gap (a piece depends on its own segment only), and fed through the stages' exact streams,
@@ -679,9 +756,11 @@ class LightweightTtsPipeline:
         first good one are held back until it arrives, so a text whose every segment fails yields
         the one second of silence alone. Streaming inside a segment is out of scope. With loudness
         an item also waits for the leveller's look-ahead (up to 0.5 s of the next segment), with
-        pitch_shift for the shifter's (0.1 s), with watermark for the rest of its last block (20 ms)."""
+        pitch_shift for the shifter's (0.1 s), with watermark for the rest of its last block (20 ms).
+        max_pause caps the silences of each segment's PCM before its join, one call per segment."""
         check_sampling(args)
         stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark)
+        shaper = self.pause_shaper(max_pause)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)
         if plan is None:
@@ -699,6 +778,8 @@ class LightweightTtsPipeline:
                 if good and voice is None and r[0]:
                     voice = list(r[0])
                 pcm = self.codec.decode_audio_batch([r if st == 0 else ([], [])])[0]
+                if shaper is not None:
+                    pcm = self._long_shape(shaper, max_pause, [pcm], [rec])[0]
                 piece, ((rec["a"], rec["b"]),) = joiner.join([pcm], [sg.pause_ms * (SAMPLE_RATE // 1000)])
                 last = i + 1 == len(segs)
                 if not started and not good:

@@ -73,6 +73,13 @@
   a server whose pipeline has no `watermark_key`. The payload is embedded in the 16 kHz PCM under the
   pipeline's key as a spread-spectrum mark (audio.Watermarker), after the leveller and before the
   resampler. Without the field the routes are unchanged.
+* `max_pause` in the body of both TTS routes (no reference counterpart: the reference sends whatever
+  silence the semantic model chose): a JSON integer in [MAX_PAUSE_MIN, MAX_PAUSE_MAX] = [20, 5000]
+  milliseconds, anything else a 400. No silence inside the audio is longer than it and none at either
+  end longer than half of it (audio.PauseShaper), capped on the 16 kHz PCM on the GPU before every
+  other stage; with `long_form` per segment, before the join, whose own pauses stay. On the stream
+  route a request that is all leading silence so far sends nothing yet. Without the field the routes
+  are unchanged.
 * `handle_watermark_detect(path, pipeline)`, POST /api/watermark/detect (no reference counterpart): an
   uploaded WAV at any supported rate, brought to 16 kHz by `load_audio(..., device=)` without volume
   normalisation, read back under the pipeline's key -> {detected, score, threshold, payload,
@@ -164,6 +171,9 @@ FORMATS = ("wav", "flac")
 # `watermark` of the same bodies (no reference counterpart): the payload of the provenance mark, 16
 # bits at the marker's defaults -- a tenant or deployment number, not a secret (the key is the secret)
 WATERMARK_MIN, WATERMARK_MAX = 0, 65535
+# `max_pause` of the same bodies (no reference counterpart): the longest silence inside the result, in
+# milliseconds (half of it at either end) -- the pipeline's range
+MAX_PAUSE_MIN, MAX_PAUSE_MAX = 20, 5000
 
 
 def map_speed(speed) -> str:
@@ -219,7 +229,8 @@ def _tts_args(body, voice_dir: str):
     takes beyond the args, each only when the body sets it to something other than its default --
     sample_rate (one of SAMPLE_RATES, not 16000), tempo (TEMPO_MIN .. TEMPO_MAX, not 1.0), loudness
     (LOUDNESS_MIN .. LOUDNESS_MAX; there is no default value that means "off" but its absence) and
-    pitch_shift (PITCH_SHIFT_MIN .. PITCH_SHIFT_MAX, not 0) -- so a
+    pitch_shift (PITCH_SHIFT_MIN .. PITCH_SHIFT_MAX, not 0), and max_pause (an integer MAX_PAUSE_MIN ..
+    MAX_PAUSE_MAX ms; absent is off) -- so a
     body without them makes exactly the call it always made. A true `long_form` adds
     long_form=True, which the handler takes out and answers by calling the long-form entry point,
     and segment_tokens when the body sets it."""
@@ -260,6 +271,11 @@ def _tts_args(body, voice_dir: str):
                              or not WATERMARK_MIN <= mark <= WATERMARK_MAX):
         return (400, {"success": False, "error": f"不支持的水印载荷: {mark} (支持: "
                                                  f"{WATERMARK_MIN} - {WATERMARK_MAX} 的整数)"}), None, None
+    max_pause = body.get("max_pause")
+    if max_pause is not None and (isinstance(max_pause, bool) or not isinstance(max_pause, int)
+                                  or not MAX_PAUSE_MIN <= max_pause <= MAX_PAUSE_MAX):
+        return (400, {"success": False, "error": f"不支持的最大停顿: {max_pause} (支持: "
+                                                 f"{MAX_PAUSE_MIN} - {MAX_PAUSE_MAX} 毫秒的整数)"}), None, None
     fmt = body.get("format")
     if fmt is None:
         fmt = "wav"
@@ -349,6 +365,8 @@ def _tts_args(body, voice_dir: str):
         kw["pitch_shift"] = float(shift)
     if mark is not None:
         kw["watermark"] = int(mark)
+    if max_pause is not None:
+        kw["max_pause"] = int(max_pause)
     if fmt != "wav":
         kw["format"] = fmt  # (the handler's, not the pipeline's: taken out before the call, as long_form is)
     return None, args, kw
