@@ -376,8 +376,72 @@ typedef struct {
 } rwkvtts_request_ext;
 #define RWKVTTS_MIROSTAT_SET 1
 
+/* ---- typical sampling ------------------------------------------------------------------------
+ * rwkvtts_request_ext keeps its 16 bytes; a caller that wants typical sampling passes the longer
+ * block below through the same pointer, with struct_size = sizeof(rwkvtts_request_ext_v2). The
+ * first 16 bytes are rwkvtts_request_ext's and mean the same; a library reads typical_set and
+ * `typical` only where struct_size covers them, so the 16-byte block keeps working, and a block
+ * whose typical_set is 0 is the shorter one exactly.
+ *
+ * Locally typical sampling (typical_set bit 0: `typical` holds; any other bit fails the request
+ * alone), ai00's third sampler kind with its own decaying penalties (参考/ai00_server/crates/
+ * ai00-core/src/sampler/typical.rs; the reference's TTS path never calls it). SEMANTIC phase only,
+ * where it REPLACES the phase's top-k, top-p and temperature: each step keeps the tokens whose
+ * surprise is closest to the distribution's entropy. Per slot there is a penalty pen[t] and a
+ * "seen" mark for each of the 8193 semantic ids, both empty at admission (ai00's init over the
+ * prompt's tokens has nothing to walk: the semantic history starts empty). For one semantic
+ * attempt, on the row as the sampler receives it, all arithmetic f32, every operation rounded to
+ * nearest on its own, never an FMA, never reassociated:
+ *   1. logit[t] -= pen[t] for every seen t (once per step: a zero-shot re-draw samples the same
+ *      adjusted row).
+ *   2. p[i] exactly as the sampler's softmax: the EOS mask to -inf, the max, glibc expf(x - max),
+ *      the sequential f32 sum in index order, the divide.
+ *   3. For every p[i] > 0: y[i] = -ln(p[i]), ln = glibc 2.35 logf (csrc/exact_math.h glibc_logf, one
+ *      source for host and kernel; rwkvtts_debug_logf exports it). entropy = the sum of
+ *      p[i] * y[i] over those i, left to right in index order, each product rounded before its
+ *      add. An entry with p[i] == 0 takes no part in this step or any later one.
+ *   4. key[i] = |y[i] - entropy|. The entries are ordered by ascending key; EQUAL KEYS GO BY
+ *      ASCENDING TOKEN ID. That tie rule is this library's: ai00 sorts with an unstable radix sort
+ *      and leaves the order of equal keys undefined.
+ *   5. Of the first min(top_k, #{p > 0}) entries of that order, walked with cum = 0: an entry is
+ *      kept if cum <= tau before it, and then cum += p; the walk stops at the first entry that is
+ *      not kept. The first entry is always kept.
+ *   6. Each kept p becomes powf(p, 1.0f / temperature), glibc 2.35 powf as csrc/exact_math.h
+ *      restates it (held to libm for temperature in [0.1, 4]; the same code outside), at
+ *      temperature 1 too, where it is the identity. sum = the kept values added left to right in
+ *      the kept order; each value becomes value / sum; cum[j] is their running sum in that order.
+ *   7. r32 is the semantic stream's next draw, with the draw + attempt indexing of every other
+ *      semantic step (ai00 calls fastrand::f32 here). The token is the first kept entry with
+ *      r32 <= cum[j]; if there is none it is the first kept entry (ai00's find_or_first).
+ *   8. After the attempt whose token is emitted, and only then: every seen pen[t] *= penalty_decay
+ *      (the repeated rounded multiply, not a power); then, if the token was seen,
+ *      pen[tok] += frequency_penalty, added to the decayed value; otherwise
+ *      pen[tok] = presence_penalty and the token becomes seen.
+ * The zero-shot EOS rules are Mirostat's: a zero-shot attempt that draws EOS
+ * and is re-drawn moves nothing, and an EOS that ends the request needs no update, so EOS is never
+ * seen. tau >= 0, top_k in [1, 8193], temperature > 0, presence_penalty and frequency_penalty
+ * finite, 0 < penalty_decay <= 1, all finite; anything else fails the request alone, and so does
+ * typical sampling together with `greedy`, RWKVTTS_SAMPLING_SEMANTIC, penalty_set or Mirostat. It
+ * combines with RWKVTTS_SAMPLING_GLOBAL, pinned_voice, fixed_semantic and zero-shot mode. */
 typedef struct {
-  int32_t status;         /* 0 ok; <0 this request failed -> (vec![], vec![]) as dbm.rs:466-469
+  float tau;               /* ai00's defaults: 0.5 */
+  int32_t top_k;           /* 128 */
+  float temperature;       /* 1.0 */
+  float presence_penalty;  /* 0.3 */
+  float frequency_penalty; /* 0.3 */
+  float penalty_decay;     /* 0.99654026 */
+} rwkvtts_typical;
+typedef struct {
+  uint32_t struct_size;  /* sizeof(rwkvtts_request_ext_v2) the caller was built with */
+  int32_t mirostat_set;  /* as in rwkvtts_request_ext */
+  struct { float tau, rate; } mirostat;
+  int32_t typical_set;   /* bit 0: `typical` holds; other bits fail the request alone */
+  rwkvtts_typical typical;
+} rwkvtts_request_ext_v2;
+#define RWKVTTS_TYPICAL_SET 1
+
+typedef struct {
+  int32_t status;        /* 0 ok; <0 this request failed -> (vec![], vec![]) as dbm.rs:466-469
                              (the others of its batch still complete) */
   int32_t n_global;
   int32_t n_semantic;
@@ -556,6 +620,22 @@ int rwkvtts_debug_advance_miro(rwkvtts_engine* e, const float* logits, int n_row
 /* Host self-test entry point: out[i] = lg(x[i]) of the Mirostat contract above, for positive
  * finite x (subnormals included). Needs no engine and no GPU. */
 void rwkvtts_debug_lg2(const float* x, int n, float* out);
+/* The same with per-row typical sampling: `rows` points to n_rows records of 152 bytes, the 120
+ * above (struct_size = 152) followed by float tau, temperature, presence_penalty,
+ * frequency_penalty, penalty_decay, int32 top_k, int32 on and int32 force_r (on = 0: the row
+ * is sampled as rwkvtts_debug_advance_miro samples its first 120 bytes; on = 1: the values in the
+ * ranges of rwkvtts_typical, neutral penalties, Mirostat off, n_sem 0; on = 3: the same, and step 7
+ * compares the f32 whose bits are force_r instead of r32, which is still drawn and counted). Up to 256 launches on the
+ * same logits while each row's penalties move; out_pen [n_steps][n_rows][8193] receives every
+ * row's penalty array after each launch (zeros where on == 0; an unseen id reads 0). */
+int rwkvtts_debug_advance_typ(rwkvtts_engine* e, const float* logits, int n_rows, const void* rows, int exact,
+                              int n_steps, int32_t* out_tok, int32_t* out_used, int32_t* out_phase, float* out_pen);
+/* Host self-test entry points: out[i] = ln(x[i]) of the typical-sampling contract above for
+ * 0 < x <= 1 (subnormals included), and the count of floats whose bits lie in [first, last],
+ * taken every `stride`, on which it differs from ref (libm's logf); *first_bad receives the bits of
+ * the first such float. Neither needs an engine or a GPU. */
+void rwkvtts_debug_logf(const float* x, int n, float* out);
+int64_t rwkvtts_debug_logf_sweep(uint32_t first, uint32_t last, uint32_t stride, float (*ref)(float), uint32_t* first_bad);
 
 /* Test hook, not part of the drop-in surface: rows [0, n_rows) x head_rows of the logits that the
  * engine's last forward step left on the device (n_rows <= the engine's row capacity; a decode step

@@ -35,27 +35,27 @@ struct rwkvtts_engine {
   }
 
 // The k_advance test hooks that take rows narrower than Engine::debug_advance's: `size` = 72 / 88 /
-// 104 bytes per row (engine.h DebugAdvanceRow / Ex / Pen). Each row is widened to a full row -- the
-// caller's bytes over the neutral defaults: temperature 1.0, top-p 0.95, penalties (1, 0, 0, 0),
-// Mirostat all zero. The 72-byte row has no struct_size and must carry a top-k; the others state
-// their own size.
+// 104 / 120 bytes per row (engine.h DebugAdvanceRow / Ex / Pen / Miro). Each row is widened to a full
+// row -- the caller's bytes over the neutral defaults: temperature 1.0, top-p 0.95, penalties
+// (1, 0, 0, 0), Mirostat and typical sampling all zero. The 72-byte row has no struct_size and must
+// carry a top-k; the others state their own size.
 static int debug_advance_narrow(rwkvtts_engine* e, const float* logits, int n_rows, const void* rows, size_t size,
                                 int exact, int n_steps, int32_t* out_tok, int32_t* out_used, int32_t* out_phase,
-                                int max_steps) {
+                                int max_steps, float* out_mu = nullptr) {
   RT_CHECK(n_rows > 0 && n_rows <= 4096, RWKVTTS_EINVAL, "debug_advance: bad sizes");
-  DebugAdvanceRowMiro neutral{};
-  neutral.pen.ex.temperature = 1.0f;
-  neutral.pen.ex.top_p = 0.95f;
-  neutral.pen.repetition = 1.0f;
-  std::vector<DebugAdvanceRowMiro> full(n_rows, neutral);
+  DebugAdvanceRowTyp neutral{};
+  neutral.miro.pen.ex.temperature = 1.0f;
+  neutral.miro.pen.ex.top_p = 0.95f;
+  neutral.miro.pen.repetition = 1.0f;
+  std::vector<DebugAdvanceRowTyp> full(n_rows, neutral);
   for (int i = 0; i < n_rows; ++i) {
-    DebugAdvanceRowEx& x = full[i].pen.ex;
+    DebugAdvanceRowEx& x = full[i].miro.pen.ex;
     memcpy(&full[i], (const char*)rows + i * size, size);
     RT_CHECK(size == sizeof(DebugAdvanceRow) ? x.row.top_k > 0 : x.struct_size == size, RWKVTTS_EINVAL,
              "debug_advance: bad row");
-    x.struct_size = (uint32_t)sizeof(DebugAdvanceRowMiro);
+    x.struct_size = (uint32_t)sizeof(DebugAdvanceRowTyp);
   }
-  return e->eng.debug_advance(logits, n_rows, full.data(), exact, n_steps, out_tok, out_used, out_phase, nullptr, max_steps);
+  return e->eng.debug_advance(logits, n_rows, full.data(), exact, n_steps, out_tok, out_used, out_phase, out_mu, max_steps);
 }
 
 extern "C" {
@@ -178,8 +178,21 @@ int rwkvtts_debug_advance_miro(rwkvtts_engine* e, const float* logits, int n_row
            "debug_advance_miro: bad arguments");
   LOCK(e);
   GUARD({
-    return e->eng.debug_advance(logits, n_rows, (const DebugAdvanceRowMiro*)rows, exact, n_steps, out_tok, out_used,
-                                out_phase, out_mu, 256);
+    return debug_advance_narrow(e, logits, n_rows, rows, sizeof(DebugAdvanceRowMiro), exact, n_steps, out_tok, out_used,
+                                out_phase, 256, out_mu);
+  })
+}
+
+// The same with per-row typical-sampling blocks (engine.h DebugAdvanceRowTyp); also returns every
+// row's penalty array after each launch.
+int rwkvtts_debug_advance_typ(rwkvtts_engine* e, const float* logits, int n_rows, const void* rows, int exact,
+                              int n_steps, int32_t* out_tok, int32_t* out_used, int32_t* out_phase, float* out_pen) {
+  RT_CHECK(e && logits && rows && out_tok && out_used && out_phase && out_pen, RWKVTTS_EINVAL,
+           "debug_advance_typ: bad arguments");
+  LOCK(e);
+  GUARD({
+    return e->eng.debug_advance(logits, n_rows, (const DebugAdvanceRowTyp*)rows, exact, n_steps, out_tok, out_used,
+                                out_phase, nullptr, 256, out_pen);
   })
 }
 

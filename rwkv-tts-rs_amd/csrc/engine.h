@@ -45,6 +45,15 @@ struct DebugAdvanceRowMiro {
   float tau, rate, mu;
   int32_t on;
 };
+// rwkvtts_debug_advance_typ: the row above (struct_size = 152) plus its typical-sampling block
+struct DebugAdvanceRowTyp {
+  DebugAdvanceRowMiro miro;
+  float tau, temperature, presence, frequency, decay;
+  int32_t top_k;
+  int32_t on;       // 0, 1, or 3: step 7 compares the f32 whose bits are force_r instead of the row's draw
+  int32_t force_r;  // (the draw is still made and counted)
+};
+static_assert(sizeof(DebugAdvanceRowTyp) == 152, "test-hook row layouts");
 static_assert(sizeof(DebugAdvanceRow) == 72 && sizeof(DebugAdvanceRowEx) == 88 && sizeof(DebugAdvanceRowPen) == 104 &&
                   sizeof(DebugAdvanceRowMiro) == 120,
               "test-hook row layouts");
@@ -117,8 +126,9 @@ class Engine {
   // sample_block, the certified fast path or the exact walk -- on caller-given logit rows and
   // per-row controller states, for n_steps <= max_steps consecutive launches on the same rows. Full
   // rows (api.cpp widens the narrower ones); out_mu (may be null): every row's mu after each launch.
-  int debug_advance(const float* logits, int n_rows, const struct DebugAdvanceRowMiro* rows, int exact, int n_steps,
-                    int32_t* out_tok, int32_t* out_used, int32_t* out_phase, float* out_mu, int max_steps);
+  int debug_advance(const float* logits, int n_rows, const struct DebugAdvanceRowTyp* rows, int exact, int n_steps,
+                    int32_t* out_tok, int32_t* out_used, int32_t* out_phase, float* out_mu, int max_steps,
+                    float* out_pen = nullptr);  // [n_steps][n_rows][8193]: the typical-sampling penalties after each launch
   // Test hook (rwkvtts_debug_last_logits): rows [0, n_rows) of the logits the last forward step left on
   // the device (its head GEMM's split-K slabs summed in order, as infer returns them)
   int debug_last_logits(int n_rows, int head_rows, float* out);
@@ -310,6 +320,7 @@ class Engine {
   std::vector<int> par_host_;
   std::vector<SlotCtrl> ctrl_stage_;  // [S] host copy of each admitted slot's initial control block
   std::vector<SlotSampling> samp_stage_;  // [S] and of its sampling block
+  std::vector<SlotTyp> typ_stage_;        // [S] and of its typical-sampling block
   // per-step tables
   uint32_t* d_tok_ = nullptr;
   int4* d_rows_ = nullptr;
@@ -328,6 +339,8 @@ class Engine {
   int32_t* d_sem_ = nullptr;
   SlotSampling* d_samp_ = nullptr;    // [S] AdvanceArgs::samp
   uint16_t* d_pen_counts_ = nullptr;  // [S][kPenCounts] AdvanceArgs::pen_counts
+  SlotTyp* d_typ_ = nullptr;          // [S] AdvanceArgs::typ
+  float* d_typ_pen_ = nullptr;        // [S][kTypPenStride] AdvanceArgs::typ_pen (a slot's row is cleared by its first typical step)
   SlotCtrl* h_ctrl_ = nullptr;  // pinned mirror
   // token progress: pinned [2 unit buffers][S][RWKVTTS_SEMANTIC_LIMIT], token i of a slot at index i;
   // allocated when the first request with a sink is admitted (engines that never see one: no change)

@@ -420,6 +420,12 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
     RT_OK(alloc(&d_gran_att_, (size_t)ng));
     sync_bufs_.push_back({(int*)d_gran_att_, (size_t)ng * sizeof(uint64_t)});
   }
+  // the typical-sampling blocks and penalty rows, allocated last: every buffer above keeps the
+  // place it had relative to the others (all off until a slot's admission says otherwise)
+  typ_stage_.assign(S_, SlotTyp{});
+  RT_OK(alloc(&d_typ_, (size_t)S_));
+  RT_HIP(hipMemcpy(d_typ_, typ_stage_.data(), sizeof(SlotTyp) * (size_t)S_, hipMemcpyHostToDevice));
+  RT_OK(alloc(&d_typ_pen_, (size_t)S_ * kTypPenStride));
 
   RT_HIP(hipDeviceSynchronize());
   return RWKVTTS_OK;
@@ -863,6 +869,8 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
       a.sem_out = d_sem_;
       a.samp = d_samp_;
       a.pen_counts = d_pen_counts_;
+      a.typ = d_typ_;
+      a.typ_pen = d_typ_pen_;
       a.n_rows = n_lg;
       a.stamps = dbg_astamps_;
       a.kind = kind;
@@ -919,6 +927,7 @@ int Engine::run_step(const StepPlan& p, bool upload) {
   const int n_seg = (int)p.segs.size(), n_lg = (int)p.lg_rows.size();
   if (p.tok_from_ctrl && use_graphs_ && !profiling) {
     // one graph per (R, head_rows, kind, advance): kind < 4 and advance < 2 are the low three bits
+    static_assert(kAdvTyp < 4, "a further AdvanceKind needs a wider graph key");
     auto key = std::make_pair(R, p.head_rows * 8 + p.kind * 2 + (p.advance ? 1 : 0));
     auto it = graphs_.find(key);
     if (it == graphs_.end()) {
@@ -1019,24 +1028,27 @@ int Engine::debug_last_logits(int n_rows, int head_rows, float* out) {
 // block; logits are [n_rows][8193] host floats (one partial). Per step and row: out_tok = the
 // token the step emitted (global or semantic; -1 if it emitted none: finished or stopped),
 // out_used = draws the step consumed, out_phase = the phase after the step.
-int Engine::debug_advance(const float* logits, int n_rows, const DebugAdvanceRowMiro* mrows, int exact, int n_steps,
-                          int32_t* out_tok, int32_t* out_used, int32_t* out_phase, float* out_mu, int max_steps) {
+int Engine::debug_advance(const float* logits, int n_rows, const DebugAdvanceRowTyp* trows, int exact, int n_steps,
+                          int32_t* out_tok, int32_t* out_used, int32_t* out_phase, float* out_mu, int max_steps,
+                          float* out_pen) {
   RT_HIP(hipSetDevice(device_));
   RT_CHECK(n_rows > 0 && n_rows <= 4096 && n_steps > 0 && n_steps <= max_steps, RWKVTTS_EINVAL, "debug_advance: bad sizes");
   constexpr int LD = RWKVTTS_EOS_TOKEN + 1;
   std::vector<SlotCtrl> c(n_rows);
   std::vector<SlotSampling> samp(n_rows);
-  bool any_pen = false;
+  std::vector<SlotTyp> typ(n_rows);
+  bool any_pen = false, any_typ = false;
   AdvanceKind kind = kAdvFixed;  // as admission_of derives a slot's, the step's the highest (step_kind)
   std::string why;               // the range checks are validate's (sched.h); the hook reports its own messages
   for (int i = 0; i < n_rows; ++i) {
-    const DebugAdvanceRowMiro& mr = mrows[i];
+    const DebugAdvanceRowTyp& tr = trows[i];
+    const DebugAdvanceRowMiro& mr = tr.miro;
     const DebugAdvanceRowPen& pr = mr.pen;
     const DebugAdvanceRowEx& e = pr.ex;
     const DebugAdvanceRow& r = e.row;
     RT_CHECK((r.phase == kPhGlobal || r.phase == kPhSemantic) && r.n_sem >= 0 &&
                  r.n_sem + n_steps <= RWKVTTS_SEMANTIC_LIMIT && (r.mode == 0 || r.mode == 1) &&
-                 e.struct_size == sizeof(DebugAdvanceRowMiro) &&
+                 e.struct_size == sizeof(DebugAdvanceRowTyp) &&
                  phase_sampling_ok(rwkvtts_phase_sampling{e.temperature, e.top_p, r.top_k}, "row", why),
              RWKVTTS_EINVAL, "debug_advance: bad row");
     samp[i] = SlotSampling{{pr.repetition, pr.frequency, pr.presence, pr.window}, {mr.tau, mr.rate, mr.mu, mr.on}};
@@ -1050,6 +1062,13 @@ int Engine::debug_advance(const float* logits, int n_rows, const DebugAdvanceRow
              "debug_advance: bad mirostat");
     const bool own = !neutral || e.temperature != 1.0f || e.top_p != 0.95f || r.top_k < 1 || r.top_k > kFastTopK;
     kind = std::max(kind, mr.on ? kAdvMiro : (own ? kAdvParams : kAdvFixed));
+    // a typical row: the request's rules (sched.h validate) -- no penalties, no Mirostat, an empty history
+    typ[i] = SlotTyp{tr.tau, tr.temperature, tr.presence, tr.frequency, tr.decay, tr.top_k, tr.on, tr.force_r};
+    RT_CHECK(tr.on == 0 || ((tr.on == 1 || tr.on == (1 | kTypForceR)) && neutral && mr.on == 0 && r.n_sem == 0 &&
+                            typical_ok(rwkvtts_typical{tr.tau, tr.top_k, tr.temperature, tr.presence, tr.frequency, tr.decay}, why)),
+             RWKVTTS_EINVAL, "debug_advance: bad typical block");
+    if (tr.on) kind = kAdvTyp;
+    any_typ |= tr.on != 0;
     SlotCtrl& x = c[i];
     memset(&x, 0, sizeof(x));
     x.mode = r.mode;
@@ -1072,8 +1091,11 @@ int Engine::debug_advance(const float* logits, int n_rows, const DebugAdvanceRow
   int32_t *d_slot = nullptr, *d_sem = nullptr;
   uint16_t* d_cnt = nullptr;  // [n_rows][kPenCounts], only when some row is penalised
   SlotSampling* d_samp = nullptr;
+  SlotTyp* d_typ = nullptr;  // and, only when some row samples typically, [n_rows][kTypPenStride] penalties
+  float* d_tpen = nullptr;
+  std::vector<float> tpen(any_typ && out_pen ? (size_t)n_rows * kTypPenStride : 0);
   auto cleanup = [&] {
-    for (void* p : {(void*)d_lg, (void*)d_c, (void*)d_slot, (void*)d_sem, (void*)d_cnt, (void*)d_samp})
+    for (void* p : {(void*)d_lg, (void*)d_c, (void*)d_slot, (void*)d_sem, (void*)d_cnt, (void*)d_samp, (void*)d_typ, (void*)d_tpen})
       if (p) hipFree(p);
   };
   int rc = RWKVTTS_OK;
@@ -1082,7 +1104,9 @@ int Engine::debug_advance(const float* logits, int n_rows, const DebugAdvanceRow
         hipMalloc(&d_slot, 4 * (size_t)n_rows) != hipSuccess ||
         hipMalloc(&d_sem, 4 * (size_t)n_rows * RWKVTTS_SEMANTIC_LIMIT) != hipSuccess ||
         hipMalloc(&d_samp, sizeof(SlotSampling) * n_rows) != hipSuccess ||
-        (any_pen && hipMalloc(&d_cnt, sizeof(uint16_t) * (size_t)n_rows * kPenCounts) != hipSuccess)) {
+        hipMalloc(&d_typ, sizeof(SlotTyp) * n_rows) != hipSuccess ||
+        (any_typ && hipMalloc(&d_tpen, sizeof(float) * (size_t)n_rows * kTypPenStride) != hipSuccess) ||
+        ((any_pen || any_typ) && hipMalloc(&d_cnt, sizeof(uint16_t) * (size_t)n_rows * kPenCounts) != hipSuccess)) {
       set_error("debug_advance: allocation");
       rc = RWKVTTS_ENOMEM;
       break;
@@ -1093,6 +1117,8 @@ int Engine::debug_advance(const float* logits, int n_rows, const DebugAdvanceRow
         hipMemcpy(d_c, c.data(), sizeof(SlotCtrl) * n_rows, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_slot, slot.data(), 4 * (size_t)n_rows, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_samp, samp.data(), sizeof(SlotSampling) * n_rows, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_typ, typ.data(), sizeof(SlotTyp) * n_rows, hipMemcpyHostToDevice) != hipSuccess ||
+        (d_tpen && hipMemset(d_tpen, 0, sizeof(float) * (size_t)n_rows * kTypPenStride) != hipSuccess) ||
         hipMemset(d_sem, 0xFF, 4 * (size_t)n_rows * RWKVTTS_SEMANTIC_LIMIT) != hipSuccess) {
       set_error("debug_advance: upload");
       rc = RWKVTTS_EHIP;
@@ -1108,6 +1134,8 @@ int Engine::debug_advance(const float* logits, int n_rows, const DebugAdvanceRow
     a.sem_out = d_sem;
     a.samp = d_samp;
     a.pen_counts = d_cnt;
+    a.typ = d_typ;
+    a.typ_pen = d_tpen;
     a.n_rows = n_rows;
     a.kind = kind;
     std::vector<SlotCtrl> prev = c, now(n_rows);
@@ -1115,7 +1143,8 @@ int Engine::debug_advance(const float* logits, int n_rows, const DebugAdvanceRow
       launch_advance(a, stream_, exact ? 0 : 1);
       if (hipStreamSynchronize(stream_) != hipSuccess ||
           hipMemcpy(now.data(), d_c, sizeof(SlotCtrl) * n_rows, hipMemcpyDeviceToHost) != hipSuccess ||
-          (out_mu && hipMemcpy(samp.data(), d_samp, sizeof(SlotSampling) * n_rows, hipMemcpyDeviceToHost) != hipSuccess)) {
+          (out_mu && hipMemcpy(samp.data(), d_samp, sizeof(SlotSampling) * n_rows, hipMemcpyDeviceToHost) != hipSuccess) ||
+          (!tpen.empty() && hipMemcpy(tpen.data(), d_tpen, sizeof(float) * tpen.size(), hipMemcpyDeviceToHost) != hipSuccess)) {
         set_error("debug_advance: launch");
         rc = RWKVTTS_EHIP;
         break;
@@ -1125,6 +1154,8 @@ int Engine::debug_advance(const float* logits, int n_rows, const DebugAdvanceRow
         const int64_t o = (int64_t)s * n_rows + i;
         out_phase[o] = q.phase;
         if (out_mu) out_mu[o] = samp[i].miro.mu;
+        if (out_pen)
+          for (int t = 0; t < LD; ++t) out_pen[o * LD + t] = tpen.empty() ? 0.0f : tpen[(size_t)i * kTypPenStride + t];
         if (p.phase == kPhGlobal) {
           out_tok[o] = q.n_global > p.n_global ? q.global_out[p.n_global] : -1;
           out_used[o] = (int32_t)(q.gdraw - p.gdraw);
@@ -1392,6 +1423,8 @@ int Engine::admit(ServeState& st, Job* j) {
   // every admission, neutral blocks included: nothing of the previous owner's survives
   samp_stage_[slot] = ad.samp;
   RT_HIP(hipMemcpyAsync(d_samp_ + slot, &samp_stage_[slot], sizeof(SlotSampling), hipMemcpyHostToDevice, stream_));
+  typ_stage_[slot] = ad.typ;
+  RT_HIP(hipMemcpyAsync(d_typ_ + slot, &typ_stage_[slot], sizeof(SlotTyp), hipMemcpyHostToDevice, stream_));
   Active a;
   a.job = j;
   a.slot = slot;

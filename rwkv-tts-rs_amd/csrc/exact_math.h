@@ -143,5 +143,47 @@ __host__ __device__ inline float glibc_powf(float x, float y) {
   return glibc_powf_t(x, y, [](int i) { return exp2_tab(i); });
 }
 
+// glibc 2.35 logf (sysdeps/ieee754/flt-32/e_logf.c, x86_64 FMA variant) for 0 < x <= 1, subnormals
+// included: the domain of the typical sampler's surprise -ln(p). x <= 0, x > 1, inf and NaN take
+// none of glibc's special cases. The 16-entry table (1/c, ln c) of libm-2.35's __logf_data, the
+// degree-3 polynomial in r = z / c - 1 in double with the fused operations glibc's build has, one
+// double -> float rounding. tests/test_typ_cpu.py checks every float of the domain against libm.
+__host__ __device__ inline double logf_tab(int i) {  // 2 i: invc, 2 i + 1: logc
+  static constexpr double kTab[32] = {
+    0x1.661ec79f8f3bep+0, -0x1.57bf7808caadep-2, 0x1.571ed4aaf883dp+0, -0x1.2bef0a7c06ddbp-2,
+    0x1.49539f0f010b0p+0, -0x1.01eae7f513a67p-2, 0x1.3c995b0b80385p+0, -0x1.b31d8a68224e9p-3,
+    0x1.30d190c8864a5p+0, -0x1.6574f0ac07758p-3, 0x1.25e227b0b8ea0p+0, -0x1.1aa2bc79c8100p-3,
+    0x1.1bb4a4a1a343fp+0, -0x1.a4e76ce8c0e5ep-4, 0x1.12358f08ae5bap+0, -0x1.1973c5a611cccp-4,
+    0x1.0953f419900a7p+0, -0x1.252f438e10c1ep-5, 0x1.0000000000000p+0, 0x0.0p+0,
+    0x1.e608cfd9a47acp-1, 0x1.aa5aa5df25984p-5,  0x1.ca4b31f026aa0p-1, 0x1.c5e53aa362eb4p-4,
+    0x1.b2036576afce6p-1, 0x1.526e57720db08p-3,  0x1.9c2d163a1aa2dp-1, 0x1.bc2860d224770p-3,
+    0x1.886e6037841edp-1, 0x1.1058bc8a07ee1p-2,  0x1.767dcf5534862p-1, 0x1.4043057b6ee09p-2};
+  return kTab[i];
+}
+__host__ __device__ inline float glibc_logf(float x) {
+#pragma clang fp contract(off)  // only the fused operations glibc's build has, written as fma
+  uint32_t ix = __builtin_bit_cast(uint32_t, x);
+  if (ix == 0x3f800000u) return 0.0f;
+  if (ix < 0x00800000u) {  // a subnormal is normalised first
+    ix = __builtin_bit_cast(uint32_t, x * 0x1p23f);
+    ix -= 23u << 23;
+  }
+  const uint32_t tmp = ix - 0x3f330000u;
+  const int i = (int)((tmp >> (23 - 4)) % 16u);
+  const int k = (int32_t)tmp >> 23;
+  const uint32_t iz = ix - (tmp & 0xff800000u);
+  const double invc = logf_tab(2 * i), logc = logf_tab(2 * i + 1);
+  const double z = (double)__builtin_bit_cast(float, iz);
+  const double Ln2 = 0x1.62e42fefa39efp-1;
+  const double A0 = -0x1.00ea348b88334p-2, A1 = 0x1.5575b0be00b6ap-2, A2 = -0x1.ffffef20a4123p-2;
+  const double r = __builtin_fma(z, invc, -1.0);
+  const double y0 = __builtin_fma((double)k, Ln2, logc);
+  const double r2 = r * r;
+  double y = __builtin_fma(A1, r, A2);
+  y = __builtin_fma(A0, r2, y);
+  y = __builtin_fma(y, r2, y0 + r);
+  return (float)y;
+}
+
 
 }  // namespace rwkvtts

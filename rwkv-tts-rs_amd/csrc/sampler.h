@@ -48,7 +48,12 @@ struct AdvanceArgs {
   // at its first semantic step instead of being read, the emitted id is counted after every step
   // and the id that leaves the window is uncounted. Rows of slots without penalties are never
   // touched. May be null when no row's slot is penalised.
+  // A slot with typical sampling (typ[slot].on) counts its emitted ids here too: seen = count > 0.
   uint16_t* pen_counts;
+  // [S] typical-sampling block of each slot and [S][kTypPenStride] its decaying penalties: read and
+  // moved by k_advance_typ alone. May be null when kind < kAdvTyp.
+  const SlotTyp* typ;
+  float* typ_pen;
 };
 constexpr int kPenCounts = RWKVTTS_EOS_TOKEN;  // ids [0, 8192): EOS never enters the history
 

@@ -2094,7 +2094,277 @@ __device__ __attribute__((always_inline)) int sample_miro(const SampleSmem& sm, 
   return sm.ired[5];
 }
 
-template <bool kParams, bool kMiro = false>
+// ---------------------------------------------------------------------------------------
+// Typical sampling (rwkvtts.h rwkvtts_request_ext_v2::typical), semantic rows of k_advance_typ.
+// ---------------------------------------------------------------------------------------
+// Step 1 on the row in registers, before advance_prep sees it (element i = tid + k NT): every seen
+// id loses its penalty, one rounded subtract. An id is seen when the slot's count row holds a
+// positive count for it; EOS (id 8192) is never emitted into the history and is never seen. At the
+// slot's first semantic step both rows are cleared instead of read.
+template <int NT, int PT>
+__device__ __attribute__((always_inline)) void typ_penalise(float* raw, float* pen, uint16_t* cnt, int n_sem) {
+  const int tid = threadIdx.x;
+  if (n_sem == 0) {
+#pragma unroll
+    for (int k = 0; k < PT; ++k) {
+      const int i = tid + k * NT;
+      if (i < kTypPenStride) pen[i] = 0.0f;
+      if (i < kPenCounts) cnt[i] = 0;
+    }
+    return;
+  }
+  uint32_t cn[PT];
+  float pv[PT];
+#pragma unroll
+  for (int k = 0; k < PT; ++k) {
+    const int i = tid + k * NT;
+    cn[k] = i < kPenCounts ? cnt[i] : 0u;
+    pv[k] = i < kPenCounts ? pen[i] : 0.0f;
+  }
+#pragma unroll
+  for (int k = 0; k < PT; ++k)
+    if (cn[k] != 0u) raw[k] = __fsub_rn(raw[k], pv[k]);
+}
+
+// Step 8, after the attempt whose token `id` (< 8192) is emitted, by the thread that owns each id
+// (the same element-to-thread map as typ_penalise, so a row cleared in this launch is written in
+// program order): every seen penalty takes one rounded multiply by the decay; the emitted id then
+// adds the frequency penalty to its decayed value, or, unseen, is set to the presence penalty.
+template <int NT, int PT>
+__device__ __attribute__((always_inline)) void typ_update(float* pen, uint16_t* cnt, int id, float decay, float freq,
+                                                          float pres) {
+  const int tid = threadIdx.x;
+  uint32_t cn[PT];
+  float pv[PT];
+#pragma unroll
+  for (int k = 0; k < PT; ++k) {
+    const int i = tid + k * NT;
+    cn[k] = i < kPenCounts ? cnt[i] : 0u;
+    pv[k] = i < kPenCounts ? pen[i] : 0.0f;
+  }
+#pragma unroll
+  for (int k = 0; k < PT; ++k) {
+    const int i = tid + k * NT;
+    if (i >= kPenCounts) continue;
+    if (cn[k] != 0u) {
+      float v = __fmul_rn(pv[k], decay);
+      if (i == id) v = __fadd_rn(v, freq);
+      pen[i] = v;
+    } else if (i == id) {
+      pen[i] = pres;
+    }
+    if (i == id) cnt[i] = (uint16_t)(cn[k] + 1u);
+  }
+}
+
+// Steps 2-7 on a prepared semantic row. On entry p holds e = glibc expf(l - max) and fred[21] the
+// draw r, as advance_prep leaves them; n <= 8193.
+//  (2) p = e / sum with the exact sequential f32 sum, as the general path of sample_block divides.
+//  (3) the products p * y, y = -glibc logf(p), of the first n - 1 ids go to the keys region (n - 1
+//      <= 8192 floats fill it exactly; the scan scratch behind it stays free) and are summed in index
+//      order by the same exact_seq_sum; the last id's product is added after the walk, which is where
+//      the index order puts it. Zero probabilities contribute +0.
+//  (4) key bits of |y - entropy| for every id (0xFFFFFFFF where p == 0) over the keys / dscan / list
+//      regions as one array of n words, the ids of the survivors as 16-bit values behind it. The
+//      m-th smallest key, m = min(top_k, #{p > 0}), by a radix select: four passes over 8 bits of
+//      the key, most significant first, each a 256-bin LDS histogram of the keys that match the
+//      prefix found so far (a wave whose active lanes all hold one digit adds once), scanned by wave
+//      0. Then every key below the threshold and the first `need` ids (ascending) equal to it are
+//      compacted from contiguous chunks, and the m ids are sorted by (key, id) with a bitonic network
+//      that reads the keys through the ids.
+//  (5) wave 0 walks the order 64 ranks at a time: the kept prefix ends behind the first rank whose
+//      inclusive cumulative exceeds tau.
+//  (6) every thread raises kept probabilities to 1 / T (glibc powf, exact_math.h) into the dead key
+//      array; wave 0 sums them in order, divides, accumulates and (7) finds the first rank with
+//      r <= cum, rank 0 if there is none.
+// Returns the token, an index < n.
+template <int NT>
+__device__ __attribute__((always_inline)) int sample_typ(const SampleSmem& sm, int n, float tau, int top_k, float tinv,
+                                                         bool forced, float forced_r, uint64_t* stamps) {
+  constexpr int NW = NT / 64;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float* prod = (float*)sm.keys;
+  uint32_t* kb = (uint32_t*)sm.keys;
+  uint16_t* sid = (uint16_t*)((char*)sm.keys + (((size_t)n * 4 + 15) & ~(size_t)15));
+  float* val = (float*)sm.keys;
+  uint32_t* hist = (uint32_t*)sm.runs;  // 256 bins
+  float ent = 0.0f;
+  int npos = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    SampleSmem s2 = sm;
+    if (pass == 1) {
+      int cp = 0;
+      for (int i = tid; i < n; i += NT) {
+        const float v = sm.p[i];
+        float t = 0.0f;
+        if (v > 0.0f) {
+          ++cp;
+          t = __fmul_rn(v, -glibc_logf(v));
+          if (t == 0.0f) t = 0.0f;  // (-0 from p == 1: adds as +0 does)
+        }
+        if (i < n - 1) prod[i] = t;
+        else sm.fred[24] = t;
+      }
+      cp = wave_sum_i(cp);
+      if (lane == 0) sm.ired[8 + wave] = cp;
+      s2.p = prod;
+      __syncthreads();
+#pragma unroll
+      for (int w = 0; w < NW; ++w) npos += sm.ired[8 + w];
+      STAMP(2);
+    }
+    const float s = exact_seq_sum<NT>(s2, pass == 0 ? n : n - 1, stamps);
+    if (pass == 0) {
+      if (s > 0.0f)
+        for (int i = tid; i < n; i += NT) sm.p[i] = sm.p[i] / s;
+    } else {
+      ent = __fadd_rn(s, sm.fred[24]);
+    }
+    __syncthreads();
+  }
+  const int m = min(top_k, npos);
+  if (m <= 0 || n > RWKVTTS_EOS_TOKEN + 1) return 0;  // no positive entry (a row of -inf or NaN)
+  for (int i = tid; i < n; i += NT) {
+    const float v = sm.p[i];
+    kb[i] = v > 0.0f ? __builtin_bit_cast(uint32_t, fabsf(__fsub_rn(-glibc_logf(v), ent))) : 0xFFFFFFFFu;
+  }
+  STAMP(7);
+  // radix select: `prefix` under `mask` holds the digits found; kk-th smallest among the matching keys
+  uint32_t prefix = 0, mask = 0;
+  int kk = m;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    if (tid < 256) hist[tid] = 0;
+    __syncthreads();  // (orders kb too)
+    for (int i = tid; i < n; i += NT) {
+      const uint32_t u = kb[i];
+      const bool act = (u & mask) == prefix;
+      const uint32_t d = (u >> shift) & 255u;
+      const uint64_t am = __ballot(act);
+      if (am) {
+        const int fl = __builtin_ctzll(am);
+        const uint32_t d0 = readlane_t(d, fl);
+        const uint64_t same = __ballot(act && d == d0);
+        if (lane == fl) atomicAdd(&hist[d0], (uint32_t)__popcll(same));
+        if (act && d != d0) atomicAdd(&hist[d], 1u);
+      }
+    }
+    __syncthreads();
+    if (tid < 64) {
+      uint32_t h[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) h[q] = hist[4 * lane + q];
+      const int own = (int)(h[0] + h[1] + h[2] + h[3]);
+      int x = own;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(x, o);
+        if (lane >= o) x += t;
+      }
+      int run = x - own;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (run < kk && kk <= run + (int)h[q]) {
+          sm.ired[25] = 4 * lane + q;
+          sm.ired[26] = kk - run;
+        }
+        run += (int)h[q];
+      }
+    }
+    __syncthreads();
+    prefix |= (uint32_t)sm.ired[25] << shift;
+    mask |= 255u << shift;
+    kk = sm.ired[26];
+  }
+  STAMP(8);
+  {
+    const uint32_t T = prefix;
+    const int need = kk;
+    const int chunk = (n + NT - 1) / NT;
+    const int b = min(n, tid * chunk), e = min(n, b + chunk);
+    int pk = 0;  // #{key == T} << 16 | #{key < T}
+    for (int i = b; i < e; ++i) pk += (kb[i] < T ? 1 : 0) + (kb[i] == T ? 0x10000 : 0);
+    int tot;
+    const int ex = block_excl_scan<NT>(pk, sm.scan, &tot);
+    int ol = ex & 0xFFFF, oe = ex >> 16;
+    const int nlt = tot & 0xFFFF;  // nlt + need == m
+    for (int i = b; i < e; ++i) {
+      const uint32_t u = kb[i];
+      if (u < T) sid[ol++] = (uint16_t)i;
+      else if (u == T && oe++ < need) sid[nlt + oe - 1] = (uint16_t)i;
+    }
+    __syncthreads();
+  }
+  {  // ascending by (key, id): the smaller of a pair goes to the lower rank, ranks past m are maximal
+    int M = 1;
+    while (M < m) M <<= 1;
+    for (int k = 2; k <= M; k <<= 1) {
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        const bool flip = j == (k >> 1);
+        for (int t = tid; t < (M >> 1); t += NT) {
+          const int q = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+          const int ixj = flip ? (q ^ (2 * j - 1)) : (q | j);
+          if (ixj < m) {
+            const uint32_t ia = sid[q], ib = sid[ixj];
+            const uint32_t ka = kb[ia], kc = kb[ib];
+            if (ka > kc || (ka == kc && ia > ib)) {
+              sid[q] = (uint16_t)ib;
+              sid[ixj] = (uint16_t)ia;
+            }
+          }
+        }
+        __syncthreads();
+      }
+    }
+  }
+  STAMP(9);
+  if (tid < 64) {
+    int nk = m;
+    bool found = false;
+    float cum = 0.0f;
+    for (int q0 = 0; q0 < m && !found; q0 += 64) {
+      const bool in = q0 + lane < m;
+      float tot2;
+      const float pre = prefix64(cum, in ? sm.p[sid[q0 + lane]] : 0.0f, &tot2);
+      const uint64_t hit = __ballot(in && !(pre <= tau));
+      if (hit) {
+        found = true;
+        nk = min(m, q0 + __builtin_ctzll(hit) + 1);
+      }
+      cum = tot2;
+    }
+    if (tid == 0) sm.ired[27] = nk;
+  }
+  __syncthreads();
+  const int nk = sm.ired[27];
+  {
+    const uint64_t* et = sm.etab;  // filled by advance_prep
+    auto tab = [et](int i) { return et[i]; };
+    // (the keys died with the sort's last barrier: the walk above read p and the ids only)
+    for (int j = tid; j < nk; j += NT) val[j] = glibc_powf_t(sm.p[sid[j]], tinv, tab);
+  }
+  __syncthreads();
+  if (tid < 64) {
+    float S = 0.0f;  // (+0 pads the last round: s + 0 == s exactly)
+    for (int q0 = 0; q0 < nk; q0 += 64) S = add64(S, q0 + lane < nk ? val[q0 + lane] : 0.0f);
+    const float r = forced ? forced_r : sm.fred[21];  // (forced: the test hook's r; the draw is still made and counted)
+    int rank = -1;
+    float cum = 0.0f;
+    for (int q0 = 0; q0 < nk && rank < 0; q0 += 64) {
+      const bool in = q0 + lane < nk;
+      float tot2;
+      const float pre = prefix64(cum, in ? __fdiv_rn(val[q0 + lane], S) : 0.0f, &tot2);
+      const uint64_t hit = __ballot(in && r <= pre);
+      if (hit) rank = q0 + __builtin_ctzll(hit);
+      cum = tot2;
+    }
+    if (rank < 0) rank = 0;  // find_or_first
+    if (tid == 0) sm.ired[5] = min((int)sid[rank], n - 1);
+  }
+  __syncthreads();
+  return sm.ired[5];
+}
+
+template <bool kParams, bool kMiro = false, bool kTyp = false>
 __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a, char* smem) {
   constexpr int NT = kSampleThreads;
   const int row = blockIdx.x;
@@ -2154,7 +2424,24 @@ __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a
     miro = !glob && a.samp[slot].miro.on != 0;
     mu = a.samp[slot].miro.mu;
   }
-  const int prep_k = (kMiro && miro) ? 0 : top_k;
+  // Typical sampling (k_advance_typ, semantic rows of a slot whose SlotTyp block is on): it too
+  // replaces the phase's top-k, top-p and temperature. The row loses its penalties once, here, so
+  // the zero-shot re-draw samples the same adjusted row; the penalties move once, below, after the
+  // attempt whose token is emitted.
+  bool typ = false;
+  SlotTyp tp{};
+  float* typ_pen = nullptr;
+  uint16_t* typ_cnt = nullptr;
+  if constexpr (kTyp) {
+    typ = !glob && a.typ[slot].on != 0;
+    if (typ) {
+      tp = a.typ[slot];
+      typ_pen = a.typ_pen + (int64_t)slot * kTypPenStride;
+      typ_cnt = a.pen_counts + (int64_t)slot * kPenCounts;
+      typ_penalise<NT, PT>(raw, typ_pen, typ_cnt, c->n_sem);
+    }
+  }
+  const int prep_k = ((kMiro && miro) || (kTyp && typ)) ? 0 : top_k;
   // attempt 1 (zero-shot only): EOS drawn while the window rule does not stop the request ->
   // re-draw with EOS masked from the same logits and the next draw (zero_shot_inference.rs:287-297)
   int id = 0, status;
@@ -2163,7 +2450,11 @@ __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a
   for (int attempt = 0; attempt < 2; ++attempt) {
     if (glob) advance_prep<NT, 4096, PT>(raw, sm, false, prep_k, key, draw + attempt, c->gblk, &c->gblk_id, stamps);
     else advance_prep<NT, NS, PT>(raw, sm, masked, prep_k, key, draw + attempt, c->sblk, &c->sblk_id, stamps);
-    if (kMiro && miro) {
+    if (kTyp && typ) {
+      status = 0;
+      id = sample_typ<NT>(sm, n, tp.tau, tp.top_k, __fdiv_rn(1.0f, tp.temperature), (tp.on & kTypForceR) != 0,
+                          __builtin_bit_cast(float, tp.force_r), stamps);
+    } else if (kMiro && miro) {
       status = 0;
       id = sample_miro<NT>(sm, n, mu, stamps);
     } else {
@@ -2195,6 +2486,15 @@ __device__ __attribute__((always_inline)) void advance_body(const AdvanceArgs& a
       if (c->n_global == RWKVTTS_N_GLOBAL) c->phase = kPhGFeed;
     }
     return;
+  }
+  if constexpr (kTyp) {
+    // (an emitted id is below 8192: EOS ends the request or was re-drawn masked above)
+    if (typ && !stop && (uint32_t)id < (uint32_t)kPenCounts)
+      typ_update<NT, PT>(typ_pen, typ_cnt, id, tp.decay, tp.frequency, tp.presence);
+    if (typ && stamps) {  // debug runs only: the end of the decay pass (stamp 14 is the exact sum's scratch until here)
+      __syncthreads();
+      STAMP(14);
+    }
   }
   if (threadIdx.x == 0) {
     c->sdraw += used;
@@ -2260,11 +2560,30 @@ __global__ __launch_bounds__(kSampleThreads, 2) void k_advance_miro(AdvanceArgs 
   tl_end(a.tl);
 }
 
+// and for launches in which some slot samples typically: a fourth instantiation, so that the three
+// above keep their instructions. It is compiled without the packed f32 instructions (v_pk_add_f32,
+// v_pk_mul_f32, v_pk_fma_f32), which the row's slab adds would otherwise use: with them the kernel
+// reaches the 256-VGPR limit and spills 16 bytes to scratch; without them it takes 237 VGPRs and no
+// scratch (same compiler, same flags). A packed add rounds as a scalar one does, so the tokens do
+// not depend on it: the attribute may go when a compiler fits the kernel without scratch either way.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define RWKVTTS_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define RWKVTTS_NO_PK_F32
+#endif
+__global__ __launch_bounds__(kSampleThreads, 2) RWKVTTS_NO_PK_F32 void k_advance_typ(AdvanceArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  tl_begin(a.tl);
+  advance_body<true, true, true>(a, smem);
+  tl_end(a.tl);
+}
+
 int launch_advance(const AdvanceArgs& a0, hipStream_t st, int cert) {
   AdvanceArgs a = a0;
   a.cert = cert;  // 0: always walk the exact sequential sum (RWKVTTS_FORM_EXACT_SAMPLER)
   const size_t lds = smem_bytes<kSampleThreads>(RWKVTTS_EOS_TOKEN + 1);
   switch (a.kind) {
+    case kAdvTyp: RT_LAUNCH(k_advance_typ, dim3(a.n_rows), dim3(kSampleThreads), lds, st, a); break;
     case kAdvMiro: RT_LAUNCH(k_advance_miro, dim3(a.n_rows), dim3(kSampleThreads), lds, st, a); break;
     case kAdvParams: RT_LAUNCH(k_advance_params, dim3(a.n_rows), dim3(kSampleThreads), lds, st, a); break;
     case kAdvFixed: RT_LAUNCH(k_advance, dim3(a.n_rows), dim3(kSampleThreads), lds, st, a); break;

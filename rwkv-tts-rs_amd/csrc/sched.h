@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -64,16 +65,21 @@ inline bool is_pinned(const rwkvtts_request& q) { return q.pinned_voice != 0; }
 // The extension block as a job carries it, by value: the first min(struct_size, sizeof) bytes of
 // the caller's block, the rest zero, struct_size still the caller's (validate judges it), and
 // whether there was a block at all.
+// The storage is the longest block the library knows (rwkvtts_request_ext_v2, whose first 16 bytes
+// are rwkvtts_request_ext's); `ext` names those first bytes.
 struct HeldExt {
-  rwkvtts_request_ext ext{};
+  union {
+    rwkvtts_request_ext ext;
+    rwkvtts_request_ext_v2 v2{};
+  };
   bool present = false;
   void hold(const rwkvtts_request_ext* e) {
-    memset(&ext, 0, sizeof(ext));
+    memset(&v2, 0, sizeof(v2));
     present = e != nullptr;
     if (e) {
       uint32_t sz = 0;
       memcpy(&sz, e, sizeof(sz));
-      memcpy(&ext, e, std::min<size_t>(std::max<size_t>(sz, sizeof(sz)), sizeof(ext)));
+      memcpy(&v2, e, std::min<size_t>(std::max<size_t>(sz, sizeof(sz)), sizeof(v2)));
     }
   }
   const rwkvtts_request_ext* ptr() const { return present ? &ext : nullptr; }
@@ -84,6 +90,15 @@ inline HeldExt ext_copy(const rwkvtts_request_ext* e) {
   return h;
 }
 inline bool has_mirostat(const rwkvtts_request_ext* ext) { return ext && (ext->mirostat_set & RWKVTTS_MIROSTAT_SET); }
+// the longer block behind the pointer, where the caller's struct_size covers all of it (validate
+// has refused a block that sets typical_set from a shorter one)
+inline const rwkvtts_request_ext_v2* ext_v2(const rwkvtts_request_ext* ext) {
+  return ext && ext->struct_size >= sizeof(rwkvtts_request_ext_v2) ? (const rwkvtts_request_ext_v2*)ext : nullptr;
+}
+inline bool has_typical(const rwkvtts_request_ext* ext) {
+  const rwkvtts_request_ext_v2* v = ext_v2(ext);
+  return v && (v->typical_set & RWKVTTS_TYPICAL_SET);
+}
 
 // The ranges of the three sampling options, for validate and the k_advance test hook
 // (Engine::debug_advance): each fills `why` and returns false for a bad value. Comparisons are
@@ -106,6 +121,17 @@ inline bool penalties_ok(const rwkvtts_penalties& p, std::string& why) {
 inline bool mirostat_ok(float tau, float rate, std::string& why) {
   if (!(tau >= 0.5f && tau <= 10.0f)) why = "mirostat: tau must be in [0.5, 10]";
   else if (!(rate >= 0.001f && rate <= 1.0f)) why = "mirostat: rate must be in [0.001, 1]";
+  else return true;
+  return false;
+}
+
+inline bool typical_ok(const rwkvtts_typical& t, std::string& why) {
+  if (!(t.tau >= 0.0f && std::isfinite(t.tau))) why = "typical: tau must be >= 0 and finite";
+  else if (t.top_k < 1 || t.top_k > RWKVTTS_EOS_TOKEN + 1) why = "typical: top_k must be in [1, 8193]";
+  else if (!(t.temperature > 0.0f && std::isfinite(t.temperature))) why = "typical: temperature must be > 0 and finite";
+  else if (!std::isfinite(t.presence_penalty)) why = "typical: presence_penalty must be finite";
+  else if (!std::isfinite(t.frequency_penalty)) why = "typical: frequency_penalty must be finite";
+  else if (!(t.penalty_decay > 0.0f && t.penalty_decay <= 1.0f)) why = "typical: penalty_decay must be in (0, 1]";
   else return true;
   return false;
 }
@@ -184,6 +210,25 @@ inline bool validate(const rwkvtts_request& q, int n_vocab, std::string& why, co
         why = "mirostat replaces the semantic phase's top-k, top-p and temperature: semantic_sampling excludes it";
       if (!why.empty()) return false;
     }
+    // the longer block (rwkvtts_request_ext_v2): its fields too are read only where struct_size covers them
+    if (have >= offsetof(rwkvtts_request_ext_v2, typical_set) + sizeof(int32_t)) {
+      int32_t tset = 0;
+      memcpy(&tset, (const char*)ext + offsetof(rwkvtts_request_ext_v2, typical_set), sizeof(tset));
+      if (tset & ~RWKVTTS_TYPICAL_SET) {
+        why = "typical_set: unknown bits";
+        return false;
+      }
+      if (tset) {
+        if (have < sizeof(rwkvtts_request_ext_v2)) why = "ext: struct_size does not cover typical";
+        else if (!typical_ok(((const rwkvtts_request_ext_v2*)ext)->typical, why)) return false;
+        else if (q.greedy) why = "typical and greedy exclude each other";
+        else if (q.sampling_set & RWKVTTS_SAMPLING_SEMANTIC)
+          why = "typical replaces the semantic phase's top-k, top-p and temperature: semantic_sampling excludes it";
+        else if (q.penalty_set) why = "typical has its own penalties: penalty_set excludes it";
+        else if (ext->mirostat_set) why = "typical and mirostat exclude each other";
+        if (!why.empty()) return false;
+      }
+    }
   }
   return true;
 }
@@ -206,13 +251,15 @@ struct Admission {
   // the slot's sampling block: penalties (1, 0, 0, 0) without penalty_set; Mirostat {tau, rate,
   // mu = 2 tau, on = 1} with rwkvtts_request_ext::mirostat, all zero without
   SlotSampling samp;
+  SlotTyp typ;  // the slot's typical-sampling block: the request's values and on = 1, all zero without
   uint64_t gseed, sseed;  // the engine derives gkey / skey from them (StdRng::seed_from_u64)
   bool zero_shot;
   bool pinned;           // is_pinned: decodes as normal mode from its first logits row on
   int total;             // Active::total
   // the controller the slot's steps need: kAdvMiro with a Mirostat block; else kAdvParams where a
   // phase's temperature or top-p differs from the reference's (1.0, 0.95), its top-k is outside
-  // the fast path's [1, kFastTopK] or the penalties are not neutral; else kAdvFixed
+  // the fast path's [1, kFastTopK] or the penalties are not neutral; else kAdvFixed. kAdvTyp with a
+  // typical-sampling block.
   AdvanceKind kind;
 };
 
@@ -268,6 +315,12 @@ inline Admission admission_of(const rwkvtts_request& q, uint64_t entropy, const 
   const bool own = c.temp_g != 1.0f || c.temp_s != 1.0f || c.top_p_g != 0.95f || c.top_p_s != 0.95f || c.top_k_g < 1 ||
                    c.top_k_g > kFastTopK || c.top_k_s < 1 || c.top_k_s > kFastTopK || !penalties_neutral(a.samp.pen);
   a.kind = a.samp.miro.on ? kAdvMiro : (own ? kAdvParams : kAdvFixed);
+  a.typ = SlotTyp{};
+  if (has_typical(ext)) {
+    const rwkvtts_typical& t = ext_v2(ext)->typical;
+    a.typ = SlotTyp{t.tau, t.temperature, t.presence_penalty, t.frequency_penalty, t.penalty_decay, t.top_k, 1, 0};
+    a.kind = kAdvTyp;
+  }
   c.fixed = q.fixed_semantic > 0;
   c.sem_limit = sem_limit_of(q);
   if (a.zero_shot) {

@@ -18,7 +18,9 @@ constexpr int kFastTopK = 256;  // largest top-k of the sampler's fast path (sam
 // k_advance_miro is k_advance_params plus the Mirostat path for the semantic rows of slots whose
 // block is on. The kernels form a chain -- each kind's kernel gives a row of a lower kind the same
 // token -- so the values are ordered and the kind of a step is the maximum over its slots.
-enum AdvanceKind : int32_t { kAdvFixed = 0, kAdvParams = 1, kAdvMiro = 2 };
+// kAdvTyp: k_advance_typ is k_advance_miro plus the typical-sampling path for the semantic rows of
+// slots whose SlotTyp block is on.
+enum AdvanceKind : int32_t { kAdvFixed = 0, kAdvParams = 1, kAdvMiro = 2, kAdvTyp = 3 };
 
 enum SlotPhase : int32_t { kPhGlobal = 0, kPhGFeed = 1, kPhSemantic = 2, kPhDone = 3 };
 
@@ -87,5 +89,23 @@ struct SlotSampling {
   SlotMiro miro;
 };
 static_assert(sizeof(SlotSampling) == 32, "sampling blocks are copied as an array");
+
+// Typical sampling (rwkvtts.h rwkvtts_request_ext_v2::typical): the parameters of a slot's semantic
+// phase, one array of SlotTyp beside the sampling blocks (AdvanceArgs::typ), written whole at every
+// admission like them (on = 0 for a request without it). SlotSampling keeps its 32 bytes: typical
+// sampling excludes penalties and Mirostat, so a slot whose block is on carries a neutral one there.
+// The state the kernel moves is not here but in the slot's rows of AdvanceArgs::typ_pen (the
+// decaying penalty of every semantic id) and AdvanceArgs::pen_counts (how often each id was emitted:
+// an id is "seen" when its count is positive); k_advance_typ clears both rows at the slot's first
+// semantic step, so nothing survives from the slot's previous owner.
+struct SlotTyp {
+  float tau, temperature, presence, frequency, decay;
+  int32_t top_k;
+  int32_t on;       // 0 off, 1 on; | kTypForceR (test hook only): step 7 compares force_r instead of the draw
+  int32_t force_r;  // bits of that f32
+};
+constexpr int kTypForceR = 2;
+static_assert(sizeof(SlotTyp) == 32, "typical blocks are copied as an array");
+constexpr int kTypPenStride = 8196;  // floats per slot of AdvanceArgs::typ_pen (8193 ids, 16-byte rows)
 
 }  // namespace rwkvtts

@@ -4,6 +4,7 @@
 #include <math.h>
 #include <string.h>
 
+#include <algorithm>
 #include <thread>
 #include <vector>
 
@@ -154,6 +155,39 @@ extern "C" void rwkvtts_debug_powf(const float* x, const float* y, int n, float*
 // source the decode-step controller runs (exact_math.h lg2f), and the sampler's expf for arrays.
 extern "C" void rwkvtts_debug_lg2(const float* x, int n, float* out) {
   for (int i = 0; i < n; ++i) out[i] = rwkvtts::lg2f(x[i]);
+}
+// Host self-test hooks of the typical-sampling contract (tests/typ_ref.py, tests/test_typ_cpu.py):
+// ln of rwkvtts.h, the same source the decode-step controller runs (exact_math.h glibc_logf), and
+// its sweep against a reference logf over a range of bit patterns, split over up to 16 threads.
+extern "C" void rwkvtts_debug_logf(const float* x, int n, float* out) {
+  for (int i = 0; i < n; ++i) out[i] = rwkvtts::glibc_logf(x[i]);
+}
+extern "C" int64_t rwkvtts_debug_logf_sweep(uint32_t first, uint32_t last, uint32_t stride, float (*ref)(float),
+                                            uint32_t* first_bad) {
+  if (!ref || stride == 0 || last < first) return -1;
+  const unsigned nt = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+  std::vector<int64_t> bad(nt, 0);
+  std::vector<uint32_t> where(nt, 0xFFFFFFFFu);
+  std::vector<std::thread> th;
+  for (unsigned t = 0; t < nt; ++t)
+    th.emplace_back([&, t] {
+      for (uint64_t u = (uint64_t)first + (uint64_t)t * stride; u <= last; u += (uint64_t)nt * stride) {
+        const float x = __builtin_bit_cast(float, (uint32_t)u);
+        const float a = rwkvtts::glibc_logf(x), b = ref(x);
+        if (__builtin_bit_cast(uint32_t, a) != __builtin_bit_cast(uint32_t, b)) {
+          if (bad[t]++ == 0) where[t] = (uint32_t)u;
+        }
+      }
+    });
+  for (std::thread& x : th) x.join();
+  int64_t tot = 0;
+  uint32_t fb = 0xFFFFFFFFu;
+  for (unsigned t = 0; t < nt; ++t) {
+    tot += bad[t];
+    fb = std::min(fb, where[t]);
+  }
+  if (first_bad) *first_bad = fb;
+  return tot;
 }
 extern "C" void rwkvtts_debug_expf_n(const float* x, int n, float* out) {
   for (int i = 0; i < n; ++i) out[i] = rwkvtts::glibc_expf(x[i]);

@@ -109,6 +109,21 @@ class RequestExt(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("mirostat_set", ctypes.c_int32), ("mirostat", MirostatParams)]
 
 
+TYPICAL_SET = 1
+
+
+class TypicalParams(ctypes.Structure):
+    _fields_ = [("tau", ctypes.c_float), ("top_k", ctypes.c_int32), ("temperature", ctypes.c_float),
+                ("presence_penalty", ctypes.c_float), ("frequency_penalty", ctypes.c_float),
+                ("penalty_decay", ctypes.c_float)]
+
+
+class RequestExtV2(ctypes.Structure):
+    """rwkvtts_request_ext_v2: RequestExt's 16 bytes, then the typical-sampling block. Passed where a
+    RequestExt pointer goes, with struct_size = its own size."""
+    _fields_ = RequestExt._fields_ + [("typical_set", ctypes.c_int32), ("typical", TypicalParams)]
+
+
 class Request(ctypes.Structure):
     _fields_ = [("text_tokens", ctypes.POINTER(ctypes.c_int32)), ("n_text", ctypes.c_int32),
                 ("property_tokens", ctypes.POINTER(ctypes.c_int32)), ("n_property", ctypes.c_int32),
@@ -356,6 +371,14 @@ EXPORTS = {
     "rwkvtts_debug_advance_miro": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                                   ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_void_p]),
+    "rwkvtts_debug_advance_typ": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p]),
+    # host self-test hooks of the typical-sampling contract (tests/typ_ref.py): ln for arrays, and its
+    # sweep against a reference logf (tests/test_typ_cpu.py)
+    "rwkvtts_debug_logf": (None, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "rwkvtts_debug_logf_sweep": (ctypes.c_int64, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                                  ctypes.c_void_p]),
     # host self-test hook of the Mirostat contract (tests/miro_ref.py): lg for arrays
     "rwkvtts_debug_lg2": (None, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     # test hook (tests/test_gpu_value_tile.py): the logits the last forward step left on the device

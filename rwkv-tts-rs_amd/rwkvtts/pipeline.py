@@ -67,7 +67,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from .properties import convert_standard_properties_to_tokens
-from .runtime import LayeredRandomnessConfig, Mirostat, Penalties, PhaseSampling, SamplerArgs, TtsBatchRequest
+from .runtime import LayeredRandomnessConfig, Mirostat, Penalties, PhaseSampling, SamplerArgs, TtsBatchRequest, Typical
 
 SAMPLE_RATE = 16000
 
@@ -101,6 +101,8 @@ class LightweightTtsPipelineArgs:  # :18-65 (Default)
     penalties: Optional[Penalties] = None
     # Mirostat in the semantic phase (runtime.Mirostat; None: top-k / top-p / temperature as before)
     mirostat: Optional[Mirostat] = None
+    # typical sampling in the semantic phase (runtime.Typical; None: as before), in all five entry points
+    typical: Optional[Typical] = None
     # no reference counterpart: with voice_global_tokens set and voice_semantic_tokens None, a
     # normal-mode request whose 32 global tokens are those (rwkvtts_request.pinned_voice): the same
     # voice again, still with its property tokens. Without it that combination ignores the tokens.
@@ -143,6 +145,15 @@ def check_sampling(args) -> None:
         if getattr(args, "semantic_sampling", None) is not None:
             raise ValueError("mirostat replaces the semantic phase's top-k, top-p and temperature: "
                              "semantic_sampling excludes it")
+    typ = getattr(args, "typical", None)
+    if typ is not None:
+        if not isinstance(typ, Typical):
+            raise ValueError("typical must be a Typical")
+        typ.check()
+        for what in ("semantic_sampling", "penalties", "mirostat"):
+            if getattr(args, what, None) is not None:
+                raise ValueError("typical replaces the semantic phase's top-k, top-p and temperature and has its "
+                                 f"own penalties: {what} excludes it")
     check_voice_pin(args)
 
 
@@ -453,7 +464,8 @@ class LightweightTtsPipeline:
                             max_tokens=args.max_tokens, seed=args.seed, voice_fidelity=0.8,
                             layered_randomness=LayeredRandomnessConfig(), token_chunk_size=512,
                             global_sampling=args.global_sampling, semantic_sampling=args.semantic_sampling,
-                            penalties=args.penalties, mirostat=args.mirostat)
+                            penalties=args.penalties, mirostat=args.mirostat,
+                            typical=args.typical)
         return TtsBatchRequest(self.manager._tokens(text), props, rg, rs, sargs, args.voice_id,
                                pinned_voice=rg is not None and rs is None)
 

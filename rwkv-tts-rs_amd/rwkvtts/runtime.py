@@ -15,6 +15,7 @@ C-ABI (include/rwkvtts.h). Names and argument meaning follow the Rust originals:
 """
 import ctypes
 import dataclasses
+import math
 import threading
 from typing import List, Optional, Sequence
 
@@ -131,13 +132,24 @@ def request_ext(r: "TtsBatchRequest"):
     """-> the request's _ffi.RequestExt (rwkvtts_request_ext), or None when it asks for nothing
     beyond _ffi.Request: such a request goes through the entry points without a block."""
     miro = getattr(r.args, "mirostat", None)
-    if miro is None:
+    typ = getattr(r.args, "typical", None)
+    if miro is None and typ is None:
         return None
-    x = _ffi.RequestExt()
-    x.struct_size = ctypes.sizeof(_ffi.RequestExt)
-    x.mirostat_set = _ffi.MIROSTAT_SET
-    x.mirostat.tau = float(miro.tau)
-    x.mirostat.rate = float(miro.rate)
+    # the 16-byte block unless typical sampling is asked for: then the longer one (_ffi.RequestExtV2)
+    x = _ffi.RequestExt() if typ is None else _ffi.RequestExtV2()
+    x.struct_size = ctypes.sizeof(x)
+    if miro is not None:
+        x.mirostat_set = _ffi.MIROSTAT_SET
+        x.mirostat.tau = float(miro.tau)
+        x.mirostat.rate = float(miro.rate)
+    if typ is not None:
+        x.typical_set = _ffi.TYPICAL_SET
+        x.typical.tau = float(typ.tau)
+        x.typical.top_k = int(typ.top_k)
+        x.typical.temperature = float(typ.temperature)
+        x.typical.presence_penalty = float(typ.presence_penalty)
+        x.typical.frequency_penalty = float(typ.frequency_penalty)
+        x.typical.penalty_decay = float(typ.penalty_decay)
     return x
 
 
@@ -149,7 +161,7 @@ def _ext_array(requests):
     arr = (ctypes.POINTER(_ffi.RequestExt) * len(exts))()
     for i, x in enumerate(exts):
         if x is not None:
-            arr[i] = ctypes.pointer(x)
+            arr[i] = ctypes.cast(ctypes.pointer(x), ctypes.POINTER(_ffi.RequestExt))
     return arr, exts
 
 
@@ -507,6 +519,46 @@ class Mirostat:
 
 
 @dataclasses.dataclass
+class Typical:
+    """Locally typical sampling of a request's semantic phase (rwkvtts.h rwkvtts_request_ext_v2.typical;
+    参考/ai00_server/crates/ai00-core/src/sampler/typical.rs, which the reference's TTS path never
+    calls; the defaults are its TypicalParams'). Each step keeps, of the `top_k` tokens whose
+    surprise -ln p lies closest to the distribution's entropy, those reached before their
+    cumulative probability passes `tau`, and samples among them at `temperature`. An emitted token
+    is penalised by `presence_penalty` the first time and by `frequency_penalty` more every further
+    time, and every penalty shrinks by `penalty_decay` per step. It replaces the semantic phase's
+    top-k, top-p and temperature (semantic_sampling, greedy, penalties and mirostat exclude it) and
+    leaves the global phase alone. tau >= 0, top_k in [1, 8193], temperature > 0, the penalties
+    finite, penalty_decay in (0, 1]."""
+    tau: float = 0.5
+    top_k: int = 128
+    temperature: float = 1.0
+    presence_penalty: float = 0.3
+    frequency_penalty: float = 0.3
+    penalty_decay: float = 0.99654026
+
+    def check(self, what: str = "typical") -> "Typical":
+        """Raises ValueError for a value the engine would refuse (sched.h validate)."""
+        def num(name):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError(f"{what}: {name} must be a finite number")
+            return v
+        if num("tau") < 0:
+            raise ValueError(f"{what}: tau must be >= 0")
+        k = self.top_k
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 8193:
+            raise ValueError(f"{what}: top_k must be an integer in [1, 8193]")
+        if num("temperature") <= 0:
+            raise ValueError(f"{what}: temperature must be > 0")
+        num("presence_penalty")
+        num("frequency_penalty")
+        if not 0 < num("penalty_decay") <= 1:
+            raise ValueError(f"{what}: penalty_decay must be in (0, 1]")
+        return self
+
+
+@dataclasses.dataclass
 class SamplerArgs:  # src/rwkv_sampler.rs:234-290
     """temperature, top_p and top_k are carried and ignored, as in the reference
     (normal_mode_inference.rs:114-127 fixes the parameters per phase). global_sampling /
@@ -525,6 +577,8 @@ class SamplerArgs:  # src/rwkv_sampler.rs:234-290
     penalties: Optional[Penalties] = None
     # Mirostat in the semantic phase (None: the phase samples with top-k / top-p / temperature)
     mirostat: Optional[Mirostat] = None
+    # typical sampling in the semantic phase (None: as above)
+    typical: Optional[Typical] = None
 
 
 @dataclasses.dataclass
@@ -662,7 +716,8 @@ class DynamicBatchManager:
                 fn = lib().rwkvtts_manager_submit_stream if stream else lib().rwkvtts_manager_submit
                 check(fn(self._h, ctypes.byref(q), ctypes.byref(t)), "manager_submit")
             else:  # (the manager copies the block)
-                check(lib().rwkvtts_manager_submit_ex(self._h, ctypes.byref(q), ctypes.byref(ext), 1 if stream else 0,
+                xp = ctypes.cast(ctypes.pointer(ext), ctypes.POINTER(_ffi.RequestExt))
+                check(lib().rwkvtts_manager_submit_ex(self._h, ctypes.byref(q), xp, 1 if stream else 0,
                                                       ctypes.byref(t)), "manager_submit_ex")
         finally:
             self._leave()

@@ -107,7 +107,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from .pipeline import LightweightTtsPipelineArgs
-from .runtime import Mirostat, Penalties, PhaseSampling
+from .runtime import Mirostat, Penalties, PhaseSampling, Typical
 
 
 def peak_scale(samples) -> np.float32:
@@ -311,6 +311,19 @@ def _tts_args(body, voice_dir: str):
             sampling["mirostat"] = Mirostat(**{k: v for k, v in miro.items() if v is not None}).check()
         except ValueError as e:
             return (400, {"success": False, "error": f"不支持的 Mirostat 参数: {e}"}), None, None
+    typ = body.get("typical")
+    if typ is not None:
+        fields = {"tau", "top_k", "temperature", "presence_penalty", "frequency_penalty", "penalty_decay"}
+        try:
+            if not isinstance(typ, dict) or set(typ) - fields:
+                raise ValueError("typical: an object with any of " + ", ".join(sorted(fields)))
+            for what in ("semantic_sampling", "penalties", "mirostat"):
+                if what in sampling:
+                    raise ValueError("typical replaces the semantic phase's top-k, top-p and temperature and has "
+                                     f"its own penalties: {what} excludes it")
+            sampling["typical"] = Typical(**{k: v for k, v in typ.items() if v is not None}).check()
+        except ValueError as e:
+            return (400, {"success": False, "error": f"不支持的 Typical 参数: {e}"}), None, None
     long_form = body.get("long_form")
     if long_form is not None and not isinstance(long_form, bool):
         return (400, {"success": False, "error": f"不支持的长文本开关: {long_form} (支持: true, false)"}), None, None

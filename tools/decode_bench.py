@@ -10,6 +10,8 @@ request carries penalties. The report adds the most often repeated token's count
 [--mirostat-tau T] [--mirostat-rate R] [--mirostat-slots N]: Mirostat (runtime.Mirostat; either option
 selects it, the other keeps its default 3.0 / 0.1) in the semantic phase of the first N requests
 (default: all of them); it excludes the three sampling options.
+[--typical] [--typical-slots N]: typical sampling (runtime.Typical with ai00's defaults) in the
+semantic phase of the first N requests (default: all of them); it excludes every option above.
 Env: DB_B requests (default 32), DB_F16=1 fp16 weights, DB_ZS=1 zero-shot prompts (32 reference
 global tokens + 128 reference semantic tokens per request), DB_QUANT=int8|nf4 (every layer quantised,
 the server's --quant-layers 24 --quant-type ...), DB_FORMS=n (rwkvtts_engine_desc.forms: RWKVTTS_FORM_* bits)."""
@@ -39,6 +41,8 @@ ap.add_argument("--penalty-slots", type=int, default=None)
 ap.add_argument("--mirostat-tau", type=float, default=None)
 ap.add_argument("--mirostat-rate", type=float, default=None)
 ap.add_argument("--mirostat-slots", type=int, default=None)
+ap.add_argument("--typical", action="store_true")
+ap.add_argument("--typical-slots", type=int, default=None)
 opt = ap.parse_args()
 S, reps = opt.S, opt.reps
 sampling = None
@@ -56,6 +60,11 @@ if opt.mirostat_tau is not None or opt.mirostat_rate is not None:
         ap.error("--mirostat-* replaces the semantic phase's top-k, top-p and temperature")
     mirostat = rwkvtts.Mirostat(**{k: v for k, v in (("tau", opt.mirostat_tau), ("rate", opt.mirostat_rate))
                                    if v is not None}).check()
+typical = None
+if opt.typical:
+    if sampling is not None or penalties is not None or mirostat is not None:
+        ap.error("--typical replaces the semantic phase's sampling and has its own penalties")
+    typical = rwkvtts.Typical().check()
 f16 = os.environ.get("DB_F16", "0") == "1"
 B = int(os.environ.get("DB_B", "32"))
 zs = os.environ.get("DB_ZS", "0") == "1"
@@ -82,6 +91,8 @@ for i in range(B):
         reqs[-1].args.penalties = penalties
     if mirostat is not None and i < (B if opt.mirostat_slots is None else opt.mirostat_slots):
         reqs[-1].args.mirostat = mirostat
+    if typical is not None and i < (B if opt.typical_slots is None else opt.typical_slots):
+        reqs[-1].args.typical = typical
 for r in range(reps):
     t0 = time.perf_counter()
     out = rt.generate_batch(reqs)
@@ -90,7 +101,7 @@ for r in range(reps):
     h = hashlib.sha1(repr(out).encode()).hexdigest()[:12]
     us = st['decode_ms'] / max(st['steps'], 1) * 1000
     top = max((max(np.bincount(np.asarray(s, dtype=np.int64), minlength=1)) for _, s in out if len(s)), default=0)
-    print(f"rep {r}: B={B} f16={int(f16)} zs={int(zs)} quant={qt} sampling={sampling} penalties={penalties} mirostat={mirostat} "
+    print(f"rep {r}: B={B} f16={int(f16)} zs={int(zs)} quant={qt} sampling={sampling} penalties={penalties} mirostat={mirostat} typical={typical} "
           f"max_repeat={top} decode {us:.1f} us/step over {st['steps']} steps "
           f"({B * 320 / us * 1e6:.0f} samples/s decode-only), "
           f"prefill {st['prefill_ms']:.2f} ms, wall {wall * 1000:.1f} ms, tokens {h}", flush=True)
