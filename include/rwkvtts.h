@@ -182,6 +182,33 @@ typedef struct {
 #define RWKVTTS_QUANT_INT8 1 /* 128-element blocks along K: f16 (min, max), u8 q; w = min + q (max - min)/255 */
 #define RWKVTTS_QUANT_NF4 2  /* 64-element blocks along K: f16 absmax, 4-bit NormalFloat index; w = nf4[q] absmax */
 #define RWKVTTS_QUANT_SF4 3  /* rejected (RWKVTTS_EUNSUPPORTED): its code table is not available offline */
+/* OCP Microscaling weights (no reference counterpart): the same six matrices per quantised layer, in
+ * blocks of 32 along K that share one power-of-two scale 2^e (E8M0 byte e + 127); the elements are
+ * E4M3 (MXFP8: 1.4.3, bias 7, largest 448, the NaN code never produced) or E2M1 (MXFP4: magnitudes
+ * 0, .5, 1, 1.5, 2, 3, 4, 6). For a block of bf16 weights v[0..31], emax = 8 (E4M3) or 2 (E2M1):
+ *   1. block maximum   amax = max |v|.
+ *   2. scale exponent  e = floor(log2 amax) - emax, clamped to [e_min, 127] with e_min = -117 (MXFP8)
+ *                      or -125 (MXFP4); e = e_min when amax == 0. The stored byte is e + 127 (0xFF,
+ *                      the E8M0 NaN, is never produced).
+ *   3. element         q = v * 2^-e (exact), rounded to the nearest element value, ties to even on
+ *                      the element's mantissa, saturated to +-448 / +-6; a zero keeps its sign.
+ *   4. dequantised     w = element * 2^e. The smallest non-zero element magnitude is 2^-9 (E4M3) or
+ *                      2^-1 (E2M1), so with e >= e_min every w is ZERO OR A BF16 NORMAL (>= 2^-126),
+ *                      and with e <= 127 - emax (amax is finite) it is finite: w is exactly a bf16
+ *                      number. A layer quantised to MX is therefore, bit for bit, a bf16 layer whose
+ *                      six matrices hold w: the engine's logits and state equal those of an
+ *                      unquantised engine on that blob (tests/test_gpu_mx.py rests on this).
+ *   5. non-finite      a matrix holding an Inf or a NaN fails rwkvtts_engine_create with
+ *                      RWKVTTS_EINVAL.
+ * bf16 models only: an f16 blob with an MX type fails with RWKVTTS_EUNSUPPORTED (E8M0 spans 2^-127 ..
+ * 2^127, f16 2^-24 .. 2^15: the dequantised weights would not be f16 numbers). */
+#define RWKVTTS_QUANT_MXFP8 4
+#define RWKVTTS_QUANT_MXFP4 5
+/* Debug: steps 1-4 on the device apart from the GEMM. w_bf16 [N][K] (host, row-major bf16 bits;
+ * N % 16 == 0, K % 128 == 0) is packed by the engine's pack kernel and unpacked through the GEMM's own
+ * dequantisation into out_bf16 [N][K] (host): the dequantised weights w. type: RWKVTTS_QUANT_MXFP8 /
+ * MXFP4. RWKVTTS_EINVAL for a non-finite weight (step 5) or bad arguments. */
+int rwkvtts_mx_roundtrip(int type, const uint16_t* w_bf16, int N, int K, uint16_t* out_bf16);
 
 /* weights: packed blob (header included). blob_on_device != 0: `weights` is a device pointer
  * on desc->device (e.g. a buffer filled by an RCCL broadcast); it is copied. */

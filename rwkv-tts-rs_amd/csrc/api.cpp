@@ -78,6 +78,10 @@ int rwkvtts_engine_create(const rwkvtts_engine_desc* desc, const void* weights, 
   })
 }
 
+int rwkvtts_mx_roundtrip(int type, const uint16_t* w_bf16, int N, int K, uint16_t* out_bf16) {
+  GUARD({ return mx_roundtrip(type, w_bf16, N, K, out_bf16); })
+}
+
 int rwkvtts_engine_destroy(rwkvtts_engine* e) {
   if (e) {
     std::lock_guard<std::mutex> lk(e->mu);  // wait for a call still running on another thread

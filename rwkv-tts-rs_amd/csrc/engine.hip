@@ -270,35 +270,51 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
   // the r / k / v / o / FFN matrices from the blob's row-major 16-bit copies
   {
     const int qt = desc.quant_type, ql = std::min(std::max(desc.quant_layers, 0), (int)dims.n_layer);
-    RT_CHECK(qt >= RWKVTTS_QUANT_NONE && qt <= RWKVTTS_QUANT_SF4, RWKVTTS_EINVAL, "unknown quant_type");
+    RT_CHECK(qt >= RWKVTTS_QUANT_NONE && qt <= RWKVTTS_QUANT_MXFP4, RWKVTTS_EINVAL, "unknown quant_type");
     RT_CHECK(!(qt == RWKVTTS_QUANT_SF4 && ql > 0), RWKVTTS_EUNSUPPORTED,
              "quant_type sf4: its code table is not available (web-rwkv not vendored)");
+    const bool mx = quant_is_mx(qt);
+    RT_CHECK(!(mx && ql > 0 && f16_), RWKVTTS_EUNSUPPORTED,
+             "quant_type mxfp8 / mxfp4 needs a bf16 model: the E8M0 block scales (2^-127 .. 2^127) do not fit f16's range");
     if (qt != RWKVTTS_QUANT_NONE && ql > 0) {
       RT_CHECK(C % kQ8Block == 0 && F % kQ8Block == 0, RWKVTTS_EUNSUPPORTED, "quantisation needs K % 128 == 0");
+      // (k_gemm_mx has the 128- and 256-deep K-slices the quantised launches' splits give)
+      RT_CHECK(!mx || (C / splitA_ <= 256 && C / splitO_ <= 256 && C / splitK_ <= 256 && F / splitF_ <= 256),
+               RWKVTTS_EUNSUPPORTED, "mxfp8 / mxfp4: K-slices deeper than 256");
       const size_t cb_cc = quant_code_bytes(qt, C, C), sb_cc = quant_scale_bytes(qt, C, C);
       const size_t cb_fc = quant_code_bytes(qt, F, C), sb_fc = quant_scale_bytes(qt, F, C);
       const size_t per_layer = 4 * cb_cc + 2 * cb_fc + 4 * sb_cc + 2 * sb_fc;
       uint8_t* qbuf = nullptr;
       RT_OK(alloc(&qbuf, per_layer * ql));
+      int* mx_bad = nullptr;  // Microscaling: set by the pack kernel on an Inf / NaN weight
+      if (mx) RT_OK(alloc(&mx_bad, 1));
       RT_HIP(hipDeviceSynchronize());  // alloc's memset runs on the null stream
+      // one matrix -> its codes (+ scales): Int8 / NF4 (launch_quant_pack) or a Microscaling superblock buffer
+      auto qpack = [&](const bf16_t* Wm, int N, int K, const uint8_t* codes, const uint8_t* scales) {
+        if (mx) launch_mx_pack((const uint16_t*)Wm, N, K, qt, (uint8_t*)codes, mx_bad, stream_);
+        else launch_quant_pack((const uint16_t*)Wm, N, K, f16_, qt, (uint8_t*)codes, (void*)scales, stream_);
+      };
       for (int l = 0; l < ql; ++l) {
         LayerW& w = L_[l];
         uint8_t* q = qbuf + per_layer * l;
         uint8_t* sc = q + 4 * cb_cc + 2 * cb_fc;
         w.quant = qt;
         w.q_rkv = q; w.s_rkv = sc;
-        for (int j = 0; j < 3; ++j)
-          launch_quant_pack((const uint16_t*)(j == 0 ? w.wr : j == 1 ? w.wk : w.wv), C, C, f16_, qt,
-                            q + j * cb_cc, sc + j * sb_cc, stream_);
+        for (int j = 0; j < 3; ++j) qpack(j == 0 ? w.wr : j == 1 ? w.wk : w.wv, C, C, q + j * cb_cc, sc + j * sb_cc);
         w.q_o = q + 3 * cb_cc; w.s_o = sc + 3 * sb_cc;
-        launch_quant_pack((const uint16_t*)w.wo, C, C, f16_, qt, (uint8_t*)w.q_o, (void*)w.s_o, stream_);
+        qpack(w.wo, C, C, w.q_o, (const uint8_t*)w.s_o);
         w.q_fk = q + 4 * cb_cc; w.s_fk = sc + 4 * sb_cc;
-        launch_quant_pack((const uint16_t*)w.ffn_k, F, C, f16_, qt, (uint8_t*)w.q_fk, (void*)w.s_fk, stream_);
+        qpack(w.ffn_k, F, C, w.q_fk, (const uint8_t*)w.s_fk);
         w.q_fv = q + 4 * cb_cc + cb_fc; w.s_fv = sc + 4 * sb_cc + sb_fc;
-        launch_quant_pack((const uint16_t*)w.ffn_v, C, F, f16_, qt, (uint8_t*)w.q_fv, (void*)w.s_fv, stream_);
+        qpack(w.ffn_v, C, F, w.q_fv, (const uint8_t*)w.s_fv);
       }
       RT_HIP(hipGetLastError());
       RT_HIP(hipStreamSynchronize(stream_));
+      if (mx) {
+        int bad = 0;
+        RT_HIP(hipMemcpy(&bad, mx_bad, sizeof(int), hipMemcpyDeviceToHost));
+        RT_CHECK(!bad, RWKVTTS_EINVAL, "mxfp8 / mxfp4: a quantised matrix holds a non-finite weight");
+      }
       // f16 models: per launch, the shift that brings the largest dequantised |w| to ~2^14
       // (int8: max(|min|, |max|) of the blocks; nf4: the largest block absmax)
       auto shift_of = [&](const void* scales, size_t bytes) -> int {

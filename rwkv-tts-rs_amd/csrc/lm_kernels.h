@@ -279,9 +279,29 @@ void launch_pack_frag(const bf16_t* W, int N, int K, bf16_t* out, hipStream_t st
 // and per-(column, K-block) scales: int8 [N][K / 128] u32 = f16 min | f16 max << 16; nf4
 // [N][K / 64] u16 = f16 absmax.
 constexpr int kQ8Block = 128, kQ4Block = 64;
-inline size_t quant_code_bytes(int qt, int N, int K) { return (size_t)N * K / (qt == 1 ? 1 : 2); }
-inline size_t quant_scale_bytes(int qt, int N, int K) { return qt == 1 ? (size_t)N * (K / kQ8Block) * 4 : (size_t)N * (K / kQ4Block) * 2; }
+// Microscaling matrices (RWKVTTS_QUANT_MXFP8 / MXFP4, mx_gemm.hip): codes and E8M0 scales in ONE buffer
+// of superblocks (16 columns x 128 k: 64 lanes x 32 / 16 code bytes, then the 16 columns' four scale
+// bytes each), so they count as code bytes and have no scale buffer. N % 16 == 0, K % 128 == 0.
+inline bool quant_is_mx(int qt) { return qt == RWKVTTS_QUANT_MXFP8 || qt == RWKVTTS_QUANT_MXFP4; }
+inline size_t mx_pack_bytes(int qt, int N, int K) {
+  return (size_t)(N / 16) * (K / 128) * ((qt == RWKVTTS_QUANT_MXFP4 ? 1024 : 2048) + 64);
+}
+inline size_t quant_code_bytes(int qt, int N, int K) {
+  return quant_is_mx(qt) ? mx_pack_bytes(qt, N, K) : (size_t)N * K / (qt == 1 ? 1 : 2);
+}
+inline size_t quant_scale_bytes(int qt, int N, int K) {
+  if (quant_is_mx(qt)) return 0;
+  return qt == 1 ? (size_t)N * (K / kQ8Block) * 4 : (size_t)N * (K / kQ4Block) * 2;
+}
 void launch_quant_pack(const uint16_t* W, int N, int K, int f16, int qt, uint8_t* codes, void* scales, hipStream_t st);
+// W [N][K] bf16 -> the packed MX matrix; *nonfinite is set to 1 if W holds an Inf or a NaN
+void launch_mx_pack(const uint16_t* W, int N, int K, int qt, uint8_t* out, int* nonfinite, hipStream_t st);
+// launch_gemm's form for GemmArgs::q_fmt MXFP8 / MXFP4 (k_gemm_mx; bf16 models, K-slices of 128 / 256):
+// qw the packed matrix (MS 2: the matrices of the launch's quantised tiles back to back), qs unused.
+// Partial slabs bit for bit those of the unquantised launch on the dequantised matrix.
+int launch_gemm_mx(const GemmArgs& a, hipStream_t st);
+// rwkvtts_mx_roundtrip: host W [N][K] bf16 -> pack, unpack (k_gemm_mx's dequantisation) -> host out
+int mx_roundtrip(int qt, const uint16_t* w, int N, int K, uint16_t* out);
 // Repack one layer's LoRA-up rows (0.4B ranks 64/64/32/128) into k_wkv6's coalesced order.
 void launch_pack_lora6(const bf16_t* w2t, const bf16_t* a2t, const bf16_t* v2t, const bf16_t* g2t, int C,
                        bf16_t* out, hipStream_t st);

@@ -1872,6 +1872,7 @@ bool gemm_tile_table(GemmArgs& a, int64_t x_mix_stride) {
 }
 
 int launch_gemm(const GemmArgs& a, hipStream_t st) {
+  if (quant_is_mx(a.q_fmt)) return launch_gemm_mx(a, st);  // Microscaling weights: k_gemm_mx (mx_gemm.hip)
   const int tiles = a.seg[a.nseg - 1].tile_start + (a.seg[a.nseg - 1].N + 63) / 64;
   // one or two 16-row blocks per workgroup, also for prefill steps: 64- and 128-row groups
   // (fewer weight re-reads, 135 KB X images, one workgroup per CU) were measured slower on a

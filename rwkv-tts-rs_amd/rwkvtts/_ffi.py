@@ -70,6 +70,7 @@ CODEC_FORM_SEPARATE_RESUNIT, CODEC_FORM_CHANNEL_LAST = 1, 2
 
 
 QUANT_NONE, QUANT_INT8, QUANT_NF4, QUANT_SF4 = 0, 1, 2, 3
+QUANT_MXFP8, QUANT_MXFP4 = 4, 5  # OCP Microscaling weights (bf16 models; include/rwkvtts.h)
 
 
 class Input(ctypes.Structure):
@@ -520,6 +521,7 @@ EXPORTS = {
                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "rwkvtts_pause_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PauseWindow), ctypes.c_int]),
     "rwkvtts_pause_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    "rwkvtts_mx_roundtrip": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
 }
 
 _lib = None
