@@ -1238,6 +1238,81 @@ int rwkvtts_pitch_kernel_ms(rwkvtts_pitch* p, double* ms);
 /* HIP-event time of the last call's marks kernel alone, the serial part, in ms; 0 before the first. */
 int rwkvtts_pitch_walk_ms(rwkvtts_pitch* p, double* ms);
 
+/* ---- formant: a timbre control on the same machinery, the `formant_shift` of the pipeline (no
+ * reference counterpart: the reference's age and gender are property tokens, which a cloned voice does
+ * not get) -- every grain of the pitch stage is read beta times faster under the same window and laid
+ * down at the same marks, so the period stays and the spectral envelope scales by beta (above 1: a
+ * shorter vocal tract, "smaller / younger"). It runs on a rwkvtts_pitch object, in the same launch
+ * triple, and composes with the pitch factor: f drives the mark walk, B the grain read. The contract
+ * is the pitch contract above with one line replaced:
+ *   B         int32, per signal: floor(2^(s / 12) * 65536 + 0.5) in double for a shift of s semitones
+ *             in [-6, 6] (rwkvtts_formant_ratio), so 46341 .. 92682; beta = B / 65536. A call whose
+ *             every B is 65536 is the pitch call, bit for bit (it launches the same kernels).
+ *   table     T = 16 taps, 64 phases, one table per B: h[ph * 16 + t]. In double: fc = 1 if
+ *             B <= 65536, else 65536 / B (the cutoff is min(1, 1 / beta) of Nyquist, so a grain read
+ *             faster does not alias); u = (t - 7) - ph / 64; z = fc * u; sinc = 1 where z == 0, 0 where
+ *             z is another integer (z == floor(z)), else sin(pi * z) / (pi * z) (pi * z one multiply);
+ *             k = (u + 8) / 16; bh = 0.35875 - 0.48829 cos(2 pi k) + 0.14128 cos(4 pi k) -
+ *             0.01168 cos(6 pi k) (the resampler's window family, Blackman-Harris squared);
+ *             v[t] = sinc * (bh * bh); h = (float)(v[t] / sum_t v[t]), the sum in ascending t. At
+ *             B <= 65536 phase 0 is the exact unit tap h[7] = 1.
+ *   unchanged periods, analysis and synthesis marks, the pairing, the Hann rows w_P and the
+ *             denominator den = sum of w.
+ *   numerator grain q = (s, a, p), k = k(q), covers output o with r = o - (s - p) in [0, 2p). Its term
+ *             is w_p[r] * xi (one rounded multiply, then one rounded add onto num, grains in
+ *             ascending q), where P = (a << 16) + (r - p) * B in int64, i0 = P >> 16 (arithmetic: the
+ *             floor), ph = (P & 65535) >> 10 (the fraction truncated to 6 bits, never rounded up, so
+ *             no read position moves past the next sample and an integer position reads phase 0) and
+ *             xi = sum over t = 0 .. 15 in ascending t, from +0, of h[ph * 16 + t] * x[i0 - 7 + t]:
+ *             one rounded multiply and one rounded add per tap, never fused. Reads outside [0, n)
+ *             are +0. y[o] = num / den as before.
+ * So silence still comes back bit for bit. At B == 65536 every P is an integer position, phase 0 is
+ * the unit tap and xi == x[a - p + r] up to the sign of a zero, which num does not keep: a job with
+ * B == 65536 inside a call with other ratios equals the pitch path bitwise (tests/test_gpu_formant.py).
+ * The interpolation error of T = 16, 64 phases against exact band-limited evaluation is measured in
+ * DESIGN.md §38; nobody has listened to the output and every default is untuned. */
+int rwkvtts_formant_ratio(double semitones, int32_t* B);
+/* The library's own table builder (host only): out[64 * 16]. B outside 46341 .. 92682 is
+ * RWKVTTS_EINVAL, here and in every call that takes a B. */
+int rwkvtts_formant_table(const rwkvtts_pitch_desc* desc, int32_t B, float* out);
+/* rwkvtts_pitch_plan with the grain read's reach R = ceil(Lmax * B / 65536) + 8 beside the grain's
+ * Lmax (r - p in [-p, p - 1] puts i0 in [a - ceil(p B / 65536), a + floor((p - 1) B / 65536)], and the
+ * taps reach 7 below and 8 above i0): *out_ready_end = max(0, n_known - (2 Lmax + max(Wc + Lmax, R))),
+ * *in_first_needed = max(0, min(a_prev - max(Lmax, R), floor(a_prev / Ha) * Ha)). It never asks for
+ * less than rwkvtts_pitch_plan (a B below 65536 reaches less than Lmax; the tail a stream keeps is the
+ * pitch stage's then), so a window that passes it passes the pitch stage's check too. An output
+ * waits max(0, R - (Wc + Lmax)) samples longer than the pitch stage's: nothing at the defaults, where
+ * the period frames look further (960) than any grain read (at most 461). At B == 65536 it is
+ * rwkvtts_pitch_plan. The carried state stays the two marks. */
+int rwkvtts_formant_plan(const rwkvtts_pitch_desc* desc, int32_t B, int64_t n_known, int final, int64_t out_first,
+                         int64_t a_prev, int64_t s_prev, int64_t* out_ready_end, int64_t* in_first_needed);
+/* rwkvtts_pitch_batch with a B per signal. Period and marks kernels as there; if any B is not 65536
+ * the synthesis is k_formant_synth for the whole call: a workgroup per 320-output piece stages the
+ * span of x its grains read and the job's table in LDS. The span is at most 320 + 2 Lmax +
+ * 2 ceil(Lmax * 27146 / 65536) + 18 samples (12.9 KB at Lmax = 1024); a lag_max whose span and table
+ * exceed 64 KB of LDS would be RWKVTTS_EINVAL (none in the desc's range does). */
+int rwkvtts_formant_batch(rwkvtts_pitch* p, const float* const* in, const int64_t* n_in, const double* factor,
+                          const int32_t* B, int n, float* const* out);
+typedef struct {  /* rwkvtts_pitch_window and B */
+  uint32_t struct_size;
+  const float* in;
+  int64_t in_first;
+  int64_t n_in;
+  int32_t final;
+  double factor;
+  int64_t out_first;
+  int64_t a_prev;
+  int64_t s_prev;
+  int64_t out_count;
+  float* out;
+  int64_t a_last;
+  int64_t s_last;
+  int32_t B;
+} rwkvtts_formant_window;
+/* rwkvtts_pitch_windows with a B per window; refused as there, and also where a window asks for more
+ * than rwkvtts_formant_plan allows for its B (which is never less strict than rwkvtts_pitch_plan). */
+int rwkvtts_formant_windows(rwkvtts_pitch* p, rwkvtts_formant_window* w, int n);
+
 /* ---- wm: a provenance watermark on the GPU, the `watermark` of the pipeline -- a time-domain
  * spread-spectrum mark that carries a payload under a key, and its detector (no reference counterpart:
  * the reference marks nothing) -----------------------------------------------------------------

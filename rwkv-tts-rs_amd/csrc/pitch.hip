@@ -24,39 +24,16 @@
 #include <vector>
 
 #include "common.h"
+#include "formant_plan.h"
+#include "pitch_dev.h"
 #include "pitch_plan.h"
 #include "stage.h"
 
 namespace rwkvtts {
 
-constexpr int kPitchThreads = 320;  // five waves: the 291 lags of the default range in one pass
 constexpr int kPitchWaves = kPitchThreads / 64;
 constexpr int kPitchChunk = 4096;  // periods in LDS at a time in the walk
 constexpr int kPitchNone = 0x7fffffff;
-
-// One grid row of each kernel: outputs [out_first, out_first + out_count) of one signal. The given
-// samples are signal indices [in_first, in_end), stored at x[in_off ...]; every other index reads as
-// zero (the host has checked that those are below 0 or past the end of a final window). Frames
-// [j0, j0 + nf) are measured, frame j at per[per_off + j - j0]. The walks start at a_prev and s_prev;
-// analysis marks go to am[am_off ...] (at most am_cap), grains to gr[sm_off ...] (at most sm_cap).
-struct PitchJob {
-  int64_t in_off, out_off, per_off, am_off, sm_off;
-  int32_t in_first, in_end, out_first, out_count;
-  int32_t j0, nf, a_prev, s_prev, am_cap, sm_cap;
-  double factor;
-};
-
-struct PitchGrain {  // synthesis mark, its analysis mark and that mark's period
-  int32_t s, a, p, pad;
-};
-
-struct PitchState {
-  int32_t ns, a_last, s_last, pad;
-};
-
-__device__ inline float pitch_x(const float* __restrict__ x, const PitchJob& j, int64_t idx) {
-  return (idx >= j.in_first && idx < j.in_end) ? x[j.in_off + (idx - j.in_first)] : 0.0f;
-}
 
 // one step of a lag's two chains
 #define PITCH_STEP(a, b)                                           \
@@ -204,10 +181,6 @@ __global__ __launch_bounds__(64) void k_pitch_marks(const PitchJob* __restrict__
   }
 }
 
-// Correctly rounded f32 divide through double (53 >= 2 * 24 + 2 bits; the device's double divide is
-// correctly rounded).
-__device__ inline float pitch_div(float a, float b) { return (float)((double)a / (double)b); }
-
 // grid (320-sample pieces of the longest job, jobs): a lane per output sample.
 __global__ __launch_bounds__(kPitchThreads) void k_pitch_synth(const float* __restrict__ x,
                                                                const float* __restrict__ tab,
@@ -256,6 +229,7 @@ struct PitchWin {
   float* out;
   int64_t* a_last;
   int64_t* s_last;
+  int32_t B = kFormantOne;  // the grain read's ratio (formant.hip); 65536 reads the grain as it is
 };
 
 }  // namespace rwkvtts
@@ -268,6 +242,11 @@ struct rwkvtts_pitch : Stage<PitchJob> {  // d_table: the rows Lmin .. Lmax
   DevBuf<PitchGrain> d_gr;
   DevBuf<PitchState> d_state;
   std::vector<PitchState> last;
+  DevBuf<FormantJob> d_fj;  // only calls with a B other than 65536 use these three
+  DevBuf<float> d_ftab;     // the call's tables, one per distinct B
+  std::vector<FormantJob> fj;
+  std::vector<int32_t> tab_b;  // the B of each table in d_ftab
+  std::vector<float> ftab;
   hipEvent_t ev2 = nullptr, ev3 = nullptr;  // bracket the marks kernel
   double walk_ms = 0.0;
 };
@@ -278,12 +257,18 @@ static int pitch_run(rwkvtts_pitch* v, const std::vector<PitchWin>& ws, const ch
   const PitchCfg& c = v->cfg;
   int64_t tot_in = 0, tot_out = 0, tot_per = 0, tot_am = 0, tot_sm = 0, max_nf = 0, max_out = 0;
   size_t n_jobs = 0;
+  bool shifted = false;  // some job reads its grains at another rate: the whole call goes through k_formant_synth
   int rc;
   for (const PitchWin& w : ws) {
     const char* bad = pitch_window_check(c, w.in_first, w.n_in, w.final, w.factor, w.out_first, w.a_prev, w.s_prev,
                                          w.out_count, w.in != nullptr, w.out != nullptr);
     RT_CHECK(!bad, RWKVTTS_EINVAL, std::string(who) + ": " + bad);
+    RT_CHECK(formant_b_ok(w.B), RWKVTTS_EINVAL, std::string(who) + ": B must be 46341 .. 92682");
     if (w.out_count == 0) continue;
+    RT_CHECK(w.out_first + w.out_count <= formant_ready_end(c, w.B, w.in_first + w.n_in, w.final) &&
+                 w.in_first <= formant_in_first_needed(c, w.B, w.a_prev),
+             RWKVTTS_EINVAL, std::string(who) + ": a requested output's grain read leaves the given samples");
+    shifted = shifted || w.B != kFormantOne;
     const PitchGeom g = pitch_geometry(c, w.out_first, w.out_count, w.a_prev, w.s_prev);
     tot_in += w.n_in;
     tot_out += w.out_count;
@@ -306,6 +291,8 @@ static int pitch_run(rwkvtts_pitch* v, const std::vector<PitchWin>& ws, const ch
   std::lock_guard<std::mutex> lock(v->mu);
   v->desc.clear();
   v->last.assign(n_jobs, PitchState{0, 0, 0, 0});
+  std::vector<int32_t> tab_b;
+  v->fj.clear();
   int64_t in_off = 0, out_off = 0, per_off = 0, am_off = 0, sm_off = 0;
   for (const PitchWin& w : ws) {
     if (w.out_count == 0) continue;
@@ -328,6 +315,11 @@ static int pitch_run(rwkvtts_pitch* v, const std::vector<PitchWin>& ws, const ch
     j.sm_cap = (int32_t)g.sm_cap;
     j.factor = w.factor;
     v->desc.push_back(j);
+    if (shifted) {
+      size_t t = std::find(tab_b.begin(), tab_b.end(), w.B) - tab_b.begin();
+      if (t == tab_b.size()) tab_b.push_back(w.B);
+      v->fj.push_back(FormantJob{w.B, (int32_t)t});
+    }
     in_off += w.n_in;
     out_off += w.out_count;
     per_off += j.nf;
@@ -338,6 +330,19 @@ static int pitch_run(rwkvtts_pitch* v, const std::vector<PitchWin>& ws, const ch
       (rc = v->d_am.reserve((size_t)tot_am)) || (rc = v->d_gr.reserve((size_t)tot_sm)) ||
       (rc = v->d_state.reserve(n_jobs)) || (rc = stage_upload(v, ws)))
     return rc;
+  if (shifted) {
+    const size_t tl = (size_t)kFormantTaps * kFormantPhases;
+    if ((rc = v->d_fj.reserve(n_jobs))) return rc;
+    if (tab_b != v->tab_b || v->d_ftab.cap < tab_b.size() * tl) {  // (the tables of the last call are still there)
+      v->tab_b.clear();
+      if ((rc = v->d_ftab.reserve(tab_b.size() * tl))) return rc;
+      v->ftab.resize(tab_b.size() * tl);
+      for (size_t t = 0; t < tab_b.size(); ++t) formant_make_table(tab_b[t], v->ftab.data() + t * tl);
+      RT_HIP(hipMemcpyAsync(v->d_ftab.p, v->ftab.data(), v->ftab.size() * sizeof(float), hipMemcpyHostToDevice, v->stream));
+      v->tab_b = tab_b;
+    }
+    RT_HIP(hipMemcpyAsync(v->d_fj.p, v->fj.data(), n_jobs * sizeof(FormantJob), hipMemcpyHostToDevice, v->stream));
+  }
   // the event pair brackets all three kernels: start of the period kernel, end of the synthesis
   const size_t lds = (size_t)(c.Wc + c.Lmax + 1 + 2 * (c.Lmax - c.Lmin + 3)) * sizeof(float);  // 28.7 KB at the widest
   hipExtLaunchKernelGGL(k_pitch_period, dim3((unsigned)max_nf, (unsigned)n_jobs), dim3(kPitchThreads), lds, v->stream,
@@ -346,10 +351,16 @@ static int pitch_run(rwkvtts_pitch* v, const std::vector<PitchWin>& ws, const ch
   hipExtLaunchKernelGGL(k_pitch_marks, dim3((unsigned)n_jobs), dim3(64), 0, v->stream, v->ev2, v->ev3, 0u, v->d_desc.p,
                         v->d_per.p, v->d_am.p, v->d_gr.p, v->d_state.p, c);
   RT_HIP(hipGetLastError());
-  hipExtLaunchKernelGGL(k_pitch_synth, dim3((unsigned)((max_out + kPitchThreads - 1) / kPitchThreads), (unsigned)n_jobs),
-                        dim3(kPitchThreads), 0, v->stream, nullptr, v->ev1, 0u, v->d_in.p, v->d_table, v->d_desc.p,
-                        v->d_gr.p, v->d_state.p, v->d_out.p, c);
-  RT_HIP(hipGetLastError());
+  const unsigned pieces = (unsigned)((max_out + kPitchThreads - 1) / kPitchThreads);
+  if (shifted) {
+    if ((rc = formant_synth_launch(c, pieces, (unsigned)n_jobs, v->stream, v->ev1, v->d_in.p, v->d_table, v->d_ftab.p,
+                                   v->d_desc.p, v->d_fj.p, v->d_gr.p, v->d_state.p, v->d_out.p)))
+      return rc;
+  } else {
+    hipExtLaunchKernelGGL(k_pitch_synth, dim3(pieces, (unsigned)n_jobs), dim3(kPitchThreads), 0, v->stream, nullptr,
+                          v->ev1, 0u, v->d_in.p, v->d_table, v->d_desc.p, v->d_gr.p, v->d_state.p, v->d_out.p, c);
+    RT_HIP(hipGetLastError());
+  }
   RT_HIP(hipMemcpyAsync(v->last.data(), v->d_state.p, n_jobs * sizeof(PitchState), hipMemcpyDeviceToHost, v->stream));
   if ((rc = stage_download(v, ws))) return rc;
   float ms = 0.0f;
@@ -416,7 +427,7 @@ extern "C" int rwkvtts_pitch_destroy(rwkvtts_pitch* v) {
   (void)hipSetDevice(v->device);
   if (v->ev2) (void)hipEventDestroy(v->ev2);
   if (v->ev3) (void)hipEventDestroy(v->ev3);
-  stage_free(v, {v->d_per.p, v->d_am.p, v->d_gr.p, v->d_state.p});
+  stage_free(v, {v->d_per.p, v->d_am.p, v->d_gr.p, v->d_state.p, v->d_fj.p, v->d_ftab.p});
   return RWKVTTS_OK;
 }
 
@@ -453,4 +464,31 @@ extern "C" int rwkvtts_pitch_walk_ms(rwkvtts_pitch* v, double* ms) {
   std::lock_guard<std::mutex> lock(v->mu);
   *ms = v->walk_ms;
   return RWKVTTS_OK;
+}
+
+// ---- formant shift: the same launches with a grain-read ratio per job (formant.hip) ---------------
+extern "C" int rwkvtts_formant_batch(rwkvtts_pitch* v, const float* const* in, const int64_t* n_in, const double* factor,
+                                     const int32_t* B, int n, float* const* out) {
+  RT_CHECK(v && n >= 0 && (n == 0 || (in && n_in && factor && B && out)), RWKVTTS_EINVAL, "formant_batch: bad arguments");
+  return guard_alloc("formant_batch", [&] {
+    std::vector<PitchWin> ws((size_t)n);
+    for (int i = 0; i < n; ++i) {
+      RT_CHECK(n_in[i] >= 0 && n_in[i] <= kPitchMaxSamples, RWKVTTS_EINVAL, "formant_batch: n_in out of range");
+      ws[(size_t)i] = PitchWin{in[i], 0, n_in[i], 1, factor[i], 0, 0, 0, n_in[i], out[i], nullptr, nullptr, B[i]};
+    }
+    return pitch_run(v, ws, "formant_batch");
+  });
+}
+
+extern "C" int rwkvtts_formant_windows(rwkvtts_pitch* v, rwkvtts_formant_window* w, int n) {
+  RT_CHECK(v && n >= 0 && (n == 0 || w), RWKVTTS_EINVAL, "formant_windows: bad arguments");
+  if (n == 0) return RWKVTTS_OK;
+  return guard_alloc("formant_windows", [&] {
+    std::vector<PitchWin> ws;
+    int rc = read_windows("formant_windows", w, n, ws, [](rwkvtts_formant_window* wi) {
+      return PitchWin{wi->in, wi->in_first, wi->n_in, wi->final ? 1 : 0, wi->factor, wi->out_first, wi->a_prev,
+                      wi->s_prev, wi->out_count, wi->out, &wi->a_last, &wi->s_last, wi->B};
+    });
+    return rc ? rc : pitch_run(v, ws, "formant_windows");
+  });
 }

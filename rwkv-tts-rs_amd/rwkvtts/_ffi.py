@@ -270,6 +270,10 @@ class PitchWindow(ctypes.Structure):
                 ("s_last", ctypes.c_int64)]
 
 
+class FormantWindow(ctypes.Structure):  # PitchWindow and B
+    _fields_ = PitchWindow._fields_ + [("B", ctypes.c_int32)]
+
+
 class WmDesc(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("block", ctypes.c_int32), ("taps", ctypes.c_int32),
                 ("bits", ctypes.c_int32), ("bit_len", ctypes.c_int32), ("band_lo", ctypes.c_float),
@@ -488,6 +492,15 @@ EXPORTS = {
     "rwkvtts_pitch_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PitchWindow), ctypes.c_int]),
     "rwkvtts_pitch_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
     "rwkvtts_pitch_walk_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    # formant: the pitch object's calls with a grain-read ratio B per signal (ratio, table and plan: host only)
+    "rwkvtts_formant_ratio": (ctypes.c_int, [ctypes.c_double, ctypes.POINTER(ctypes.c_int32)]),
+    "rwkvtts_formant_table": (ctypes.c_int, [ctypes.POINTER(PitchDesc), ctypes.c_int32, ctypes.c_void_p]),
+    "rwkvtts_formant_plan": (ctypes.c_int, [ctypes.POINTER(PitchDesc), ctypes.c_int32, ctypes.c_int64, ctypes.c_int,
+                                            ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "rwkvtts_formant_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "rwkvtts_formant_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(FormantWindow), ctypes.c_int]),
     # watermark: table, strength, threshold and plan (host only), batched / exact stream embedding, the detector
     "rwkvtts_wm_table": (ctypes.c_int, [ctypes.POINTER(WmDesc), ctypes.c_void_p]),
     "rwkvtts_wm_strength": (ctypes.c_float, [ctypes.c_double]),

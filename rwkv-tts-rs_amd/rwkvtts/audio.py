@@ -725,6 +725,9 @@ def pitch_factor(semitones: float) -> float:
     return 2.0 ** (float(semitones) / 12.0)
 
 
+FORMANT_ONE = 65536  # the grain-read ratio B of no formant shift
+
+
 def _pitch_table(lag_min: int, lag_max: int) -> np.ndarray:
     """Rows P = lag_min .. lag_max back to back, row P at (P - lag_min) * (P + lag_min - 1):
     w_P[i] = (float)(0.5 - 0.5 * cos(2 * pi * (i + 0.5) / (2P))), in double: the table both sides read."""
@@ -750,10 +753,18 @@ class PitchShifter(_NativeStage):
     unvoiced 80, theta 0.2, floor 1e-3. Every default is untuned and nobody has listened to the
     output: the repository has no real checkpoint. The kernels read the table `_pitch_table` builds.
 
+    formant (csrc/formant.hip): every call that shifts also takes a formant shift in
+    semitones per signal, -6 .. 6. The grains are then read 2^(formant / 12) times faster under the same
+    window, through a 16-tap polyphase interpolator, and laid down at the same marks: the period stays
+    and the spectral envelope moves (up: a shorter vocal tract, "smaller / younger"). It composes with
+    the pitch shift in the same launches; formant alone runs at pitch 0. None or 0 everywhere is the
+    pitch path as it always was, bit for bit.
+
     evaluator: a callable (shifter, items) -> [(ndarray, a_last, s_last)] standing in for the native
     window call, items being [(samples from in_first on, in_first, final, factor, out_first, a_prev,
     s_prev, out_count)]; no GPU object is created then (the host-only plan / table entry points are
-    still the library's)."""
+    still the library's). With a formant ratio other than 65536 in the call it is called as
+    evaluator(shifter, items, Bs), Bs the ratio of each item."""
     _NAME = "pitch"
 
     def __init__(self, device: int = 0, hop: int = 160, window: int = 640, lag_min: int = 32, lag_max: int = 320,
@@ -778,53 +789,99 @@ class PitchShifter(_NativeStage):
             raise ValueError("a pitch shift must be in [-12, 12] semitones")
         return f
 
+    @staticmethod
+    def formant_ratio(semitones) -> int:
+        """B = round(2^(semitones / 12) * 65536), the library's (rwkvtts_formant_ratio); None is 0."""
+        if semitones is None:
+            return FORMANT_ONE
+        if isinstance(semitones, bool) or not -6.0 <= float(semitones) <= 6.0:  # (NaN fails)
+            raise ValueError("a formant shift must be in [-6, 6] semitones")
+        B = ctypes.c_int32()
+        _native("formant_ratio", float(semitones), ctypes.byref(B))
+        return B.value
+
+    def formant_table(self, B: int) -> np.ndarray:
+        """The (64, 16) interpolation table of ratio B the kernel reads (rwkvtts_formant_table)."""
+        tab = np.empty((64, 16), dtype=F32)
+        _native("formant_table", ctypes.byref(self._desc), int(B), tab.ctypes.data_as(ctypes.c_void_p))
+        return tab
+
     # ---- host-only plan ----
-    def plan(self, n_known: int, final: bool, out_first: int = 0, a_prev: int = 0, s_prev: int = 0):
-        """(out_ready_end, in_first_needed) of rwkvtts_pitch_plan."""
+    def plan(self, n_known: int, final: bool, out_first: int = 0, a_prev: int = 0, s_prev: int = 0,
+             B: int = FORMANT_ONE):
+        """(out_ready_end, in_first_needed) of rwkvtts_pitch_plan; with a ratio B other than 65536, of
+        rwkvtts_formant_plan."""
         end, first = ctypes.c_int64(), ctypes.c_int64()
-        _native("pitch_plan", ctypes.byref(self._desc), int(n_known), 1 if final else 0, int(out_first), int(a_prev),
-                int(s_prev), ctypes.byref(end), ctypes.byref(first))
+        args = (int(n_known), 1 if final else 0, int(out_first), int(a_prev), int(s_prev), ctypes.byref(end),
+                ctypes.byref(first))
+        if int(B) == FORMANT_ONE:
+            _native("pitch_plan", ctypes.byref(self._desc), *args)
+        else:
+            _native("formant_plan", ctypes.byref(self._desc), int(B), *args)
         return end.value, first.value
 
     # ---- the kernels ----
-    def shift_windows(self, items) -> list:
+    def _ratios(self, formant, n):
+        """formant: None, or a formant shift in semitones per item -> None (the pitch path), or the Bs."""
+        if formant is None:
+            return None
+        Bs = [self.formant_ratio(s) for s in formant]
+        if len(Bs) != n:
+            raise ValueError("one formant shift per signal")
+        return Bs if any(B != FORMANT_ONE for B in Bs) else None
+
+    def shift_windows(self, items, formant=None) -> list:
         """[(samples from in_first on, in_first, final, factor, out_first, a_prev, s_prev, out_count)]
         -> [(outputs [out_first, + out_count) of the whole-signal result, a_last, s_last)], the state
-        after each window's last output, all windows in one launch triple. Raises
-        RwkvTtsError(EINVAL), with nothing computed, if a window asks for more than plan() allows."""
+        after each window's last output, all windows in one launch triple. formant: a formant shift in
+        semitones per window (None: none). Raises RwkvTtsError(EINVAL), with nothing computed, if a
+        window asks for more than plan() allows."""
         items = [(np.ascontiguousarray(x, dtype=F32).reshape(-1), int(a), bool(fin), float(f), int(o), int(ap), int(sp),
                   int(c)) for x, a, fin, f, o, ap, sp, c in items]
+        Bs = self._ratios(formant, len(items))
+        name = "pitch_windows" if Bs is None else "formant_windows"
         if self._evaluator is not None:
-            for x, a, fin, f, o, ap, sp, c in items:  # the native call's own refusals, from the host-only plan
-                if not 0.5 <= f <= 2.0:
-                    raise _ffi.RwkvTtsError(_ffi.EINVAL, "pitch_windows")
-                end, first = self.plan(a + x.size, fin, o, ap, sp)
+            for (x, a, fin, f, o, ap, sp, c), B in zip(items, Bs or [FORMANT_ONE] * len(items)):
+                if not 0.5 <= f <= 2.0:  # the native call's own refusals, from the host-only plan
+                    raise _ffi.RwkvTtsError(_ffi.EINVAL, name)
+                end, first = self.plan(a + x.size, fin, o, ap, sp, B)
                 if c < 0 or (c > 0 and (o + c > end or a > first)):
-                    raise _ffi.RwkvTtsError(_ffi.EINVAL, "pitch_windows")
-            return [(np.ascontiguousarray(y, dtype=F32), int(al), int(sl)) for y, al, sl in self._evaluator(self, items)]
-        ws, outs = self._windows("pitch_windows", _ffi.PitchWindow, items, factor=3, out_first=4, a_prev=5, s_prev=6)
+                    raise _ffi.RwkvTtsError(_ffi.EINVAL, name)
+            res = self._evaluator(self, items) if Bs is None else self._evaluator(self, items, Bs)
+            return [(np.ascontiguousarray(y, dtype=F32), int(al), int(sl)) for y, al, sl in res]
+        if Bs is None:
+            ws, outs = self._windows(name, _ffi.PitchWindow, items, factor=3, out_first=4, a_prev=5, s_prev=6)
+        else:
+            ws, outs = self._windows(name, _ffi.FormantWindow, [it[:7] + (B, it[7]) for it, B in zip(items, Bs)],
+                                     factor=3, out_first=4, a_prev=5, s_prev=6, B=7)
         return [(o, int(w.a_last), int(w.s_last)) for o, w in zip(outs, ws)]
 
-    def shift_batch(self, signals, semitones) -> list:
+    def shift_batch(self, signals, semitones, formant=None) -> list:
         """[signal], [semitones] -> [shifted signal], ragged, a shift per signal, in one launch triple;
-        an empty signal gives an empty one."""
+        an empty signal gives an empty one. formant: a formant shift in semitones per signal."""
         xs = [np.ascontiguousarray(x, dtype=F32).reshape(-1) for x in signals]
         fs = [self.factor(s) for s in semitones]
         if len(xs) != len(fs):
             raise ValueError("shift_batch: one shift per signal")
+        Bs = self._ratios(formant, len(xs))
         if self._evaluator is not None:
-            return [y for y, _, _ in self.shift_windows([(x, 0, True, f, 0, 0, 0, x.size) for x, f in zip(xs, fs)])]
+            return [y for y, _, _ in self.shift_windows([(x, 0, True, f, 0, 0, 0, x.size) for x, f in zip(xs, fs)], formant)]
         if not xs:
             return []
         outs, ins, lens, ous = self._ragged(xs, [x.size for x in xs])
-        self._call("pitch_batch", ins, lens, (ctypes.c_double * len(fs))(*fs), len(xs), ous)
+        if Bs is None:
+            self._call("pitch_batch", ins, lens, (ctypes.c_double * len(fs))(*fs), len(xs), ous)
+        else:
+            self._call("formant_batch", ins, lens, (ctypes.c_double * len(fs))(*fs), (ctypes.c_int32 * len(Bs))(*Bs),
+                       len(xs), ous)
         return outs
 
-    def shift(self, x, semitones: float) -> np.ndarray:
-        return self.shift_batch([x], [semitones])[0]
+    def shift(self, x, semitones: float, formant: float = 0.0) -> np.ndarray:
+        return self.shift_batch([x], [semitones], [formant])[0]
 
-    def stream(self, semitones: float) -> "PitchStream":
-        return PitchStream(self, semitones)
+    def stream(self, semitones: float, formant: float = 0.0) -> "PitchStream":
+        return PitchStream(self, semitones) if self.formant_ratio(formant) == FORMANT_ONE else FormantStream(
+            self, semitones, formant)
 
     def walk_ms(self) -> float:
         """HIP-event time of the last call's marks kernel alone (the serial walk)."""
@@ -840,26 +897,44 @@ class PitchStream(_ExactStream):
     after it are known (0.1 s at the defaults); the kept tail is what rwkvtts_pitch_plan asks for,
     fewer than window + 9 * lag_max + hop samples."""
 
-    def __init__(self, shifter: PitchShifter, semitones: float):
+    def __init__(self, shifter: PitchShifter, semitones: float, formant=None):
         super().__init__()
         self.p = shifter
         self.f = shifter.factor(semitones)
+        self.formant = formant   # semitones; None: the pitch path
+        self.B = shifter.formant_ratio(formant)
         self._out_next = 0       # outputs [0, _out_next) went out
         self._state = (0, 0)     # (a, s) after them
 
     def _emit(self, n_known, final):
         a, s = self._state
-        end, _ = self.p.plan(n_known, final, self._out_next, a, s)
+        end, _ = self.p.plan(n_known, final, self._out_next, a, s, self.B)
         count = end - self._out_next
         if count <= 0:
             return np.zeros(0, dtype=F32)
-        out, a, s = self.p.shift_windows([(self._tail, self._tail_first, final, self.f, self._out_next, a, s, count)])[0]
+        out, a, s = self.p.shift_windows([(self._tail, self._tail_first, final, self.f, self._out_next, a, s, count)],
+                                         None if self.formant is None else [self.formant])[0]
         self._state = (a, s)
         self._out_next += count
         return out
 
     def _first_needed(self, n_known):
-        return self.p.plan(n_known, False, self._out_next, *self._state)[1]
+        return self.p.plan(n_known, False, self._out_next, *self._state, self.B)[1]
+
+
+class FormantStream(PitchStream):
+    """PitchShifter.stream(semitones, formant): PitchStream with the grains read at the formant ratio;
+    the concatenation of what feed returns is bitwise PitchShifter.shift(the concatenated input,
+    semitones, formant). An output goes out once `lag` samples after it are known: 2 * lag_max +
+    max(window + lag_max, R) with R = ceil(lag_max * B / 65536) + 8, the grain read's reach -- the pitch
+    stream's window + 3 * lag_max (0.1 s at the defaults) wherever the period frames look further than
+    the grain read, which they do at the defaults (960 against at most 461). The carried state stays
+    the two marks."""
+
+    def __init__(self, shifter: PitchShifter, semitones: float, formant: float):
+        super().__init__(shifter, semitones, formant)
+        reach = (shifter.lag_max * self.B + 65535 >> 16) + 8
+        self.lag = 2 * shifter.lag_max + max(shifter.window + shifter.lag_max, reach)
 
 
 # ---- provenance watermark on the GPU ---------------------------------------------------------

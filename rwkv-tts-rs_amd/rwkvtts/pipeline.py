@@ -23,6 +23,11 @@ All five also take `pitch_shift` (no reference counterpart: the reference's only
 in semitones, -12 .. 12, moves the fundamental of the 16 kHz PCM on the GPU and keeps its spectral
 envelope and its length (audio.PitchShifter), first of the stages -- before the
 stretch, and in long-form after the join -- exact over stream chunks.
+All five also take `formant_shift` (no reference counterpart: the reference's age and gender are
+property tokens, which a cloned voice does not get): None / 0 leaves the PCM as it is; a shift in
+semitones, -6 .. 6, moves the spectral envelope of the 16 kHz PCM on the GPU and keeps its fundamental
+and its length (the same stage with its grains read faster or slower), alone or
+together with `pitch_shift` in the same launches, exact over stream chunks.
 All five also take `watermark` (no reference counterpart: the reference marks nothing): None leaves the
 PCM unmarked; a payload, an integer 0 .. 65535, embeds it as a spread-spectrum mark under the
 pipeline's `watermark_key` (audio.Watermarker) on the 16 kHz PCM, after the
@@ -193,7 +198,8 @@ class LongSpeech(np.ndarray):
 
 
 def audio_stages(stretcher, tempo, resampler, leveller=None, loudness=None, shifter=None, pitch_shift=None,
-                 marker=None, watermark=None, watermark_key=None, shaper=None, max_pause=None) -> list:
+                 marker=None, watermark=None, watermark_key=None, shaper=None, max_pause=None,
+                 formant_shift=None) -> list:
     """The stages behind the vocoder in the order they apply -- the pause cap at 16 kHz, then the pitch
     shift, then the stretch, then the leveller, then the watermark, then the resampler; None is no
     stage -- each as (batch, stream): batch([pcm]) -> [pcm] in one native call (one cap, one shift, one
@@ -202,8 +208,11 @@ def audio_stages(stretcher, tempo, resampler, leveller=None, loudness=None, shif
     stages = []
     if shaper is not None:
         stages.append((lambda pcm: shaper.shape_batch(pcm, max_pause), lambda: shaper.stream(max_pause)))
-    if shifter is not None:
+    if shifter is not None and formant_shift is None:
         stages.append((lambda pcm: shifter.shift_batch(pcm, [pitch_shift] * len(pcm)), lambda: shifter.stream(pitch_shift)))
+    elif shifter is not None:  # the same stage and launches, the grains read at the formant ratio
+        stages.append((lambda pcm: shifter.shift_batch(pcm, [pitch_shift] * len(pcm), [formant_shift] * len(pcm)),
+                       lambda: shifter.stream(pitch_shift, formant_shift)))
     if stretcher is not None:
         stages.append((lambda pcm: stretcher.stretch_batch(pcm, [tempo] * len(pcm)), lambda: stretcher.stream(tempo)))
     if leveller is not None:
@@ -314,16 +323,16 @@ class LightweightTtsPipeline:
         return v
 
     # ---- pitch (no reference counterpart: the reference has the `pitch` property token only)
-    def shifter(self, pitch_shift: Optional[float]):
-        """None for None / 0 (nothing is created: the PCM is the vocoder's); otherwise the pipeline's
-        one PitchShifter (the untuned defaults of audio.PitchShifter), on the codec's GPU. The shift
-        is in semitones per call, not a part of the object. A shift outside -12 .. 12 raises
-        ValueError before anything is generated."""
-        if pitch_shift is None:
-            return None
-        if isinstance(pitch_shift, bool) or not -12.0 <= float(pitch_shift) <= 12.0:  # (NaN fails)
-            raise ValueError("pitch_shift must be in [-12, 12] semitones")
-        if float(pitch_shift) == 0.0:
+    def shifter(self, pitch_shift: Optional[float], formant_shift: Optional[float] = None):
+        """None where both are None / 0 (nothing is created: the PCM is the vocoder's); otherwise the
+        pipeline's one PitchShifter (the untuned defaults of audio.PitchShifter), on the codec's GPU.
+        Both shifts are in semitones per call, not a part of the object. A pitch_shift outside
+        -12 .. 12 or a formant_shift outside -6 .. 6 raises ValueError before anything is generated."""
+        if pitch_shift is not None and (isinstance(pitch_shift, bool) or not -12.0 <= float(pitch_shift) <= 12.0):
+            raise ValueError("pitch_shift must be in [-12, 12] semitones")  # (NaN fails)
+        if formant_shift is not None and (isinstance(formant_shift, bool) or not -6.0 <= float(formant_shift) <= 6.0):
+            raise ValueError("formant_shift must be in [-6, 6] semitones")
+        if not float(pitch_shift or 0.0) and not float(formant_shift or 0.0):
             return None
         with self._stage_cache_lock:
             if self._shifter is None:
@@ -396,16 +405,18 @@ class LightweightTtsPipeline:
 
     def _stages(self, sample_rate: Optional[int], tempo: Optional[float], loudness: Optional[float] = None,
                 pitch_shift: Optional[float] = None, watermark: Optional[int] = None,
-                max_pause: Optional[int] = None):  # -> (stages, output rate)
+                max_pause: Optional[int] = None, formant_shift: Optional[float] = None):  # -> (stages, output rate)
         rs = self.resampler(sample_rate)
         lv = self.leveller(loudness)
-        sh = self.shifter(pitch_shift)
+        sh = self.shifter(pitch_shift, formant_shift)
         mk = self.marker(watermark)
         ps = self.pause_shaper(max_pause)
         # (without max_pause the call is the one it always was: stand-ins of audio_stages see no new keyword)
         kw = {} if ps is None else {"shaper": ps, "max_pause": int(max_pause)}
+        if sh is not None and float(formant_shift or 0.0):  # (the same for formant_shift)
+            kw["formant_shift"] = float(formant_shift)
         return (audio_stages(self.stretcher(tempo), tempo, rs, lv, None if lv is None else float(loudness),
-                             sh, None if sh is None else float(pitch_shift),
+                             sh, None if sh is None else float(pitch_shift or 0.0),
                              mk, None if mk is None else int(watermark), self.watermark_key, **kw),
                 rs.sr_out if rs else SAMPLE_RATE)
 
@@ -472,7 +483,7 @@ class LightweightTtsPipeline:
     def generate_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
                         tempo: Optional[float] = None, loudness: Optional[float] = None,
                         watermark: Optional[int] = None, max_pause: Optional[int] = None,
-                        pitch_shift: Optional[float] = None) -> np.ndarray:
+                        formant_shift: Optional[float] = None, pitch_shift: Optional[float] = None) -> np.ndarray:
         """sample_rate None / 16000: the vocoder's 16 kHz PCM. Any other rate: that PCM resampled on
         the GPU (resampler()); the failed-request second of silence is sample_rate zeros.
         tempo None / 1.0: nothing. Any other: the 16 kHz PCM time-stretched on the GPU (stretcher())
@@ -483,6 +494,10 @@ class LightweightTtsPipeline:
         pitch_shift None / 0: nothing. A shift in semitones, -12 .. 12: the 16 kHz PCM's fundamental
         moved on the GPU (shifter()) before the stretch, its envelope and length kept; independent of
         args.pitch, which stays the property token.
+        formant_shift None / 0: nothing. A shift in semitones, -6 .. 6: the same stage reads every
+        grain 2^(formant_shift / 12) times faster (audio.PitchShifter), so the
+        fundamental and the length stay and the spectral envelope moves: up for a smaller, younger
+        voice, down for a larger, older one. It composes with pitch_shift in the same launches.
         watermark None: nothing. A payload 0 .. 65535: the 16 kHz PCM marked on the GPU (marker())
         under the pipeline's key, after the leveller and before the resampler; the failed-request
         second of silence is not marked (silence carries no mark).
@@ -491,7 +506,7 @@ class LightweightTtsPipeline:
         than the vocoder's PCM by what was cut; the failed-request second of silence is not shaped.
         args.global_sampling / semantic_sampling outside their ranges raise ValueError, like tempo."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift)
         try:
             req = self._request(args)
         except ValueError:  # untokenisable text: the request fails -> empty result
@@ -507,7 +522,8 @@ class LightweightTtsPipeline:
     def stream_speech(self, args: LightweightTtsPipelineArgs, chunk_frames: int = 16,
                       sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                       loudness: Optional[float] = None, watermark: Optional[int] = None,
-                      max_pause: Optional[int] = None, pitch_shift: Optional[float] = None):
+                      max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
+                      pitch_shift: Optional[float] = None):
         """generate_speech as a generator of float32 PCM chunks (SpeechChunk: an ndarray that also
         carries t0, t1, n_known, done), each decoded while the request is still generating tokens.
 
@@ -537,7 +553,9 @@ class LightweightTtsPipeline:
 
         pitch_shift (semitones, -12 .. 12, not 0): PitchShifter.stream(pitch_shift) comes first, and
         the concatenation is bitwise generate_speech(args, pitch_shift=...). A shifted item lags its
-        frames by the shifter's look-ahead, 0.1 s at the defaults.
+        frames by the shifter's look-ahead, 0.1 s at the defaults. formant_shift (semitones, -6 .. 6,
+        not 0) goes through the same stream (FormantStream), bitwise generate_speech(args,
+        formant_shift=...), with the same lag at the defaults.
 
         watermark (a payload 0 .. 65535): Watermarker.stream(key, payload) sits after the leveller, and
         the concatenation is bitwise generate_speech(args, watermark=...). A marked item lags its
@@ -560,6 +578,9 @@ class LightweightTtsPipeline:
         if pitch_shift is not None:
             self.shifter(pitch_shift)  # (the same for a bad shift)
             kw["pitch_shift"] = pitch_shift
+        if formant_shift is not None:
+            self.shifter(pitch_shift, formant_shift)
+            kw["formant_shift"] = formant_shift
         if watermark is not None:
             self.marker(watermark)  # (and for a bad payload or a missing key)
             kw["watermark"] = watermark
@@ -571,14 +592,15 @@ class LightweightTtsPipeline:
     def stream_request(self, req: Optional[TtsBatchRequest], chunk_frames: int = 16,
                        sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                        loudness: Optional[float] = None, watermark: Optional[int] = None,
-                       max_pause: Optional[int] = None, pitch_shift: Optional[float] = None):
+                       max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
+                       pitch_shift: Optional[float] = None):
         """stream_speech for a request that is already built (None: a request that failed before it
         was submitted)."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         if req is not None:
             check_sampling(req.args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift)
         streams = [stream() for _, stream in stages]
         H = self.codec.halo()
         g, sem, t0, yielded, status = None, [], 0, False, 0
@@ -614,19 +636,21 @@ class LightweightTtsPipeline:
     def generate_speech_batch(self, batch_args: Sequence[LightweightTtsPipelineArgs],
                               sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                               loudness: Optional[float] = None, watermark: Optional[int] = None,
-                              max_pause: Optional[int] = None, pitch_shift: Optional[float] = None) -> List[np.ndarray]:
+                              max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
+                              pitch_shift: Optional[float] = None) -> List[np.ndarray]:
         """sample_rate other than None / 16000: the whole batch is resampled in one resample_batch
         call (a failed item stays an empty array). tempo other than None / 1.0: the whole batch is
         first stretched in one stretch_batch call, one tempo for the call. loudness other than None:
         the whole batch is levelled in one level_batch call between the two, one target for the call.
         pitch_shift other than None / 0: the whole batch is shifted in one shift_batch call before
-        all of them, one shift for the call. watermark other than None: the whole batch is marked in
+        all of them, one shift for the call (formant_shift: in that same call). watermark other than
+        None: the whole batch is marked in
         one embed_batch call after the leveller, one payload for the call. max_pause other than None:
         the silences of the whole batch are capped in one shape_batch call before all of them, one
         cap for the call."""
         for a in batch_args:
             check_sampling(a)
-        stages, _ = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause)
+        stages, _ = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift)
         reqs, idx = [], []
         for i, a in enumerate(batch_args):
             try:
@@ -710,7 +734,8 @@ class LightweightTtsPipeline:
                              tempo: Optional[float] = None, segment_tokens: int = 64, pauses=None,
                              trim: bool = True, keep: int = 800, fade: int = 80,
                              loudness: Optional[float] = None, watermark: Optional[int] = None,
-                             max_pause: Optional[int] = None, pitch_shift: Optional[float] = None) -> "LongSpeech":
+                             max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
+                             pitch_shift: Optional[float] = None) -> "LongSpeech":
         """generate_speech for a text of any length: the text is cut into segments of at most
         segment_tokens text tokens (segment.split_text), the segments decode side by side in the
         manager's slots and engines with one voice (_long_submit), and their PCM is joined on the
@@ -724,14 +749,15 @@ class LightweightTtsPipeline:
         keep and fade are unmeasured defaults. loudness levels the joined
         signal as one (generate_speech), so the segments, decoded as independent requests, come out
         at one level; the second of silence is not levelled. pitch_shift shifts the joined signal as
-        one, after the join and before the stretch. watermark marks the joined signal as one, so a
+        one, after the join and before the stretch, and formant_shift with it. watermark marks the
+        joined signal as one, so a
         job carries one continuous sequence across its segments and pauses. max_pause caps the
         silences of every segment's PCM before the join, all segments in one shape_batch call; the
         pauses the join puts between segments are deliberate and stay. A record's `cut` is what the
         cap removed from its segment, and its a, b then refer to the shaped segment. The second of
         silence is not shaped."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, formant_shift=formant_shift)
         shaper = self.pause_shaper(max_pause)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)
@@ -757,7 +783,7 @@ class LightweightTtsPipeline:
                            tempo: Optional[float] = None, segment_tokens: int = 64, pauses=None,
                            trim: bool = True, keep: int = 800, fade: int = 80, loudness: Optional[float] = None,
                            watermark: Optional[int] = None, max_pause: Optional[int] = None,
-                           pitch_shift: Optional[float] = None):
+                           formant_shift: Optional[float] = None, pitch_shift: Optional[float] = None):
         """generate_long_speech as a generator of LongSpeech items, one per segment, in order: segment
         i is emitted once it and every segment before it are done -- decoded, joined alone with its
         gap (a piece depends on its own segment only), and fed through the stages' exact streams,
@@ -768,10 +794,11 @@ class LightweightTtsPipeline:
         first good one are held back until it arrives, so a text whose every segment fails yields
         the one second of silence alone. Streaming inside a segment is out of scope. With loudness
         an item also waits for the leveller's look-ahead (up to 0.5 s of the next segment), with
-        pitch_shift for the shifter's (0.1 s), with watermark for the rest of its last block (20 ms).
+        pitch_shift or formant_shift for the shifter's (0.1 s), with watermark for the rest of its last
+        block (20 ms).
         max_pause caps the silences of each segment's PCM before its join, one call per segment."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, formant_shift=formant_shift)
         shaper = self.pause_shaper(max_pause)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)

@@ -68,6 +68,12 @@
   of the finished 16 kHz PCM's fundamental on the GPU that keeps the spectral envelope and the
   length (audio.PitchShifter), before the stretch, and works for every voice. Without the field (or
   with 0) the routes are unchanged.
+* `formant_shift` in the body of both TTS routes (no reference counterpart: the reference's age and
+  gender are property tokens, which a request with a `voice_id` does not get): a JSON number in
+  [FORMANT_SHIFT_MIN, FORMANT_SHIFT_MAX] = [-6, 6] semitones, anything else a 400; above 0 moves the
+  spectral envelope up (a shorter vocal tract: smaller, younger), below 0 down, with the fundamental
+  and the length kept (the pitch stage with its grains read faster or slower), alone or together
+  with `pitch_shift`. Without the field (or with 0) the routes are unchanged.
 * `watermark` in the body of both TTS routes (no reference counterpart: the reference marks nothing):
   a JSON integer in [WATERMARK_MIN, WATERMARK_MAX] = [0, 65535], anything else a 400, and a 400 too on
   a server whose pipeline has no `watermark_key`. The payload is embedded in the 16 kHz PCM under the
@@ -166,6 +172,9 @@ LOUDNESS_MIN, LOUDNESS_MAX = -40.0, -10.0
 # `pitch_shift` of the same bodies (no reference counterpart): semitones, an octave either way -- the
 # kernel's own range
 PITCH_SHIFT_MIN, PITCH_SHIFT_MAX = -12.0, 12.0
+# `formant_shift` of the same bodies (no reference counterpart): semitones by which the spectral envelope
+# moves with the fundamental kept -- half an octave either way, the kernel's own range
+FORMANT_SHIFT_MIN, FORMANT_SHIFT_MAX = -6.0, 6.0
 # `format` of the same bodies (no reference counterpart): the container of the audio that goes out
 FORMATS = ("wav", "flac")
 # `watermark` of the same bodies (no reference counterpart): the payload of the provenance mark, 16
@@ -229,7 +238,8 @@ def _tts_args(body, voice_dir: str):
     takes beyond the args, each only when the body sets it to something other than its default --
     sample_rate (one of SAMPLE_RATES, not 16000), tempo (TEMPO_MIN .. TEMPO_MAX, not 1.0), loudness
     (LOUDNESS_MIN .. LOUDNESS_MAX; there is no default value that means "off" but its absence) and
-    pitch_shift (PITCH_SHIFT_MIN .. PITCH_SHIFT_MAX, not 0), and max_pause (an integer MAX_PAUSE_MIN ..
+    pitch_shift (PITCH_SHIFT_MIN .. PITCH_SHIFT_MAX, not 0), formant_shift (FORMANT_SHIFT_MIN ..
+    FORMANT_SHIFT_MAX, not 0), and max_pause (an integer MAX_PAUSE_MIN ..
     MAX_PAUSE_MAX ms; absent is off) -- so a
     body without them makes exactly the call it always made. A true `long_form` adds
     long_form=True, which the handler takes out and answers by calling the long-form entry point,
@@ -266,6 +276,13 @@ def _tts_args(body, voice_dir: str):
           or not PITCH_SHIFT_MIN <= shift <= PITCH_SHIFT_MAX):  # (NaN fails the comparison)
         return (400, {"success": False, "error": f"不支持的音高偏移: {shift} (支持: "
                                                  f"{PITCH_SHIFT_MIN} - {PITCH_SHIFT_MAX} 半音)"}), None, None
+    formant = body.get("formant_shift")
+    if formant is None:
+        formant = 0.0
+    elif (isinstance(formant, bool) or not isinstance(formant, (int, float))
+          or not FORMANT_SHIFT_MIN <= formant <= FORMANT_SHIFT_MAX):  # (NaN fails the comparison)
+        return (400, {"success": False, "error": f"不支持的共振峰偏移: {formant} (支持: "
+                                                 f"{FORMANT_SHIFT_MIN} - {FORMANT_SHIFT_MAX} 半音)"}), None, None
     mark = body.get("watermark")
     if mark is not None and (isinstance(mark, bool) or not isinstance(mark, int)
                              or not WATERMARK_MIN <= mark <= WATERMARK_MAX):
@@ -376,6 +393,8 @@ def _tts_args(body, voice_dir: str):
         kw["loudness"] = float(loudness)
     if float(shift) != 0.0:
         kw["pitch_shift"] = float(shift)
+    if float(formant) != 0.0:
+        kw["formant_shift"] = float(formant)
     if mark is not None:
         kw["watermark"] = int(mark)
     if max_pause is not None:
