@@ -245,6 +245,57 @@ typedef struct {
 int rwkvtts_infer(rwkvtts_engine* e, const rwkvtts_input* inputs, int n_inputs, int head_rows,
                   float* logits, int32_t* consumed, int32_t* has_logits);
 
+/* ---- adapters: per-request LoRA (ai00's `Lora { path, alpha }`, 参考/ai00_server/crates/ai00-core/
+ * src/reload.rs, which it can only blend at load; here per state slot, over ONE copy of the base
+ * weights) ---------------------------------------------------------------------------------------
+ * An adapter holds, per layer and per target matrix W [N][K], a pair of bf16 matrices A [r][K] and
+ * B [N][r], and one f32 scale s (alpha / r). The targets are the six matrices the quantisers treat:
+ * r, k, v, o, FFN key, FFN value (bits 0..5 of `mask`, in that order). A row of a forward step whose
+ * slot is bound to the adapter computes y = W x + B (s (A x)) for every target the adapter carries;
+ * a target it does not carry contributes nothing. Operation by operation:
+ *   1. x is the f32 input the base GEMM sees (the mixed LayerNorm row; the WKV output; for the FFN
+ *      value target relu(sum of the key GEMM's split-K slabs in slab order)^2, the adapter's key delta
+ *      included), taken as bf16 planes hi = RNE(x), lo = RNE(x - hi).
+ *   2. t = A x in f32: K is cut into four contiguous quarters; within a quarter the 32-deep MFMA steps
+ *      run in ascending k, the x_hi and x_lo chains apart and added at the quarter's end; the quarters
+ *      are added as ((q0 + q1) + q2) + q3. The order does not depend on the step's row count.
+ *   3. t = t * s, one rounded f32 multiply.
+ *   4. t is taken as hi + lo bf16 planes again; d = B t in f32, the t_hi and t_lo chains apart and
+ *      added at the end (K = r, zero-padded to a multiple of 32).
+ *   5. d is added (one f32 add) to split-K slab 0 of the base GEMM's output before anything reads it.
+ * A row's delta depends on that row and its adapter only, so outputs stay chunk- and batch-invariant
+ * bit for bit, and a row without an adapter is bit for bit what it is on an engine with none loaded.
+ * A step that carries an adapter row runs the separate launches (as quantised engines do); a step
+ * that carries none is untouched. Quantised base layers are allowed: the delta does not look at how
+ * W is stored. One rank per adapter, r in {16, 32, 48, 64}.
+ *
+ * Blob: a 64-byte rwkvtts_adapter_header, then layer-major, per layer the carried targets in the
+ * order r, k, v, o, key, value, each as A [r][K] then B [N][r], row-major bf16 bits, no padding.
+ *
+ * bf16 engines only: an f16 engine refuses a load with RWKVTTS_EUNSUPPORTED. */
+#define RWKVTTS_MAX_ADAPTERS 64
+#define RWKVTTS_ADAPTER_MAGIC 0x41524F4Cu /* "LORA" */
+typedef struct {
+  uint32_t magic;   /* RWKVTTS_ADAPTER_MAGIC */
+  uint32_t version; /* 1 */
+  int32_t n_layer, n_embd, n_ffn; /* must equal the engine's */
+  int32_t rank;     /* 16, 32, 48 or 64 */
+  uint32_t mask;    /* bit t: target t is carried (1 .. 63) */
+  float s;          /* alpha / rank, finite */
+  uint32_t reserved[8];
+} rwkvtts_adapter_header;
+/* id in [0, RWKVTTS_MAX_ADAPTERS), chosen by the caller; `blob` is a host buffer. RWKVTTS_EINVAL for a
+ * bad id, header, rank, dims or size, a non-finite value, or an id that is live (unload it first). */
+int rwkvtts_engine_adapter_load(rwkvtts_engine* e, int id, const void* blob, size_t bytes);
+/* RWKVTTS_EBUSY while a slot is bound to the adapter; RWKVTTS_EINVAL for an id that is not live. */
+int rwkvtts_engine_adapter_unload(rwkvtts_engine* e, int id);
+/* Binds a state slot to a live adapter (-1: none). The binding belongs to the slot until it is set
+ * again; rwkvtts_slot_reset leaves it alone; rwkvtts_infer honours it. The generate entries run a
+ * request's rows with the request's adapter (rwkvtts_request_ext_v3.adapter, -1 without the field) from
+ * its admission to a slot until it retires; then the slot has the binding set here again, so a caller's
+ * binding survives a generate call and a finished request holds no adapter busy. */
+int rwkvtts_slot_set_adapter(rwkvtts_engine* e, int slot, int id);
+
 /* ---- sampler: sample_logits_with_top_p_k (src/rwkv_sampler.rs:55-211) ------------------ */
 /* rand 0.8.5 StdRng (ChaCha12, seed_from_u64 via PCG32) is represented statelessly by its
  * 32-byte key and the index of the next u32 draw. */
@@ -466,6 +517,19 @@ typedef struct {
   rwkvtts_typical typical;
 } rwkvtts_request_ext_v2;
 #define RWKVTTS_TYPICAL_SET 1
+/* The v2 block, longer by the request's adapter, through the same pointer under the same struct_size
+ * rule: a library reads `adapter` only where struct_size covers it and otherwise takes -1 (none), so
+ * both shorter blocks keep working. A caller of this block that wants no adapter sets -1 (0 is an id).
+ * An id that is not live fails the request alone with RWKVTTS_EINVAL. */
+typedef struct {
+  uint32_t struct_size;  /* sizeof(rwkvtts_request_ext_v3) the caller was built with */
+  int32_t mirostat_set;
+  struct { float tau, rate; } mirostat;
+  int32_t typical_set;
+  rwkvtts_typical typical;
+  int32_t adapter;       /* a live adapter id, or -1 */
+  int32_t reserved;      /* 0 */
+} rwkvtts_request_ext_v3;
 
 typedef struct {
   int32_t status;        /* 0 ok; <0 this request failed -> (vec![], vec![]) as dbm.rs:466-469
@@ -588,6 +652,12 @@ typedef struct {
                                                one engine per GPU, across processes: rwkvtts_stats) */
 } rwkvtts_manager_stats;
 int rwkvtts_manager_get_stats(rwkvtts_manager* m, rwkvtts_manager_stats* out);
+/* The adapter calls on every engine of the manager (rwkvtts_engine_adapter_load / _unload): each engine's
+ * owner thread performs the call between two units of work, and the call returns when all have done
+ * it, with the first failure. An unload returns RWKVTTS_EBUSY while a request that is queued or
+ * decoding names the adapter. */
+int rwkvtts_manager_adapter_load(rwkvtts_manager* m, int id, const void* blob, size_t bytes);
+int rwkvtts_manager_adapter_unload(rwkvtts_manager* m, int id);
 
 /* Step-level statistics of the last generate call (bench / roofline). */
 typedef struct {

@@ -114,6 +114,22 @@ int rwkvtts_slot_write(rwkvtts_engine* e, int slot, const float* in) {
   GUARD({ return e->eng.slot_write(slot, in); })
 }
 
+int rwkvtts_engine_adapter_load(rwkvtts_engine* e, int id, const void* blob, size_t bytes) {
+  RT_CHECK(e && blob, RWKVTTS_EINVAL, "adapter_load: null argument");
+  LOCK(e);
+  GUARD({ return e->eng.adapter_load(id, blob, bytes); })
+}
+int rwkvtts_engine_adapter_unload(rwkvtts_engine* e, int id) {
+  RT_CHECK(e, RWKVTTS_EINVAL, "null engine");
+  LOCK(e);
+  GUARD({ return e->eng.adapter_unload(id); })
+}
+int rwkvtts_slot_set_adapter(rwkvtts_engine* e, int slot, int id) {
+  RT_CHECK(e, RWKVTTS_EINVAL, "null engine");
+  LOCK(e);
+  GUARD({ return e->eng.slot_set_adapter(slot, id); })
+}
+
 int rwkvtts_infer(rwkvtts_engine* e, const rwkvtts_input* inputs, int n_inputs, int head_rows,
                   float* logits, int32_t* consumed, int32_t* has_logits) {
   RT_CHECK(e && inputs && consumed && has_logits && n_inputs > 0, RWKVTTS_EINVAL, "infer: bad arguments");

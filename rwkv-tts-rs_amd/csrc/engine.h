@@ -2,6 +2,7 @@
 // reference (src/shared_runtime.rs:23-284) re-designed as one owner thread per GPU with
 // device-resident state slots, ragged-batch forward steps and hipGraph-replayed decode steps.
 #pragma once
+#include <algorithm>
 #include <map>
 #include <string>
 #include <vector>
@@ -113,6 +114,11 @@ class Engine {
   int slot_read(int slot, float* out);
   int slot_write(int slot, const float* in);
   int64_t state_floats() const;
+  // per-request LoRA adapters (include/rwkvtts.h "adapters"; lora.hip)
+  int adapter_load(int id, const void* blob, size_t bytes);
+  int adapter_unload(int id);
+  int slot_set_adapter(int slot, int id);
+  bool adapter_live(int id) const { return id >= 0 && id < RWKVTTS_MAX_ADAPTERS && adapters_[id].dev != nullptr; }
 
   int infer(const rwkvtts_input* in, int n, int head_rows, float* logits, int32_t* consumed,
             int32_t* has_logits);
@@ -181,6 +187,11 @@ class Engine {
   int launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_from_ctrl, bool advance,
                      AdvanceKind kind = kAdvFixed);  // AdvanceArgs::kind
   int upload_plan(const StepPlan& p);
+  // the step's LoRA row tiles (lora.hip: up to 16 rows that share an adapter each) from the plan's
+  // rows and the slots' bindings, uploaded to d_lora_tiles_; sets lora_tiles_
+  int upload_lora_tiles(const StepPlan& p);
+  // tiles a step of R rows can have however its rows are bound: the grid of a captured decode step
+  static int lora_max_tiles(int R) { return std::min(R, RWKVTTS_MAX_ADAPTERS + (R + 15) / 16); }
   void prof_begin(hipEvent_t* ev);
   void prof_end(const char* name, hipEvent_t ev);
   int flush_prof();
@@ -312,6 +323,21 @@ class Engine {
   const bf16_t* head_ = nullptr;
   const float *ln0_w_ = nullptr, *ln0_b_ = nullptr, *lnout_w_ = nullptr, *lnout_b_ = nullptr;
   std::vector<LayerW> L_;
+  // adapters: the resident buffers (offset table, then the packed matrices), the device table k_lora
+  // reads, each slot's binding (-1: none), and the tile table of the last uploaded plan
+  struct Adapter {
+    void* dev = nullptr;  // null: the id is free
+    int rank = 0;
+  };
+  Adapter adapters_[RWKVTTS_MAX_ADAPTERS];
+  int n_adapters_ = 0;
+  LoraDev* d_lora_dev_ = nullptr;  // [RWKVTTS_MAX_ADAPTERS]
+  int* d_lora_tiles_ = nullptr;    // kLoraTileHead + lora_max_tiles(Rmax_) * kLoraTileInts ints
+  std::vector<int> lora_tiles_host_;
+  std::vector<int> slot_adapter_;  // [S] the adapter a slot's rows run with
+  std::vector<int> slot_bound_;    // [S] rwkvtts_slot_set_adapter's binding (a request's adapter covers it while it holds the slot)
+  int lora_tiles_ = 0;             // tiles of the last uploaded plan (0: the step carries no adapter)
+  int lora_grid_ = 0;              // tiles the next launch_forward's k_lora grids cover (run_step)
   // state
   float* wkv_ = nullptr;     // [S][L][H][N][N]
   float* att_sh_ = nullptr;  // [2][S][L][C]

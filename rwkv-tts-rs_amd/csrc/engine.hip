@@ -103,6 +103,8 @@ Engine::~Engine() {
   for (auto& g : graphs_) hipGraphExecDestroy(g.second);
   for (auto& e : pending_prof_) hipEventDestroy(e.second);
   for (void* p : allocs_) hipFree(p);
+  for (Adapter& a : adapters_)
+    if (a.dev) hipFree(a.dev);
   for (void* p : {(void*)d_samp_logits_, (void*)d_keys_, (void*)d_draws_, (void*)d_out_, d_wide_})
     if (p) hipFree(p);
   if (h_ctrl_) hipHostFree(h_ctrl_);
@@ -371,6 +373,8 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
   RT_OK(alloc(&ffn_sh_, (size_t)2 * S_ * Lc * C));
   RT_OK(alloc(&slot_par_, (size_t)S_));
   par_host_.assign(S_, 0);
+  slot_adapter_.assign(S_, -1);
+  slot_bound_.assign(S_, -1);
   ctrl_stage_.assign(S_, SlotCtrl{});
   samp_stage_.assign(S_, SlotSampling{{1.0f, 0.0f, 0.0f, 0}, {0.0f, 0.0f, 0.0f, 0}});
   // tables
@@ -527,6 +531,147 @@ int Engine::slot_write(int slot, const float* in) {
 }
 
 // ------------------------------------------------------------------------------------------
+// adapters (include/rwkvtts.h "adapters"; the kernels are lora.hip's)
+// ------------------------------------------------------------------------------------------
+// target t's W is [N][K]: r, k, v, o are C x C, the FFN key F x C, the FFN value C x F
+static inline void lora_target_shape(int t, int C, int F, int* N, int* K) {
+  *N = t == 4 ? F : C;
+  *K = t == 5 ? F : C;
+}
+
+int Engine::adapter_load(int id, const void* blob, size_t bytes) {
+  RT_HIP(hipSetDevice(device_));
+  RT_CHECK(id >= 0 && id < RWKVTTS_MAX_ADAPTERS, RWKVTTS_EINVAL, "adapter_load: id must be in [0, 64)");
+  RT_CHECK(!f16_, RWKVTTS_EUNSUPPORTED, "adapter_load: adapters need a bf16 engine (this one is f16)");
+  const int C = dims.n_embd, F = dims.n_ffn, Lc = dims.n_layer;
+  RT_CHECK(C % 128 == 0 && F % 128 == 0, RWKVTTS_EUNSUPPORTED, "adapter_load: n_embd and n_ffn must be multiples of 128");
+  RT_CHECK(!adapters_[id].dev, RWKVTTS_EINVAL, "adapter_load: the id is live (unload it first)");
+  rwkvtts_adapter_header h;
+  RT_CHECK(blob && bytes >= sizeof(h), RWKVTTS_EINVAL, "adapter_load: blob shorter than its header");
+  memcpy(&h, blob, sizeof(h));
+  RT_CHECK(h.magic == RWKVTTS_ADAPTER_MAGIC && h.version == 1, RWKVTTS_EINVAL, "adapter_load: bad magic or version");
+  RT_CHECK(h.n_layer == Lc && h.n_embd == C && h.n_ffn == F, RWKVTTS_EINVAL, "adapter_load: dims differ from the engine's");
+  const int r = h.rank;
+  RT_CHECK(r == 16 || r == 32 || r == 48 || r == 64, RWKVTTS_EINVAL, "adapter_load: rank must be 16, 32, 48 or 64");
+  RT_CHECK(h.mask >= 1 && h.mask < 64, RWKVTTS_EINVAL, "adapter_load: mask must be in [1, 63]");
+  RT_CHECK(std::isfinite(h.s), RWKVTTS_EINVAL, "adapter_load: non-finite scale");
+  const int rp = (r + 31) / 32 * 32;  // the rank padded to the MFMA depth
+  size_t in_elems = 0, out_elems = 0;
+  for (int t = 0; t < 6; ++t) {
+    if (!(h.mask >> t & 1)) continue;
+    int N, K;
+    lora_target_shape(t, C, F, &N, &K);
+    in_elems += (size_t)r * K + (size_t)N * r;
+    out_elems += (size_t)rp * K + (size_t)N * rp;
+  }
+  in_elems *= Lc;
+  out_elems *= Lc;
+  RT_CHECK(bytes == sizeof(h) + in_elems * 2, RWKVTTS_EINVAL, "adapter_load: blob size does not match its header");
+  // the first adapter: the tables k_lora reads (engines that never load one allocate nothing)
+  if (!d_lora_dev_) RT_OK(alloc(&d_lora_dev_, (size_t)RWKVTTS_MAX_ADAPTERS));
+  if (!d_lora_tiles_) RT_OK(alloc(&d_lora_tiles_, (size_t)kLoraTileHead + (size_t)lora_max_tiles(Rmax_) * kLoraTileInts));
+  // resident buffer: [Lc][6][2] element offsets (from the buffer's start, as bf16 elements), the packed
+  // matrices, one flag word. The raw matrices are staged in a buffer of their own for the pack kernels
+  // and freed before this returns.
+  const size_t offs_bytes = (size_t)Lc * 12 * sizeof(int64_t);
+  const size_t flag_off = align_up(offs_bytes + out_elems * 2, 16);
+  uint8_t *dev = nullptr, *stage = nullptr;
+  RT_HIP(hipMalloc((void**)&stage, in_elems * 2));
+  if (hipError_t me = hipMalloc((void**)&dev, flag_off + 16); me != hipSuccess) {
+    (void)hipFree(stage);
+    RT_HIP(me);
+  }
+  std::vector<int64_t> offs((size_t)Lc * 12, -1);
+  hipError_t e = hipMemsetAsync(dev + flag_off, 0, 16, stream_);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(stage, (const uint8_t*)blob + sizeof(h), in_elems * 2, hipMemcpyHostToDevice, stream_);
+  if (e == hipSuccess) {
+    const uint16_t* src = (const uint16_t*)stage;
+    uint16_t* base = (uint16_t*)dev;
+    int64_t at = (int64_t)(offs_bytes / 2);
+    int* flag = (int*)(dev + flag_off);
+    for (int l = 0; l < Lc; ++l)
+      for (int t = 0; t < 6; ++t) {
+        if (!(h.mask >> t & 1)) continue;
+        int N, K;
+        lora_target_shape(t, C, F, &N, &K);
+        offs[(l * 6 + t) * 2] = at;
+        launch_lora_pack(src, r, K, rp, K, base + at, flag, stream_);  // A [r][K] -> [rp][K]
+        src += (size_t)r * K;
+        at += (int64_t)rp * K;
+        offs[(l * 6 + t) * 2 + 1] = at;
+        launch_lora_pack(src, N, r, N, rp, base + at, flag, stream_);  // B [N][r] -> [N][rp]
+        src += (size_t)N * r;
+        at += (int64_t)N * rp;
+      }
+    e = hipGetLastError();
+  }
+  int bad = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(dev, offs.data(), offs_bytes, hipMemcpyHostToDevice, stream_);
+  if (e == hipSuccess) e = hipMemcpyAsync(&bad, dev + flag_off, sizeof(int), hipMemcpyDeviceToHost, stream_);
+  const LoraDev ld{(const bf16_t*)dev, (const int64_t*)dev, h.s, rp / 16};
+  if (e == hipSuccess) e = hipMemcpyAsync(d_lora_dev_ + id, &ld, sizeof(ld), hipMemcpyHostToDevice, stream_);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+  (void)hipFree(stage);
+  if (e != hipSuccess || bad) {
+    (void)hipFree(dev);
+    RT_HIP(e);
+    RT_CHECK(false, RWKVTTS_EINVAL, "adapter_load: non-finite value in a matrix");
+  }
+  adapters_[id] = {dev, r};
+  ++n_adapters_;
+  return RWKVTTS_OK;
+}
+
+int Engine::adapter_unload(int id) {
+  RT_HIP(hipSetDevice(device_));
+  RT_CHECK(adapter_live(id), RWKVTTS_EINVAL, "adapter_unload: the id is not live");
+  for (int s = 0; s < S_; ++s)
+    RT_CHECK(slot_adapter_[s] != id && slot_bound_[s] != id, RWKVTTS_EBUSY, "adapter_unload: a slot is bound to the adapter");
+  RT_HIP(hipStreamSynchronize(stream_));  // no step that read it is in flight
+  RT_HIP(hipFree(adapters_[id].dev));
+  adapters_[id] = Adapter{};
+  --n_adapters_;
+  return RWKVTTS_OK;
+}
+
+int Engine::slot_set_adapter(int slot, int id) {
+  RT_CHECK(slot >= 0 && slot < S_, RWKVTTS_EINVAL, "slot out of range");
+  RT_CHECK(id == -1 || adapter_live(id), RWKVTTS_EINVAL, "slot_set_adapter: the id is not live");
+  slot_adapter_[slot] = slot_bound_[slot] = id;
+  return RWKVTTS_OK;
+}
+
+// Rows in step order: a row joins its adapter's open tile, a full tile (16 rows) closes. So the prompt
+// rows of one request fill tiles 16 at a time, and decode rows of slots that share an adapter share a
+// tile. A row without an adapter is in no tile.
+int Engine::upload_lora_tiles(const StepPlan& p) {
+  lora_tiles_ = 0;
+  if (n_adapters_ == 0) return RWKVTTS_OK;
+  std::vector<int>& tb = lora_tiles_host_;
+  tb.assign(kLoraTileHead, 0);
+  int open[RWKVTTS_MAX_ADAPTERS];
+  std::fill(open, open + RWKVTTS_MAX_ADAPTERS, -1);
+  for (int r = 0; r < (int)p.rows.size(); ++r) {
+    const int ad = slot_adapter_[p.rows[r].x];
+    if (ad < 0) continue;
+    if (open[ad] < 0) {
+      open[ad] = lora_tiles_++;
+      tb.resize(tb.size() + kLoraTileInts, 0);
+      tb[kLoraTileHead + open[ad] * kLoraTileInts] = ad;
+    }
+    int* tile = tb.data() + kLoraTileHead + open[ad] * kLoraTileInts;
+    tile[4 + tile[1]++] = r;
+    if (tile[1] == 16) open[ad] = -1;
+  }
+  if (lora_tiles_ == 0) return RWKVTTS_OK;
+  RT_CHECK(lora_tiles_ <= lora_max_tiles(Rmax_), RWKVTTS_EHIP, "LoRA tile table overflow");
+  tb[0] = lora_tiles_;
+  RT_HIP(hipMemcpyAsync(d_lora_tiles_, tb.data(), tb.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
+  return RWKVTTS_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // forward step
 // ------------------------------------------------------------------------------------------
 __global__ void k_rows_parity(int4* rows, const int* slot_par, int R) {
@@ -614,6 +759,17 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
   // whole forward falls back.
   bool any_quant = false;
   for (const LayerW& lw : L_) any_quant = any_quant || lw.quant != 0;
+  // a step that carries adapter rows takes the separate launches, as a quantised engine does: k_lora
+  // follows each of the four base GEMM launches and adds into its slab 0 before anything reads it
+  const bool lora = lora_grid_ > 0;
+  any_quant = any_quant || lora;
+  LoraArgs la{};
+  la.tiles = d_lora_tiles_;
+  la.adapters = d_lora_dev_;
+  auto lora_launch = [&](const char* name, int layer, int target0, int n_targets, int N, int K, float* out, int ldo) {
+    la.layer = layer; la.target0 = target0; la.N = N; la.K = K; la.out = out; la.ldo = ldo;
+    timed(name, name, [&](unsigned long long* tl) { la.tl = tl; launch_lora(la, lora_grid_, n_targets, stream_); });
+  };
   // (every row count: with the 1-us weight-stream hold the persistent halves win at B = 1, 8 and 32,
   // profiles/r04h7_small_batch_ab.txt)
   bool use_att = att_persist_ && inplace && Lc >= 2 && !dbg_stamps_ && !any_quant && emb_fused;
@@ -783,8 +939,18 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
         prof_end("ln_mix_att", ev);
       }
       timed("gemm_rkv", "gemm_rkv_lora", [&](unsigned long long* tl) { g.tl = tl; launch_gemm(g, stream_); });
+      if (lora) {  // r, k, v: mix planes 0, 2, 3 -> columns [0, 3C) of the rkv launch's slab 0
+        la.xhi = xm_hi_; la.xlo = xm_lo_; la.ldx = C; la.x_mix_stride = RC; la.x_part = nullptr;
+        la.xmix[0] = 0; la.xmix[1] = 2; la.xmix[2] = 3; la.col_stride = C;
+        lora_launch("lora_rkv", l, 0, 3, C, C, partA_, ldA_);
+      }
       timed("wkv", "wkv", [&](unsigned long long* tl) { k.tl = tl; launch_wkv(k, n_seg, H_, stream_); });
       timed("gemm_wo", "gemm_wo", [&](unsigned long long* tl) { go.tl = tl; launch_gemm(go, stream_); });
+      if (lora) {
+        la.xhi = z_hi_; la.xlo = z_lo_; la.ldx = C; la.x_mix_stride = 0; la.x_part = nullptr;
+        la.xmix[0] = 0; la.col_stride = 0;
+        lora_launch("lora_wo", l, 3, 1, C, C, partO_, C);
+      }
     }
     GemmArgs gk{};
     gk.f16 = f16_;
@@ -833,6 +999,11 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
     if (!persisted) {
       timed("ln_ffn", "ln_mix_ffn", [&](unsigned long long* tl) { f.tl = tl; launch_ln_mix(f, R, stream_); });
       timed("gemm_key", "gemm_ffn_key", [&](unsigned long long* tl) { gk.tl = tl; launch_gemm(gk, stream_); });
+      if (lora) {  // before the relu^2 planes / the slab sum: both read slab 0 after it
+        la.xhi = xf_hi_; la.xlo = xf_lo_; la.ldx = C; la.x_mix_stride = 0; la.x_part = nullptr;
+        la.xmix[0] = 0; la.col_stride = 0;
+        lora_launch("lora_key", l, 4, 1, F, C, partK_, F);
+      }
       if (planes) launch_relu2_planes(partK_, splitK_, (int64_t)Rmax_ * F, F, F, R, xk_hi_, xk_lo_, stream_);
       if (presum) launch_sum_slabs(partK_, splitK_, (int64_t)Rmax_ * F, F, F, R, stream_);
       {  // (timed() spelled out, as ln_att: a refused launch returns before prof_end)
@@ -841,6 +1012,11 @@ int Engine::launch_forward(int R, int n_seg, int n_lg, int head_rows, bool tok_f
         prof_begin(&ev);
         RT_CHECK(launch_gemm(gv, stream_) >= 0, RWKVTTS_EUNSUPPORTED, "FFN value GEMM: no form for this key split");
         prof_end("gemm_ffn_value", ev);
+      }
+      if (lora) {  // x = relu(sum of the key slabs)^2 in registers: one slab once they are pre-summed
+        la.xhi = la.xlo = nullptr; la.col_stride = 0;
+        la.x_part = partK_; la.x_nsplit = presum ? 1 : splitK_; la.x_ld = F; la.x_part_stride = (int64_t)Rmax_ * F;
+        lora_launch("lora_value", l, 5, 1, C, F, partF_, C);
       }
     }
   }
@@ -914,7 +1090,7 @@ int Engine::upload_plan(const StepPlan& p) {
   }
   if (p.tok_from_ctrl)  // decode steps keep the parity fixed: set rows[].w once here
     hipLaunchKernelGGL(k_rows_parity, dim3((R + 255) / 256), dim3(256), 0, stream_, d_rows_, slot_par_, R);
-  return RWKVTTS_OK;
+  return upload_lora_tiles(p);
 }
 
 // Runs one forward step. Decode steps (tok_from_ctrl) replay a cached hipGraph.
@@ -944,7 +1120,13 @@ int Engine::run_step(const StepPlan& p, bool upload) {
   if (p.tok_from_ctrl && use_graphs_ && !profiling) {
     // one graph per (R, head_rows, kind, advance): kind < 4 and advance < 2 are the low three bits
     static_assert(kAdvTyp < 4, "a further AdvanceKind needs a wider graph key");
-    auto key = std::make_pair(R, p.head_rows * 8 + p.kind * 2 + (p.advance ? 1 : 0));
+    // a step that carries adapter rows: bit 30 on top, so every other step keeps the key it had
+    // (head_rows * 8 + 7 stays below it: checked here).
+    // Its k_lora grids cover every tiling R rows can have: the tile table is read from a fixed address,
+    // and regrouping at an admission recaptures nothing.
+    RT_CHECK(p.head_rows < (1 << 26), RWKVTTS_EINVAL, "head_rows too large for the graph key");
+    auto key = std::make_pair(R, p.head_rows * 8 + p.kind * 2 + (p.advance ? 1 : 0) + (lora_tiles_ > 0 ? 1 << 30 : 0));
+    lora_grid_ = lora_tiles_ > 0 ? lora_max_tiles(R) : 0;
     auto it = graphs_.find(key);
     if (it == graphs_.end()) {
       // the one-launch step's argument table is uploaded before the capture (no synchronous copy
@@ -970,6 +1152,7 @@ int Engine::run_step(const StepPlan& p, bool upload) {
     return RWKVTTS_OK;
   }
   last_graph_ = {-1, -1};
+  lora_grid_ = lora_tiles_;
   RT_OK(launch_forward(R, n_seg, n_lg, p.head_rows, p.tok_from_ctrl, p.advance, p.kind));
   return RWKVTTS_OK;
 }
@@ -1406,6 +1589,12 @@ int Engine::admit(ServeState& st, Job* j) {
     fail_job(st.src, j, RWKVTTS_EINVAL, 0);
     return RWKVTTS_OK;
   }
+  const int adapter = adapter_of(ext);
+  if (adapter != -1 && !adapter_live(adapter)) {  // an unknown adapter: this request fails alone too
+    set_error("request rejected: adapter " + std::to_string(adapter) + " is not loaded");
+    fail_job(st.src, j, RWKVTTS_EINVAL, 0);
+    return RWKVTTS_OK;
+  }
   if (pinned_without_tokens(q)) {  // nothing to decode: the given voice, no semantic tokens, no slot
     j->res->n_global = RWKVTTS_N_GLOBAL;
     memcpy(j->res->global_tokens, q.ref_global, sizeof(int32_t) * RWKVTTS_N_GLOBAL);
@@ -1432,6 +1621,9 @@ int Engine::admit(ServeState& st, Job* j) {
   memcpy(ad.ctrl.gkey, rg.key, 32);
   memcpy(ad.ctrl.skey, rs.key, 32);
   RT_OK(slot_reset(slot, false));  // ordered before the slot's first step on stream_
+  // every admission: -1 for a request without the field. The request's adapter covers the slot while
+  // the request holds it; rwkvtts_slot_set_adapter's binding (slot_bound_) is back once it retires.
+  slot_adapter_[slot] = adapter;
   // from per-slot host storage: admissions are not synchronised, so the source must outlive the
   // stream-ordered copy (the slot's entry is rewritten only after the slot retires)
   ctrl_stage_[slot] = ad.ctrl;
@@ -1615,6 +1807,7 @@ int Engine::finish_unit(const Unit& u, ServeState& st) {
     memcpy(r.global_tokens, c.global_out, sizeof(int32_t) * RWKVTTS_N_GLOBAL);
     r.n_semantic = c.n_sem;
     st.src.finish(act[i].job);
+    slot_adapter_[act[i].slot] = slot_bound_[act[i].slot];  // the caller's own binding again
     st.free_slots.push_back(act[i].slot);
     act.erase(act.begin() + i);
   }
@@ -1688,7 +1881,10 @@ int Engine::serve(JobSource& src) {
   }
   if (rc != RWKVTTS_OK) {
     for (Job* j : st.fresh) fail_job(src, j, rc, 0);  // the failing admission and the ones after it
-    for (auto& a : st.act) fail_job(src, a.job, rc, a.sink ? a.delivered : -1);
+    for (auto& a : st.act) {
+      slot_adapter_[a.slot] = slot_bound_[a.slot];
+      fail_job(src, a.job, rc, a.sink ? a.delivered : -1);
+    }
     return rc;
   }
   return dump_stamps();

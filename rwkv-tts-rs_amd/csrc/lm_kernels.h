@@ -302,6 +302,44 @@ void launch_mx_pack(const uint16_t* W, int N, int K, int qt, uint8_t* out, int* 
 int launch_gemm_mx(const GemmArgs& a, hipStream_t st);
 // rwkvtts_mx_roundtrip: host W [N][K] bf16 -> pack, unpack (k_gemm_mx's dequantisation) -> host out
 int mx_roundtrip(int qt, const uint16_t* w, int N, int K, uint16_t* out);
+// ---- per-request LoRA adapters (lora.hip) ----------------------------------------------------------
+// A resident adapter as k_lora reads it: every matrix in fragment order (launch_lora_pack) in one
+// buffer; offs[(layer * 6 + target) * 2] is A's element offset from base (-1: the adapter does not
+// carry the target) and [.. + 1] B's. Targets in the blob's order: r, k, v, o, FFN key, FFN value.
+struct LoraDev {
+  const bf16_t* base;
+  const int64_t* offs;
+  float s;   // alpha / rank
+  int rb;    // 16-wide blocks of the rank padded to the MFMA depth: 2 (ranks 16, 32) or 4 (48, 64)
+};
+constexpr int kLoraTileHead = 4;   // ints before tile 0 of a step's tile table ([0]: the tile count)
+constexpr int kLoraTileInts = 20;  // per tile: adapter, rows, -, -, row index x 16
+struct LoraArgs {
+  const int* tiles;         // the step's tile table
+  const LoraDev* adapters;  // [RWKVTTS_MAX_ADAPTERS]
+  int layer;
+  int target0;              // first target of the launch (blockIdx.z counts on from it)
+  int N, K;                 // one target's W is [N][K]; K % 128 == 0, N % 16 == 0
+  const bf16_t* xhi;        // X planes [rows][ldx]; target z reads mix plane xmix[z]
+  const bf16_t* xlo;
+  int ldx;
+  int xmix[3];
+  int64_t x_mix_stride;
+  const float* x_part;      // non-null (the value target): X = relu(sum of x_nsplit f32 slabs)^2
+  int x_nsplit;
+  int x_ld;
+  int64_t x_part_stride;
+  float* out;               // slab 0 of the base launch's output, [rows][ldo]
+  int ldo;
+  int col_stride;           // target z's first output column: z * col_stride
+  unsigned long long* tl;   // debug timeline slot (null in production)
+};
+// Adds every tiled row's delta into a.out; the grid covers n_tiles tiles (those past the table's count
+// exit) x n_targets targets. Returns the workgroup count.
+int launch_lora(const LoraArgs& a, int n_tiles, int n_targets, hipStream_t st);
+// W [N][K] bf16 -> zero-padded [Np][Kp] in fragment order; *nonfinite = 1 for an Inf or a NaN
+void launch_lora_pack(const uint16_t* W, int N, int K, int Np, int Kp, uint16_t* out, int* nonfinite, hipStream_t st);
+
 // Repack one layer's LoRA-up rows (0.4B ranks 64/64/32/128) into k_wkv6's coalesced order.
 void launch_pack_lora6(const bf16_t* w2t, const bf16_t* a2t, const bf16_t* v2t, const bf16_t* g2t, int C,
                        bf16_t* out, hipStream_t st);

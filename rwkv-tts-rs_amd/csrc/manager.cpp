@@ -93,6 +93,32 @@ auto hold_ext(J* j, const rwkvtts_request_ext* e, int) -> decltype(j->ext.hold(e
 template <typename J>
 void hold_ext(J*, const rwkvtts_request_ext*, long) {}
 
+// The same for the adapter calls and a job's adapter: a stand-in engine without adapters refuses the
+// calls with RWKVTTS_EUNSUPPORTED, and its jobs name none.
+template <typename E>
+auto eng_adapter_load(E& e, int id, const void* b, size_t n, int) -> decltype(e.adapter_load(id, b, n)) {
+  return e.adapter_load(id, b, n);
+}
+template <typename E>
+int eng_adapter_load(E&, int, const void*, size_t, long) { return RWKVTTS_EUNSUPPORTED; }
+template <typename E>
+auto eng_adapter_unload(E& e, int id, int) -> decltype(e.adapter_unload(id)) { return e.adapter_unload(id); }
+template <typename E>
+int eng_adapter_unload(E&, int, long) { return RWKVTTS_EUNSUPPORTED; }
+template <typename J>
+auto job_adapter(const J* j, int) -> decltype(adapter_of(j->ext.ptr())) { return adapter_of(j->ext.ptr()); }
+template <typename J>
+int job_adapter(const J*, long) { return -1; }
+
+// One adapter call for an engine's owner thread (Worker::next runs it between units of work)
+struct AdapterCall {
+  int id = 0;
+  const void* blob = nullptr;  // null: unload
+  size_t bytes = 0;
+  int rc = 1;                  // 1: not run yet
+  std::string err;
+};
+
 struct MJob : Job {
   uint64_t ticket = 0;
   std::vector<int32_t> text, props, ref_g, ref_s;  // owned copies of the request arrays
@@ -118,7 +144,25 @@ class Worker : public JobSource {
   Worker(Manager* m, int idx) : m_(m), idx_(idx) {}
   bool next(int max, bool wait, std::vector<Job*>& out) override {
     std::unique_lock<std::mutex> lk(mu_);
-    if (wait) cv_.wait(lk, [&] { return !inbox_.empty() || closing_; });
+    while (true) {
+      // adapter calls first: this is the owner thread, between two units of work
+      while (!calls_.empty()) {
+        AdapterCall* c = calls_.front();
+        calls_.pop_front();
+        bool queued = false;  // an unload while a job routed here and not admitted yet names the adapter
+        for (const MJob* j : inbox_) queued = queued || (!c->blob && job_adapter(static_cast<const Job*>(j), 0) == c->id);
+        lk.unlock();
+        int rc = RWKVTTS_EBUSY;
+        if (queued) set_error("adapter_unload: a queued request names the adapter");
+        else rc = c->blob ? eng_adapter_load(eng, c->id, c->blob, c->bytes, 0) : eng_adapter_unload(eng, c->id, 0);
+        lk.lock();
+        if (rc != RWKVTTS_OK) c->err = rwkvtts_last_error();
+        c->rc = rc;
+        call_cv_.notify_all();
+      }
+      if (!wait || !inbox_.empty() || closing_) break;
+      cv_.wait(lk);
+    }
     while (max > 0 && !inbox_.empty()) {
       out.push_back(inbox_.front());
       inbox_.pop_front();
@@ -146,6 +190,16 @@ class Worker : public JobSource {
     }
     cv_.notify_one();
   }
+  // Hands the call to the owner thread and returns once it has run (at the engine's next admission
+  // point: between two units of work, or at once when the engine idles).
+  int call(AdapterCall& c) {
+    std::unique_lock<std::mutex> lk(mu_);
+    if (closing_) return RWKVTTS_ECLOSED;
+    calls_.push_back(&c);
+    cv_.notify_one();
+    call_cv_.wait(lk, [&] { return c.rc != 1; });
+    return c.rc;
+  }
   void run(rwkvtts_engine_desc desc, const void* w, size_t bytes);
 
   Engine eng;
@@ -163,6 +217,8 @@ class Worker : public JobSource {
   std::mutex mu_;
   std::condition_variable cv_;
   std::deque<MJob*> inbox_;
+  std::deque<AdapterCall*> calls_;
+  std::condition_variable call_cv_;
   bool closing_ = false;
 };
 
@@ -415,6 +471,38 @@ class Manager {
       queue_.push_back(j);
     }
     q_cv_.notify_one();
+    return RWKVTTS_OK;
+  }
+
+  // Every engine's owner thread performs the call between units; returns when all have done it, with
+  // the first failure. blob == null: unload, refused while a request that is still queued names the id.
+  int adapter_call(int id, const void* blob, size_t bytes) {
+    if (!blob) {
+      std::lock_guard<std::mutex> lk(q_mu_);
+      for (const MJob* j : queue_)
+        RT_CHECK(job_adapter(static_cast<const Job*>(j), 0) != id, RWKVTTS_EBUSY,
+                 "adapter_unload: a queued request names the adapter");
+    }
+    std::vector<AdapterCall> calls(workers_.size());
+    std::vector<std::thread> th;
+    for (size_t i = 0; i < workers_.size(); ++i) {
+      calls[i].id = id;
+      calls[i].blob = blob;
+      calls[i].bytes = bytes;
+      Worker* wk = workers_[i].get();
+      if (wk->init_rc != RWKVTTS_OK || wk->dead) {
+        calls[i].rc = RWKVTTS_OK;  // (an engine that serves nothing)
+        continue;
+      }
+      AdapterCall* c = &calls[i];
+      th.emplace_back([wk, c] { c->rc = wk->call(*c); });
+    }
+    for (auto& t : th) t.join();
+    for (const AdapterCall& c : calls)
+      if (c.rc != RWKVTTS_OK) {
+        set_error(c.err.empty() ? "manager adapter call failed" : c.err);
+        return c.rc;
+      }
     return RWKVTTS_OK;
   }
 
@@ -766,6 +854,26 @@ int rwkvtts_manager_generate_batch(rwkvtts_manager* m, const rwkvtts_request* re
     if (rc != RWKVTTS_OK) return rc;
   }
   return RWKVTTS_OK;
+}
+
+int rwkvtts_manager_adapter_load(rwkvtts_manager* m, int id, const void* blob, size_t bytes) {
+  RT_CHECK(m && blob, RWKVTTS_EINVAL, "manager_adapter_load: null argument");
+  try {
+    return m->m.adapter_call(id, blob, bytes);
+  } catch (const std::exception& ex) {
+    set_error(ex.what());
+    return RWKVTTS_ENOMEM;
+  }
+}
+
+int rwkvtts_manager_adapter_unload(rwkvtts_manager* m, int id) {
+  RT_CHECK(m, RWKVTTS_EINVAL, "manager_adapter_unload: null argument");
+  try {
+    return m->m.adapter_call(id, nullptr, 0);
+  } catch (const std::exception& ex) {
+    set_error(ex.what());
+    return RWKVTTS_ENOMEM;
+  }
 }
 
 int rwkvtts_manager_get_stats(rwkvtts_manager* m, rwkvtts_manager_stats* out) {

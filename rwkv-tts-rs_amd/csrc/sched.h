@@ -65,21 +65,22 @@ inline bool is_pinned(const rwkvtts_request& q) { return q.pinned_voice != 0; }
 // The extension block as a job carries it, by value: the first min(struct_size, sizeof) bytes of
 // the caller's block, the rest zero, struct_size still the caller's (validate judges it), and
 // whether there was a block at all.
-// The storage is the longest block the library knows (rwkvtts_request_ext_v2, whose first 16 bytes
-// are rwkvtts_request_ext's); `ext` names those first bytes.
+// The storage is the longest block the library knows (rwkvtts_request_ext_v3, whose first bytes are
+// rwkvtts_request_ext_v2's, whose first 16 are rwkvtts_request_ext's); `ext` names those first bytes.
 struct HeldExt {
   union {
     rwkvtts_request_ext ext;
-    rwkvtts_request_ext_v2 v2{};
+    rwkvtts_request_ext_v2 v2;
+    rwkvtts_request_ext_v3 v3{};
   };
   bool present = false;
   void hold(const rwkvtts_request_ext* e) {
-    memset(&v2, 0, sizeof(v2));
+    memset(&v3, 0, sizeof(v3));
     present = e != nullptr;
     if (e) {
       uint32_t sz = 0;
       memcpy(&sz, e, sizeof(sz));
-      memcpy(&v2, e, std::min<size_t>(std::max<size_t>(sz, sizeof(sz)), sizeof(v2)));
+      memcpy(&v3, e, std::min<size_t>(std::max<size_t>(sz, sizeof(sz)), sizeof(v3)));
     }
   }
   const rwkvtts_request_ext* ptr() const { return present ? &ext : nullptr; }
@@ -98,6 +99,11 @@ inline const rwkvtts_request_ext_v2* ext_v2(const rwkvtts_request_ext* ext) {
 inline bool has_typical(const rwkvtts_request_ext* ext) {
   const rwkvtts_request_ext_v2* v = ext_v2(ext);
   return v && (v->typical_set & RWKVTTS_TYPICAL_SET);
+}
+// the request's adapter: rwkvtts_request_ext_v3::adapter where the caller's struct_size covers it, else -1
+inline int adapter_of(const rwkvtts_request_ext* ext) {
+  if (!ext || ext->struct_size < offsetof(rwkvtts_request_ext_v3, adapter) + sizeof(int32_t)) return -1;
+  return ((const rwkvtts_request_ext_v3*)ext)->adapter;
 }
 
 // The ranges of the three sampling options, for validate and the k_advance test hook

@@ -125,6 +125,15 @@ class RequestExtV2(ctypes.Structure):
     _fields_ = RequestExt._fields_ + [("typical_set", ctypes.c_int32), ("typical", TypicalParams)]
 
 
+class RequestExtV3(ctypes.Structure):
+    """rwkvtts_request_ext_v3: RequestExtV2's bytes, then the request's adapter id (-1: none)."""
+    _fields_ = RequestExtV2._fields_ + [("adapter", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+MAX_ADAPTERS = 64
+ADAPTER_MAGIC = 0x41524F4C
+
+
 class Request(ctypes.Structure):
     _fields_ = [("text_tokens", ctypes.POINTER(ctypes.c_int32)), ("n_text", ctypes.c_int32),
                 ("property_tokens", ctypes.POINTER(ctypes.c_int32)), ("n_property", ctypes.c_int32),
@@ -329,6 +338,11 @@ EXPORTS = {
     "rwkvtts_engine_dims": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Dims)]),
     "rwkvtts_state_floats": (ctypes.c_int64, [ctypes.c_void_p]),
     "rwkvtts_slot_reset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "rwkvtts_engine_adapter_load": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t]),
+    "rwkvtts_engine_adapter_unload": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "rwkvtts_slot_set_adapter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    "rwkvtts_manager_adapter_load": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t]),
+    "rwkvtts_manager_adapter_unload": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "rwkvtts_slot_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "rwkvtts_slot_write": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "rwkvtts_infer": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.c_int, ctypes.c_int,

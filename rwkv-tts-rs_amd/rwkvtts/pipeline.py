@@ -112,6 +112,10 @@ class LightweightTtsPipelineArgs:  # :18-65 (Default)
     # normal-mode request whose 32 global tokens are those (rwkvtts_request.pinned_voice): the same
     # voice again, still with its property tokens. Without it that combination ignores the tokens.
     pin_voice: bool = False
+    # no reference counterpart: the name of the LoRA adapter the request decodes with
+    # (DynamicBatchManager.load_adapter; None: the base model), in all five entry points; long form
+    # gives every segment the job's adapter
+    adapter: Optional[str] = None
 
 
 def check_voice_pin(args) -> None:
@@ -477,8 +481,11 @@ class LightweightTtsPipeline:
                             global_sampling=args.global_sampling, semantic_sampling=args.semantic_sampling,
                             penalties=args.penalties, mirostat=args.mirostat,
                             typical=args.typical)
-        return TtsBatchRequest(self.manager._tokens(text), props, rg, rs, sargs, args.voice_id,
-                               pinned_voice=rg is not None and rs is None)
+        req = TtsBatchRequest(self.manager._tokens(text), props, rg, rs, sargs, args.voice_id,
+                              pinned_voice=rg is not None and rs is None)
+        if args.adapter is not None:  # (without it the request is the one it always was)
+            req.adapter = args.adapter
+        return req
 
     def generate_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
                         tempo: Optional[float] = None, loudness: Optional[float] = None,

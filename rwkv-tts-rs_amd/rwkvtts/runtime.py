@@ -17,7 +17,7 @@ import ctypes
 import dataclasses
 import math
 import threading
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Union
 
 import numpy as np
 
@@ -128,16 +128,26 @@ def request_struct(r: "TtsBatchRequest"):
     return q, keep
 
 
-def request_ext(r: "TtsBatchRequest"):
+def request_ext(r: "TtsBatchRequest", adapter_ids=None):
     """-> the request's _ffi.RequestExt (rwkvtts_request_ext), or None when it asks for nothing
-    beyond _ffi.Request: such a request goes through the entry points without a block."""
+    beyond _ffi.Request: such a request goes through the entry points without a block.
+    adapter_ids: name -> id (DynamicBatchManager.adapters), for a request that names its adapter;
+    a name that is not there raises ValueError."""
     miro = getattr(r.args, "mirostat", None)
     typ = getattr(r.args, "typical", None)
-    if miro is None and typ is None:
+    adapter = getattr(r, "adapter", None)
+    if miro is None and typ is None and adapter is None:
         return None
-    # the 16-byte block unless typical sampling is asked for: then the longer one (_ffi.RequestExtV2)
-    x = _ffi.RequestExt() if typ is None else _ffi.RequestExtV2()
+    # the shortest block that holds what is asked for: 16 bytes, _ffi.RequestExtV2 with typical
+    # sampling, _ffi.RequestExtV3 with an adapter
+    x = _ffi.RequestExtV3() if adapter is not None else _ffi.RequestExt() if typ is None else _ffi.RequestExtV2()
     x.struct_size = ctypes.sizeof(x)
+    if adapter is not None:
+        if isinstance(adapter, str):
+            if adapter not in (adapter_ids or {}):
+                raise ValueError(f"unknown adapter: {adapter}")
+            adapter = adapter_ids[adapter]
+        x.adapter = int(adapter)
     if miro is not None:
         x.mirostat_set = _ffi.MIROSTAT_SET
         x.mirostat.tau = float(miro.tau)
@@ -278,6 +288,25 @@ class SharedRwkvRuntime:
     def write_slot(self, slot: int, state: np.ndarray):
         s = np.ascontiguousarray(state, dtype=np.float32)
         check(lib().rwkvtts_slot_write(self._h, slot, s.ctypes.data_as(ctypes.c_void_p)), "slot_write")
+
+    # ---- adapters (rwkvtts.h "adapters"; weights.pack_adapter builds the blob) ----
+    @_locked
+    def load_adapter(self, adapter_id: int, blob: np.ndarray):
+        """Makes a LoRA adapter resident under `adapter_id` (0 .. 63, not live)."""
+        b = np.ascontiguousarray(blob, dtype=np.uint8)
+        check(lib().rwkvtts_engine_adapter_load(self._h, int(adapter_id), b.ctypes.data_as(ctypes.c_void_p), b.nbytes),
+              "adapter_load")
+
+    @_locked
+    def unload_adapter(self, adapter_id: int):
+        """EBUSY while a slot is bound to it."""
+        check(lib().rwkvtts_engine_adapter_unload(self._h, int(adapter_id)), "adapter_unload")
+
+    @_locked
+    def set_slot_adapter(self, slot: int, adapter_id: Optional[int]):
+        """Binds a state slot to a resident adapter (None or -1: none) until it is set again; infer honours it."""
+        check(lib().rwkvtts_slot_set_adapter(self._h, int(slot), -1 if adapter_id is None else int(adapter_id)),
+              "slot_set_adapter")
 
     # ---- Runtime<Rnn>::infer ----
     @_locked
@@ -607,6 +636,10 @@ class TtsBatchRequest:  # src/rwkv_sampler.rs:222-231 (text already tokenised)
     # no reference counterpart (rwkvtts.h rwkvtts_request.pinned_voice): a normal-mode request whose
     # 32 global tokens are ref_global_tokens (ref_semantic_tokens None); the property tokens are kept
     pinned_voice: bool = False
+    # no reference counterpart (rwkvtts.h rwkvtts_request_ext_v3.adapter): the LoRA adapter the request
+    # decodes with (None: the base model) -- a resident id (SharedRwkvRuntime.load_adapter), or on a
+    # DynamicBatchManager the name it was loaded under
+    adapter: Optional[Union[int, str]] = None
 
 
 @dataclasses.dataclass
@@ -659,6 +692,7 @@ class DynamicBatchManager:
         # refuses new ones and waits until every call still in flight is a waiter the native
         # manager has registered (those return inside destroy, before the handle is freed)
         self._gate = threading.Condition()
+        self.adapters = {}  # name -> id of the loaded LoRA adapters (load_adapter)
         self._inflight = 0
         self._closing = False
 
@@ -724,7 +758,7 @@ class DynamicBatchManager:
         t = ctypes.c_uint64()
         self._enter()
         try:
-            ext = request_ext(request)
+            ext = request_ext(request, self.adapters)
             if ext is None:
                 fn = lib().rwkvtts_manager_submit_stream if stream else lib().rwkvtts_manager_submit
                 check(fn(self._h, ctypes.byref(q), ctypes.byref(t)), "manager_submit")
@@ -735,6 +769,33 @@ class DynamicBatchManager:
         finally:
             self._leave()
         return int(t.value)
+
+    def load_adapter(self, name: str, blob: np.ndarray):
+        """Makes a LoRA adapter (weights.pack_adapter) resident on every engine under `name`; requests
+        name it with TtsBatchRequest.adapter. ValueError for a name that is loaded or when 64 are."""
+        b = np.ascontiguousarray(blob, dtype=np.uint8)
+        with self._gate:
+            free = sorted(set(range(_ffi.MAX_ADAPTERS)) - set(self.adapters.values()))
+            if name in self.adapters or not free:
+                raise ValueError(f"adapter {name!r} is loaded already" if name in self.adapters else "64 adapters are loaded")
+        self._enter()
+        try:
+            check(lib().rwkvtts_manager_adapter_load(self._h, free[0], b.ctypes.data_as(ctypes.c_void_p), b.nbytes),
+                  "manager_adapter_load")
+        finally:
+            self._leave()
+        self.adapters[name] = free[0]
+
+    def unload_adapter(self, name: str):
+        """EBUSY (RwkvTtsError) while a request that is queued or decoding names the adapter."""
+        if name not in self.adapters:
+            raise ValueError(f"unknown adapter: {name}")
+        self._enter()
+        try:
+            check(lib().rwkvtts_manager_adapter_unload(self._h, self.adapters[name]), "manager_adapter_unload")
+        finally:
+            self._leave()
+        del self.adapters[name]
 
     def wait_tokens(self, ticket: int, have_semantic: int = 0, timeout_ms: int = -1):
         """Blocks until more than have_semantic semantic tokens of the request are known or it is

@@ -86,6 +86,10 @@
   other stage; with `long_form` per segment, before the join, whose own pauses stay. On the stream
   route a request that is all leading silence so far sends nothing yet. Without the field the routes
   are unchanged.
+* `adapter` in the body of both TTS routes (no reference counterpart): the name of a LoRA adapter the
+  pipeline's manager has loaded (`DynamicBatchManager.load_adapter`); the request decodes with it, with
+  `long_form` every segment. Anything but a non-empty string, or a name that is not loaded, is a 400.
+  Without the field the routes are unchanged.
 * `handle_watermark_detect(path, pipeline)`, POST /api/watermark/detect (no reference counterpart): an
   uploaded WAV at any supported rate, brought to 16 kHz by `load_audio(..., device=)` without volume
   normalisation, read back under the pipeline's key -> {detected, score, threshold, payload,
@@ -341,6 +345,11 @@ def _tts_args(body, voice_dir: str):
             sampling["typical"] = Typical(**{k: v for k, v in typ.items() if v is not None}).check()
         except ValueError as e:
             return (400, {"success": False, "error": f"不支持的 Typical 参数: {e}"}), None, None
+    adapter = body.get("adapter")  # (whether the name is loaded is the manager's to say: _no_adapter)
+    if adapter is not None:
+        if not isinstance(adapter, str) or not adapter:
+            return (400, {"success": False, "error": f"不支持的适配器: {adapter} (需要已加载适配器的名称)"}), None, None
+        sampling["adapter"] = adapter
     long_form = body.get("long_form")
     if long_form is not None and not isinstance(long_form, bool):
         return (400, {"success": False, "error": f"不支持的长文本开关: {long_form} (支持: true, false)"}), None, None
@@ -411,10 +420,18 @@ def _no_key(kw, pipeline):
     return None
 
 
+def _no_adapter(args, pipeline):
+    """The 400 of an `adapter` whose name the pipeline's manager has not loaded, else None."""
+    name = getattr(args, "adapter", None)
+    if name is not None and name not in getattr(getattr(pipeline, "manager", None), "adapters", {}):
+        return 400, {"success": False, "error": f"适配器 '{name}' 未加载"}
+    return None
+
+
 def handle_tts_json(body, pipeline, voice_dir: str = "assets/raf") -> Tuple[int, dict]:
     t0 = time.perf_counter()
     err, args, kw = _tts_args(body, voice_dir)
-    err = err or _no_key(kw, pipeline)
+    err = err or _no_key(kw, pipeline) or _no_adapter(args, pipeline)
     if err:
         return err
     rate = kw.get("sample_rate", 16000)
@@ -479,7 +496,7 @@ def handle_tts_stream(body, pipeline, voice_dir: str = "assets/raf", chunk_frame
     A refused body gives /api/tts's status and JSON body (as one bytes item); so does a failure
     before the first chunk (500). A failure after the first chunk can only end the stream."""
     err, args, kw = _tts_args(body, voice_dir)
-    err = err or _no_key(kw, pipeline)
+    err = err or _no_key(kw, pipeline) or _no_adapter(args, pipeline)
     if err:
         return err[0], iter([json.dumps(err[1], ensure_ascii=False).encode("utf-8")])
     rate = kw.get("sample_rate", 16000)

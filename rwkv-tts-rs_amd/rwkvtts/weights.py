@@ -214,3 +214,48 @@ def pack_checkpoint(sd, d, dtype=_ffi.DTYPE_BF16):
         else:
             buf[off:off + 4 * r * c] = a.reshape(-1).view(np.uint8)
     return buf
+
+
+# ---------------- LoRA adapters (rwkvtts.h "adapters") ----------------
+ADAPTER_TARGETS = ("att.receptance", "att.key", "att.value", "att.output", "ffn.key", "ffn.value")
+ADAPTER_RANKS = (16, 32, 48, 64)
+
+
+def adapter_target_shape(d, t):
+    """(N, K) of target t's base matrix W [N][K]."""
+    C, F = d["n_embd"], d["n_ffn"]
+    return (F if t == 4 else C), (F if t == 5 else C)
+
+
+def pack_adapter(sd, d, alpha):
+    """Pack a LoRA state dict (numpy arrays `blocks.{l}.{att.receptance|att.key|att.value|att.output|
+    ffn.key|ffn.value}.lora_A` [r][K] and `.lora_B` [N][r]) into an adapter blob: the 64-byte header
+    (magic, version, n_layer, n_embd, n_ffn, rank, mask, s = alpha / r), then layer-major the carried
+    targets' A and B as row-major bf16 bits. A target missing from the dict clears its mask bit; a
+    target is carried by every layer or by none, and all share one rank."""
+    L = d["n_layer"]
+    have = [f"blocks.0.{n}.lora_A" in sd for n in ADAPTER_TARGETS]
+    if not any(have):
+        raise ValueError("pack_adapter: the state dict holds no lora_A / lora_B pair")
+    rank = None
+    parts = []
+    for layer in range(L):
+        for t, name in enumerate(ADAPTER_TARGETS):
+            ka, kb = f"blocks.{layer}.{name}.lora_A", f"blocks.{layer}.{name}.lora_B"
+            if (ka in sd) != have[t] or (kb in sd) != have[t]:
+                raise ValueError(f"pack_adapter: target {name} must be in every layer, A and B, or in none")
+            if not have[t]:
+                continue
+            a, b = np.asarray(sd[ka], dtype=np.float32), np.asarray(sd[kb], dtype=np.float32)
+            N, K = adapter_target_shape(d, t)
+            rank = a.shape[0] if rank is None else rank
+            if a.shape != (rank, K) or b.shape != (N, rank):
+                raise ValueError(f"pack_adapter: {ka} / {kb} have shapes {a.shape} / {b.shape}, "
+                                 f"expected ({rank}, {K}) / ({N}, {rank})")
+            parts += [f32_to_bf16_bits(a).reshape(-1), f32_to_bf16_bits(b).reshape(-1)]
+    if rank not in ADAPTER_RANKS:
+        raise ValueError(f"pack_adapter: rank {rank} is not one of {ADAPTER_RANKS}")
+    hdr = np.zeros(16, dtype=np.uint32)
+    hdr[:7] = [_ffi.ADAPTER_MAGIC, 1, L, d["n_embd"], d["n_ffn"], rank, sum(1 << t for t in range(6) if have[t])]
+    hdr[7:8] = np.array([alpha / rank], dtype=np.float32).view(np.uint32)
+    return np.concatenate([hdr.view(np.uint8), np.concatenate(parts).view(np.uint8)])
