@@ -209,6 +209,18 @@ typedef struct {
  * dequantisation into out_bf16 [N][K] (host): the dequantised weights w. type: RWKVTTS_QUANT_MXFP8 /
  * MXFP4. RWKVTTS_EINVAL for a non-finite weight (step 5) or bad arguments. */
 int rwkvtts_mx_roundtrip(int type, const uint16_t* w_bf16, int N, int K, uint16_t* out_bf16);
+/* Debug: RWKVTTS_QUANT_INT8 / NF4 on the device apart from the GEMM. w [N][K] (host, row-major bit
+ * patterns of `dtype`, RWKVTTS_DTYPE_*; N % 16 == 0, K % 128 == 0) is packed by the engine's pack
+ * kernel and unpacked through the GEMM's own dequantisation into out [N][K] (host, f32): the weights
+ * the quantised launches multiply by, before an f16 engine's shift and the hi / lo split. Every step
+ * is one f32 operation rounded once, f16(.) to nearest even:
+ *   Int8, per 128 elements of a row: mn = f16(min x), mx = f16(max x), d = mx - mn;
+ *     q = floor(fma(clamp((x - mn) / d, 0, 1), 255, 0.5)), 0 when mx == mn;
+ *     w = fma(q, d / 255, mn).
+ *   NF4, per 64 elements: s = f16(max |x|); q = #{i < 15 : x / s > (t[i] + t[i+1]) / 2}, 7 when
+ *     s == 0; w = t[q] * s, t the NormalFloat-4 table.
+ * No w is ever -0. RWKVTTS_EINVAL for another type or dtype, or bad arguments. */
+int rwkvtts_quant_roundtrip(int type, int dtype, const uint16_t* w, int N, int K, float* out);
 
 /* weights: packed blob (header included). blob_on_device != 0: `weights` is a device pointer
  * on desc->device (e.g. a buffer filled by an RCCL broadcast); it is copied. */

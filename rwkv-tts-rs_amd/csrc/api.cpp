@@ -82,6 +82,10 @@ int rwkvtts_mx_roundtrip(int type, const uint16_t* w_bf16, int N, int K, uint16_
   GUARD({ return mx_roundtrip(type, w_bf16, N, K, out_bf16); })
 }
 
+int rwkvtts_quant_roundtrip(int type, int dtype, const uint16_t* w, int N, int K, float* out) {
+  GUARD({ return quant_roundtrip(type, dtype, w, N, K, out); })
+}
+
 int rwkvtts_engine_destroy(rwkvtts_engine* e) {
   if (e) {
     std::lock_guard<std::mutex> lk(e->mu);  // wait for a call still running on another thread

@@ -294,6 +294,8 @@ inline size_t quant_scale_bytes(int qt, int N, int K) {
   return qt == 1 ? (size_t)N * (K / kQ8Block) * 4 : (size_t)N * (K / kQ4Block) * 2;
 }
 void launch_quant_pack(const uint16_t* W, int N, int K, int f16, int qt, uint8_t* codes, void* scales, hipStream_t st);
+// rwkvtts_quant_roundtrip: host W [N][K] 16-bit -> k_quant_pack, unpack (gemm2_body's dequantisation) -> host out f32
+int quant_roundtrip(int qt, int dtype, const uint16_t* w, int N, int K, float* out);
 // W [N][K] bf16 -> the packed MX matrix; *nonfinite is set to 1 if W holds an Inf or a NaN
 void launch_mx_pack(const uint16_t* W, int N, int K, int qt, uint8_t* out, int* nonfinite, hipStream_t st);
 // launch_gemm's form for GemmArgs::q_fmt MXFP8 / MXFP4 (k_gemm_mx; bf16 models, K-slices of 128 / 256):

@@ -31,6 +31,26 @@ __device__ __constant__ float kNF4[16] = {
     -0.18477343022823334f, -0.09105003625154495f, 0.0f, 0.07958029955625534f, 0.16093020141124725f,
     0.24611230194568634f, 0.33791524171829224f, 0.44070982933044434f, 0.5626170039176941f,
     0.7229568362236023f, 1.0f};
+// The dequantisation of RWKVTTS_QUANT_INT8 (qf 1) / NF4 (qf 2), one lane's 8 weights of a K-step: the 8
+// codes (c8: one byte each; c4: one nibble each, low first), the step's scale word (Int8: f16 min |
+// f16 max << 16; NF4: f16 absmax) and the NF4 code table. w: the weights before the f16 shift and the
+// hi / lo split. gemm2_body's QW forms and k_quant_unpack (rwkvtts_quant_roundtrip) both call it.
+__device__ __forceinline__ void quant_dequant8(int qf, uint2 c8, uint32_t c4, uint32_t scale, const float* lut,
+                                               float (&w)[8]) {
+  if (qf == 1) {
+    const float mn = h16_to_f32((uint16_t)(scale & 0xFFFFu)), mx = h16_to_f32((uint16_t)(scale >> 16));
+    const float step = (mx - mn) / 255.0f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const uint32_t q = ((e < 4 ? c8.x : c8.y) >> (8 * (e & 3))) & 255u;
+      w[e] = fmaf((float)q, step, mn);
+    }
+  } else {
+    const float sc = h16_to_f32((uint16_t)scale);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) w[e] = lut[(c4 >> (4 * e)) & 15u] * sc;
+  }
+}
 
 template <int CTRL>
 __device__ inline float dpp_mov(float v) {
@@ -1025,19 +1045,7 @@ __device__ __attribute__((always_inline)) void gemm2_body(const GA& a, const int
 #pragma unroll
       for (int t = 0; t < KSTEPS; ++t) {
         float w[8];
-        if (qf == 1) {
-          const float mn = h16_to_f32((uint16_t)(qsc[t] & 0xFFFFu)), mx = h16_to_f32((uint16_t)(qsc[t] >> 16));
-          const float step = (mx - mn) / 255.0f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const uint32_t q = ((e < 4 ? bq8[t].x : bq8[t].y) >> (8 * (e & 3))) & 255u;
-            w[e] = fmaf((float)q, step, mn);
-          }
-        } else {
-          const float sc = h16_to_f32((uint16_t)qsc[t]);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) w[e] = s_qlut[(bq4[t] >> (4 * e)) & 15u] * sc;
-        }
+        quant_dequant8(qf, bq8[t], bq4[t], qsc[t], s_qlut, w);
         if constexpr (F16) {
           const float up = __builtin_amdgcn_ldexpf(1.0f, a.q_shift);
 #pragma unroll
@@ -1977,6 +1985,62 @@ void launch_quant_pack(const uint16_t* W, int N, int K, int f16, int qt, uint8_t
   const dim3 grid((unsigned)((n + 255) / 256));
   if (qt == 1) hipLaunchKernelGGL(k_quant_pack<1>, grid, dim3(256), 0, st, W, N, K, f16, codes, scales);
   else hipLaunchKernelGGL(k_quant_pack<2>, grid, dim3(256), 0, st, W, N, K, f16, codes, scales);
+}
+
+// quant_unpack: codes + scales (k_quant_pack's layout) -> row-major f32 [N][K], one thread per lane of a
+// (16-column tile, 32-deep K-step) fragment: its 8 codes and scale word exactly as gemm2_body's load_w
+// fetches them, through the GEMM's quant_dequant8. N % 16 == 0, K % 128 == 0.
+__global__ __launch_bounds__(256) void k_quant_unpack(const uint8_t* codes, const void* scales, int N, int K, int qt,
+                                                      float* out) {
+  __shared__ float s_qlut[16];
+  if (threadIdx.x < 16) s_qlut[threadIdx.x] = kNF4[threadIdx.x];
+  __syncthreads();
+  const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= (int64_t)N * (K / 8)) return;
+  const int lane = (int)(id & 63), li = lane & 15, g = lane >> 4;
+  const int64_t frag = id >> 6;
+  const int kb = (int)(frag % (K >> 5)), nb = (int)(frag / (K >> 5));
+  const int n = nb * 16 + li, k0 = kb * 32 + g * 8;
+  uint2 c8 = make_uint2(0u, 0u);
+  uint32_t c4 = 0, sc;
+  if (qt == 1) {
+    c8 = *(const uint2*)(codes + id * 8);
+    sc = ((const uint32_t*)scales)[(int64_t)n * (K / kQ8Block) + k0 / kQ8Block];
+  } else {
+    c4 = *(const uint32_t*)(codes + id * 4);
+    sc = ((const uint16_t*)scales)[(int64_t)n * (K / kQ4Block) + k0 / kQ4Block];
+  }
+  float w[8];
+  quant_dequant8(qt, c8, c4, sc, s_qlut, w);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) out[(int64_t)n * K + k0 + e] = w[e];
+}
+
+// rwkvtts_quant_roundtrip (include/rwkvtts.h): pack and unpack on the device
+int quant_roundtrip(int qt, int dtype, const uint16_t* w, int N, int K, float* out) {
+  RT_CHECK(qt == RWKVTTS_QUANT_INT8 || qt == RWKVTTS_QUANT_NF4, RWKVTTS_EINVAL, "quant_roundtrip: type must be int8 or nf4");
+  RT_CHECK(dtype == RWKVTTS_DTYPE_BF16 || dtype == RWKVTTS_DTYPE_F16, RWKVTTS_EINVAL, "quant_roundtrip: unknown dtype");
+  RT_CHECK(w && out && N > 0 && K > 0 && N % 16 == 0 && K % 128 == 0, RWKVTTS_EINVAL,
+           "quant_roundtrip: N must be a multiple of 16 and K of 128");
+  const size_t wb = (size_t)N * K * 2, ob = (size_t)N * K * 4;
+  const size_t cb = quant_code_bytes(qt, N, K), sb = quant_scale_bytes(qt, N, K);  // multiples of 16 bytes
+  uint8_t* d = nullptr;
+  RT_HIP(hipMalloc(&d, ob + wb + cb + sb));
+  float* dout = (float*)d;
+  uint16_t* dw = (uint16_t*)(d + ob);
+  uint8_t* dc = d + ob + wb;
+  uint8_t* ds = dc + cb;
+  hipError_t e = hipMemcpy(dw, w, wb, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    launch_quant_pack(dw, N, K, dtype == RWKVTTS_DTYPE_F16, qt, dc, ds, nullptr);
+    const dim3 grid((unsigned)(((int64_t)N * (K / 8) + 255) / 256));
+    hipLaunchKernelGGL(k_quant_unpack, grid, dim3(256), 0, nullptr, dc, (const void*)ds, N, K, qt, dout);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  RT_HIP(e);
+  return RWKVTTS_OK;
 }
 
 __global__ void k_pack_lora(const bf16_t* w2t, const bf16_t* a2t, const bf16_t* v2t, const bf16_t* g2t, int C,

@@ -549,6 +549,8 @@ EXPORTS = {
     "rwkvtts_pause_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PauseWindow), ctypes.c_int]),
     "rwkvtts_pause_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
     "rwkvtts_mx_roundtrip": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "rwkvtts_quant_roundtrip": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_void_p]),
 }
 
 _lib = None

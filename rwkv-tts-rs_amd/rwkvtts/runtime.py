@@ -214,6 +214,19 @@ def mx_roundtrip(quant_type, w_bf16: np.ndarray) -> np.ndarray:
     return out
 
 
+def quant_roundtrip(quant_type, dtype: int, w: np.ndarray) -> np.ndarray:
+    """Debug: [N][K] 16-bit patterns (uint16) of `dtype` (_ffi.DTYPE_*) -> the Int8 / NF4 dequantised
+    weights as float32, through the engine's pack kernel and the GEMM's dequantisation
+    (rwkvtts_quant_roundtrip)."""
+    w = np.ascontiguousarray(w, dtype=np.uint16)
+    if w.ndim != 2:
+        raise _ffi.RwkvTtsError(_ffi.EINVAL, "quant_roundtrip: w must be [N][K]")
+    out = np.empty(w.shape, dtype=np.float32)
+    _ffi.check(_ffi.lib().rwkvtts_quant_roundtrip(parse_quant_type(quant_type), int(dtype), w.ctypes.data, w.shape[0],
+                                                  w.shape[1], out.ctypes.data), "quant_roundtrip")
+    return out
+
+
 def quant_config(quant_layers: int, quant_type) -> tuple:
     """bin/server.rs:1059-1071 (create_quant_config): layers [0, quant_layers) quantised, or none."""
     t = parse_quant_type(quant_type)

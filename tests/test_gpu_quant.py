@@ -10,10 +10,19 @@ no form: steps of up to 64 rows (bf16; every step of an f16 engine) sum the key 
 quantised value matrix; test_quantised_chunk_invariance compares the two routes bitwise.
 
 c384 is also the one width whose head GEMM (K = 384, wanted slice 512) once got a 384-deep K slice that
-no GEMM kernel has (Engine::init pick()): its logits were never computed."""
+no GEMM kernel has (Engine::init pick()): its logits were never computed.
+
+test_roundtrip: the pack rule on its own. rwkvtts_quant_roundtrip (k_quant_pack, then the GEMM's own
+dequantisation) on tests/quant_ref.py's 16 x 256 edge matrix, bit for bit against the exact restatement:
+constant and all-zero blocks, a single non-zero element, f16 rounding of min / max / absmax that moves
+the range inside the data (bf16 only: an f16 matrix cannot hold it), v = 0.5 -- the one float32 for which
+v * 255 is n + 0.5 exactly -- and its two float32 neighbours, the pairs of dtype numbers closest to each
+NF4 midpoint from either side (and on it, where one exists), -0, +-absmax, f16-subnormal scales. Each
+edge is asserted present through the reference's intermediates before the comparison."""
 import numpy as np
 import pytest
 
+import quant_ref
 import rwkvtts
 from rwkvtts import weights as W
 from forward_check import FULL, tokens
@@ -97,6 +106,28 @@ def test_quantised_chunk_invariance():
         assert np.array_equal(st_whole, st_halves)
     finally:
         rt.close()
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("qt", ["int8", "nf4"])
+def test_roundtrip(qt, dt):
+    dtype = rwkvtts._ffi.DTYPE_F16 if dt == "f16" else rwkvtts._ffi.DTYPE_BF16
+    w, edges = quant_ref.edge_matrix(dtype, qt)
+    ex = quant_ref.exact(w, dtype, qt)
+    quant_ref.assert_edges(w, dtype, qt, edges, ex)
+    # 32 rows (the edge rows again in reverse order): a second 16-column tile in the fragment order
+    w, want = np.vstack([w, w[::-1]]), np.vstack([ex["w"], ex["w"][::-1]]).view(np.uint32)
+    got = rwkvtts.runtime.quant_roundtrip(qt, dtype, w).view(np.uint32)
+    bad = np.argwhere(got != want)
+    assert not len(bad), [(int(r), int(c), hex(w[r, c]), hex(got[r, c]), hex(want[r, c])) for r, c in bad[:8]]
+
+
+def test_roundtrip_refusals():
+    w = np.zeros((16, 128), np.uint16)
+    for args in (("mxfp4", 0, w), ("int8", 2, w), ("int8", 0, w[:8]), ("nf4", 1, w[:, :64]), ("int8", 0, w[0])):
+        with pytest.raises(rwkvtts._ffi.RwkvTtsError) as e:
+            rwkvtts.runtime.quant_roundtrip(*args)
+        assert e.value.code == rwkvtts._ffi.EINVAL
 
 
 def test_sf4_rejected():
