@@ -1698,6 +1698,103 @@ int rwkvtts_pause_windows(rwkvtts_pause* p, rwkvtts_pause_window* w, int n);
 /* HIP-event time of the last call's three kernels (no copies), in ms; 0 before the first. */
 int rwkvtts_pause_kernel_ms(rwkvtts_pause* p, double* ms);
 
+/* ---- highband: blind bandwidth extension by spectral folding on the GPU, the `highband` of the
+ * pipeline -- 16 kHz PCM in, 32 kHz PCM out whose 0-8 kHz band is the input's and whose 8-12 kHz band
+ * is synthesised from the input's own 4-8 kHz band (no reference counterpart: the reference emits
+ * 16 kHz only) ------------------------------------------------------------------------------------
+ * Last of the stages before the resampler, which then runs from 32 kHz. n_out = 2 n. An output is a
+ * function of its position and the samples alone, so a stream's pieces are bitwise the one-shot
+ * result and a window carries no state. The arithmetic contract (every output bit is defined by IEEE
+ * f32 rounded add, subtract and multiply, never fused, and a correctly rounded divide):
+ *   sizes     HP4 has 31 taps, the interpolator 32, SH 63; a block is B = 160 input samples (10 ms),
+ *             320 outputs. The sizes are fixed: the kernels unroll over them.
+ *   table     hp[31], ip[32], sh[63], r[320], f32, built in double one operation at a time and rounded
+ *             once. With sinc-type terms written out and t the tap's distance from the centre:
+ *             hp: t = k - 15, lp[k] = (k == 15 ? 0.5 : sin(pi t / 2) / (pi t)) * (0.54 + 0.46 cos(pi t / 15)),
+ *                 S = the sum of lp in ascending k, hp[k] = (k == 15 ? 1 : 0) - lp[k] / S
+ *                 (a linear-phase high-pass at 4 kHz of 16 kHz);
+ *             ip: t = 15.5 - k, q[k] = sin(pi t) / (pi t) * (0.54 + 0.46 cos(pi t / 16)), ip[k] = q[k] / sum q
+ *                 (the half-sample phase of a half-band windowed sinc);
+ *             sh: t = k - 31, the inverse transform of the amplitude A(f) that is linear from 1 at 8.5 kHz
+ *                 to 0.35 at 12 kHz, linear from there to 0 at 13 kHz and 0 elsewhere (32 kHz rate):
+ *                 per linear piece (w1, a1) .. (w2, a2), w = 2 pi f / 32000, beta = (a2 - a1) / (w2 - w1),
+ *                 (a2 sin(w2 t) - a1 sin(w1 t)) / t + beta (cos(w2 t) - cos(w1 t)) / (t t), and
+ *                 a1 (w2 - w1) + beta (w2 - w1)(w2 - w1) / 2 at t = 0; the two pieces added, divided by pi,
+ *                 times 0.54 + 0.46 cos(pi t / 31). The -6 dB point sits at 8.5 kHz so that 7.5 kHz, where
+ *                 the interpolator's leakage folds to, is already in the stop band;
+ *             r[i] = (float)((double)(i + 1) / 320.0).
+ *   FIR sums  every sum below is sequential in ascending k from +0, one rounded multiply then one rounded
+ *             add per tap; x, b and v outside the signal read +0.
+ *   split     b[n] = sum_k hp[k] * x[n + 15 - k], n in [0, N)
+ *   interp    u[2n] = x[n] (bit for bit), u[2n+1] = sum_k ip[k] * x[n + 16 - k];
+ *             ub[2n] = b[n], ub[2n+1] = sum_k ip[k] * b[n + 16 - k]
+ *   fold      v[m] = ub[m] for even m, -ub[m] for odd m (the spectrum mirrored about 8 kHz)
+ *   shape     w[m] = sum_k sh[k] * v[m + 31 - k], m in [0, 2N)
+ *   gain      block j covers input samples [160 j, 160 j + 160); the last may be partial. Pb_j and Px_j:
+ *             64 partials p[l] = the sum of s[i] * s[i] over the block's i = l (mod 64), ascending from +0,
+ *             then p[l] += p[l + s] for l < s, s = 32, 16, 8, 4, 2, 1; the energy is p[0] (s = b, then x).
+ *             r = Pb_j / Px_j, or 0 where Px_j < floor. s(r) = 0 for r <= r_lo, 1 for r >= r_hi, else with
+ *             t = (r - r_lo) / (r_hi - r_lo): (t * t) * (3 - 2 * t). g_j = G * s(r), g_{-1} = g_0.
+ *             G = (float)10^((level_db + highband_db) / 20), in double (rwkvtts_highband_gain).
+ *   output    sample i of block j, m = 320 j + i: gain = g_{j-1} + (g_j - g_{j-1}) * r[i];
+ *             y[m] = u[m] + gain * w[m], and y[m] = u[m] where gain == 0.
+ * So a block pair without high-band content (voiced, low) and silence come back as the plain
+ * interpolation, silence as +0. A non-finite sample leaves the outputs within reach of it unspecified;
+ * nothing is read or written out of bounds. Every default is untuned and nobody has listened to the
+ * output: the repository has no real checkpoint. */
+#define RWKVTTS_HIGHBAND_TABLE_LEN 446 /* 31 + 32 + 63 + 320 */
+typedef struct {
+  uint32_t struct_size;
+  float level_db; /* the level of highband 0 dB, -40 .. 20; 0 = -6 */
+  float r_lo;     /* finite, > 0; 0 = 0.02 */
+  float r_hi;     /* finite, > r_lo; 0 = 0.2 (white noise sits near 0.5) */
+  float floor;    /* the least Px of a block that gets a high band: finite, > 0; 0 = 1e-6 */
+} rwkvtts_highband_desc;
+/* The library's own table builder (host only): out[446]. Anything outside the ranges above (NaN
+ * included) is RWKVTTS_EINVAL, here and in every call that takes a desc. */
+int rwkvtts_highband_table(const rwkvtts_highband_desc* desc, float* out);
+/* G of a highband value in dB (host only), -12 .. 12; outside that (NaN included) RWKVTTS_EINVAL. */
+int rwkvtts_highband_gain(const rwkvtts_highband_desc* desc, double highband_db, float* out);
+/* Streaming plan (host only, a pure function). With samples [0, n_known) of a signal known:
+ * *out_ready_end = min(320 * max(0, floor((n_known - 15) / 160)), 2 * max(0, n_known - 46)): an output
+ * is exact once its block's gain is (the block complete and the 15 samples HP4 looks ahead) and the
+ * 46 samples the three filters look ahead are known -- a lag of at most 160 + 46 samples, 12.9 ms.
+ * With final (n_known is the signal's length) it is 2 * n_known.
+ * *in_first_needed = max(0, 160 * (floor(out_first / 320) - 1) - 15): the block before the cursor's,
+ * whose gain starts the cursor block's ramp, and HP4's history (the filters' own 46 samples of history
+ * lie inside it). Either pointer may be NULL. Monotone in n_known and in out_first. */
+int rwkvtts_highband_plan(const rwkvtts_highband_desc* desc, int64_t n_known, int final, int64_t out_first,
+                          int64_t* out_ready_end, int64_t* in_first_needed);
+typedef struct rwkvtts_highband rwkvtts_highband;
+/* table == NULL: the table of rwkvtts_highband_table; otherwise the caller's [446] table (copied). */
+int rwkvtts_highband_create(int device, const rwkvtts_highband_desc* desc, const float* table,
+                            rwkvtts_highband** out);
+int rwkvtts_highband_destroy(rwkvtts_highband* h);
+/* n signals (ragged), each with its own G (finite, >= 0), in one launch pair (gain, synth). Host
+ * buffers; out[i] has capacity 2 * n_in[i]. n_in[i] == 0 writes nothing. Calls on one handle serialise
+ * on its lock. */
+int rwkvtts_highband_batch(rwkvtts_highband* h, const float* const* in, const int64_t* n_in, const float* G, int n,
+                           float* const* out);
+typedef struct {
+  uint32_t struct_size;
+  const float* in;    /* points at sample in_first of the signal */
+  int64_t in_first;
+  int64_t n_in;
+  int32_t final;      /* 1: in_first + n_in is the signal's length */
+  float G;
+  int64_t out_first;  /* outputs [out_first, out_first + out_count), any position */
+  int64_t out_count;
+  float* out;         /* capacity out_count */
+} rwkvtts_highband_window;
+/* n windows (of any signals, any G) in one launch pair: outputs [out_first, out_first + out_count) of
+ * the whole-signal result, bitwise, whatever follows the known samples. RWKVTTS_EINVAL before anything
+ * is launched (and nothing written) if a requested output needs a sample or a block gain that is not
+ * given: out_first + out_count > out_ready_end(in_first + n_in, final) or in_first >
+ * in_first_needed(out_first) by rwkvtts_highband_plan. */
+int rwkvtts_highband_windows(rwkvtts_highband* h, const rwkvtts_highband_window* w, int n);
+/* HIP-event time of the last launch pair (both kernels, no copies), in ms; 0 before the first. */
+int rwkvtts_highband_kernel_ms(rwkvtts_highband* h, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

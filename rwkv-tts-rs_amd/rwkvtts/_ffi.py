@@ -265,6 +265,17 @@ class LevelWindow(ctypes.Structure):
                 ("s_last", ctypes.c_float), ("n_last", ctypes.c_int64), ("g_last", ctypes.c_float)]
 
 
+class HighBandDesc(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("level_db", ctypes.c_float), ("r_lo", ctypes.c_float),
+                ("r_hi", ctypes.c_float), ("floor", ctypes.c_float)]
+
+
+class HighBandWindow(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("in_", ctypes.c_void_p), ("in_first", ctypes.c_int64),
+                ("n_in", ctypes.c_int64), ("final", ctypes.c_int32), ("G", ctypes.c_float),
+                ("out_first", ctypes.c_int64), ("out_count", ctypes.c_int64), ("out", ctypes.c_void_p)]
+
+
 class PitchDesc(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("hop", ctypes.c_int32), ("window", ctypes.c_int32),
                 ("lag_min", ctypes.c_int32), ("lag_max", ctypes.c_int32), ("unvoiced", ctypes.c_int32),
@@ -548,6 +559,19 @@ EXPORTS = {
                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "rwkvtts_pause_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PauseWindow), ctypes.c_int]),
     "rwkvtts_pause_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    # highband: table, gain and plan (host only), batched / exact stream windows
+    "rwkvtts_highband_table": (ctypes.c_int, [ctypes.POINTER(HighBandDesc), ctypes.c_void_p]),
+    "rwkvtts_highband_gain": (ctypes.c_int, [ctypes.POINTER(HighBandDesc), ctypes.c_double,
+                                             ctypes.POINTER(ctypes.c_float)]),
+    "rwkvtts_highband_plan": (ctypes.c_int, [ctypes.POINTER(HighBandDesc), ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "rwkvtts_highband_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(HighBandDesc), ctypes.c_void_p,
+                                               ctypes.POINTER(ctypes.c_void_p)]),
+    "rwkvtts_highband_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "rwkvtts_highband_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_int, ctypes.c_void_p]),
+    "rwkvtts_highband_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HighBandWindow), ctypes.c_int]),
+    "rwkvtts_highband_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
     "rwkvtts_mx_roundtrip": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "rwkvtts_quant_roundtrip": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_void_p]),

@@ -719,6 +719,145 @@ class LevelStream(_ExactStream):
         return self.v.plan(n_known, False, self._block_next)[1]
 
 
+# ---- high-band synthesis on the GPU ----------------------------------------------------------
+HIGHBAND_RATE = 32000  # the stage's output rate: twice the vocoder's
+
+
+def _highband_table() -> np.ndarray:
+    """hp[31], ip[32], sh[63], r[320] of include/rwkvtts.h, in double, one operation at a time, rounded
+    once: the table the kernels read."""
+    import math
+    pi = math.pi
+    lp = []
+    for k in range(31):
+        t = float(k - 15)
+        lp.append((0.5 if k == 15 else math.sin(pi * t / 2.0) / (pi * t)) * (0.54 + 0.46 * math.cos(pi * t / 15.0)))
+    s = 0.0
+    for v in lp:
+        s = s + v
+    out = [(1.0 if k == 15 else 0.0) - lp[k] / s for k in range(31)]
+    q = []
+    for k in range(32):
+        t = 15.5 - float(k)
+        q.append(math.sin(pi * t) / (pi * t) * (0.54 + 0.46 * math.cos(pi * t / 16.0)))
+    s = 0.0
+    for v in q:
+        s = s + v
+    out += [v / s for v in q]
+    edges = ((8500.0, 1.0), (12000.0, 0.35), (13000.0, 0.0))
+    for k in range(63):
+        t = float(k - 31)
+        acc = 0.0
+        for (f1, a1), (f2, a2) in zip(edges[:-1], edges[1:]):
+            w1, w2 = 2.0 * pi * f1 / 32000.0, 2.0 * pi * f2 / 32000.0
+            beta = (a2 - a1) / (w2 - w1)
+            if k == 31:
+                seg = a1 * (w2 - w1) + beta * (w2 - w1) * (w2 - w1) / 2.0
+            else:
+                seg = (a2 * math.sin(w2 * t) - a1 * math.sin(w1 * t)) / t + beta * (math.cos(w2 * t) - math.cos(w1 * t)) / (t * t)
+            acc = acc + seg
+        out.append(acc / pi * (0.54 + 0.46 * math.cos(pi * t / 31.0)))
+    out += [float(i + 1) / 320.0 for i in range(320)]
+    return np.array(out, dtype=np.float64).astype(F32)
+
+
+class HighBand(_NativeStage):
+    """Blind bandwidth extension by spectral folding as HIP kernels (csrc/highband.hip; the arithmetic
+    contract is in include/rwkvtts.h): 16 kHz PCM in, 32 kHz PCM out, n_out = 2 n. The
+    0-8 kHz band is the input's (even outputs are the input's samples bit for bit); the 8-12 kHz band is
+    the input's 4-8 kHz band mirrored about 8 kHz, shaped with a downward tilt and scaled per 10 ms
+    block by how fricative-like the block is (the share of its energy above 4 kHz through a smoothstep),
+    so voiced, low blocks and silence come out as the plain interpolation. An output is a function of
+    its position and the samples alone, so a stream's pieces are bitwise the one-shot result. The
+    pipeline applies it last before the resampler. A highband value is a level in dB per signal,
+    -12 .. 12, relative to level_db.
+
+    0 means the default as in the C desc: level_db -6, r_lo 0.02, r_hi 0.2, floor 1e-6. Every default is
+    untuned and nobody has listened to the output: the repository has no real checkpoint. The kernels
+    read the table `_highband_table` builds."""
+    _NAME = "highband"
+
+    def __init__(self, device: int = 0, level_db: float = 0.0, r_lo: float = 0.0, r_hi: float = 0.0, floor: float = 0.0):
+        self.device = int(device)
+        self._desc = _ffi.HighBandDesc(struct_size=ctypes.sizeof(_ffi.HighBandDesc), level_db=float(level_db),
+                                       r_lo=float(r_lo), r_hi=float(r_hi), floor=float(floor))
+        super().__init__(None)
+        self.plan(0, False)  # (refuses a bad description before anything is built)
+        self.table = _highband_table()
+        self._create(self.table)
+
+    # ---- host-only plan ----
+    def gain(self, highband: float) -> np.float32:
+        """G = (float)10^((level_db + highband) / 20) (rwkvtts_highband_gain); ValueError outside -12 .. 12."""
+        if isinstance(highband, bool) or not -12.0 <= float(highband) <= 12.0:  # (NaN fails)
+            raise ValueError("highband must be in [-12, 12] dB")
+        G = ctypes.c_float()
+        _native("highband_gain", ctypes.byref(self._desc), float(highband), ctypes.byref(G))
+        return F32(G.value)
+
+    def plan(self, n_known: int, final: bool, out_first: int = 0):
+        """(out_ready_end, in_first_needed) of rwkvtts_highband_plan."""
+        end, first = ctypes.c_int64(), ctypes.c_int64()
+        _native("highband_plan", ctypes.byref(self._desc), int(n_known), 1 if final else 0, int(out_first),
+                ctypes.byref(end), ctypes.byref(first))
+        return end.value, first.value
+
+    # ---- the kernels ----
+    def extend_windows(self, items) -> list:
+        """[(samples from in_first on, in_first, final, G, out_first, out_count)] -> [outputs [out_first,
+        out_first + out_count) of the whole-signal result], all windows in one launch pair. Raises
+        RwkvTtsError(EINVAL), with nothing computed, if a window asks for more than plan() allows."""
+        items = [(np.ascontiguousarray(x, dtype=F32).reshape(-1), int(a), bool(f), float(F32(g)), int(o), int(c))
+                 for x, a, f, g, o, c in items]
+        return self._windows("highband_windows", _ffi.HighBandWindow, items, G=3, out_first=4)[1]
+
+    def extend_batch(self, signals, highband) -> list:
+        """[signal], [highband in dB] -> [32 kHz signal], ragged, a level per signal, in one launch pair;
+        an empty signal gives an empty one."""
+        xs = [np.ascontiguousarray(x, dtype=F32).reshape(-1) for x in signals]
+        gs = [self.gain(v) for v in highband]
+        if len(xs) != len(gs):
+            raise ValueError("extend_batch: one highband value per signal")
+        if not xs:
+            return []
+        outs, ins, lens, ous = self._ragged(xs, [2 * x.size for x in xs])
+        self._call("highband_batch", ins, lens, (ctypes.c_float * len(gs))(*[float(g) for g in gs]), len(xs), ous)
+        return outs
+
+    def extend(self, x, highband: float = 0.0) -> np.ndarray:
+        return self.extend_batch([x], [highband])[0]
+
+    def stream(self, highband: float = 0.0) -> "HighBandStream":
+        return HighBandStream(self, highband)
+
+
+class HighBandStream(_ExactStream):
+    """HighBand.stream(highband): feed(pcm_chunk, final=False) -> the outputs that became exact with
+    it. The concatenation of what feed returns is bitwise HighBand.extend(the concatenated input,
+    highband), however the input was cut. An output goes out once its block is complete and the filters'
+    look-ahead is known: a lag of at most 206 input samples, 12.9 ms; the kept tail is what
+    rwkvtts_highband_plan asks for, fewer than 2 * 160 + 15 samples before the cursor's block."""
+
+    def __init__(self, hb: HighBand, highband: float):
+        super().__init__()
+        self.hb = hb
+        self.G = hb.gain(highband)
+        self._out_next = 0     # outputs [0, _out_next) went out
+
+    def _emit(self, n_known, final):
+        end, _ = self.hb.plan(n_known, final, self._out_next)
+        count = end - self._out_next
+        if count > 0:
+            out = self.hb.extend_windows([(self._tail, self._tail_first, final, self.G, self._out_next, count)])[0]
+        else:
+            out = np.zeros(0, dtype=F32)
+        self._out_next = max(end, self._out_next)
+        return out
+
+    def _first_needed(self, n_known):
+        return self.hb.plan(n_known, False, self._out_next)[1]
+
+
 # ---- pitch shift on the GPU ------------------------------------------------------------------
 def pitch_factor(semitones: float) -> float:
     """f = 2^(semitones / 12), in double: what the native side takes per signal."""

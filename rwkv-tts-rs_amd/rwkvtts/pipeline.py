@@ -28,6 +28,11 @@ property tokens, which a cloned voice does not get): None / 0 leaves the PCM as 
 semitones, -6 .. 6, moves the spectral envelope of the 16 kHz PCM on the GPU and keeps its fundamental
 and its length (the same stage with its grains read faster or slower), alone or
 together with `pitch_shift` in the same launches, exact over stream chunks.
+All five also take `highband` (no reference counterpart: the reference emits 16 kHz only): None leaves
+the band above 8 kHz of a wide-band `sample_rate` empty, as a resampler alone does; a level in dB,
+-12 .. 12, takes the 16 kHz PCM to 32 kHz on the GPU with an 8-12 kHz band folded down from its own
+4-8 kHz band (audio.HighBand), last before the resampler, which then runs from
+32 kHz; it needs `sample_rate` 32000, 44100 or 48000; exact over stream chunks.
 All five also take `watermark` (no reference counterpart: the reference marks nothing): None leaves the
 PCM unmarked; a payload, an integer 0 .. 65535, embeds it as a spread-spectrum mark under the
 pipeline's `watermark_key` (audio.Watermarker) on the 16 kHz PCM, after the
@@ -203,9 +208,10 @@ class LongSpeech(np.ndarray):
 
 def audio_stages(stretcher, tempo, resampler, leveller=None, loudness=None, shifter=None, pitch_shift=None,
                  marker=None, watermark=None, watermark_key=None, shaper=None, max_pause=None,
-                 formant_shift=None) -> list:
+                 formant_shift=None, extender=None, highband=None) -> list:
     """The stages behind the vocoder in the order they apply -- the pause cap at 16 kHz, then the pitch
-    shift, then the stretch, then the leveller, then the watermark, then the resampler; None is no
+    shift, then the stretch, then the leveller, then the watermark, then the high band (16 kHz to 32 kHz),
+    then the resampler; None is no
     stage -- each as (batch, stream): batch([pcm]) -> [pcm] in one native call (one cap, one shift, one
     tempo, one loudness, one key and payload for the call), stream() -> an object whose feed(pcm, final)
     is exact over chunks. The pause cap removes samples, so every stage behind it does less work."""
@@ -224,6 +230,8 @@ def audio_stages(stretcher, tempo, resampler, leveller=None, loudness=None, shif
     if marker is not None:
         stages.append((lambda pcm: marker.embed_batch(pcm, [watermark_key] * len(pcm), [watermark] * len(pcm)),
                        lambda: marker.stream(watermark_key, watermark)))
+    if extender is not None:
+        stages.append((lambda pcm: extender.extend_batch(pcm, [highband] * len(pcm)), lambda: extender.stream(highband)))
     if resampler is not None:
         stages.append((resampler.resample_batch, resampler.stream))
     return stages
@@ -262,24 +270,46 @@ class LightweightTtsPipeline:
         self._marker = None  # audio.Watermarker (created on the first watermark or detect_watermark, kept)
         self._encoder = None  # audio.FlacEncoder (created on the first `format: "flac"`, kept)
         self._shapers = {}  # threshold -> audio.PauseShaper (created on the first max_pause, kept)
+        self._extender = None  # audio.HighBand (created on the first highband, kept)
         self._pause_threshold = None  # the loudness threshold of `max_pause` (None: audio.PauseShaper's default)
-        self._stage_cache_lock = threading.Lock()  # guards all eight (the server's worker threads share the pipeline)
+        self._stage_cache_lock = threading.Lock()  # guards all nine (the server's worker threads share the pipeline)
 
     # ---- output rates other than 16 kHz (no reference counterpart: the reference emits 16 kHz only)
-    def resampler(self, sample_rate: Optional[int]):
-        """None for None / 16000 (nothing is created: the PCM is the vocoder's); otherwise the
-        pipeline's Resampler 16000 -> sample_rate with zero alignment (output o at input time
-        o * 16000 / sample_rate: no delay, nothing cut), on the codec's GPU."""
-        if sample_rate is None or int(sample_rate) == SAMPLE_RATE:
+    def resampler(self, sample_rate: Optional[int], sr_in: int = SAMPLE_RATE):
+        """None for None / sr_in (nothing is created: the PCM is the vocoder's, or the high-band stage's
+        at 32 kHz); otherwise the pipeline's Resampler sr_in -> sample_rate with zero alignment (output o
+        at input time o * sr_in / sample_rate: no delay, nothing cut), on the codec's GPU. sr_in is
+        16000, or 32000 behind `highband`."""
+        if sample_rate is None or int(sample_rate) == int(sr_in):
             return None
         rate = int(sample_rate)
+        key = rate if int(sr_in) == SAMPLE_RATE else (int(sr_in), rate)
         with self._stage_cache_lock:
-            r = self._resamplers.get(rate)
+            r = self._resamplers.get(key)
             if r is None:
                 from .audio import Resampler
-                r = self._resamplers[rate] = Resampler(SAMPLE_RATE, rate, device=getattr(self.codec, "device", 0),
-                                                       align="zero")
+                r = self._resamplers[key] = Resampler(int(sr_in), rate, device=getattr(self.codec, "device", 0),
+                                                      align="zero")
         return r
+
+    # ---- the band above 8 kHz (no reference counterpart: the reference emits 16 kHz only)
+    def extender(self, highband: Optional[float], sample_rate: Optional[int] = 32000):
+        """None for None (nothing is created: a wide-band rate is the resampler's alone); otherwise the
+        pipeline's one HighBand (the untuned defaults of audio.HighBand), on the codec's GPU. The level
+        is in dB per call, -12 .. 12 relative to the default, not a part of the object. A level outside
+        that, or a sample_rate other than 32000, 44100 or 48000 (the stage emits 32 kHz: a lower rate
+        would throw its band away), raises ValueError before anything is generated."""
+        if highband is None:
+            return None
+        if isinstance(highband, bool) or not -12.0 <= float(highband) <= 12.0:  # (NaN fails)
+            raise ValueError("highband must be in [-12, 12] dB")
+        if sample_rate is None or isinstance(sample_rate, bool) or int(sample_rate) not in (32000, 44100, 48000):
+            raise ValueError("highband needs sample_rate 32000, 44100 or 48000")
+        with self._stage_cache_lock:
+            if self._extender is None:
+                from .audio import HighBand
+                self._extender = HighBand(device=getattr(self.codec, "device", 0))
+        return self._extender
 
     # ---- speaking rate (no reference counterpart: the reference has the `speed` property token only)
     def stretcher(self, tempo: Optional[float]):
@@ -409,8 +439,10 @@ class LightweightTtsPipeline:
 
     def _stages(self, sample_rate: Optional[int], tempo: Optional[float], loudness: Optional[float] = None,
                 pitch_shift: Optional[float] = None, watermark: Optional[int] = None,
-                max_pause: Optional[int] = None, formant_shift: Optional[float] = None):  # -> (stages, output rate)
-        rs = self.resampler(sample_rate)
+                max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
+                highband: Optional[float] = None):  # -> (stages, output rate)
+        hb = self.extender(highband, sample_rate)
+        rs = self.resampler(sample_rate) if hb is None else self.resampler(sample_rate, 32000)
         lv = self.leveller(loudness)
         sh = self.shifter(pitch_shift, formant_shift)
         mk = self.marker(watermark)
@@ -419,10 +451,12 @@ class LightweightTtsPipeline:
         kw = {} if ps is None else {"shaper": ps, "max_pause": int(max_pause)}
         if sh is not None and float(formant_shift or 0.0):  # (the same for formant_shift)
             kw["formant_shift"] = float(formant_shift)
+        if hb is not None:  # (and for highband)
+            kw["extender"], kw["highband"] = hb, float(highband)
         return (audio_stages(self.stretcher(tempo), tempo, rs, lv, None if lv is None else float(loudness),
                              sh, None if sh is None else float(pitch_shift or 0.0),
                              mk, None if mk is None else int(watermark), self.watermark_key, **kw),
-                rs.sr_out if rs else SAMPLE_RATE)
+                rs.sr_out if rs else (SAMPLE_RATE if hb is None else 32000))
 
     # ---- text / attribute handling (:148-193)
     @staticmethod
@@ -490,7 +524,8 @@ class LightweightTtsPipeline:
     def generate_speech(self, args: LightweightTtsPipelineArgs, sample_rate: Optional[int] = None,
                         tempo: Optional[float] = None, loudness: Optional[float] = None,
                         watermark: Optional[int] = None, max_pause: Optional[int] = None,
-                        formant_shift: Optional[float] = None, pitch_shift: Optional[float] = None) -> np.ndarray:
+                        formant_shift: Optional[float] = None, highband: Optional[float] = None,
+                        pitch_shift: Optional[float] = None) -> np.ndarray:
         """sample_rate None / 16000: the vocoder's 16 kHz PCM. Any other rate: that PCM resampled on
         the GPU (resampler()); the failed-request second of silence is sample_rate zeros.
         tempo None / 1.0: nothing. Any other: the 16 kHz PCM time-stretched on the GPU (stretcher())
@@ -511,9 +546,14 @@ class LightweightTtsPipeline:
         max_pause None: nothing. A cap in milliseconds, an integer 20 .. 5000: the silences of the
         16 kHz PCM capped on the GPU (pause_shaper()), first of the stages, so the result is shorter
         than the vocoder's PCM by what was cut; the failed-request second of silence is not shaped.
+        highband None: nothing. A level in dB, -12 .. 12 relative to the default: the 16 kHz PCM, after
+        every stage at that rate, taken to 32 kHz on the GPU with a band from 8 to 12 kHz folded down from
+        its own 4-8 kHz band (extender(); audio.HighBand), and the resampler then
+        runs from 32 kHz (none at sample_rate 32000). It needs sample_rate 32000, 44100 or 48000; the
+        failed-request second of silence is sample_rate zeros.
         args.global_sampling / semantic_sampling outside their ranges raise ValueError, like tempo."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband)
         try:
             req = self._request(args)
         except ValueError:  # untokenisable text: the request fails -> empty result
@@ -530,7 +570,7 @@ class LightweightTtsPipeline:
                       sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                       loudness: Optional[float] = None, watermark: Optional[int] = None,
                       max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                      pitch_shift: Optional[float] = None):
+                      highband: Optional[float] = None, pitch_shift: Optional[float] = None):
         """generate_speech as a generator of float32 PCM chunks (SpeechChunk: an ndarray that also
         carries t0, t1, n_known, done), each decoded while the request is still generating tokens.
 
@@ -572,7 +612,13 @@ class LightweightTtsPipeline:
         concatenation is bitwise generate_speech(args, max_pause=...). t0 and t1 stay the vocoder's
         frames, and a chunk's length no longer follows from them: an item holds what became exact
         with its frames -- nothing while the request is still in its leading silence (which is latency
-        no more), less than its frames where a silence was cut."""
+        no more), less than its frames where a silence was cut.
+
+        highband (dB, -12 .. 12; sample_rate 32000, 44100 or 48000): HighBand.stream(highband) sits last
+        before the resampler, which then runs from 32 kHz, and the concatenation is bitwise
+        generate_speech(args, highband=..., sample_rate=...). An item's length follows from the two plan
+        functions; it lags its frames by at most 206 samples of 16 kHz, 12.9 ms, more than the
+        resampler alone."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         check_sampling(args)
@@ -594,20 +640,23 @@ class LightweightTtsPipeline:
         if max_pause is not None:
             self.pause_shaper(max_pause)  # (and for a bad cap)
             kw["max_pause"] = max_pause
+        if highband is not None:
+            self.extender(highband, sample_rate)  # (and for a bad level or a rate the stage cannot serve)
+            kw["highband"] = highband
         return self.stream_request(req, chunk_frames, sample_rate=sample_rate, tempo=tempo, loudness=loudness, **kw)
 
     def stream_request(self, req: Optional[TtsBatchRequest], chunk_frames: int = 16,
                        sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                        loudness: Optional[float] = None, watermark: Optional[int] = None,
                        max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                       pitch_shift: Optional[float] = None):
+                       highband: Optional[float] = None, pitch_shift: Optional[float] = None):
         """stream_speech for a request that is already built (None: a request that failed before it
         was submitted)."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         if req is not None:
             check_sampling(req.args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband)
         streams = [stream() for _, stream in stages]
         H = self.codec.halo()
         g, sem, t0, yielded, status = None, [], 0, False, 0
@@ -644,7 +693,7 @@ class LightweightTtsPipeline:
                               sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                               loudness: Optional[float] = None, watermark: Optional[int] = None,
                               max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                              pitch_shift: Optional[float] = None) -> List[np.ndarray]:
+                              highband: Optional[float] = None, pitch_shift: Optional[float] = None) -> List[np.ndarray]:
         """sample_rate other than None / 16000: the whole batch is resampled in one resample_batch
         call (a failed item stays an empty array). tempo other than None / 1.0: the whole batch is
         first stretched in one stretch_batch call, one tempo for the call. loudness other than None:
@@ -654,10 +703,11 @@ class LightweightTtsPipeline:
         None: the whole batch is marked in
         one embed_batch call after the leveller, one payload for the call. max_pause other than None:
         the silences of the whole batch are capped in one shape_batch call before all of them, one
-        cap for the call."""
+        cap for the call. highband other than None: the whole batch goes to 32 kHz in one extend_batch call
+        before the resampler, one level for the call."""
         for a in batch_args:
             check_sampling(a)
-        stages, _ = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift)
+        stages, _ = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband)
         reqs, idx = [], []
         for i, a in enumerate(batch_args):
             try:
@@ -742,7 +792,7 @@ class LightweightTtsPipeline:
                              trim: bool = True, keep: int = 800, fade: int = 80,
                              loudness: Optional[float] = None, watermark: Optional[int] = None,
                              max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                             pitch_shift: Optional[float] = None) -> "LongSpeech":
+                             highband: Optional[float] = None, pitch_shift: Optional[float] = None) -> "LongSpeech":
         """generate_speech for a text of any length: the text is cut into segments of at most
         segment_tokens text tokens (segment.split_text), the segments decode side by side in the
         manager's slots and engines with one voice (_long_submit), and their PCM is joined on the
@@ -762,9 +812,11 @@ class LightweightTtsPipeline:
         silences of every segment's PCM before the join, all segments in one shape_batch call; the
         pauses the join puts between segments are deliberate and stay. A record's `cut` is what the
         cap removed from its segment, and its a, b then refer to the shaped segment. The second of
-        silence is not shaped."""
+        silence is not shaped. highband runs where the resampler does, on the joined signal, last before
+        it."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, formant_shift=formant_shift)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, formant_shift=formant_shift,
+                                    highband=highband)
         shaper = self.pause_shaper(max_pause)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)
@@ -790,7 +842,8 @@ class LightweightTtsPipeline:
                            tempo: Optional[float] = None, segment_tokens: int = 64, pauses=None,
                            trim: bool = True, keep: int = 800, fade: int = 80, loudness: Optional[float] = None,
                            watermark: Optional[int] = None, max_pause: Optional[int] = None,
-                           formant_shift: Optional[float] = None, pitch_shift: Optional[float] = None):
+                           formant_shift: Optional[float] = None, highband: Optional[float] = None,
+                        pitch_shift: Optional[float] = None):
         """generate_long_speech as a generator of LongSpeech items, one per segment, in order: segment
         i is emitted once it and every segment before it are done -- decoded, joined alone with its
         gap (a piece depends on its own segment only), and fed through the stages' exact streams,
@@ -803,9 +856,12 @@ class LightweightTtsPipeline:
         an item also waits for the leveller's look-ahead (up to 0.5 s of the next segment), with
         pitch_shift or formant_shift for the shifter's (0.1 s), with watermark for the rest of its last
         block (20 ms).
-        max_pause caps the silences of each segment's PCM before its join, one call per segment."""
+        max_pause caps the silences of each segment's PCM before its join, one call per segment.
+        highband: each joined piece goes through the high-band stream, then the resampler's, as it does
+        through the resampler's alone without it; an item waits for 12.9 ms more of the next piece."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, formant_shift=formant_shift)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, formant_shift=formant_shift,
+                                    highband=highband)
         shaper = self.pause_shaper(max_pause)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)

@@ -74,6 +74,13 @@
   spectral envelope up (a shorter vocal tract: smaller, younger), below 0 down, with the fundamental
   and the length kept (the pitch stage with its grains read faster or slower), alone or together
   with `pitch_shift`. Without the field (or with 0) the routes are unchanged.
+* `highband` in the body of both TTS routes (no reference counterpart: the reference emits 16 kHz
+  only, and a resampler alone leaves everything above 8 kHz empty): a JSON number in [HIGHBAND_MIN,
+  HIGHBAND_MAX] = [-12, 12] dB relative to the stage's default level, anything else a 400, and a 400
+  too unless `sample_rate` is one of HIGHBAND_RATES = 32000, 44100, 48000. The 16 kHz PCM goes to
+  32 kHz on the GPU with a band from 8 to 12 kHz folded down from its own 4-8 kHz band
+  (audio.HighBand), last before the resampler, which then runs from 32 kHz. Without the field the
+  routes are unchanged.
 * `watermark` in the body of both TTS routes (no reference counterpart: the reference marks nothing):
   a JSON integer in [WATERMARK_MIN, WATERMARK_MAX] = [0, 65535], anything else a 400, and a 400 too on
   a server whose pipeline has no `watermark_key`. The payload is embedded in the 16 kHz PCM under the
@@ -179,6 +186,10 @@ PITCH_SHIFT_MIN, PITCH_SHIFT_MAX = -12.0, 12.0
 # `formant_shift` of the same bodies (no reference counterpart): semitones by which the spectral envelope
 # moves with the fundamental kept -- half an octave either way, the kernel's own range
 FORMANT_SHIFT_MIN, FORMANT_SHIFT_MAX = -6.0, 6.0
+# `highband` of the same bodies (no reference counterpart): the level of the synthesised 8-12 kHz band in
+# dB relative to the stage's default -- the pipeline's range -- and the output rates that can carry it
+HIGHBAND_MIN, HIGHBAND_MAX = -12.0, 12.0
+HIGHBAND_RATES = (32000, 44100, 48000)
 # `format` of the same bodies (no reference counterpart): the container of the audio that goes out
 FORMATS = ("wav", "flac")
 # `watermark` of the same bodies (no reference counterpart): the payload of the provenance mark, 16
@@ -243,7 +254,8 @@ def _tts_args(body, voice_dir: str):
     sample_rate (one of SAMPLE_RATES, not 16000), tempo (TEMPO_MIN .. TEMPO_MAX, not 1.0), loudness
     (LOUDNESS_MIN .. LOUDNESS_MAX; there is no default value that means "off" but its absence) and
     pitch_shift (PITCH_SHIFT_MIN .. PITCH_SHIFT_MAX, not 0), formant_shift (FORMANT_SHIFT_MIN ..
-    FORMANT_SHIFT_MAX, not 0), and max_pause (an integer MAX_PAUSE_MIN ..
+    FORMANT_SHIFT_MAX, not 0), highband (HIGHBAND_MIN .. HIGHBAND_MAX with a sample_rate of HIGHBAND_RATES;
+    absent is off), and max_pause (an integer MAX_PAUSE_MIN ..
     MAX_PAUSE_MAX ms; absent is off) -- so a
     body without them makes exactly the call it always made. A true `long_form` adds
     long_form=True, which the handler takes out and answers by calling the long-form entry point,
@@ -287,6 +299,14 @@ def _tts_args(body, voice_dir: str):
           or not FORMANT_SHIFT_MIN <= formant <= FORMANT_SHIFT_MAX):  # (NaN fails the comparison)
         return (400, {"success": False, "error": f"不支持的共振峰偏移: {formant} (支持: "
                                                  f"{FORMANT_SHIFT_MIN} - {FORMANT_SHIFT_MAX} 半音)"}), None, None
+    highband = body.get("highband")
+    if highband is not None and (isinstance(highband, bool) or not isinstance(highband, (int, float))
+                                 or not HIGHBAND_MIN <= highband <= HIGHBAND_MAX):  # (NaN fails the comparison)
+        return (400, {"success": False, "error": f"不支持的高频带电平: {highband} (支持: "
+                                                 f"{HIGHBAND_MIN} - {HIGHBAND_MAX} dB)"}), None, None
+    if highband is not None and rate not in HIGHBAND_RATES:
+        return (400, {"success": False, "error": f"highband 需要采样率 {', '.join(str(r) for r in HIGHBAND_RATES)}"
+                                                 f" (当前: {rate})"}), None, None
     mark = body.get("watermark")
     if mark is not None and (isinstance(mark, bool) or not isinstance(mark, int)
                              or not WATERMARK_MIN <= mark <= WATERMARK_MAX):
@@ -404,6 +424,8 @@ def _tts_args(body, voice_dir: str):
         kw["pitch_shift"] = float(shift)
     if float(formant) != 0.0:
         kw["formant_shift"] = float(formant)
+    if highband is not None:
+        kw["highband"] = float(highband)
     if mark is not None:
         kw["watermark"] = int(mark)
     if max_pause is not None:
