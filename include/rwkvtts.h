@@ -1795,6 +1795,79 @@ int rwkvtts_highband_windows(rwkvtts_highband* h, const rwkvtts_highband_window*
 /* HIP-event time of the last launch pair (both kernels, no copies), in ms; 0 before the first. */
 int rwkvtts_highband_kernel_ms(rwkvtts_highband* h, double* ms);
 
+/* ---- limit: a look-ahead true-peak limiter on the GPU, the `limit` of the pipeline -- PCM at the
+ * output rate in, the same number of samples out (no reference counterpart: the reference peak-normalises
+ * a finished WAV, which a stream cannot do) -------------------------------------------------------
+ * Last of the stages, directly behind the resampler. n_out = n. An output is a function of its position
+ * and the samples alone, so a stream's pieces are bitwise the one-shot result and a window carries no
+ * state. The arithmetic contract (every output bit is defined by IEEE f32 rounded add and multiply, never
+ * fused, a correctly rounded divide, and exact compares). x[n] = +0 outside [0, N);
+ * c = (float)10^(limit / 20), in double (rwkvtts_limit_ceiling):
+ *   sizes     three phases of 12 taps; the minimum and the box reach 32 samples either side (a look-ahead
+ *             of 64). The sizes are fixed: the kernel unrolls over them.
+ *   table     h_q[k], q = 1, 2, 3, k = 0 .. 11, at [12 (q - 1) + k], f32, built in double one operation at
+ *             a time and rounded once: t = (k - 5) - q / 4, w[k] = sin(pi t) / (pi t) * (0.5 + 0.5 cos(pi t / 6)),
+ *             S = the sum of w in ascending k, h_q[k] = w[k] / S (a Hann-windowed sinc at the q / 4 sample
+ *             offset, each phase summing to 1).
+ *   estimate  v_q[n] = sum_k h_q[k] * x[n + k - 5], sequential in ascending k from +0, one rounded multiply
+ *             then one rounded add per tap, as the high band's FIRs;
+ *             p[n] = max(|x[n]|, |v_1[n]|, |v_2[n]|, |v_3[n]|).
+ *   gain      r[n] = c / p[n] (one correctly rounded divide) where p[n] > c, else 1; r = 1 outside [0, N).
+ *   minimum   m[n] = min of r[n + j], |j| <= 32 (any order: a minimum has one value).
+ *   smoothing g[n] = (sum of m[n + j], j = -32 .. 32, added in ascending j from +0) / 65.0f, one correctly
+ *             rounded divide. Where every m in reach is 1 the sum is exactly 65 and g exactly 1.
+ *   apply     y[n] = min(max(x[n] * g[n], -c), c).
+ * Three properties. Sample bound: every m[k] with |k - n| <= 32 is at most r[n], its window holding n, so
+ * g[n] <= r[n] <= c / |x[n]| up to rounding, the clamp binds only at that rounding, and |y[n]| <= c for
+ * every sample. Pass-through: a signal whose estimate never passes c comes back bit for bit, silence as
+ * silence. Reach: y[n] is a pure function of x[n - 69 .. n + 70] (64 + 5 back, 64 + 6 ahead): a lag of
+ * 70 samples, 1.5 ms at 48 kHz, 4.4 ms at 16 kHz, and no state. The bound is on the samples; between them
+ * the estimate under-reads a little and the moving gain adds its own (DESIGN.md §41 has the figure). A
+ * non-finite sample leaves the outputs within reach of it unspecified; nothing is read or written out of
+ * bounds. The look-ahead, the box smoothing and the 12 taps are untuned defaults and nobody has listened
+ * to the output: the repository has no real checkpoint. */
+#define RWKVTTS_LIMIT_TABLE_LEN 36 /* 3 x 12 */
+typedef struct {
+  uint32_t struct_size;
+  uint32_t reserved; /* 0 */
+} rwkvtts_limit_desc;
+/* The library's own table builder (host only): out[36]. */
+int rwkvtts_limit_table(const rwkvtts_limit_desc* desc, float* out);
+/* c of a limit in dB (host only), -12 .. 0; outside that (NaN included) RWKVTTS_EINVAL. */
+int rwkvtts_limit_ceiling(double limit_db, float* c);
+/* Streaming plan (host only, a pure function). With samples [0, n_known) of a signal known:
+ * *out_ready_end = max(0, n_known - 70), or n_known with final (n_known is the signal's length);
+ * *in_first_needed = max(0, out_first - 69). Either pointer may be NULL. */
+int rwkvtts_limit_plan(int64_t n_known, int final, int64_t out_first, int64_t* out_ready_end,
+                       int64_t* in_first_needed);
+typedef struct rwkvtts_limit rwkvtts_limit;
+/* table == NULL: the table of rwkvtts_limit_table; otherwise the caller's [36] table (copied). */
+int rwkvtts_limit_create(int device, const rwkvtts_limit_desc* desc, const float* table, rwkvtts_limit** out);
+int rwkvtts_limit_destroy(rwkvtts_limit* l);
+/* n signals (ragged), each with its own ceiling c[i] in (0, 1], in one launch. Host buffers; out[i] has
+ * capacity n_in[i]. n_in[i] == 0 writes nothing. Calls on one handle serialise on its lock. */
+int rwkvtts_limit_batch(rwkvtts_limit* l, const float* const* in, const int64_t* n_in, const float* c, int n,
+                        float* const* out);
+typedef struct {
+  uint32_t struct_size;
+  const float* in;    /* points at sample in_first of the signal */
+  int64_t in_first;
+  int64_t n_in;
+  int32_t final;      /* 1: in_first + n_in is the signal's length */
+  float c;
+  int64_t out_first;  /* outputs [out_first, out_first + out_count), any position */
+  int64_t out_count;
+  float* out;         /* capacity out_count */
+} rwkvtts_limit_window;
+/* n windows (of any signals, any ceiling) in one launch: outputs [out_first, out_first + out_count) of
+ * the whole-signal result, bitwise, whatever follows the known samples. RWKVTTS_EINVAL before anything
+ * is launched (and nothing written) if a requested output needs a sample that is not given: out_first +
+ * out_count > out_ready_end(in_first + n_in, final) or in_first > in_first_needed(out_first) by
+ * rwkvtts_limit_plan. */
+int rwkvtts_limit_windows(rwkvtts_limit* l, const rwkvtts_limit_window* w, int n);
+/* HIP-event time of the last launch (the kernel, no copies), in ms; 0 before the first. */
+int rwkvtts_limit_kernel_ms(rwkvtts_limit* l, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

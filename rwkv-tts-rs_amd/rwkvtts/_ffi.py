@@ -276,6 +276,16 @@ class HighBandWindow(ctypes.Structure):
                 ("out_first", ctypes.c_int64), ("out_count", ctypes.c_int64), ("out", ctypes.c_void_p)]
 
 
+class LimitDesc(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class LimitWindow(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("in_", ctypes.c_void_p), ("in_first", ctypes.c_int64),
+                ("n_in", ctypes.c_int64), ("final", ctypes.c_int32), ("c", ctypes.c_float),
+                ("out_first", ctypes.c_int64), ("out_count", ctypes.c_int64), ("out", ctypes.c_void_p)]
+
+
 class PitchDesc(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("hop", ctypes.c_int32), ("window", ctypes.c_int32),
                 ("lag_min", ctypes.c_int32), ("lag_max", ctypes.c_int32), ("unvoiced", ctypes.c_int32),
@@ -572,6 +582,18 @@ EXPORTS = {
                                               ctypes.c_int, ctypes.c_void_p]),
     "rwkvtts_highband_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HighBandWindow), ctypes.c_int]),
     "rwkvtts_highband_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    # limit: table, ceiling and plan (host only), batched / exact stream windows
+    "rwkvtts_limit_table": (ctypes.c_int, [ctypes.POINTER(LimitDesc), ctypes.c_void_p]),
+    "rwkvtts_limit_ceiling": (ctypes.c_int, [ctypes.c_double, ctypes.POINTER(ctypes.c_float)]),
+    "rwkvtts_limit_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "rwkvtts_limit_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(LimitDesc), ctypes.c_void_p,
+                                            ctypes.POINTER(ctypes.c_void_p)]),
+    "rwkvtts_limit_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "rwkvtts_limit_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_int, ctypes.c_void_p]),
+    "rwkvtts_limit_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(LimitWindow), ctypes.c_int]),
+    "rwkvtts_limit_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
     "rwkvtts_mx_roundtrip": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "rwkvtts_quant_roundtrip": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_void_p]),

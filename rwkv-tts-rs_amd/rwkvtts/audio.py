@@ -858,6 +858,127 @@ class HighBandStream(_ExactStream):
         return self.hb.plan(n_known, False, self._out_next)[1]
 
 
+# ---- the true-peak limiter on the GPU --------------------------------------------------------
+def _limit_table() -> np.ndarray:
+    """h_q[k], q = 1, 2, 3, k = 0 .. 11 of include/rwkvtts.h, in double, one operation at a time,
+    rounded once: the table the kernel reads."""
+    import math
+    pi = math.pi
+    out = []
+    for q in (1, 2, 3):
+        h = []
+        for k in range(12):
+            t = float(k - 5) - float(q) / 4.0
+            h.append(math.sin(pi * t) / (pi * t) * (0.5 + 0.5 * math.cos(pi * t / 6.0)))
+        s = 0.0
+        for v in h:
+            s = s + v
+        out += [v / s for v in h]
+    return np.array(out, dtype=np.float64).astype(F32)
+
+
+class Limiter(_NativeStage):
+    """A look-ahead true-peak limiter as one HIP kernel (csrc/limit.hip; the arithmetic contract is in
+    include/rwkvtts.h): PCM at any rate in, the same number of samples out. The peak of
+    each sample and of three interpolated points between it and the next is held against the ceiling;
+    the gain that takes it there is spread by a 65-sample minimum and a 65-sample mean, so the gain
+    arrives 64 samples early and moves smoothly. No output sample is above the ceiling; a signal whose
+    estimate never passes it comes back bit for bit. An output is a function of its position and
+    x[n - 69 .. n + 70] alone, so a stream's pieces are bitwise the one-shot result. The pipeline applies it
+    last, behind the resampler. A limit is a ceiling in dB per signal, -12 .. 0.
+
+    Every constant is an untuned default and nobody has listened to the output: the repository has no
+    real checkpoint. The kernel reads the table `_limit_table` builds.
+
+    evaluator: a callable (limiter, items) -> [ndarray] standing in for the native window call, items
+    being [(samples from in_first on, in_first, final, c, out_first, out_count)]; no GPU object is
+    created then (the host-only ceiling / plan entry points are still the library's)."""
+    _NAME = "limit"
+
+    def __init__(self, device: int = 0, evaluator=None):
+        self.device = int(device)
+        self._desc = _ffi.LimitDesc(struct_size=ctypes.sizeof(_ffi.LimitDesc), reserved=0)
+        super().__init__(evaluator)
+        self.table = _limit_table()
+        self._create(self.table)
+
+    # ---- host-only plan ----
+    @staticmethod
+    def ceiling(limit: float) -> np.float32:
+        """c = (float)10^(limit / 20) (rwkvtts_limit_ceiling); ValueError outside -12 .. 0."""
+        if isinstance(limit, bool) or not isinstance(limit, (int, float, np.integer, np.floating)) \
+                or not -12.0 <= float(limit) <= 0.0:  # (NaN fails)
+            raise ValueError("limit must be in [-12, 0] dB")
+        c = ctypes.c_float()
+        _native("limit_ceiling", float(limit), ctypes.byref(c))
+        return F32(c.value)
+
+    @staticmethod
+    def plan(n_known: int, final: bool, out_first: int = 0):
+        """(out_ready_end, in_first_needed) of rwkvtts_limit_plan."""
+        end, first = ctypes.c_int64(), ctypes.c_int64()
+        _native("limit_plan", int(n_known), 1 if final else 0, int(out_first), ctypes.byref(end), ctypes.byref(first))
+        return end.value, first.value
+
+    # ---- the kernel ----
+    def limit_windows(self, items) -> list:
+        """[(samples from in_first on, in_first, final, c, out_first, out_count)] -> [outputs [out_first,
+        out_first + out_count) of the whole-signal result], all windows in one launch. Raises
+        RwkvTtsError(EINVAL), with nothing computed, if a window asks for more than plan() allows."""
+        items = [(np.ascontiguousarray(x, dtype=F32).reshape(-1), int(a), bool(f), float(F32(c)), int(o), int(n))
+                 for x, a, f, c, o, n in items]
+        if self._evaluator is not None:
+            return [np.ascontiguousarray(y, dtype=F32) for y in self._evaluator(self, items)]
+        return self._windows("limit_windows", _ffi.LimitWindow, items, c=3, out_first=4)[1]
+
+    def limit_batch(self, signals, limit) -> list:
+        """[signal], [limit in dB] -> [limited signal], ragged, a ceiling per signal, in one launch; an
+        empty signal gives an empty one."""
+        xs = [np.ascontiguousarray(x, dtype=F32).reshape(-1) for x in signals]
+        cs = [self.ceiling(v) for v in limit]
+        if len(xs) != len(cs):
+            raise ValueError("limit_batch: one limit per signal")
+        if self._evaluator is not None:
+            return self.limit_windows([(x, 0, True, c, 0, x.size) for x, c in zip(xs, cs)])
+        if not xs:
+            return []
+        outs, ins, lens, ous = self._ragged(xs, [x.size for x in xs])
+        self._call("limit_batch", ins, lens, (ctypes.c_float * len(cs))(*[float(c) for c in cs]), len(xs), ous)
+        return outs
+
+    def limit(self, x, limit: float) -> np.ndarray:
+        return self.limit_batch([x], [limit])[0]
+
+    def stream(self, limit: float) -> "LimiterStream":
+        return LimiterStream(self, limit)
+
+
+class LimiterStream(_ExactStream):
+    """Limiter.stream(limit): feed(pcm_chunk, final=False) -> the outputs that became exact with it. The
+    concatenation of what feed returns is bitwise Limiter.limit(the concatenated input, limit), however
+    the input was cut. An output goes out once the 70 samples behind it are known (1.5 ms at 48 kHz);
+    the kept tail is what rwkvtts_limit_plan asks for, 69 samples before the cursor."""
+
+    def __init__(self, limiter: Limiter, limit: float):
+        super().__init__()
+        self.lim = limiter
+        self.c = limiter.ceiling(limit)
+        self._out_next = 0     # outputs [0, _out_next) went out
+
+    def _emit(self, n_known, final):
+        end, _ = self.lim.plan(n_known, final, self._out_next)
+        count = end - self._out_next
+        if count > 0:
+            out = self.lim.limit_windows([(self._tail, self._tail_first, final, self.c, self._out_next, count)])[0]
+        else:
+            out = np.zeros(0, dtype=F32)
+        self._out_next = max(end, self._out_next)
+        return out
+
+    def _first_needed(self, n_known):
+        return self.lim.plan(n_known, False, self._out_next)[1]
+
+
 # ---- pitch shift on the GPU ------------------------------------------------------------------
 def pitch_factor(semitones: float) -> float:
     """f = 2^(semitones / 12), in double: what the native side takes per signal."""

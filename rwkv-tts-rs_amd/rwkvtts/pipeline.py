@@ -33,6 +33,11 @@ the band above 8 kHz of a wide-band `sample_rate` empty, as a resampler alone do
 -12 .. 12, takes the 16 kHz PCM to 32 kHz on the GPU with an 8-12 kHz band folded down from its own
 4-8 kHz band (audio.HighBand), last before the resampler, which then runs from
 32 kHz; it needs `sample_rate` 32000, 44100 or 48000; exact over stream chunks.
+All five also take `limit` (no reference counterpart: the reference peak-normalises a finished WAV): None
+leaves the peaks where the stages before put them; a true-peak ceiling in dB, -12 .. 0, holds every
+sample of the result, and the estimated peaks between samples, under it on the GPU with 64 samples of
+look-ahead (audio.Limiter), last of the stages, behind the resampler at the output
+rate -- in long-form on the joined signal -- exact over stream chunks.
 All five also take `watermark` (no reference counterpart: the reference marks nothing): None leaves the
 PCM unmarked; a payload, an integer 0 .. 65535, embeds it as a spread-spectrum mark under the
 pipeline's `watermark_key` (audio.Watermarker) on the 16 kHz PCM, after the
@@ -208,10 +213,10 @@ class LongSpeech(np.ndarray):
 
 def audio_stages(stretcher, tempo, resampler, leveller=None, loudness=None, shifter=None, pitch_shift=None,
                  marker=None, watermark=None, watermark_key=None, shaper=None, max_pause=None,
-                 formant_shift=None, extender=None, highband=None) -> list:
+                 formant_shift=None, extender=None, highband=None, limiter=None, limit=None) -> list:
     """The stages behind the vocoder in the order they apply -- the pause cap at 16 kHz, then the pitch
     shift, then the stretch, then the leveller, then the watermark, then the high band (16 kHz to 32 kHz),
-    then the resampler; None is no
+    then the resampler, then the true-peak limiter at the output rate; None is no
     stage -- each as (batch, stream): batch([pcm]) -> [pcm] in one native call (one cap, one shift, one
     tempo, one loudness, one key and payload for the call), stream() -> an object whose feed(pcm, final)
     is exact over chunks. The pause cap removes samples, so every stage behind it does less work."""
@@ -234,6 +239,8 @@ def audio_stages(stretcher, tempo, resampler, leveller=None, loudness=None, shif
         stages.append((lambda pcm: extender.extend_batch(pcm, [highband] * len(pcm)), lambda: extender.stream(highband)))
     if resampler is not None:
         stages.append((resampler.resample_batch, resampler.stream))
+    if limiter is not None:
+        stages.append((lambda pcm: limiter.limit_batch(pcm, [limit] * len(pcm)), lambda: limiter.stream(limit)))
     return stages
 
 
@@ -271,8 +278,9 @@ class LightweightTtsPipeline:
         self._encoder = None  # audio.FlacEncoder (created on the first `format: "flac"`, kept)
         self._shapers = {}  # threshold -> audio.PauseShaper (created on the first max_pause, kept)
         self._extender = None  # audio.HighBand (created on the first highband, kept)
+        self._limiter = None  # audio.Limiter (created on the first limit, kept)
         self._pause_threshold = None  # the loudness threshold of `max_pause` (None: audio.PauseShaper's default)
-        self._stage_cache_lock = threading.Lock()  # guards all nine (the server's worker threads share the pipeline)
+        self._stage_cache_lock = threading.Lock()  # guards all ten (the server's worker threads share the pipeline)
 
     # ---- output rates other than 16 kHz (no reference counterpart: the reference emits 16 kHz only)
     def resampler(self, sample_rate: Optional[int], sr_in: int = SAMPLE_RATE):
@@ -310,6 +318,21 @@ class LightweightTtsPipeline:
                 from .audio import HighBand
                 self._extender = HighBand(device=getattr(self.codec, "device", 0))
         return self._extender
+
+    # ---- the peak ceiling (no reference counterpart: the reference peak-normalises a finished WAV)
+    def limiter(self, limit: Optional[float]):
+        """None for None (nothing is created: nothing holds the peaks); otherwise the pipeline's one
+        Limiter (the untuned defaults of audio.Limiter), on the codec's GPU. The ceiling is in dB per
+        call, -12 .. 0, not a part of the object. A ceiling outside that, a bool or a NaN raises
+        ValueError before anything is generated."""
+        if limit is None:
+            return None
+        from .audio import Limiter
+        Limiter.ceiling(limit)
+        with self._stage_cache_lock:
+            if self._limiter is None:
+                self._limiter = Limiter(device=getattr(self.codec, "device", 0))
+        return self._limiter
 
     # ---- speaking rate (no reference counterpart: the reference has the `speed` property token only)
     def stretcher(self, tempo: Optional[float]):
@@ -440,7 +463,8 @@ class LightweightTtsPipeline:
     def _stages(self, sample_rate: Optional[int], tempo: Optional[float], loudness: Optional[float] = None,
                 pitch_shift: Optional[float] = None, watermark: Optional[int] = None,
                 max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                highband: Optional[float] = None):  # -> (stages, output rate)
+                highband: Optional[float] = None, limit: Optional[float] = None):  # -> (stages, output rate)
+        lm = self.limiter(limit)
         hb = self.extender(highband, sample_rate)
         rs = self.resampler(sample_rate) if hb is None else self.resampler(sample_rate, 32000)
         lv = self.leveller(loudness)
@@ -453,6 +477,8 @@ class LightweightTtsPipeline:
             kw["formant_shift"] = float(formant_shift)
         if hb is not None:  # (and for highband)
             kw["extender"], kw["highband"] = hb, float(highband)
+        if lm is not None:  # (and for limit)
+            kw["limiter"], kw["limit"] = lm, float(limit)
         return (audio_stages(self.stretcher(tempo), tempo, rs, lv, None if lv is None else float(loudness),
                              sh, None if sh is None else float(pitch_shift or 0.0),
                              mk, None if mk is None else int(watermark), self.watermark_key, **kw),
@@ -525,7 +551,7 @@ class LightweightTtsPipeline:
                         tempo: Optional[float] = None, loudness: Optional[float] = None,
                         watermark: Optional[int] = None, max_pause: Optional[int] = None,
                         formant_shift: Optional[float] = None, highband: Optional[float] = None,
-                        pitch_shift: Optional[float] = None) -> np.ndarray:
+                        limit: Optional[float] = None, pitch_shift: Optional[float] = None) -> np.ndarray:
         """sample_rate None / 16000: the vocoder's 16 kHz PCM. Any other rate: that PCM resampled on
         the GPU (resampler()); the failed-request second of silence is sample_rate zeros.
         tempo None / 1.0: nothing. Any other: the 16 kHz PCM time-stretched on the GPU (stretcher())
@@ -551,9 +577,13 @@ class LightweightTtsPipeline:
         its own 4-8 kHz band (extender(); audio.HighBand), and the resampler then
         runs from 32 kHz (none at sample_rate 32000). It needs sample_rate 32000, 44100 or 48000; the
         failed-request second of silence is sample_rate zeros.
+        limit None: nothing. A ceiling in dB, -12 .. 0: the result at its output rate, behind every other
+        stage, limited on the GPU (limiter(); audio.Limiter): no sample above
+        10^(limit / 20), the same length; the second of silence stays silence. stream_speech's concatenation
+        is bitwise this result, each chunk 70 output samples behind its frames.
         args.global_sampling / semantic_sampling outside their ranges raise ValueError, like tempo."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband, limit)
         try:
             req = self._request(args)
         except ValueError:  # untokenisable text: the request fails -> empty result
@@ -570,7 +600,8 @@ class LightweightTtsPipeline:
                       sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                       loudness: Optional[float] = None, watermark: Optional[int] = None,
                       max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                      highband: Optional[float] = None, pitch_shift: Optional[float] = None):
+                      highband: Optional[float] = None, limit: Optional[float] = None,
+                      pitch_shift: Optional[float] = None):
         """generate_speech as a generator of float32 PCM chunks (SpeechChunk: an ndarray that also
         carries t0, t1, n_known, done), each decoded while the request is still generating tokens.
 
@@ -643,20 +674,24 @@ class LightweightTtsPipeline:
         if highband is not None:
             self.extender(highband, sample_rate)  # (and for a bad level or a rate the stage cannot serve)
             kw["highband"] = highband
+        if limit is not None:
+            self.limiter(limit)  # (and for a bad ceiling)
+            kw["limit"] = limit
         return self.stream_request(req, chunk_frames, sample_rate=sample_rate, tempo=tempo, loudness=loudness, **kw)
 
     def stream_request(self, req: Optional[TtsBatchRequest], chunk_frames: int = 16,
                        sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                        loudness: Optional[float] = None, watermark: Optional[int] = None,
                        max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                       highband: Optional[float] = None, pitch_shift: Optional[float] = None):
+                       highband: Optional[float] = None, limit: Optional[float] = None,
+                       pitch_shift: Optional[float] = None):
         """stream_speech for a request that is already built (None: a request that failed before it
         was submitted)."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         if req is not None:
             check_sampling(req.args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband, limit)
         streams = [stream() for _, stream in stages]
         H = self.codec.halo()
         g, sem, t0, yielded, status = None, [], 0, False, 0
@@ -693,7 +728,8 @@ class LightweightTtsPipeline:
                               sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                               loudness: Optional[float] = None, watermark: Optional[int] = None,
                               max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                              highband: Optional[float] = None, pitch_shift: Optional[float] = None) -> List[np.ndarray]:
+                              highband: Optional[float] = None, limit: Optional[float] = None,
+                              pitch_shift: Optional[float] = None) -> List[np.ndarray]:
         """sample_rate other than None / 16000: the whole batch is resampled in one resample_batch
         call (a failed item stays an empty array). tempo other than None / 1.0: the whole batch is
         first stretched in one stretch_batch call, one tempo for the call. loudness other than None:
@@ -704,10 +740,11 @@ class LightweightTtsPipeline:
         one embed_batch call after the leveller, one payload for the call. max_pause other than None:
         the silences of the whole batch are capped in one shape_batch call before all of them, one
         cap for the call. highband other than None: the whole batch goes to 32 kHz in one extend_batch call
-        before the resampler, one level for the call."""
+        before the resampler, one level for the call. limit other than None: the whole batch is limited in
+        one limit_batch call behind the resampler, one ceiling for the call."""
         for a in batch_args:
             check_sampling(a)
-        stages, _ = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband)
+        stages, _ = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband, limit)
         reqs, idx = [], []
         for i, a in enumerate(batch_args):
             try:
@@ -792,7 +829,8 @@ class LightweightTtsPipeline:
                              trim: bool = True, keep: int = 800, fade: int = 80,
                              loudness: Optional[float] = None, watermark: Optional[int] = None,
                              max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                             highband: Optional[float] = None, pitch_shift: Optional[float] = None) -> "LongSpeech":
+                             highband: Optional[float] = None, limit: Optional[float] = None,
+                             pitch_shift: Optional[float] = None) -> "LongSpeech":
         """generate_speech for a text of any length: the text is cut into segments of at most
         segment_tokens text tokens (segment.split_text), the segments decode side by side in the
         manager's slots and engines with one voice (_long_submit), and their PCM is joined on the
@@ -813,10 +851,10 @@ class LightweightTtsPipeline:
         pauses the join puts between segments are deliberate and stay. A record's `cut` is what the
         cap removed from its segment, and its a, b then refer to the shaped segment. The second of
         silence is not shaped. highband runs where the resampler does, on the joined signal, last before
-        it."""
+        it; limit behind it, on the joined signal at the output rate (there is none inside the join)."""
         check_sampling(args)
         stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, formant_shift=formant_shift,
-                                    highband=highband)
+                                    highband=highband, limit=limit)
         shaper = self.pause_shaper(max_pause)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)
@@ -843,7 +881,7 @@ class LightweightTtsPipeline:
                            trim: bool = True, keep: int = 800, fade: int = 80, loudness: Optional[float] = None,
                            watermark: Optional[int] = None, max_pause: Optional[int] = None,
                            formant_shift: Optional[float] = None, highband: Optional[float] = None,
-                        pitch_shift: Optional[float] = None):
+                           limit: Optional[float] = None, pitch_shift: Optional[float] = None):
         """generate_long_speech as a generator of LongSpeech items, one per segment, in order: segment
         i is emitted once it and every segment before it are done -- decoded, joined alone with its
         gap (a piece depends on its own segment only), and fed through the stages' exact streams,
@@ -858,10 +896,11 @@ class LightweightTtsPipeline:
         block (20 ms).
         max_pause caps the silences of each segment's PCM before its join, one call per segment.
         highband: each joined piece goes through the high-band stream, then the resampler's, as it does
-        through the resampler's alone without it; an item waits for 12.9 ms more of the next piece."""
+        through the resampler's alone without it; an item waits for 12.9 ms more of the next piece.
+        limit: the limiter's stream is the last of them; an item waits for 70 more output samples."""
         check_sampling(args)
         stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, formant_shift=formant_shift,
-                                    highband=highband)
+                                    highband=highband, limit=limit)
         shaper = self.pause_shaper(max_pause)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)

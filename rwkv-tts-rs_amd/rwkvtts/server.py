@@ -81,6 +81,12 @@
   32 kHz on the GPU with a band from 8 to 12 kHz folded down from its own 4-8 kHz band
   (audio.HighBand), last before the resampler, which then runs from 32 kHz. Without the field the
   routes are unchanged.
+* `limit` in the body of both TTS routes (no reference counterpart: the reference peak-normalises the
+  finished WAV, which a stream cannot do, so the stream route hard-clamps at +-1): a JSON number in
+  [LIMIT_MIN, LIMIT_MAX] = [-12, 0] dB, anything else a 400. The result at its output rate is limited
+  on the GPU to that true-peak ceiling (audio.Limiter), last of the stages, behind the resampler.
+  /api/tts then writes its WAV (or FLAC) at scale 1.0, as with `loudness`: the peak rule would undo the
+  ceiling, and both routes send the same samples. Without the field the routes are unchanged.
 * `watermark` in the body of both TTS routes (no reference counterpart: the reference marks nothing):
   a JSON integer in [WATERMARK_MIN, WATERMARK_MAX] = [0, 65535], anything else a 400, and a 400 too on
   a server whose pipeline has no `watermark_key`. The payload is embedded in the 16 kHz PCM under the
@@ -190,6 +196,8 @@ FORMANT_SHIFT_MIN, FORMANT_SHIFT_MAX = -6.0, 6.0
 # dB relative to the stage's default -- the pipeline's range -- and the output rates that can carry it
 HIGHBAND_MIN, HIGHBAND_MAX = -12.0, 12.0
 HIGHBAND_RATES = (32000, 44100, 48000)
+# `limit` of the same bodies (no reference counterpart): the true-peak ceiling in dB -- the pipeline's range
+LIMIT_MIN, LIMIT_MAX = -12.0, 0.0
 # `format` of the same bodies (no reference counterpart): the container of the audio that goes out
 FORMATS = ("wav", "flac")
 # `watermark` of the same bodies (no reference counterpart): the payload of the provenance mark, 16
@@ -307,6 +315,11 @@ def _tts_args(body, voice_dir: str):
     if highband is not None and rate not in HIGHBAND_RATES:
         return (400, {"success": False, "error": f"highband 需要采样率 {', '.join(str(r) for r in HIGHBAND_RATES)}"
                                                  f" (当前: {rate})"}), None, None
+    limit = body.get("limit")
+    if limit is not None and (isinstance(limit, bool) or not isinstance(limit, (int, float))
+                              or not LIMIT_MIN <= limit <= LIMIT_MAX):  # (NaN fails the comparison)
+        return (400, {"success": False, "error": f"不支持的峰值上限: {limit} (支持: "
+                                                 f"{LIMIT_MIN} - {LIMIT_MAX} dB)"}), None, None
     mark = body.get("watermark")
     if mark is not None and (isinstance(mark, bool) or not isinstance(mark, int)
                              or not WATERMARK_MIN <= mark <= WATERMARK_MAX):
@@ -426,6 +439,8 @@ def _tts_args(body, voice_dir: str):
         kw["formant_shift"] = float(formant)
     if highband is not None:
         kw["highband"] = float(highband)
+    if limit is not None:
+        kw["limit"] = float(limit)
     if mark is not None:
         kw["watermark"] = int(mark)
     if max_pause is not None:
@@ -463,14 +478,16 @@ def handle_tts_json(body, pipeline, voice_dir: str = "assets/raf") -> Tuple[int,
         audio = pipeline.generate_long_speech(args, **kw) if long_form else pipeline.generate_speech(args, **kw)
     except Exception as e:  # noqa: BLE001 -- rendered as the reference's 500 body
         return 500, {"success": False, "error": f"生成TTS音频失败: {e}"}
-    # (levelled PCM goes out at scale 1.0, as the stream route sends it: the peak rule would undo the target)
-    if flac:  # the same samples as the WAV below: the peak rule's scale, or 1.0 for levelled PCM
+    # (levelled PCM goes out at scale 1.0, as the stream route sends it: the peak rule would undo the target;
+    # limited PCM likewise: the rule would undo the ceiling)
+    as_is = "loudness" in kw or "limit" in kw
+    if flac:  # the same samples as the WAV below: the peak rule's scale, or 1.0 for levelled or limited PCM
         try:
-            wav = pipeline.encoder().encode(audio, rate, scale=1.0 if "loudness" in kw else float(peak_scale(audio)))
+            wav = pipeline.encoder().encode(audio, rate, scale=1.0 if as_is else float(peak_scale(audio)))
         except Exception as e:  # noqa: BLE001 -- rendered as the reference's 500 body
             return 500, {"success": False, "error": f"生成TTS音频失败: {e}"}
     else:
-        wav = levelled_samples_to_wav(audio, rate) if "loudness" in kw else convert_samples_to_wav(audio, rate)
+        wav = levelled_samples_to_wav(audio, rate) if as_is else convert_samples_to_wav(audio, rate)
     b64 =base64.standard_b64encode(wav).decode("ascii")
     total = time.perf_counter() - t0
     out = {"success": True, "message": "TTS生成成功", "audio_base64": b64,
