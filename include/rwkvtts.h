@@ -1868,6 +1868,90 @@ int rwkvtts_limit_windows(rwkvtts_limit* l, const rwkvtts_limit_window* w, int n
 /* HIP-event time of the last launch (the kernel, no copies), in ms; 0 before the first. */
 int rwkvtts_limit_kernel_ms(rwkvtts_limit* l, double* ms);
 
+/* ---- equaliser: a long FIR on the GPU whose taps the caller shapes, the `eq` of the pipeline -- 16 kHz
+ * PCM in, the same number of samples out (no reference counterpart: the reference has no tone control)
+ * At 16 kHz, behind the stretch and before the leveller. n_out = n. The filter is causal and has no
+ * state but the samples themselves, so a stream's pieces are bitwise the one-shot result. The arithmetic
+ * contract (every output bit is defined by IEEE f32 rounded multiply and rounded add, never fused;
+ * DESIGN.md §42):
+ *   bands     1 .. 8 of (kind, freq_hz, gain_db, q); kind peak, lowshelf, highshelf, highpass, lowpass;
+ *             freq_hz in [50, 7600], gain_db in [-18, 18] (not read for the two pass kinds), q in [0.3, 4].
+ *             Anything else (a NaN fails every comparison) is RWKVTTS_EINVAL.
+ *   biquad    the RBJ Audio-EQ-Cookbook forms at fs = 16000, in double, one operation at a time:
+ *             w = 2 pi freq / fs, cs = cos w, al = sin w / (2 q), A = 10^(gain / 40), be = 2 sqrt(A) al;
+ *             peak       b = (1 + al A, -2 cs, 1 - al A), a = (1 + al / A, -2 cs, 1 - al / A);
+ *             lowshelf   b = (A ((A + 1) - (A - 1) cs + be), 2 A ((A - 1) - (A + 1) cs), A ((A + 1) - (A - 1) cs - be)),
+ *                        a = ((A + 1) + (A - 1) cs + be, -2 ((A - 1) + (A + 1) cs), (A + 1) + (A - 1) cs - be);
+ *             highshelf  b = (A ((A + 1) + (A - 1) cs + be), -2 A ((A - 1) + (A + 1) cs), A ((A + 1) + (A - 1) cs - be)),
+ *                        a = ((A + 1) - (A - 1) cs + be, 2 ((A - 1) - (A + 1) cs), (A + 1) - (A - 1) cs - be);
+ *             lowpass    b = ((1 - cs) / 2, 1 - cs, (1 - cs) / 2), a = (1 + al, -2 cs, 1 - al);
+ *             highpass   b = ((1 + cs) / 2, -(1 + cs), (1 + cs) / 2), a as lowpass;
+ *             then all five of b0 b1 b2 a1 a2 are divided by a0.
+ *   design    h64[0, 8192): the unit impulse through the bands in their listed order, each in direct form I
+ *             in double, t = b0 x; t = t + b1 x1; t = t + b2 x2; t = t - a1 y1; t = t - a2 y2.
+ *             tail(k) = |h64[k]| + tail(k + 1), tail(8192) = 0 (summed from the far end). N is the smallest
+ *             multiple of 64 in [64, 4096] with tail(N) <= 2^-24 tail(0); if there is none the filter rings too
+ *             long for the stage: RWKVTTS_EINVAL, the message naming the band with the lowest freq_hz / q.
+ *             h[k] = (float)h64[k], k < N: a truncated IIR, as the leveller's K-weighting is.
+ *   filter    acc = +0; for k = 0 .. N - 1 ascending: acc = acc + h[k] * x[n - k] (the multiply rounded, then the
+ *             add rounded); y[n] = acc. x[i] = +0 for i < 0.
+ * Reach: y[n] is a pure function of x[n - N + 1 .. n]: no look-ahead, no lag; a stream keeps its last N - 1
+ * samples. A non-finite sample leaves the N outputs from it on unspecified; nothing is read or written out
+ * of bounds. The device profiles built on this (rwkvtts/audio.py) are untuned and nobody has listened to
+ * the output: the repository has no real checkpoint. */
+#define RWKVTTS_EQ_MAX_BANDS 8
+#define RWKVTTS_EQ_MAX_TAPS 4096
+#define RWKVTTS_EQ_TAP_STEP 64
+enum { RWKVTTS_EQ_PEAK = 0, RWKVTTS_EQ_LOWSHELF = 1, RWKVTTS_EQ_HIGHSHELF = 2, RWKVTTS_EQ_HIGHPASS = 3, RWKVTTS_EQ_LOWPASS = 4 };
+typedef struct {
+  int32_t kind;
+  int32_t reserved; /* 0 */
+  double freq_hz;
+  double gain_db;
+  double q;
+} rwkvtts_eq_band;
+/* The design (host only, a pure function): *n_taps = N, taps[0, N) = h (taps has capacity
+ * RWKVTTS_EQ_MAX_TAPS, or is NULL), *sum_abs = tail(0) in double (or NULL). */
+int rwkvtts_eq_design(const rwkvtts_eq_band* bands, int n_bands, float* taps, int32_t* n_taps, double* sum_abs);
+/* Streaming plan (host only, a pure function) of a filter of n_taps taps. With samples [0, n_known) of
+ * a signal known: *out_ready_end = n_known, with or without final (there is no look-ahead);
+ * *in_first_needed = max(0, out_first - (n_taps - 1)). Either pointer may be NULL. */
+int rwkvtts_eq_plan(int32_t n_taps, int64_t n_known, int final, int64_t out_first, int64_t* out_ready_end,
+                    int64_t* in_first_needed);
+typedef struct rwkvtts_eq rwkvtts_eq;
+typedef struct {
+  uint32_t struct_size;
+  uint32_t reserved; /* 0 */
+} rwkvtts_eq_desc;
+int rwkvtts_eq_create(int device, const rwkvtts_eq_desc* desc, rwkvtts_eq** out);
+int rwkvtts_eq_destroy(rwkvtts_eq* e);
+/* The tap sets of a call: n_sets of them back to back in table, set s of set_taps[s] taps (a multiple of
+ * RWKVTTS_EQ_TAP_STEP in [64, 4096]; from rwkvtts_eq_design, or the caller's own), copied to the device with
+ * the call.
+ * n signals (ragged), signal i filtered with set set[i], in one launch. Host buffers; out[i] has capacity
+ * n_in[i]. n_in[i] == 0 writes nothing. Calls on one handle serialise on its lock. */
+int rwkvtts_eq_batch(rwkvtts_eq* e, const float* const* in, const int64_t* n_in, const int32_t* set, int n,
+                     const float* table, const int32_t* set_taps, int n_sets, float* const* out);
+typedef struct {
+  uint32_t struct_size;
+  const float* in;    /* points at sample in_first of the signal */
+  int64_t in_first;
+  int64_t n_in;
+  int32_t final;      /* not read: an output never waits for a later sample */
+  int32_t set;        /* the window's tap set */
+  int64_t out_first;  /* outputs [out_first, out_first + out_count), any position */
+  int64_t out_count;
+  float* out;         /* capacity out_count */
+} rwkvtts_eq_window;
+/* n windows (of any signals, any set) in one launch: outputs [out_first, out_first + out_count) of the
+ * whole-signal result, bitwise. RWKVTTS_EINVAL before anything is launched (and nothing written) if a
+ * requested output needs a sample that is not given: out_first + out_count > in_first + n_in or
+ * in_first > in_first_needed(out_first) by rwkvtts_eq_plan. */
+int rwkvtts_eq_windows(rwkvtts_eq* e, const rwkvtts_eq_window* w, int n, const float* table, const int32_t* set_taps,
+                       int n_sets);
+/* HIP-event time of the last launch (the kernel, no copies), in ms; 0 before the first. */
+int rwkvtts_eq_kernel_ms(rwkvtts_eq* e, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -286,6 +286,21 @@ class LimitWindow(ctypes.Structure):
                 ("out_first", ctypes.c_int64), ("out_count", ctypes.c_int64), ("out", ctypes.c_void_p)]
 
 
+class EqBand(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("reserved", ctypes.c_int32), ("freq_hz", ctypes.c_double),
+                ("gain_db", ctypes.c_double), ("q", ctypes.c_double)]
+
+
+class EqDesc(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class EqWindow(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("in_", ctypes.c_void_p), ("in_first", ctypes.c_int64),
+                ("n_in", ctypes.c_int64), ("final", ctypes.c_int32), ("set", ctypes.c_int32),
+                ("out_first", ctypes.c_int64), ("out_count", ctypes.c_int64), ("out", ctypes.c_void_p)]
+
+
 class PitchDesc(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("hop", ctypes.c_int32), ("window", ctypes.c_int32),
                 ("lag_min", ctypes.c_int32), ("lag_max", ctypes.c_int32), ("unvoiced", ctypes.c_int32),
@@ -594,6 +609,18 @@ EXPORTS = {
                                            ctypes.c_int, ctypes.c_void_p]),
     "rwkvtts_limit_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(LimitWindow), ctypes.c_int]),
     "rwkvtts_limit_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    # eq: design and plan (host only), batched / exact stream windows, the call's tap sets with each
+    "rwkvtts_eq_design": (ctypes.c_int, [ctypes.POINTER(EqBand), ctypes.c_int, ctypes.c_void_p,
+                                         ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)]),
+    "rwkvtts_eq_plan": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                       ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "rwkvtts_eq_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(EqDesc), ctypes.POINTER(ctypes.c_void_p)]),
+    "rwkvtts_eq_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "rwkvtts_eq_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "rwkvtts_eq_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(EqWindow), ctypes.c_int, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_int]),
+    "rwkvtts_eq_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
     "rwkvtts_mx_roundtrip": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "rwkvtts_quant_roundtrip": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_void_p]),

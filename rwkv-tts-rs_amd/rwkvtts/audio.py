@@ -214,9 +214,10 @@ class _NativeStage:
         return (outs, P(*[x.ctypes.data for x in xs]), (ctypes.c_int64 * len(xs))(*[x.size for x in xs]),
                 P(*[o.ctypes.data for o in outs]))
 
-    def _windows(self, name, Struct, items, **own):
+    def _windows(self, name, Struct, items, *more, **own):
         """One rwkvtts_<name> call over items (samples, in_first, final, .., out_count) -> (the
-        Struct array, the outputs); own: the stage's further fields by their position in an item."""
+        Struct array, the outputs); own: the stage's further fields by their position in an item;
+        more: the call's arguments behind the window count."""
         ws = (Struct * len(items))()
         outs = [np.empty(max(it[-1], 0), dtype=F32) for it in items]
         for w, it, out in zip(ws, items, outs):
@@ -226,7 +227,7 @@ class _NativeStage:
             for field, k in own.items():
                 setattr(w, field, it[k])
         if items:
-            self._call(name, ws, len(items))
+            self._call(name, ws, len(items), *more)
         return ws, outs
 
     def kernel_ms(self) -> float:
@@ -977,6 +978,183 @@ class LimiterStream(_ExactStream):
 
     def _first_needed(self, n_known):
         return self.lim.plan(n_known, False, self._out_next)[1]
+
+
+# ---- the equaliser on the GPU ----------------------------------------------------------------
+EQ_KINDS = ("peak", "lowshelf", "highshelf", "highpass", "lowpass")  # their RWKVTTS_EQ_* values, in order
+EQ_FREQ, EQ_GAIN, EQ_Q, EQ_MAX_BANDS = (50.0, 7600.0), (-18.0, 18.0), (0.3, 4.0), 8
+# Device profiles: names for band lists (kind, freq_hz, gain_db, q). Untuned, and nobody has listened to them.
+EQ_PROFILES = {
+    "telephony": (("highpass", 300.0, 0.0, 0.7071), ("lowpass", 3400.0, 0.0, 0.7071)),
+    "small_speaker": (("highpass", 250.0, 0.0, 0.7071), ("peak", 2500.0, 3.0, 1.0)),
+    "presence": (("peak", 3000.0, 4.0, 1.0), ("highshelf", 6000.0, 2.0, 0.7071)),
+    "warm": (("lowshelf", 200.0, 3.0, 0.7071), ("highshelf", 5000.0, -3.0, 0.7071)),
+}
+
+
+def eq_bands(eq) -> tuple:
+    """An `eq` value -- a profile name, or 1 .. 8 bands, each (kind, freq_hz, gain_db, q) or a mapping with
+    "type", "freq", "gain" (optional for the two pass kinds, which do not read it) and "q" -- as a tuple of
+    (kind, freq_hz, gain_db, q) with float fields; ValueError for anything else (an unknown name or kind, a
+    bool, a NaN, a value outside 50 .. 7600 Hz, -18 .. 18 dB, 0.3 .. 4)."""
+    if isinstance(eq, str):
+        if eq not in EQ_PROFILES:
+            raise ValueError(f"eq: unknown profile {eq!r} (known: {', '.join(EQ_PROFILES)})")
+        return EQ_PROFILES[eq]
+    if not isinstance(eq, (list, tuple)) or not 1 <= len(eq) <= EQ_MAX_BANDS:
+        raise ValueError(f"eq must be a profile name or 1 .. {EQ_MAX_BANDS} bands")
+
+    def number(v, lo, hi, what):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not lo <= float(v) <= hi:
+            raise ValueError(f"eq: {what} must be in [{lo}, {hi}]")  # (NaN fails)
+        return float(v)
+
+    out = []
+    for band in eq:
+        if isinstance(band, dict):
+            band = (band.get("type"), band.get("freq"), band.get("gain", 0.0), band.get("q"))
+        if not isinstance(band, (list, tuple)) or len(band) != 4:
+            raise ValueError("eq: a band is (kind, freq_hz, gain_db, q)")
+        kind, freq, gain, q = band
+        if not isinstance(kind, str) or kind not in EQ_KINDS:
+            raise ValueError(f"eq: a band's kind must be one of {', '.join(EQ_KINDS)}")
+        passes = kind in ("highpass", "lowpass")
+        out.append((kind, number(freq, *EQ_FREQ, "freq_hz"), 0.0 if passes else number(gain, *EQ_GAIN, "gain_db"),
+                    number(q, *EQ_Q, "q")))
+    return tuple(out)
+
+
+class Equaliser(_NativeStage):
+    """A FIR of 64 .. 4096 taps the caller shapes, as one HIP kernel (csrc/eq.hip; the arithmetic contract
+    is in include/rwkvtts.h): 16 kHz PCM in, the same number of samples out. A spec is what
+    eq_bands takes: a profile name or 1 .. 8 cookbook biquads. design() turns it into taps -- the cascade's
+    impulse response in double, cut where its tail is under 2^-24 of its sum -- and the kernel runs the
+    sequential f32 sum over them, so a stream's pieces are bitwise the one-shot result, with no lag. The
+    pipeline applies it after the stretch and before the leveller.
+
+    The profiles are untuned and nobody has listened to the output: the repository has no real checkpoint.
+
+    evaluator: a callable (equaliser, items, table) -> [ndarray] standing in for the native window call,
+    items being [(samples from in_first on, in_first, final, set, out_first, out_count)] and table the
+    call's tap sets; no GPU object is created then (the host-only design / plan are still the library's)."""
+    _NAME = "eq"
+
+    def __init__(self, device: int = 0, evaluator=None):
+        self.device = int(device)
+        self._desc = _ffi.EqDesc(struct_size=ctypes.sizeof(_ffi.EqDesc), reserved=0)
+        super().__init__(evaluator)
+        self._designed = {}  # bands -> taps
+        if evaluator is None:  # (no table of its own: the tap sets travel with each call)
+            h = ctypes.c_void_p()
+            _native("eq_create", self.device, ctypes.byref(self._desc), ctypes.byref(h))
+            self._h = h
+
+    # ---- host-only design and plan ----
+    @staticmethod
+    def design(spec) -> np.ndarray:
+        """The taps of a spec (rwkvtts_eq_design), f32, a multiple of 64 of them; ValueError for a bad
+        spec and for a filter that rings past 4096 taps."""
+        bands = eq_bands(spec)
+        arr = (_ffi.EqBand * len(bands))(*[_ffi.EqBand(kind=EQ_KINDS.index(k), reserved=0, freq_hz=f, gain_db=g, q=q)
+                                          for k, f, g, q in bands])
+        taps, n = np.empty(4096, dtype=F32), ctypes.c_int32()
+        rc = _ffi.lib().rwkvtts_eq_design(arr, len(bands), taps.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n), None)
+        if rc == _ffi.EINVAL:
+            raise ValueError(_ffi.lib().rwkvtts_last_error().decode("utf-8", "replace"))
+        _ffi.check(rc, "eq_design")
+        return taps[:n.value].copy()
+
+    def taps(self, spec) -> np.ndarray:
+        """design(spec), kept per band list."""
+        bands = eq_bands(spec)
+        with self._lock:
+            t = self._designed.get(bands)
+        if t is None:
+            t = self.design(bands)
+            with self._lock:
+                self._designed[bands] = t
+        return t
+
+    @staticmethod
+    def plan(n_taps: int, n_known: int, final: bool, out_first: int = 0):
+        """(out_ready_end, in_first_needed) of rwkvtts_eq_plan."""
+        end, first = ctypes.c_int64(), ctypes.c_int64()
+        _native("eq_plan", int(n_taps), int(n_known), 1 if final else 0, int(out_first), ctypes.byref(end), ctypes.byref(first))
+        return end.value, first.value
+
+    # ---- the kernel ----
+    @staticmethod
+    def _table(table):
+        """[tap set] -> (the sets as f32 arrays, float table[], int32 set_taps[]) of a native call."""
+        sets = [np.ascontiguousarray(t, dtype=F32).reshape(-1) for t in table]
+        flat = np.concatenate(sets) if sets else np.zeros(0, dtype=F32)
+        return sets, flat, (ctypes.c_int32 * len(sets))(*[t.size for t in sets])
+
+    def eq_windows(self, items, table) -> list:
+        """[(samples from in_first on, in_first, final, set, out_first, out_count)], [tap set] -> [outputs
+        [out_first, out_first + out_count) of the whole-signal result], all windows in one launch. Raises
+        RwkvTtsError(EINVAL), with nothing computed, if a window asks for more than plan() allows."""
+        items = [(np.ascontiguousarray(x, dtype=F32).reshape(-1), int(a), bool(f), int(s), int(o), int(n))
+                 for x, a, f, s, o, n in items]
+        sets, flat, lens = self._table(table)
+        if self._evaluator is not None:
+            return [np.ascontiguousarray(y, dtype=F32) for y in self._evaluator(self, items, sets)]
+        return self._windows("eq_windows", _ffi.EqWindow, items, flat.ctypes.data_as(ctypes.c_void_p), lens, len(sets),
+                             set=3, out_first=4)[1]
+
+    def eq_batch(self, pcm, specs, table=None) -> list:
+        """[signal], [spec] -> [equalised signal], ragged, a spec per signal, in one launch: the distinct
+        band lists of the call are designed once and their tap sets go to the device back to back. With
+        table (a list of tap sets, each a multiple of 64 taps in 64 .. 4096) nothing is designed and
+        specs[i] is the index of signal i's set in it. An empty signal gives an empty one."""
+        xs = [np.ascontiguousarray(x, dtype=F32).reshape(-1) for x in pcm]
+        if len(xs) != len(specs):
+            raise ValueError("eq_batch: one spec per signal")
+        if table is None:
+            bands = [eq_bands(s) for s in specs]
+            distinct = list(dict.fromkeys(bands))
+            table, specs = [self.taps(b) for b in distinct], [distinct.index(b) for b in bands]
+        if self._evaluator is not None:
+            return self.eq_windows([(x, 0, True, s, 0, x.size) for x, s in zip(xs, specs)], table)
+        if not xs:
+            return []
+        sets, flat, lens = self._table(table)
+        outs, ins, n_in, ous = self._ragged(xs, [x.size for x in xs])
+        self._call("eq_batch", ins, n_in, (ctypes.c_int32 * len(xs))(*[int(s) for s in specs]), len(xs),
+                   flat.ctypes.data_as(ctypes.c_void_p), lens, len(sets), ous)
+        return outs
+
+    def eq(self, x, spec) -> np.ndarray:
+        return self.eq_batch([x], [spec])[0]
+
+    def stream(self, spec) -> "EqStream":
+        return EqStream(self, spec)
+
+
+class EqStream(_ExactStream):
+    """Equaliser.stream(spec): feed(pcm_chunk, final=False) -> as many samples as it was given, at once:
+    the filter is causal. The concatenation of what feed returns is bitwise Equaliser.eq(the concatenated
+    input, spec), however the input was cut; the kept tail is what rwkvtts_eq_plan asks for, the last
+    N - 1 samples."""
+
+    def __init__(self, equaliser: Equaliser, spec):
+        super().__init__()
+        self.eq = equaliser
+        self.h = equaliser.taps(spec)
+        self._out_next = 0     # outputs [0, _out_next) went out
+
+    def _emit(self, n_known, final):
+        end, _ = self.eq.plan(self.h.size, n_known, final, self._out_next)
+        count = end - self._out_next
+        if count > 0:
+            out = self.eq.eq_windows([(self._tail, self._tail_first, final, 0, self._out_next, count)], [self.h])[0]
+        else:
+            out = np.zeros(0, dtype=F32)
+        self._out_next = max(end, self._out_next)
+        return out
+
+    def _first_needed(self, n_known):
+        return self.eq.plan(self.h.size, n_known, False, self._out_next)[1]
 
 
 # ---- pitch shift on the GPU ------------------------------------------------------------------

@@ -38,6 +38,11 @@ leaves the peaks where the stages before put them; a true-peak ceiling in dB, -1
 sample of the result, and the estimated peaks between samples, under it on the GPU with 64 samples of
 look-ahead (audio.Limiter), last of the stages, behind the resampler at the output
 rate -- in long-form on the joined signal -- exact over stream chunks.
+All five also take `eq` (no reference counterpart: the reference has no tone control): None leaves the
+spectral balance alone; a device profile name (audio.EQ_PROFILES) or 1 .. 8 bands (kind, freq_hz, gain_db,
+q) filter the 16 kHz PCM on the GPU with the FIR they design, 64 .. 4096 taps (audio.Equaliser, DESIGN.md
+section 42), after the stretch and before the leveller, which so restores the level the filter changed --
+in long-form on each segment -- exact over stream chunks, with no lag.
 All five also take `watermark` (no reference counterpart: the reference marks nothing): None leaves the
 PCM unmarked; a payload, an integer 0 .. 65535, embeds it as a spread-spectrum mark under the
 pipeline's `watermark_key` (audio.Watermarker) on the 16 kHz PCM, after the
@@ -213,9 +218,10 @@ class LongSpeech(np.ndarray):
 
 def audio_stages(stretcher, tempo, resampler, leveller=None, loudness=None, shifter=None, pitch_shift=None,
                  marker=None, watermark=None, watermark_key=None, shaper=None, max_pause=None,
-                 formant_shift=None, extender=None, highband=None, limiter=None, limit=None) -> list:
+                 formant_shift=None, extender=None, highband=None, limiter=None, limit=None,
+                 equaliser=None, eq=None) -> list:
     """The stages behind the vocoder in the order they apply -- the pause cap at 16 kHz, then the pitch
-    shift, then the stretch, then the leveller, then the watermark, then the high band (16 kHz to 32 kHz),
+    shift, then the stretch, then the equaliser, then the leveller, then the watermark, then the high band (16 kHz to 32 kHz),
     then the resampler, then the true-peak limiter at the output rate; None is no
     stage -- each as (batch, stream): batch([pcm]) -> [pcm] in one native call (one cap, one shift, one
     tempo, one loudness, one key and payload for the call), stream() -> an object whose feed(pcm, final)
@@ -230,6 +236,8 @@ def audio_stages(stretcher, tempo, resampler, leveller=None, loudness=None, shif
                        lambda: shifter.stream(pitch_shift, formant_shift)))
     if stretcher is not None:
         stages.append((lambda pcm: stretcher.stretch_batch(pcm, [tempo] * len(pcm)), lambda: stretcher.stream(tempo)))
+    if equaliser is not None:
+        stages.append((lambda pcm: equaliser.eq_batch(pcm, [eq] * len(pcm)), lambda: equaliser.stream(eq)))
     if leveller is not None:
         stages.append((lambda pcm: leveller.level_batch(pcm, [loudness] * len(pcm)), lambda: leveller.stream(loudness)))
     if marker is not None:
@@ -279,8 +287,9 @@ class LightweightTtsPipeline:
         self._shapers = {}  # threshold -> audio.PauseShaper (created on the first max_pause, kept)
         self._extender = None  # audio.HighBand (created on the first highband, kept)
         self._limiter = None  # audio.Limiter (created on the first limit, kept)
+        self._equaliser = None  # audio.Equaliser (created on the first eq, kept)
         self._pause_threshold = None  # the loudness threshold of `max_pause` (None: audio.PauseShaper's default)
-        self._stage_cache_lock = threading.Lock()  # guards all ten (the server's worker threads share the pipeline)
+        self._stage_cache_lock = threading.Lock()  # guards all eleven (the server's worker threads share the pipeline)
 
     # ---- output rates other than 16 kHz (no reference counterpart: the reference emits 16 kHz only)
     def resampler(self, sample_rate: Optional[int], sr_in: int = SAMPLE_RATE):
@@ -333,6 +342,28 @@ class LightweightTtsPipeline:
             if self._limiter is None:
                 self._limiter = Limiter(device=getattr(self.codec, "device", 0))
         return self._limiter
+
+    # ---- the spectral balance (no reference counterpart: the reference has no tone control)
+    def equaliser(self, eq):
+        """(None, None) for None (nothing is created: the balance is the vocoder's); otherwise the
+        pipeline's one Equaliser on the codec's GPU and the bands of `eq` -- a profile name or 1 .. 8
+        (kind, freq_hz, gain_db, q), not a part of the object -- designed once and kept. An unknown name
+        or kind, a value out of range, a bool, a NaN or a filter that rings past 4096 taps raises
+        ValueError before anything is generated."""
+        if eq is None:
+            return None, None
+        from .audio import Equaliser, eq_bands
+        bands = eq_bands(eq)
+        with self._stage_cache_lock:
+            e = self._equaliser
+        if e is None:
+            Equaliser.design(bands)  # (a filter the stage cannot run is refused before an object exists)
+            with self._stage_cache_lock:
+                if self._equaliser is None:
+                    self._equaliser = Equaliser(device=getattr(self.codec, "device", 0))
+                e = self._equaliser
+        e.taps(bands)
+        return e, bands
 
     # ---- speaking rate (no reference counterpart: the reference has the `speed` property token only)
     def stretcher(self, tempo: Optional[float]):
@@ -463,7 +494,8 @@ class LightweightTtsPipeline:
     def _stages(self, sample_rate: Optional[int], tempo: Optional[float], loudness: Optional[float] = None,
                 pitch_shift: Optional[float] = None, watermark: Optional[int] = None,
                 max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                highband: Optional[float] = None, limit: Optional[float] = None):  # -> (stages, output rate)
+                highband: Optional[float] = None, limit: Optional[float] = None, eq=None):  # -> (stages, output rate)
+        eqr, bands = self.equaliser(eq)
         lm = self.limiter(limit)
         hb = self.extender(highband, sample_rate)
         rs = self.resampler(sample_rate) if hb is None else self.resampler(sample_rate, 32000)
@@ -479,6 +511,8 @@ class LightweightTtsPipeline:
             kw["extender"], kw["highband"] = hb, float(highband)
         if lm is not None:  # (and for limit)
             kw["limiter"], kw["limit"] = lm, float(limit)
+        if eqr is not None:  # (and for eq)
+            kw["equaliser"], kw["eq"] = eqr, bands
         return (audio_stages(self.stretcher(tempo), tempo, rs, lv, None if lv is None else float(loudness),
                              sh, None if sh is None else float(pitch_shift or 0.0),
                              mk, None if mk is None else int(watermark), self.watermark_key, **kw),
@@ -551,7 +585,7 @@ class LightweightTtsPipeline:
                         tempo: Optional[float] = None, loudness: Optional[float] = None,
                         watermark: Optional[int] = None, max_pause: Optional[int] = None,
                         formant_shift: Optional[float] = None, highband: Optional[float] = None,
-                        limit: Optional[float] = None, pitch_shift: Optional[float] = None) -> np.ndarray:
+                        limit: Optional[float] = None, eq=None, pitch_shift: Optional[float] = None) -> np.ndarray:
         """sample_rate None / 16000: the vocoder's 16 kHz PCM. Any other rate: that PCM resampled on
         the GPU (resampler()); the failed-request second of silence is sample_rate zeros.
         tempo None / 1.0: nothing. Any other: the 16 kHz PCM time-stretched on the GPU (stretcher())
@@ -581,9 +615,13 @@ class LightweightTtsPipeline:
         stage, limited on the GPU (limiter(); audio.Limiter): no sample above
         10^(limit / 20), the same length; the second of silence stays silence. stream_speech's concatenation
         is bitwise this result, each chunk 70 output samples behind its frames.
+        eq None: nothing. A profile name of audio.EQ_PROFILES or 1 .. 8 bands (kind, freq_hz, gain_db, q):
+        the 16 kHz PCM filtered on the GPU by the FIR they design (equaliser(); audio.Equaliser, DESIGN.md
+        section 42), after the stretch and before the leveller, the same length and no lag; the second of
+        silence stays silence. stream_speech's concatenation is bitwise this result.
         args.global_sampling / semantic_sampling outside their ranges raise ValueError, like tempo."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband, limit)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband, limit, eq)
         try:
             req = self._request(args)
         except ValueError:  # untokenisable text: the request fails -> empty result
@@ -600,7 +638,7 @@ class LightweightTtsPipeline:
                       sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                       loudness: Optional[float] = None, watermark: Optional[int] = None,
                       max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                      highband: Optional[float] = None, limit: Optional[float] = None,
+                      highband: Optional[float] = None, limit: Optional[float] = None, eq=None,
                       pitch_shift: Optional[float] = None):
         """generate_speech as a generator of float32 PCM chunks (SpeechChunk: an ndarray that also
         carries t0, t1, n_known, done), each decoded while the request is still generating tokens.
@@ -677,13 +715,16 @@ class LightweightTtsPipeline:
         if limit is not None:
             self.limiter(limit)  # (and for a bad ceiling)
             kw["limit"] = limit
+        if eq is not None:
+            self.equaliser(eq)  # (and for a bad band or profile)
+            kw["eq"] = eq
         return self.stream_request(req, chunk_frames, sample_rate=sample_rate, tempo=tempo, loudness=loudness, **kw)
 
     def stream_request(self, req: Optional[TtsBatchRequest], chunk_frames: int = 16,
                        sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                        loudness: Optional[float] = None, watermark: Optional[int] = None,
                        max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                       highband: Optional[float] = None, limit: Optional[float] = None,
+                       highband: Optional[float] = None, limit: Optional[float] = None, eq=None,
                        pitch_shift: Optional[float] = None):
         """stream_speech for a request that is already built (None: a request that failed before it
         was submitted)."""
@@ -691,7 +732,7 @@ class LightweightTtsPipeline:
             raise ValueError("chunk_frames must be >= 1")
         if req is not None:
             check_sampling(req.args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband, limit)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband, limit, eq)
         streams = [stream() for _, stream in stages]
         H = self.codec.halo()
         g, sem, t0, yielded, status = None, [], 0, False, 0
@@ -728,7 +769,7 @@ class LightweightTtsPipeline:
                               sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                               loudness: Optional[float] = None, watermark: Optional[int] = None,
                               max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                              highband: Optional[float] = None, limit: Optional[float] = None,
+                              highband: Optional[float] = None, limit: Optional[float] = None, eq=None,
                               pitch_shift: Optional[float] = None) -> List[np.ndarray]:
         """sample_rate other than None / 16000: the whole batch is resampled in one resample_batch
         call (a failed item stays an empty array). tempo other than None / 1.0: the whole batch is
@@ -744,7 +785,7 @@ class LightweightTtsPipeline:
         one limit_batch call behind the resampler, one ceiling for the call."""
         for a in batch_args:
             check_sampling(a)
-        stages, _ = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband, limit)
+        stages, _ = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband, limit, eq)
         reqs, idx = [], []
         for i, a in enumerate(batch_args):
             try:
@@ -829,7 +870,7 @@ class LightweightTtsPipeline:
                              trim: bool = True, keep: int = 800, fade: int = 80,
                              loudness: Optional[float] = None, watermark: Optional[int] = None,
                              max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                             highband: Optional[float] = None, limit: Optional[float] = None,
+                             highband: Optional[float] = None, limit: Optional[float] = None, eq=None,
                              pitch_shift: Optional[float] = None) -> "LongSpeech":
         """generate_speech for a text of any length: the text is cut into segments of at most
         segment_tokens text tokens (segment.split_text), the segments decode side by side in the
@@ -851,10 +892,12 @@ class LightweightTtsPipeline:
         pauses the join puts between segments are deliberate and stay. A record's `cut` is what the
         cap removed from its segment, and its a, b then refer to the shaped segment. The second of
         silence is not shaped. highband runs where the resampler does, on the joined signal, last before
-        it; limit behind it, on the joined signal at the output rate (there is none inside the join)."""
+        it; limit behind it, on the joined signal at the output rate (there is none inside the join). eq
+        filters the joined signal as one, after the stretch and before the leveller, as the other 16 kHz
+        stages of the fold do: the filter rings through a pause as it would in one utterance."""
         check_sampling(args)
         stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, formant_shift=formant_shift,
-                                    highband=highband, limit=limit)
+                                    highband=highband, limit=limit, eq=eq)
         shaper = self.pause_shaper(max_pause)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)
@@ -881,7 +924,7 @@ class LightweightTtsPipeline:
                            trim: bool = True, keep: int = 800, fade: int = 80, loudness: Optional[float] = None,
                            watermark: Optional[int] = None, max_pause: Optional[int] = None,
                            formant_shift: Optional[float] = None, highband: Optional[float] = None,
-                           limit: Optional[float] = None, pitch_shift: Optional[float] = None):
+                           limit: Optional[float] = None, eq=None, pitch_shift: Optional[float] = None):
         """generate_long_speech as a generator of LongSpeech items, one per segment, in order: segment
         i is emitted once it and every segment before it are done -- decoded, joined alone with its
         gap (a piece depends on its own segment only), and fed through the stages' exact streams,
@@ -900,7 +943,7 @@ class LightweightTtsPipeline:
         limit: the limiter's stream is the last of them; an item waits for 70 more output samples."""
         check_sampling(args)
         stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, formant_shift=formant_shift,
-                                    highband=highband, limit=limit)
+                                    highband=highband, limit=limit, eq=eq)
         shaper = self.pause_shaper(max_pause)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)

@@ -87,6 +87,13 @@
   on the GPU to that true-peak ceiling (audio.Limiter), last of the stages, behind the resampler.
   /api/tts then writes its WAV (or FLAC) at scale 1.0, as with `loudness`: the peak rule would undo the
   ceiling, and both routes send the same samples. Without the field the routes are unchanged.
+* `eq` in the body of both TTS routes (no reference counterpart: the reference has no tone control): a
+  device profile name of audio.EQ_PROFILES ("telephony", "small_speaker", "presence", "warm"), or a list of
+  1 .. 8 objects {"type", "freq", "gain", "q"} -- type peak, lowshelf, highshelf, highpass or lowpass (which
+  two read no gain), freq 50 .. 7600 Hz, gain -18 .. 18 dB, q 0.3 .. 4 -- anything else, and a filter that
+  rings past 4096 taps, a 400. The 16 kHz PCM is filtered on the GPU (audio.Equaliser) after the stretch
+  and before the leveller. `eq` alone keeps /api/tts's peak rule. Without the field the routes are
+  unchanged.
 * `watermark` in the body of both TTS routes (no reference counterpart: the reference marks nothing):
   a JSON integer in [WATERMARK_MIN, WATERMARK_MAX] = [0, 65535], anything else a 400, and a 400 too on
   a server whose pipeline has no `watermark_key`. The payload is embedded in the 16 kHz PCM under the
@@ -320,6 +327,17 @@ def _tts_args(body, voice_dir: str):
                               or not LIMIT_MIN <= limit <= LIMIT_MAX):  # (NaN fails the comparison)
         return (400, {"success": False, "error": f"不支持的峰值上限: {limit} (支持: "
                                                  f"{LIMIT_MIN} - {LIMIT_MAX} dB)"}), None, None
+    eq = body.get("eq")
+    if eq is not None:
+        from .audio import EQ_PROFILES, Equaliser, eq_bands
+        try:
+            if not isinstance(eq, str) and not (isinstance(eq, list) and all(isinstance(b, dict) for b in eq)):
+                raise ValueError("eq must be a profile name or a list of band objects")
+            eq = eq_bands(eq)
+            Equaliser.design(eq)  # (host only: a filter that rings past the stage's 4096 taps is refused here)
+        except ValueError as e:
+            return (400, {"success": False, "error": f"不支持的均衡器: {e} (支持: {', '.join(EQ_PROFILES)}, 或 1 - 8 个 "
+                                                     '{"type", "freq", "gain", "q"} 频段)'}), None, None
     mark = body.get("watermark")
     if mark is not None and (isinstance(mark, bool) or not isinstance(mark, int)
                              or not WATERMARK_MIN <= mark <= WATERMARK_MAX):
@@ -441,6 +459,8 @@ def _tts_args(body, voice_dir: str):
         kw["highband"] = float(highband)
     if limit is not None:
         kw["limit"] = float(limit)
+    if eq is not None:
+        kw["eq"] = eq
     if mark is not None:
         kw["watermark"] = int(mark)
     if max_pause is not None:
