@@ -1952,6 +1952,94 @@ int rwkvtts_eq_windows(rwkvtts_eq* e, const rwkvtts_eq_window* w, int n, const f
 /* HIP-event time of the last launch (the kernel, no copies), in ms; 0 before the first. */
 int rwkvtts_eq_kernel_ms(rwkvtts_eq* e, double* ms);
 
+/* ---- denoise: an STFT spectral gate on the GPU, the `denoise` of the pipeline -- 16 kHz PCM in, the
+ * same number of samples out (no reference counterpart: the reference ships the vocoder's PCM as it is)
+ * First of the stages, on the vocoder's PCM. n_out = n. A frame's arithmetic depends on its absolute index
+ * and its neighbours alone, so a stream's pieces are bitwise the one-shot result and a window carries no
+ * state. The arithmetic contract (every output bit is defined by IEEE f32 rounded add and multiply, never
+ * fused, one correctly rounded divide and exact compares). x[i] = +0 outside [0, n);
+ * g_min = (float)10^(-denoise / 20), in double, denoise in [3, 30] dB; alpha the over-subtraction factor:
+ *   table     w[j], j < 512, at [j]: sqrt(0.5 - 0.5 cos(2 pi j / 512)), the square root of the periodic Hann
+ *             window; c[t], t < 256, at [512 + t]: cos(2 pi t / 512); s[t] at [768 + t]: -sin(2 pi t / 512).
+ *             All in double, rounded once.
+ *   frames    frame f >= 0 covers samples [128 f - 384, 128 f + 128): u_f[j] = x[128 f - 384 + j] * w[j]. The
+ *             signal's frames are 0 .. F - 1, F = floor((n - 1) / 128) + 4: every sample lies in four.
+ *   pairs     frames 2 m and 2 m + 1 share one 512-point complex transform: z[j] = u_2m[j] + i u_2m+1[j]
+ *             (if F is odd the last pair's second frame is all zero; it is transformed, but does not exist
+ *             for the mean and the floor below, and its gain is 1).
+ *   transform nine radix-2 decimation-in-frequency stages on z in natural order, st = 0 .. 8, h = 256 >> st:
+ *             for every j with (j & h) == 0, u = z[j], v = z[j + h], t = (j & (h - 1)) << st:
+ *             z[j] = u + v; d = u - v; z[j + h] = d if t == 0, (d.im, -d.re) if t == 128 (exact moves),
+ *             else (d.re * c[t] - d.im * s[t], d.re * s[t] + d.im * c[t]): two rounded products and one
+ *             rounded add or subtract per component. Z[k] = z[bitrev9(k)].
+ *   split     for k = 0 .. 256, m = (512 - k) mod 512, each sum rounded, the halving exact:
+ *             X_2m[k]   = ((Z[k].re + Z[m].re) / 2, (Z[k].im - Z[m].im) / 2),
+ *             X_2m+1[k] = ((Z[k].im + Z[m].im) / 2, (Z[m].re - Z[k].re) / 2).
+ *   power     P[f,k] = X.re * X.re + X.im * X.im.
+ *   mean      S[f,k] = (the sum of P[f',k] over the f' in f - 2 .. f + 2 that exist, ascending from +0)
+ *             * (float)(1.0 / count).
+ *   floor     N[f,k] = the minimum of S[f',k] over the f' in f - 94 .. f + 30 that exist (a minimum-statistics
+ *             noise floor over 1 s; a minimum has one value, whatever the order).
+ *   gain      G[f,k] = 1 where S == 0, else max(g_min, 1 - alpha * (N / S)): one correctly rounded divide,
+ *             one rounded multiply, one rounded subtract.
+ *   smoothing H[f,k] = ((G[k-1] + 2 G[k]) + G[k+1]) * 0.25, G[-1] = G[0], G[257] = G[256].
+ *   apply     Y_f[k] = (H * X.re, H * X.im). The pair is packed again: for k = 0 .. 256,
+ *             Q[k] = (Y_2m.re - Y_2m+1.im, Y_2m.im + Y_2m+1.re); for k = 1 .. 255,
+ *             Q[512 - k] = (Y_2m.re + Y_2m+1.im, Y_2m+1.re - Y_2m.im), both from Y[k].
+ *   inverse   the transform above on z[k] = (Q[k].im, Q[k].re) gives Z'; v_2m[j] = (Z'[j].im * 2^-9) * w[j],
+ *             v_2m+1[j] = (Z'[j].re * 2^-9) * w[j] (the scaling exact).
+ *   add       y[i] = (((+0 + v_f[j + 384]) + v_f+1[j + 256]) + v_f+2[j + 128]) + v_f+3[j]) * 0.5,
+ *             f = floor(i / 128), j = i mod 128: ascending frame order; the root-Hann window squared sums to
+ *             2 over the four.
+ * Reach: y[i] draws on the pairs that hold frames floor(i / 128) .. + 3, and a frame's gain on frames
+ * f - 96 .. f + 32. With n_known samples known and not final, outputs below 128 (p - 35) are exact, p the
+ * even number at or below floor(n_known / 128): an output waits for 4481 .. 4864 later samples (0.280 ..
+ * 0.304 s) and a stream keeps up to 99 + 38 hops of its past. Silence comes back as +0. A non-finite sample
+ * leaves the outputs within reach of it unspecified; nothing is read or written out of bounds. alpha, the
+ * two spans and the frame size are untuned defaults and nobody has listened to the output: the repository
+ * has no real checkpoint. */
+#define RWKVTTS_DENOISE_TABLE_LEN 1024 /* 512 + 256 + 256 */
+typedef struct {
+  uint32_t struct_size;
+  float alpha; /* in [0, 16]; the stage's default is 2 */
+} rwkvtts_denoise_desc;
+/* The library's own table builder (host only): out[1024]. */
+int rwkvtts_denoise_table(const rwkvtts_denoise_desc* desc, float* out);
+/* Streaming plan (host only, a pure function). With samples [0, n_known) of a signal known and
+ * p = floor(n_known / 128) rounded down to even: *out_ready_end = max(0, 128 (p - 35)), or n_known with
+ * final (n_known is the signal's length); with q = floor(out_first / 128) rounded down to even:
+ * *in_first_needed = max(0, 128 (max(0, q - 96) - 3)). Either pointer may be NULL. */
+int rwkvtts_denoise_plan(int64_t n_known, int final, int64_t out_first, int64_t* out_ready_end,
+                         int64_t* in_first_needed);
+typedef struct rwkvtts_denoise rwkvtts_denoise;
+/* table == NULL: the table of rwkvtts_denoise_table; otherwise the caller's [1024] table (copied). */
+int rwkvtts_denoise_create(int device, const rwkvtts_denoise_desc* desc, const float* table, rwkvtts_denoise** out);
+int rwkvtts_denoise_destroy(rwkvtts_denoise* d);
+/* n signals (ragged), each with its own g_min[i] in (0, 1], in one launch triple. Host buffers; out[i] has
+ * capacity n_in[i]. n_in[i] == 0 writes nothing. The spectra stay on the device. Calls on one handle
+ * serialise on its lock. */
+int rwkvtts_denoise_batch(rwkvtts_denoise* d, const float* const* in, const int64_t* n_in, const float* g_min, int n,
+                          float* const* out);
+typedef struct {
+  uint32_t struct_size;
+  const float* in;    /* points at sample in_first of the signal */
+  int64_t in_first;   /* 0, or any sample: the window's frames start at the first whole pair behind it */
+  int64_t n_in;
+  int32_t final;      /* 1: in_first + n_in is the signal's length */
+  float g_min;
+  int64_t out_first;  /* outputs [out_first, out_first + out_count), any position */
+  int64_t out_count;
+  float* out;         /* capacity out_count */
+} rwkvtts_denoise_window;
+/* n windows (of any signals, any g_min) in one launch triple: outputs [out_first, out_first + out_count)
+ * of the whole-signal result, bitwise, whatever follows the known samples. RWKVTTS_EINVAL before anything
+ * is launched (and nothing written) if a requested output needs a sample that is not given: out_first +
+ * out_count > out_ready_end(in_first + n_in, final) or in_first > in_first_needed(out_first) by
+ * rwkvtts_denoise_plan. */
+int rwkvtts_denoise_windows(rwkvtts_denoise* d, const rwkvtts_denoise_window* w, int n);
+/* HIP-event time of the last launch triple (the kernels, no copies), in ms; 0 before the first. */
+int rwkvtts_denoise_kernel_ms(rwkvtts_denoise* d, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -301,6 +301,16 @@ class EqWindow(ctypes.Structure):
                 ("out_first", ctypes.c_int64), ("out_count", ctypes.c_int64), ("out", ctypes.c_void_p)]
 
 
+class DenoiseDesc(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("alpha", ctypes.c_float)]
+
+
+class DenoiseWindow(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("in_", ctypes.c_void_p), ("in_first", ctypes.c_int64),
+                ("n_in", ctypes.c_int64), ("final", ctypes.c_int32), ("g_min", ctypes.c_float),
+                ("out_first", ctypes.c_int64), ("out_count", ctypes.c_int64), ("out", ctypes.c_void_p)]
+
+
 class PitchDesc(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("hop", ctypes.c_int32), ("window", ctypes.c_int32),
                 ("lag_min", ctypes.c_int32), ("lag_max", ctypes.c_int32), ("unvoiced", ctypes.c_int32),
@@ -621,6 +631,17 @@ EXPORTS = {
     "rwkvtts_eq_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(EqWindow), ctypes.c_int, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_int]),
     "rwkvtts_eq_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    # denoise: table and plan (host only), batched / exact stream windows, a g_min per signal
+    "rwkvtts_denoise_table": (ctypes.c_int, [ctypes.POINTER(DenoiseDesc), ctypes.c_void_p]),
+    "rwkvtts_denoise_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "rwkvtts_denoise_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(DenoiseDesc), ctypes.c_void_p,
+                                              ctypes.POINTER(ctypes.c_void_p)]),
+    "rwkvtts_denoise_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "rwkvtts_denoise_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int, ctypes.c_void_p]),
+    "rwkvtts_denoise_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DenoiseWindow), ctypes.c_int]),
+    "rwkvtts_denoise_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
     "rwkvtts_mx_roundtrip": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "rwkvtts_quant_roundtrip": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_void_p]),

@@ -1157,6 +1157,123 @@ class EqStream(_ExactStream):
         return self.eq.plan(self.h.size, n_known, False, self._out_next)[1]
 
 
+# ---- noise reduction on the GPU --------------------------------------------------------------
+DENOISE_MIN, DENOISE_MAX = 3.0, 30.0  # the deepest attenuation a `denoise` may ask for, in dB
+
+
+def _denoise_table() -> np.ndarray:
+    """w[512], cos[256], -sin[256] of include/rwkvtts.h, in double, rounded once: the table the kernels read."""
+    import math
+    w = [math.sqrt(0.5 - 0.5 * math.cos(2.0 * math.pi * j / 512)) for j in range(512)]
+    c = [math.cos(2.0 * math.pi * t / 512) for t in range(256)]
+    s = [-math.sin(2.0 * math.pi * t / 512) for t in range(256)]
+    return np.array(w + c + s, dtype=np.float64).astype(F32)
+
+
+class Denoiser(_NativeStage):
+    """An STFT spectral gate as three HIP kernels (csrc/denoise.hip; the arithmetic contract is in
+    include/rwkvtts.h): 16 kHz PCM in, the same number of samples out. Frames of 512 at hop
+    128 under a root-Hann window go through an LDS FFT; each bin's power, averaged over five frames, is
+    held against its own minimum over about a second (94 frames back, 30 ahead), and the bin is turned
+    down by 1 - alpha * floor / power, never below the depth the caller gives, `denoise` dB. A frame's
+    arithmetic depends on its absolute index and its neighbours alone, so a stream's pieces are bitwise
+    the one-shot result. The pipeline applies it first, on the vocoder's PCM.
+
+    alpha and the spans are untuned defaults and nobody has listened to the output: the repository has no
+    real checkpoint.
+
+    evaluator: a callable (denoiser, items) -> [ndarray] standing in for the native window call, items
+    being [(samples from in_first on, in_first, final, g_min, out_first, out_count)]; no GPU object is
+    created then (the host-only plan is still the library's)."""
+    _NAME = "denoise"
+
+    def __init__(self, device: int = 0, alpha: float = 2.0, evaluator=None):
+        if not 0.0 <= float(alpha) <= 16.0:
+            raise ValueError("alpha must be in [0, 16]")
+        self.device, self.alpha = int(device), float(alpha)
+        self._desc = _ffi.DenoiseDesc(struct_size=ctypes.sizeof(_ffi.DenoiseDesc), alpha=self.alpha)
+        super().__init__(evaluator)
+        self.table = _denoise_table()
+        self._create(self.table)
+
+    # ---- host-only plan ----
+    @staticmethod
+    def floor_gain(denoise: float) -> np.float32:
+        """g_min = (float)10^(-denoise / 20), in double; ValueError outside 3 .. 30 dB."""
+        import math
+        if isinstance(denoise, bool) or not isinstance(denoise, (int, float, np.integer, np.floating)) \
+                or not DENOISE_MIN <= float(denoise) <= DENOISE_MAX:  # (NaN fails)
+            raise ValueError(f"denoise must be in [{DENOISE_MIN}, {DENOISE_MAX}] dB")
+        return F32(math.pow(10.0, -float(denoise) / 20.0))
+
+    @staticmethod
+    def plan(n_known: int, final: bool, out_first: int = 0):
+        """(out_ready_end, in_first_needed) of rwkvtts_denoise_plan."""
+        end, first = ctypes.c_int64(), ctypes.c_int64()
+        _native("denoise_plan", int(n_known), 1 if final else 0, int(out_first), ctypes.byref(end), ctypes.byref(first))
+        return end.value, first.value
+
+    # ---- the kernels ----
+    def denoise_windows(self, items) -> list:
+        """[(samples from in_first on, in_first, final, g_min, out_first, out_count)] -> [outputs [out_first,
+        out_first + out_count) of the whole-signal result], all windows in one launch triple. Raises
+        RwkvTtsError(EINVAL), with nothing computed, if a window asks for more than plan() allows."""
+        items = [(np.ascontiguousarray(x, dtype=F32).reshape(-1), int(a), bool(f), float(F32(g)), int(o), int(n))
+                 for x, a, f, g, o, n in items]
+        if self._evaluator is not None:
+            return [np.ascontiguousarray(y, dtype=F32) for y in self._evaluator(self, items)]
+        return self._windows("denoise_windows", _ffi.DenoiseWindow, items, g_min=3, out_first=4)[1]
+
+    def denoise_batch(self, signals, denoise) -> list:
+        """[signal], [denoise in dB] -> [denoised signal], ragged, a depth per signal, in one launch triple;
+        an empty signal gives an empty one."""
+        xs = [np.ascontiguousarray(x, dtype=F32).reshape(-1) for x in signals]
+        gs = [self.floor_gain(v) for v in denoise]
+        if len(xs) != len(gs):
+            raise ValueError("denoise_batch: one denoise per signal")
+        if self._evaluator is not None:
+            return self.denoise_windows([(x, 0, True, g, 0, x.size) for x, g in zip(xs, gs)])
+        if not xs:
+            return []
+        outs, ins, lens, ous = self._ragged(xs, [x.size for x in xs])
+        self._call("denoise_batch", ins, lens, (ctypes.c_float * len(gs))(*[float(g) for g in gs]), len(xs), ous)
+        return outs
+
+    def denoise(self, x, denoise: float) -> np.ndarray:
+        return self.denoise_batch([x], [denoise])[0]
+
+    def stream(self, denoise: float) -> "DenoiseStream":
+        return DenoiseStream(self, denoise)
+
+
+class DenoiseStream(_ExactStream):
+    """Denoiser.stream(denoise): feed(pcm_chunk, final=False) -> the outputs that became exact with it. The
+    concatenation of what feed returns is bitwise Denoiser.denoise(the concatenated input, denoise),
+    however the input was cut. An output goes out once the 4481 .. 4864 samples behind it are known (0.280
+    .. 0.304 s: 30 + 2 frames of look-ahead, a frame's three further hops, and the hop and the pair that
+    have to be whole); the kept tail is what rwkvtts_denoise_plan asks for, the floor's look-back, and
+    there is no other state."""
+
+    def __init__(self, denoiser: Denoiser, denoise: float):
+        super().__init__()
+        self.dn = denoiser
+        self.g = denoiser.floor_gain(denoise)
+        self._out_next = 0     # outputs [0, _out_next) went out
+
+    def _emit(self, n_known, final):
+        end, _ = self.dn.plan(n_known, final, self._out_next)
+        count = end - self._out_next
+        if count > 0:
+            out = self.dn.denoise_windows([(self._tail, self._tail_first, final, self.g, self._out_next, count)])[0]
+        else:
+            out = np.zeros(0, dtype=F32)
+        self._out_next = max(end, self._out_next)
+        return out
+
+    def _first_needed(self, n_known):
+        return self.dn.plan(n_known, False, self._out_next)[1]
+
+
 # ---- pitch shift on the GPU ------------------------------------------------------------------
 def pitch_factor(semitones: float) -> float:
     """f = 2^(semitones / 12), in double: what the native side takes per signal."""

@@ -38,6 +38,11 @@ leaves the peaks where the stages before put them; a true-peak ceiling in dB, -1
 sample of the result, and the estimated peaks between samples, under it on the GPU with 64 samples of
 look-ahead (audio.Limiter), last of the stages, behind the resampler at the output
 rate -- in long-form on the joined signal -- exact over stream chunks.
+All five also take `denoise` (no reference counterpart: the reference ships the vocoder's PCM as it is):
+None leaves the vocoder's noise floor alone; a depth in dB, 3 .. 30, turns every bin of a 512-point STFT
+down towards its own minimum over about a second, by at most that depth, on the GPU (audio.Denoiser,
+DESIGN.md section 43), first of the stages, on the vocoder's PCM before the pause cap -- in long-form on
+each segment, before its cap and its join -- exact over stream chunks, each 0.28 .. 0.30 s behind its frames.
 All five also take `eq` (no reference counterpart: the reference has no tone control): None leaves the
 spectral balance alone; a device profile name (audio.EQ_PROFILES) or 1 .. 8 bands (kind, freq_hz, gain_db,
 q) filter the 16 kHz PCM on the GPU with the FIR they design, 64 .. 4096 taps (audio.Equaliser, DESIGN.md
@@ -219,14 +224,16 @@ class LongSpeech(np.ndarray):
 def audio_stages(stretcher, tempo, resampler, leveller=None, loudness=None, shifter=None, pitch_shift=None,
                  marker=None, watermark=None, watermark_key=None, shaper=None, max_pause=None,
                  formant_shift=None, extender=None, highband=None, limiter=None, limit=None,
-                 equaliser=None, eq=None) -> list:
-    """The stages behind the vocoder in the order they apply -- the pause cap at 16 kHz, then the pitch
+                 equaliser=None, eq=None, denoiser=None, denoise=None) -> list:
+    """The stages behind the vocoder in the order they apply -- the noise reduction and the pause cap at 16 kHz, then the pitch
     shift, then the stretch, then the equaliser, then the leveller, then the watermark, then the high band (16 kHz to 32 kHz),
     then the resampler, then the true-peak limiter at the output rate; None is no
     stage -- each as (batch, stream): batch([pcm]) -> [pcm] in one native call (one cap, one shift, one
     tempo, one loudness, one key and payload for the call), stream() -> an object whose feed(pcm, final)
     is exact over chunks. The pause cap removes samples, so every stage behind it does less work."""
     stages = []
+    if denoiser is not None:
+        stages.append((lambda pcm: denoiser.denoise_batch(pcm, [denoise] * len(pcm)), lambda: denoiser.stream(denoise)))
     if shaper is not None:
         stages.append((lambda pcm: shaper.shape_batch(pcm, max_pause), lambda: shaper.stream(max_pause)))
     if shifter is not None and formant_shift is None:
@@ -288,8 +295,9 @@ class LightweightTtsPipeline:
         self._extender = None  # audio.HighBand (created on the first highband, kept)
         self._limiter = None  # audio.Limiter (created on the first limit, kept)
         self._equaliser = None  # audio.Equaliser (created on the first eq, kept)
+        self._denoiser = None  # audio.Denoiser (created on the first denoise, kept)
         self._pause_threshold = None  # the loudness threshold of `max_pause` (None: audio.PauseShaper's default)
-        self._stage_cache_lock = threading.Lock()  # guards all eleven (the server's worker threads share the pipeline)
+        self._stage_cache_lock = threading.Lock()  # guards all twelve (the server's worker threads share the pipeline)
 
     # ---- output rates other than 16 kHz (no reference counterpart: the reference emits 16 kHz only)
     def resampler(self, sample_rate: Optional[int], sr_in: int = SAMPLE_RATE):
@@ -342,6 +350,21 @@ class LightweightTtsPipeline:
             if self._limiter is None:
                 self._limiter = Limiter(device=getattr(self.codec, "device", 0))
         return self._limiter
+
+    # ---- the noise floor (no reference counterpart: the reference ships the vocoder's PCM as it is)
+    def denoiser(self, denoise: Optional[float]):
+        """None for None (nothing is created: the floor is the vocoder's); otherwise the pipeline's one
+        Denoiser (the untuned defaults of audio.Denoiser), on the codec's GPU. The depth is in dB per
+        call, 3 .. 30, not a part of the object. A depth outside that, a bool or a NaN raises ValueError
+        before anything is generated."""
+        if denoise is None:
+            return None
+        from .audio import Denoiser
+        Denoiser.floor_gain(denoise)
+        with self._stage_cache_lock:
+            if self._denoiser is None:
+                self._denoiser = Denoiser(device=getattr(self.codec, "device", 0))
+        return self._denoiser
 
     # ---- the spectral balance (no reference counterpart: the reference has no tone control)
     def equaliser(self, eq):
@@ -494,7 +517,9 @@ class LightweightTtsPipeline:
     def _stages(self, sample_rate: Optional[int], tempo: Optional[float], loudness: Optional[float] = None,
                 pitch_shift: Optional[float] = None, watermark: Optional[int] = None,
                 max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                highband: Optional[float] = None, limit: Optional[float] = None, eq=None):  # -> (stages, output rate)
+                highband: Optional[float] = None, limit: Optional[float] = None, eq=None,
+                denoise: Optional[float] = None):  # -> (stages, output rate)
+        dn = self.denoiser(denoise)
         eqr, bands = self.equaliser(eq)
         lm = self.limiter(limit)
         hb = self.extender(highband, sample_rate)
@@ -513,6 +538,8 @@ class LightweightTtsPipeline:
             kw["limiter"], kw["limit"] = lm, float(limit)
         if eqr is not None:  # (and for eq)
             kw["equaliser"], kw["eq"] = eqr, bands
+        if dn is not None:  # (and for denoise)
+            kw["denoiser"], kw["denoise"] = dn, float(denoise)
         return (audio_stages(self.stretcher(tempo), tempo, rs, lv, None if lv is None else float(loudness),
                              sh, None if sh is None else float(pitch_shift or 0.0),
                              mk, None if mk is None else int(watermark), self.watermark_key, **kw),
@@ -585,7 +612,8 @@ class LightweightTtsPipeline:
                         tempo: Optional[float] = None, loudness: Optional[float] = None,
                         watermark: Optional[int] = None, max_pause: Optional[int] = None,
                         formant_shift: Optional[float] = None, highband: Optional[float] = None,
-                        limit: Optional[float] = None, eq=None, pitch_shift: Optional[float] = None) -> np.ndarray:
+                        limit: Optional[float] = None, denoise: Optional[float] = None, eq=None,
+                        pitch_shift: Optional[float] = None) -> np.ndarray:
         """sample_rate None / 16000: the vocoder's 16 kHz PCM. Any other rate: that PCM resampled on
         the GPU (resampler()); the failed-request second of silence is sample_rate zeros.
         tempo None / 1.0: nothing. Any other: the 16 kHz PCM time-stretched on the GPU (stretcher())
@@ -619,9 +647,13 @@ class LightweightTtsPipeline:
         the 16 kHz PCM filtered on the GPU by the FIR they design (equaliser(); audio.Equaliser, DESIGN.md
         section 42), after the stretch and before the leveller, the same length and no lag; the second of
         silence stays silence. stream_speech's concatenation is bitwise this result.
+        denoise None: nothing. A depth in dB, 3 .. 30: the vocoder's 16 kHz PCM through the spectral gate on
+        the GPU (denoiser(); audio.Denoiser, DESIGN.md section 43), first of the stages, the same length;
+        the second of silence stays silence. stream_speech's concatenation is bitwise this result, each
+        chunk 0.28 .. 0.30 s behind its frames.
         args.global_sampling / semantic_sampling outside their ranges raise ValueError, like tempo."""
         check_sampling(args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband, limit, eq)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband, limit, eq, denoise)
         try:
             req = self._request(args)
         except ValueError:  # untokenisable text: the request fails -> empty result
@@ -638,8 +670,8 @@ class LightweightTtsPipeline:
                       sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                       loudness: Optional[float] = None, watermark: Optional[int] = None,
                       max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                      highband: Optional[float] = None, limit: Optional[float] = None, eq=None,
-                      pitch_shift: Optional[float] = None):
+                      highband: Optional[float] = None, limit: Optional[float] = None,
+                      denoise: Optional[float] = None, eq=None, pitch_shift: Optional[float] = None):
         """generate_speech as a generator of float32 PCM chunks (SpeechChunk: an ndarray that also
         carries t0, t1, n_known, done), each decoded while the request is still generating tokens.
 
@@ -718,21 +750,24 @@ class LightweightTtsPipeline:
         if eq is not None:
             self.equaliser(eq)  # (and for a bad band or profile)
             kw["eq"] = eq
+        if denoise is not None:
+            self.denoiser(denoise)  # (and for a bad depth)
+            kw["denoise"] = denoise
         return self.stream_request(req, chunk_frames, sample_rate=sample_rate, tempo=tempo, loudness=loudness, **kw)
 
     def stream_request(self, req: Optional[TtsBatchRequest], chunk_frames: int = 16,
                        sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                        loudness: Optional[float] = None, watermark: Optional[int] = None,
                        max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                       highband: Optional[float] = None, limit: Optional[float] = None, eq=None,
-                       pitch_shift: Optional[float] = None):
+                       highband: Optional[float] = None, limit: Optional[float] = None,
+                       denoise: Optional[float] = None, eq=None, pitch_shift: Optional[float] = None):
         """stream_speech for a request that is already built (None: a request that failed before it
         was submitted)."""
         if chunk_frames < 1:
             raise ValueError("chunk_frames must be >= 1")
         if req is not None:
             check_sampling(req.args)
-        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband, limit, eq)
+        stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband, limit, eq, denoise)
         streams = [stream() for _, stream in stages]
         H = self.codec.halo()
         g, sem, t0, yielded, status = None, [], 0, False, 0
@@ -769,8 +804,8 @@ class LightweightTtsPipeline:
                               sample_rate: Optional[int] = None, tempo: Optional[float] = None,
                               loudness: Optional[float] = None, watermark: Optional[int] = None,
                               max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                              highband: Optional[float] = None, limit: Optional[float] = None, eq=None,
-                              pitch_shift: Optional[float] = None) -> List[np.ndarray]:
+                              highband: Optional[float] = None, limit: Optional[float] = None,
+                              denoise: Optional[float] = None, eq=None, pitch_shift: Optional[float] = None) -> List[np.ndarray]:
         """sample_rate other than None / 16000: the whole batch is resampled in one resample_batch
         call (a failed item stays an empty array). tempo other than None / 1.0: the whole batch is
         first stretched in one stretch_batch call, one tempo for the call. loudness other than None:
@@ -785,7 +820,7 @@ class LightweightTtsPipeline:
         one limit_batch call behind the resampler, one ceiling for the call."""
         for a in batch_args:
             check_sampling(a)
-        stages, _ = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband, limit, eq)
+        stages, _ = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, max_pause, formant_shift, highband, limit, eq, denoise)
         reqs, idx = [], []
         for i, a in enumerate(batch_args):
             try:
@@ -870,8 +905,8 @@ class LightweightTtsPipeline:
                              trim: bool = True, keep: int = 800, fade: int = 80,
                              loudness: Optional[float] = None, watermark: Optional[int] = None,
                              max_pause: Optional[int] = None, formant_shift: Optional[float] = None,
-                             highband: Optional[float] = None, limit: Optional[float] = None, eq=None,
-                             pitch_shift: Optional[float] = None) -> "LongSpeech":
+                             highband: Optional[float] = None, limit: Optional[float] = None,
+                             denoise: Optional[float] = None, eq=None, pitch_shift: Optional[float] = None) -> "LongSpeech":
         """generate_speech for a text of any length: the text is cut into segments of at most
         segment_tokens text tokens (segment.split_text), the segments decode side by side in the
         manager's slots and engines with one voice (_long_submit), and their PCM is joined on the
@@ -894,11 +929,12 @@ class LightweightTtsPipeline:
         silence is not shaped. highband runs where the resampler does, on the joined signal, last before
         it; limit behind it, on the joined signal at the output rate (there is none inside the join). eq
         filters the joined signal as one, after the stretch and before the leveller, as the other 16 kHz
-        stages of the fold do: the filter rings through a pause as it would in one utterance."""
+        stages of the fold do: the filter rings through a pause as it would in one utterance. denoise runs
+        on every segment's PCM before its cap and its join, all segments in one denoise_batch call."""
         check_sampling(args)
         stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, formant_shift=formant_shift,
                                     highband=highband, limit=limit, eq=eq)
-        shaper = self.pause_shaper(max_pause)
+        shaper, dn = self.pause_shaper(max_pause), self.denoiser(denoise)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)
         if plan is None:
@@ -910,6 +946,8 @@ class LightweightTtsPipeline:
         if not any(st == 0 and (r[0] or r[1]) for r, st in results):
             return LongSpeech.make(np.zeros(rate, dtype=np.float32), voice, recs)
         pcm = self.codec.decode_audio_batch([r if st == 0 else ([], []) for r, st in results])
+        if dn is not None:
+            pcm = dn.denoise_batch(pcm, [denoise] * len(pcm))
         if shaper is not None:
             pcm = self._long_shape(shaper, max_pause, pcm, recs)
         out, ab = joiner.join(pcm, [sg.pause_ms * (SAMPLE_RATE // 1000) for sg in segs])
@@ -924,7 +962,8 @@ class LightweightTtsPipeline:
                            trim: bool = True, keep: int = 800, fade: int = 80, loudness: Optional[float] = None,
                            watermark: Optional[int] = None, max_pause: Optional[int] = None,
                            formant_shift: Optional[float] = None, highband: Optional[float] = None,
-                           limit: Optional[float] = None, eq=None, pitch_shift: Optional[float] = None):
+                           limit: Optional[float] = None, denoise: Optional[float] = None, eq=None,
+                           pitch_shift: Optional[float] = None):
         """generate_long_speech as a generator of LongSpeech items, one per segment, in order: segment
         i is emitted once it and every segment before it are done -- decoded, joined alone with its
         gap (a piece depends on its own segment only), and fed through the stages' exact streams,
@@ -940,11 +979,12 @@ class LightweightTtsPipeline:
         max_pause caps the silences of each segment's PCM before its join, one call per segment.
         highband: each joined piece goes through the high-band stream, then the resampler's, as it does
         through the resampler's alone without it; an item waits for 12.9 ms more of the next piece.
-        limit: the limiter's stream is the last of them; an item waits for 70 more output samples."""
+        limit: the limiter's stream is the last of them; an item waits for 70 more output samples.
+        denoise runs on each segment's whole PCM before its cap and its join, so it adds no wait."""
         check_sampling(args)
         stages, rate = self._stages(sample_rate, tempo, loudness, pitch_shift, watermark, formant_shift=formant_shift,
                                     highband=highband, limit=limit, eq=eq)
-        shaper = self.pause_shaper(max_pause)
+        shaper, dn = self.pause_shaper(max_pause), self.denoiser(denoise)
         joiner = self.joiner(trim, keep, fade)
         plan = self._long_submit(args, segment_tokens, pauses)
         if plan is None:
@@ -962,6 +1002,8 @@ class LightweightTtsPipeline:
                 if good and voice is None and r[0]:
                     voice = list(r[0])
                 pcm = self.codec.decode_audio_batch([r if st == 0 else ([], [])])[0]
+                if dn is not None:
+                    pcm = dn.denoise(pcm, denoise)
                 if shaper is not None:
                     pcm = self._long_shape(shaper, max_pause, [pcm], [rec])[0]
                 piece, ((rec["a"], rec["b"]),) = joiner.join([pcm], [sg.pause_ms * (SAMPLE_RATE // 1000)])

@@ -87,6 +87,11 @@
   on the GPU to that true-peak ceiling (audio.Limiter), last of the stages, behind the resampler.
   /api/tts then writes its WAV (or FLAC) at scale 1.0, as with `loudness`: the peak rule would undo the
   ceiling, and both routes send the same samples. Without the field the routes are unchanged.
+* `denoise` in the body of both TTS routes (no reference counterpart: the reference ships the vocoder's
+  PCM as it is): a JSON number in [DENOISE_MIN, DENOISE_MAX] = [3, 30] dB, anything else a 400. The
+  vocoder's 16 kHz PCM goes through the spectral gate on the GPU (audio.Denoiser), first of the stages:
+  no bin is turned down by more than that depth. `denoise` alone keeps /api/tts's peak rule. Without the
+  field the routes are unchanged.
 * `eq` in the body of both TTS routes (no reference counterpart: the reference has no tone control): a
   device profile name of audio.EQ_PROFILES ("telephony", "small_speaker", "presence", "warm"), or a list of
   1 .. 8 objects {"type", "freq", "gain", "q"} -- type peak, lowshelf, highshelf, highpass or lowpass (which
@@ -205,6 +210,8 @@ HIGHBAND_MIN, HIGHBAND_MAX = -12.0, 12.0
 HIGHBAND_RATES = (32000, 44100, 48000)
 # `limit` of the same bodies (no reference counterpart): the true-peak ceiling in dB -- the pipeline's range
 LIMIT_MIN, LIMIT_MAX = -12.0, 0.0
+# `denoise` of the same bodies (no reference counterpart): the deepest attenuation in dB -- the pipeline's range
+DENOISE_MIN, DENOISE_MAX = 3.0, 30.0
 # `format` of the same bodies (no reference counterpart): the container of the audio that goes out
 FORMATS = ("wav", "flac")
 # `watermark` of the same bodies (no reference counterpart): the payload of the provenance mark, 16
@@ -327,6 +334,11 @@ def _tts_args(body, voice_dir: str):
                               or not LIMIT_MIN <= limit <= LIMIT_MAX):  # (NaN fails the comparison)
         return (400, {"success": False, "error": f"不支持的峰值上限: {limit} (支持: "
                                                  f"{LIMIT_MIN} - {LIMIT_MAX} dB)"}), None, None
+    denoise = body.get("denoise")
+    if denoise is not None and (isinstance(denoise, bool) or not isinstance(denoise, (int, float))
+                                or not DENOISE_MIN <= denoise <= DENOISE_MAX):  # (NaN fails the comparison)
+        return (400, {"success": False, "error": f"不支持的降噪深度: {denoise} (支持: "
+                                                 f"{DENOISE_MIN} - {DENOISE_MAX} dB)"}), None, None
     eq = body.get("eq")
     if eq is not None:
         from .audio import EQ_PROFILES, Equaliser, eq_bands
@@ -459,6 +471,8 @@ def _tts_args(body, voice_dir: str):
         kw["highband"] = float(highband)
     if limit is not None:
         kw["limit"] = float(limit)
+    if denoise is not None:
+        kw["denoise"] = float(denoise)
     if eq is not None:
         kw["eq"] = eq
     if mark is not None:
