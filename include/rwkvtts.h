@@ -204,10 +204,31 @@ typedef struct {
  * 2^127, f16 2^-24 .. 2^15: the dequantised weights would not be f16 numbers). */
 #define RWKVTTS_QUANT_MXFP8 4
 #define RWKVTTS_QUANT_MXFP4 5
+/* The other three concrete OCP Microscaling formats, by the same five steps with other numbers:
+ *   MXFP6 E2M3 (1.2.3, bias 1, no Inf / NaN codes; magnitudes m/8 for m = 0..7, then (1 + m/8) 2^(E-1)
+ *     up to 7.5), MXFP6 E3M2 (1.3.2, bias 3, no Inf / NaN codes; m/16 for m = 0..3, then (1 + m/4) 2^(E-3)
+ *     up to 28), MXINT8 (a two's-complement byte i, element i * 2^-6, |i| <= 127).
+ *   1. block maximum   amax = max |v| over the 32 bf16 weights of the block.
+ *   2. scale exponent  e = floor(log2 amax) - emax with emax = 2 (E2M3), 4 (E3M2), 0 (MXINT8), clamped
+ *                      to [e_min, 127] with e_min = -123 (E2M3), -122 (E3M2), -120 (MXINT8); e = e_min
+ *                      when amax == 0. The stored byte is e + 127.
+ *   3. element         q = v * 2^-e (exact), rounded to the nearest element value, ties to even on the
+ *                      element's mantissa (MXINT8: on i), saturated to +-7.5 / +-28 / +-127/64 (MXINT8
+ *                      is symmetric: i = -128 is never produced as a value). A zero keeps its sign;
+ *                      MXINT8 stores -0, which has no two's-complement code, as the free byte 0x80.
+ *   4. dequantised     w = element * 2^e. e_min is -126 less the exponent of the smallest non-zero
+ *                      element magnitude (2^-3, 2^-4, 2^-6), so every w is zero or a bf16 normal, and
+ *                      the largest element has at most 7 significant bits: w is exactly a bf16 number,
+ *                      and the bit-for-bit statement of step 4 above holds (tests/test_gpu_mx_ocp.py).
+ *   5. non-finite      as above: RWKVTTS_EINVAL from rwkvtts_engine_create.
+ * bf16 models only, as MXFP8 / MXFP4. */
+#define RWKVTTS_QUANT_MXFP6_E2M3 6
+#define RWKVTTS_QUANT_MXFP6_E3M2 7
+#define RWKVTTS_QUANT_MXINT8 8
 /* Debug: steps 1-4 on the device apart from the GEMM. w_bf16 [N][K] (host, row-major bf16 bits;
  * N % 16 == 0, K % 128 == 0) is packed by the engine's pack kernel and unpacked through the GEMM's own
- * dequantisation into out_bf16 [N][K] (host): the dequantised weights w. type: RWKVTTS_QUANT_MXFP8 /
- * MXFP4. RWKVTTS_EINVAL for a non-finite weight (step 5) or bad arguments. */
+ * dequantisation into out_bf16 [N][K] (host): the dequantised weights w. type: RWKVTTS_QUANT_MXFP8 ..
+ * MXINT8. RWKVTTS_EINVAL for a non-finite weight (step 5) or bad arguments. */
 int rwkvtts_mx_roundtrip(int type, const uint16_t* w_bf16, int N, int K, uint16_t* out_bf16);
 /* Debug: RWKVTTS_QUANT_INT8 / NF4 on the device apart from the GEMM. w [N][K] (host, row-major bit
  * patterns of `dtype`, RWKVTTS_DTYPE_*; N % 16 == 0, K % 128 == 0) is packed by the engine's pack

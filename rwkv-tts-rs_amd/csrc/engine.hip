@@ -272,17 +272,17 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
   // the r / k / v / o / FFN matrices from the blob's row-major 16-bit copies
   {
     const int qt = desc.quant_type, ql = std::min(std::max(desc.quant_layers, 0), (int)dims.n_layer);
-    RT_CHECK(qt >= RWKVTTS_QUANT_NONE && qt <= RWKVTTS_QUANT_MXFP4, RWKVTTS_EINVAL, "unknown quant_type");
+    RT_CHECK(qt >= RWKVTTS_QUANT_NONE && qt <= RWKVTTS_QUANT_MXINT8, RWKVTTS_EINVAL, "unknown quant_type");
     RT_CHECK(!(qt == RWKVTTS_QUANT_SF4 && ql > 0), RWKVTTS_EUNSUPPORTED,
              "quant_type sf4: its code table is not available (web-rwkv not vendored)");
     const bool mx = quant_is_mx(qt);
     RT_CHECK(!(mx && ql > 0 && f16_), RWKVTTS_EUNSUPPORTED,
-             "quant_type mxfp8 / mxfp4 needs a bf16 model: the E8M0 block scales (2^-127 .. 2^127) do not fit f16's range");
+             "the Microscaling types need a bf16 model, not f16: the E8M0 block scales (2^-127 .. 2^127) do not fit f16's range");
     if (qt != RWKVTTS_QUANT_NONE && ql > 0) {
       RT_CHECK(C % kQ8Block == 0 && F % kQ8Block == 0, RWKVTTS_EUNSUPPORTED, "quantisation needs K % 128 == 0");
       // (k_gemm_mx has the 128- and 256-deep K-slices the quantised launches' splits give)
       RT_CHECK(!mx || (C / splitA_ <= 256 && C / splitO_ <= 256 && C / splitK_ <= 256 && F / splitF_ <= 256),
-               RWKVTTS_EUNSUPPORTED, "mxfp8 / mxfp4: K-slices deeper than 256");
+               RWKVTTS_EUNSUPPORTED, "Microscaling types: K-slices deeper than 256");
       const size_t cb_cc = quant_code_bytes(qt, C, C), sb_cc = quant_scale_bytes(qt, C, C);
       const size_t cb_fc = quant_code_bytes(qt, F, C), sb_fc = quant_scale_bytes(qt, F, C);
       const size_t per_layer = 4 * cb_cc + 2 * cb_fc + 4 * sb_cc + 2 * sb_fc;
@@ -315,7 +315,7 @@ int Engine::init(const rwkvtts_engine_desc& desc, const void* weights, size_t by
       if (mx) {
         int bad = 0;
         RT_HIP(hipMemcpy(&bad, mx_bad, sizeof(int), hipMemcpyDeviceToHost));
-        RT_CHECK(!bad, RWKVTTS_EINVAL, "mxfp8 / mxfp4: a quantised matrix holds a non-finite weight");
+        RT_CHECK(!bad, RWKVTTS_EINVAL, "Microscaling types: a quantised matrix holds a non-finite weight");
       }
       // f16 models: per launch, the shift that brings the largest dequantised |w| to ~2^14
       // (int8: max(|min|, |max|) of the blocks; nf4: the largest block absmax)

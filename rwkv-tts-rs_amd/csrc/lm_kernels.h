@@ -279,12 +279,30 @@ void launch_pack_frag(const bf16_t* W, int N, int K, bf16_t* out, hipStream_t st
 // and per-(column, K-block) scales: int8 [N][K / 128] u32 = f16 min | f16 max << 16; nf4
 // [N][K / 64] u16 = f16 absmax.
 constexpr int kQ8Block = 128, kQ4Block = 64;
-// Microscaling matrices (RWKVTTS_QUANT_MXFP8 / MXFP4, mx_gemm.hip): codes and E8M0 scales in ONE buffer
-// of superblocks (16 columns x 128 k: 64 lanes x 32 / 16 code bytes, then the 16 columns' four scale
+// Microscaling matrices (RWKVTTS_QUANT_MXFP8 .. MXINT8, mx_gemm.hip): codes and E8M0 scales in ONE buffer
+// of superblocks (16 columns x 128 k: 64 lanes x 32 / 24 / 16 code bytes, then the 16 columns' four scale
 // bytes each), so they count as code bytes and have no scale buffer. N % 16 == 0, K % 128 == 0.
-inline bool quant_is_mx(int qt) { return qt == RWKVTTS_QUANT_MXFP8 || qt == RWKVTTS_QUANT_MXFP4; }
+// The element formats, numbered as their quant codes:
+enum MxFmt : int {
+  kMxFp8 = RWKVTTS_QUANT_MXFP8,
+  kMxFp4 = RWKVTTS_QUANT_MXFP4,
+  kMxE2M3 = RWKVTTS_QUANT_MXFP6_E2M3,
+  kMxE3M2 = RWKVTTS_QUANT_MXFP6_E3M2,
+  kMxInt8 = RWKVTTS_QUANT_MXINT8,
+};
+inline bool quant_is_mx(int qt) { return qt >= RWKVTTS_QUANT_MXFP8 && qt <= RWKVTTS_QUANT_MXINT8; }
+// code bytes per lane per superblock: 8 bits x 32 k, 4 bits x 32 k, or MXFP6's 16-byte nibble plane + 8-byte
+// 2-bit plane
+constexpr int mx_lane_bytes(int qt) {
+  switch (qt) {
+    case kMxFp4: return 16;
+    case kMxE2M3:
+    case kMxE3M2: return 24;
+    default: return 32;
+  }
+}
 inline size_t mx_pack_bytes(int qt, int N, int K) {
-  return (size_t)(N / 16) * (K / 128) * ((qt == RWKVTTS_QUANT_MXFP4 ? 1024 : 2048) + 64);
+  return (size_t)(N / 16) * (K / 128) * (64 * mx_lane_bytes(qt) + 64);
 }
 inline size_t quant_code_bytes(int qt, int N, int K) {
   return quant_is_mx(qt) ? mx_pack_bytes(qt, N, K) : (size_t)N * K / (qt == 1 ? 1 : 2);
@@ -298,7 +316,7 @@ void launch_quant_pack(const uint16_t* W, int N, int K, int f16, int qt, uint8_t
 int quant_roundtrip(int qt, int dtype, const uint16_t* w, int N, int K, float* out);
 // W [N][K] bf16 -> the packed MX matrix; *nonfinite is set to 1 if W holds an Inf or a NaN
 void launch_mx_pack(const uint16_t* W, int N, int K, int qt, uint8_t* out, int* nonfinite, hipStream_t st);
-// launch_gemm's form for GemmArgs::q_fmt MXFP8 / MXFP4 (k_gemm_mx; bf16 models, K-slices of 128 / 256):
+// launch_gemm's form for GemmArgs::q_fmt MXFP8 .. MXINT8 (k_gemm_mx; bf16 models, K-slices of 128 / 256):
 // qw the packed matrix (MS 2: the matrices of the launch's quantised tiles back to back), qs unused.
 // Partial slabs bit for bit those of the unquantised launch on the dequantised matrix.
 int launch_gemm_mx(const GemmArgs& a, hipStream_t st);

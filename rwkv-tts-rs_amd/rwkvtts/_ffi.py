@@ -71,6 +71,7 @@ CODEC_FORM_SEPARATE_RESUNIT, CODEC_FORM_CHANNEL_LAST = 1, 2
 
 QUANT_NONE, QUANT_INT8, QUANT_NF4, QUANT_SF4 = 0, 1, 2, 3
 QUANT_MXFP8, QUANT_MXFP4 = 4, 5  # OCP Microscaling weights (bf16 models; include/rwkvtts.h)
+QUANT_MXFP6_E2M3, QUANT_MXFP6_E3M2, QUANT_MXINT8 = 6, 7, 8
 
 
 class Input(ctypes.Structure):

@@ -194,13 +194,17 @@ def _unpack_results(res, sem_bufs):
 def parse_quant_type(s) -> int:
     """bin/server.rs:1029-1056 (parse_quant_type): none / int8 / nf4 / sf4, case-insensitive;
     anything else is an error. SF4 parses but the engine rejects it (table not available).
-    mxfp8 / mxfp4 (no reference counterpart): OCP Microscaling weights, bf16 models only."""
+    mxfp8 / mxfp4 / mxfp6_e2m3 (or mxfp6) / mxfp6_e3m2 / mxint8 (no reference counterpart): OCP
+    Microscaling weights, bf16 models only."""
     if isinstance(s, int):
         return s
     t = {"none": _ffi.QUANT_NONE, "int8": _ffi.QUANT_INT8, "nf4": _ffi.QUANT_NF4, "sf4": _ffi.QUANT_SF4,
-         "mxfp8": _ffi.QUANT_MXFP8, "mxfp4": _ffi.QUANT_MXFP4}.get(str(s).lower())
+         "mxfp8": _ffi.QUANT_MXFP8, "mxfp4": _ffi.QUANT_MXFP4, "mxfp6_e2m3": _ffi.QUANT_MXFP6_E2M3,
+         "mxfp6": _ffi.QUANT_MXFP6_E2M3, "mxfp6_e3m2": _ffi.QUANT_MXFP6_E3M2,
+         "mxint8": _ffi.QUANT_MXINT8}.get(str(s).lower())
     if t is None:
-        raise ValueError(f"unsupported quant type: {s}. supported: none, int8, nf4, sf4, mxfp8, mxfp4")
+        raise ValueError(f"unsupported quant type: {s}. supported: none, int8, nf4, sf4, mxfp8, mxfp4, "
+                         "mxfp6_e2m3 (mxfp6), mxfp6_e3m2, mxint8")
     return t
 
 
@@ -238,7 +242,8 @@ def quant_config(quant_layers: int, quant_type) -> tuple:
 class SharedRwkvRuntime:
     """One engine per GPU: weights resident in HBM, `max_concurrent_batches` state slots.
     quant_layers / quant_type: the server's --quant-layers / --quant-type (web-rwkv Quant: none, int8,
-    nf4; sf4 is rejected), or mxfp8 / mxfp4 (OCP Microscaling weights, bf16 models).
+    nf4; sf4 is rejected), or mxfp8 / mxfp4 / mxfp6_e2m3 / mxfp6_e3m2 / mxint8 (OCP Microscaling weights,
+    bf16 models).
     forms: rwkvtts_engine_desc.forms (_ffi.FORM_*; 0 = the shipping decode forms).
     wkv_variant: mirrors rwkvtts_engine_desc.wkv_variant; ignored (every value selects the one WKV
     kernel the shape has)."""

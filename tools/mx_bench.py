@@ -1,6 +1,7 @@
-"""Weight-format timings of the LM forward pass (DESIGN.md §37): the synthetic 0.4B bf16 weights with all
+"""Weight-format timings of the LM forward pass (DESIGN.md §37, §44): the synthetic 0.4B bf16 weights with all
 24 layers quantised, every layer through the separate launches. Types: none (with the persistent decode
-forms switched off, so that like is compared with like), int8, nf4, mxfp8, mxfp4. Nothing here is gated.
+forms switched off, so that like is compared with like), int8, nf4, mxfp8, mxfp4, mxfp6_e2m3, mxfp6_e3m2,
+mxint8. Nothing here is gated.
 
   decode32  ms per decode step, 32 requests x S semantic tokens, graph replay: the engine's own HIP-event
             decode time over its step count (rwkvtts_get_stats);
@@ -38,7 +39,10 @@ def layer_bytes(qt):
             "int8": elems + elems // 128 * 4,                # u8 codes, f16 (min, max) per 128
             "nf4": elems // 2 + elems // 64 * 2,             # nibbles, f16 absmax per 64
             "mxfp8": elems // 2048 * (2048 + 64),            # superblocks of 16 x 128: codes + 64 scale bytes
-            "mxfp4": elems // 2048 * (1024 + 64)}[qt]
+            "mxfp4": elems // 2048 * (1024 + 64),
+            "mxfp6_e2m3": elems // 2048 * (1536 + 64),       # a nibble plane and a 2-bit plane
+            "mxfp6_e3m2": elems // 2048 * (1536 + 64),
+            "mxint8": elems // 2048 * (2048 + 64)}[qt]
 
 
 def requests(n, steps):
@@ -69,7 +73,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mx_bench.json"))
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--steps", type=int, default=64)
-    ap.add_argument("--types", default="none,int8,nf4,mxfp8,mxfp4")
+    ap.add_argument("--types", default="none,int8,nf4,mxfp8,mxfp4,mxfp6_e2m3,mxfp6_e3m2,mxint8")
     opt = ap.parse_args()
     types = opt.types.split(",")
     blob = W.synth_blob(D, seed=20251205)
